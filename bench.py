@@ -15,13 +15,16 @@ compression, inputs already resident in HBM, outputs written to HBM.
 * For N > 1 every step ends with the final per-stream size all-gather over
   RCCL (the only collective: it gives every rank the global output layout).
 
-After the timed region, outside it: every output stream is checked against
+A plain run sets up, warms up, times --steps steps and prints the line (with
+the phase times of those steps).  --dump-outputs DIR then also writes what the
+last timed step returned (see dump_outputs).  Everything else is behind --full:
+after the timed region, outside it, every output stream is checked against
 the committed reference golden of the workload (tests/golden/batch_*.bin,
 made by the reference bundle) -- a mismatch fails the run; --no-verify skips
-it (profiling runs only).  On rank 0 at N=1 the line also carries the shard
-sweep (the step time of the 512 / 1024 / 2048-stream shards a rank gets at
-8 / 4 / 2 GPUs), the end-to-end host->host rate through zs_deflate_batch, and
-the CPU baselines.  --mode inflate decodes members (C3; with --format gzip the
+it (profiling runs only).  On rank 0 at N=1 the --full line also carries the
+shard sweep (the step time of the 512 / 1024 / 2048-stream shards a rank gets
+at 8 / 4 / 2 GPUs), the end-to-end host->host rate through zs_deflate_batch,
+and the CPU baselines.  --mode inflate decodes members (C3; with --format gzip the
 C5-i gunzip; with --format deflate64-raw the C5-ii deflate64 decode).
 
 Prints ONE JSON line on rank 0.  See DESIGN.md "Measurement".
@@ -84,7 +87,67 @@ def parse():
                     "comma-separated strings (A/B only)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="engine option (zs_set_option), e.g. lane_block=16; repeatable")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also, outside the timed region: the golden check, the shard sweep, the end-to-end "
+                         "host->host rate and the CPU baselines (each still has its --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.verify_skipped = "skipped (--no-verify)" if args.no_verify else "skipped (not --full)"
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_verify = args.no_shard_sweep = args.no_e2e = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_SAMPLE_BYTES = 8 << 20  # output bytes kept by --dump-outputs (float32: 32 MiB on disk)
+
+
+def dump_outputs(args, D, d_out, offs, caps, per_unit):
+    """--dump-outputs: what the caller of the timed path holds after the last
+    timed step.  The per-unit result arrays (`per_unit`: name -> int32 device
+    tensor) go out whole, as float64.  The output buffer is far larger than a
+    dump may be, so of it go the whole slots (offs[i], caps[i]; bytes past the
+    unit's length zeroed) of a fixed, seeded choice of units, as float32; the
+    choice depends on the unit count and the slot sizes only."""
+    import numpy as np
+
+    torch = D.torch
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    sfx = "_rank%d" % D.rank if D.world > 1 else ""
+
+    def save(name, a):
+        np.save(os.path.join(args.dump_outputs, name + sfx + ".npy"), a)
+
+    for name, t in per_unit.items():
+        save(name, t.cpu().numpy().astype(np.float64))
+    n = len(offs)
+    lens = per_unit["out_len"].cpu().tolist()
+    picked, room = [], DUMP_SAMPLE_BYTES
+    for i in np.random.RandomState(20240229).permutation(n).tolist():
+        if caps[i] <= room:
+            picked.append(i)
+            room -= caps[i]
+        if room <= 0 or len(picked) >= 4096:
+            break
+    picked.sort()
+    parts = []
+    for i in picked:
+        slot = torch.zeros(caps[i], dtype=torch.uint8, device=D.dev)
+        k = max(0, min(int(lens[i]), caps[i]))
+        slot[:k] = d_out[offs[i]:offs[i] + k]
+        parts.append(slot)
+    sample = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.uint8, device=D.dev)
+    # every unit's output in one number: the position-weighted byte sum (exact in float64: < 2^53)
+    w = torch.arange(max(caps) if caps else 0, dtype=torch.int64, device=D.dev) % 251 + 1
+    chk = torch.zeros(n, dtype=torch.int64, device=D.dev)
+    for i in range(n):
+        k = max(0, min(int(lens[i]), caps[i]))
+        chk[i] = (d_out[offs[i]:offs[i] + k].to(torch.int64) * w[:k]).sum()
+    save("out_checksum", chk.cpu().numpy().astype(np.float64))
+    save("out_sample_units", np.asarray(picked, dtype=np.float64))
+    save("out_sample_bytes", sample.cpu().numpy().astype(np.float32))
 
 
 def set_options(eng, args):
@@ -420,7 +483,10 @@ def main():
                   "mismatches": D.sum(bad)}
         assert verify["mismatches"] == 0, "outputs differ from the reference golden: %s" % verify
     elif args.no_verify:
-        verify["golden"] = "skipped (--no-verify)"
+        verify["golden"] = args.verify_skipped
+
+    if args.dump_outputs:
+        dump_outputs(args, D, d_out, list(out_off), list(out_cap), {"out_len": d_len, "status": d_status})
 
     extra = {}
     if D.world == 1 and D.rank == 0:
@@ -628,6 +694,9 @@ def main_inflate(args):
     out_total = D.sum(out_local)
     in_local = len(blob)
     in_total = D.sum(in_local)
+    if args.dump_outputs:
+        dump_outputs(args, D, d_out, ooffs, caps, {"out_len": d_len, "status": d_status, "consumed": d_cons,
+                                                   "phase": d_phase, "msg": d_msg})
     # parity: every member's output against its source bytes / fixture digest (on the GPU), or,
     # where the reference's own decode differs from the source, against the reference's decode
     checked = bad = 0

@@ -8,7 +8,7 @@ i=0
 for g in "" "$@"; do
   o=""
   for kv in $g; do o="$o --option $kv"; done
-  timeout -k 10 200 python3 bench.py $ARGS --no-shard-sweep --no-e2e --no-cpu-baseline $o > "$OUT/ab_$i.log" 2>&1 || { tail -3 "$OUT/ab_$i.log"; exit 1; }
+  timeout -k 10 200 python3 bench.py --full $ARGS --no-shard-sweep --no-e2e --no-cpu-baseline $o > "$OUT/ab_$i.log" 2>&1 || { tail -3 "$OUT/ab_$i.log"; exit 1; }
   python3 - "$OUT/ab_$i.log" "$g" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

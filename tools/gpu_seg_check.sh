@@ -10,9 +10,9 @@ rc=$?; tail -3 "$OUT/tests.log"; [ $rc -eq 0 ] || exit $rc
 C4D="--mode inflate --stream-bytes 262144 --replicas 1 --corpus text --no-shard-sweep --no-e2e --no-cpu-baseline"
 C5I="--mode inflate --format gzip --replicas 1 --no-shard-sweep --no-e2e --no-cpu-baseline"
 C5D="--mode inflate --format deflate64-raw --replicas 1 --no-shard-sweep --no-e2e --no-cpu-baseline"
-for n in 512 4096; do $T 200 python3 bench.py $C4D --streams $n "$@" > "$OUT/c4d_$n.log" 2>&1 || exit 1; done
-for n in 1024 8192; do $T 200 python3 bench.py $C5I --streams $n "$@" > "$OUT/c5i_$n.log" 2>&1 || exit 1; done
-for n in 1024 8192; do $T 200 python3 bench.py $C5D --streams $n "$@" > "$OUT/c5d_$n.log" 2>&1 || exit 1; done
+for n in 512 4096; do $T 200 python3 bench.py --full $C4D --streams $n "$@" > "$OUT/c4d_$n.log" 2>&1 || exit 1; done
+for n in 1024 8192; do $T 200 python3 bench.py --full $C5I --streams $n "$@" > "$OUT/c5i_$n.log" 2>&1 || exit 1; done
+for n in 1024 8192; do $T 200 python3 bench.py --full $C5D --streams $n "$@" > "$OUT/c5d_$n.log" 2>&1 || exit 1; done
 for f in "$OUT"/c*.log; do python3 - "$f" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

@@ -17,13 +17,13 @@ run() {  # name seconds command...
   if [ $rc -ne 0 ]; then echo "=== $name failed ($rc)"; exit $rc; fi
 }
 if [ "$WHAT" != profiles ]; then
-run c2_headline 400 python3 bench.py
-run c3_inflate 200 python3 bench.py --mode inflate --no-shard-sweep --no-e2e
-run c5_gunzip 200 python3 bench.py --mode inflate --format gzip --streams 8192 --replicas 1 --no-shard-sweep --no-e2e
-run c5_d64 200 python3 bench.py --mode inflate --format deflate64-raw --streams 8192 --replicas 1 --no-shard-sweep --no-e2e
-run c5_gzip_l6 200 python3 bench.py --format gzip --streams 1024 --no-shard-sweep --no-e2e
-run c4_l9 300 python3 bench.py --streams 512 --stream-bytes 262144 --level 9 --no-shard-sweep --no-e2e
-run c4_l1 300 python3 bench.py --streams 512 --stream-bytes 262144 --level 1 --no-shard-sweep --no-e2e
+run c2_headline 400 python3 bench.py --full
+run c3_inflate 200 python3 bench.py --full --mode inflate --no-shard-sweep --no-e2e
+run c5_gunzip 200 python3 bench.py --full --mode inflate --format gzip --streams 8192 --replicas 1 --no-shard-sweep --no-e2e
+run c5_d64 200 python3 bench.py --full --mode inflate --format deflate64-raw --streams 8192 --replicas 1 --no-shard-sweep --no-e2e
+run c5_gzip_l6 200 python3 bench.py --full --format gzip --streams 1024 --no-shard-sweep --no-e2e
+run c4_l9 300 python3 bench.py --full --streams 512 --stream-bytes 262144 --level 9 --no-shard-sweep --no-e2e
+run c4_l1 300 python3 bench.py --full --streams 512 --stream-bytes 262144 --level 1 --no-shard-sweep --no-e2e
 fi
 if [ "$WHAT" != benches ]; then
 run profile 600 tools/profile.sh "$OUT/prof"
