@@ -46,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include "zs_common.h"
 #include "zs_kernels.h"
+#include "zs_sweep_ring.h"
 #include <type_traits>
 
 // the window in LDS: ZS_SEG_WPOS inserted positions, a longest match past the
@@ -55,7 +56,9 @@
 #ifndef ZS_SW_EXP
 #define ZS_SW_EXP 0  // experiments (timing A/B only; 0 in the product)
 #endif
-#define ZS_SW_MW 320u    // per-wave LDS window of member positions (chain + 64 <= ZS_SW_MW: levels 4..7)
+#define ZS_SW_MW 320u    // per-wave LDS window of member positions (chain + 64 <= ZS_SW_MW: level 7)
+// chunks per run of the persistent ring (levels 4..6); bits 16..20 of ZS_SW_EXP override it (timing A/B)
+#define ZS_SW_RUN_CAP ((((ZS_SW_EXP) >> 16) & 31u) ? (((ZS_SW_EXP) >> 16) & 31u) : 16u)
 
 typedef __attribute__((address_space(3))) uint32_t zs_sw_lds_u32;
 static __device__ __forceinline__ uint32_t sw_lds_addr(const void* p) {
@@ -403,6 +406,18 @@ struct SwRing {
   uint32_t c[2 * ZS_SW_RING];
   uint32_t key[2 * ZS_SW_RING];
 };
+// The persistent ring of levels 4..6 (chain <= 128, zs_sweep_ring.h): three
+// blocks of 64 members, block b at slots 64 (b mod 3), which a wave keeps
+// across the consecutive chunks of a run -- a chunk builds its own block only,
+// the blocks before it are the previous chunks' -- and slots 0..63 again at
+// 192..255, so that the 64 steps of a block read upwards from one wave-uniform
+// base without wrapping, as they do in SwRing.  The key array doubles as the
+// window of member positions (SwRing's mwin).
+struct SwRingP {
+  uint2 ab[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
+  uint32_t c[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
+  uint32_t key[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
+};
 
 // The lock-step sweep of one stream (the workgroup), for signature form A7.
 //
@@ -438,13 +453,15 @@ extern "C" int zs_sw_stats(unsigned long long* out) {
 #define SW_STAT(i, v) do { } while (0)
 #endif
 
-template <bool A7, bool MW>
-static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, uint16_t* mw, uint32_t* next,
+template <bool A7, bool MW, bool PR>  // PR: the persistent ring (chain <= ZS_SWR_MAX_CHAIN; MW is then unused)
+static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp, uint16_t* mw, uint32_t* next,
                                                uint32_t n, uint32_t m, uint32_t olo, uint32_t ohi,
                                                const uint16_t* mem, uint2* out, int chain, int nice_cfg) {
   // n: bytes from the window's start to the stream's end; m: the window's
   // members (inserted positions); results for the own positions [olo, ohi)
   using Sig = SwSig<A7>;
+  using Ring = std::conditional_t<PR, SwRingP, SwRing>;
+  Ring* const R = (Ring*)ringp;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t budget = (uint32_t)chain, budget_s = (uint32_t)chain >> 2;
   // the steps swept: the full chain (a demand-driven variant that swept chain >> 2
@@ -464,6 +481,20 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     R->key[i] = r.w;
     R->key[i + ZS_SW_RING] = r.w;
   };
+  // PR: this lane's record of block blk (wave-uniform); a block at slot 0 is written twice (the mirror)
+  auto put_blk = [&](int blk, uint4 r) {
+    const uint32_t i = zs_swr_block_slot(blk) + lane;
+    R->ab[i] = make_uint2(r.x, r.y);
+    R->c[i] = r.z;
+    R->key[i] = r.w;
+    if (zs_swr_mirrored(blk)) {
+      R->ab[i + ZS_SWR_SLOTS] = make_uint2(r.x, r.y);
+      R->c[i + ZS_SWR_SLOTS] = r.z;
+      R->key[i + ZS_SWR_SLOTS] = r.w;
+    }
+  };
+  // the slot of step t, from the base of its 64 steps (below)
+  auto at = [&](uint32_t base, uint32_t t) -> uint32_t { return base - t; };
   auto make_rec = [&](uint32_t q) -> uint4 {
     const uint32_t w0 = sw_word(win, q);
     uint4 r = Sig::rec(win, q, w0);
@@ -481,23 +512,58 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
   };
   auto fetch = [&](int j) -> uint32_t { return j >= 0 && (uint32_t)j < m ? (uint32_t)mem[j] : 0u; };
   auto load_rec = [&](int j) { load_rec_q(j, fetch(j)); };
-  auto member = [&](int j) -> uint32_t { return MW ? (uint32_t)mw[j - mw0] : (uint32_t)mem[j]; };
+  int cc = 0;  // the chunk swept (wave-uniform)
+  auto build_blk = [&](int blk, uint32_t q) {  // PR: block blk from its members' positions (0: no member)
+    const int j = 64 * blk + (int)lane;
+    put_blk(blk, j >= 0 && (uint32_t)j < m ? make_rec(q) : make_uint4(0, 0, 0, 0));
+  };
+  auto member = [&](int j) -> uint32_t {  // j = k - t for a step t that was swept: its block is in the ring
+    if constexpr (PR) return R->key[zs_swr_member_slot(cc, lane, 64u * (uint32_t)cc + lane - (uint32_t)j)] & 0xffffu;
+    return MW ? (uint32_t)mw[j - mw0] : (uint32_t)mem[j];
+  };
   auto rmbits = [&](const Sig& S, uint32_t slot) -> uint32_t {  // a ring record's matched bits
     const uint2 ab = R->ab[slot];
     return S.mbits(ab.x, ab.y, A7 ? 0u : R->c[slot]);
   };
   // chunks are claimed one ahead: the next chunk's members (its own and the
-  // block before) are loaded while this one is swept
+  // block before) are loaded while this one is swept.  PR: a wave claims runs
+  // [c, ce) of consecutive chunks, the next run during the last chunk of this
+  // one; only a run's first chunk needs the members of the block before.
   auto claim = [&]() -> uint32_t {
     uint32_t c = 0;
     if (lane == 0) c = atomicAdd(next, 1u);
     return __builtin_amdgcn_readfirstlane(c);
   };
-  uint32_t c = claim();
+  auto claim_run = [&](uint32_t& c0, uint32_t& c1) {
+    uint32_t a = 0, r = 0;
+    if (lane == 0) {
+      // (stale at worst: any length >= 1 is a valid run)
+      const uint32_t cur = __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      r = zs_swr_run_len(cur < nchunks ? nchunks - cur : 0u, ZS_SW_RUN_CAP);
+      a = atomicAdd(next, r);
+    }
+    c0 = __builtin_amdgcn_readfirstlane(a);
+    c1 = min(c0 + (uint32_t)__builtin_amdgcn_readfirstlane(r), nchunks);
+  };
+  uint32_t c, ce = 0;
+  if constexpr (PR) claim_run(c, ce);
+  else c = claim();
   uint32_t pf_p = fetch((int)(64 * c + lane)), pf_b = fetch((int)(64 * c + lane) - 64);
+  zs_swr_range vr = zs_swr_empty();  // PR: the blocks the ring holds
+  bool fresh_n = true;               // PR: the next chunk starts a run
   for (;;) {
     if (c >= nchunks) break;
-    const uint32_t cn = claim();
+    const bool fresh = fresh_n;  // (wave-uniform) a run's first chunk: pf_b was loaded, the ring holds nothing
+    uint32_t cn, cen = ce;
+    if constexpr (PR) {
+      cn = c + 1u;
+      fresh_n = cn >= ce;
+      if (fresh_n) claim_run(cn, cen);
+      if (fresh) vr = zs_swr_empty();
+    } else {
+      cn = claim();
+    }
+    cc = (int)c;
     const int k0 = (int)(64 * c);
     const int k = k0 + (int)lane;
     const bool mem_ok = (uint32_t)k < m;
@@ -505,18 +571,34 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     const uint32_t p = pf_p, qb = pf_b;  // (0 past the members)
     if (cn < nchunks) {
       pf_p = fetch((int)(64 * cn + lane));
-      pf_b = fetch((int)(64 * cn + lane) - 64);
+      if (!PR || fresh_n) pf_b = fetch((int)(64 * cn + lane) - 64);
     }
     c = cn;
+    ce = cen;
     // the lane's position is one of the window's own (a later window of a long
     // stream: its first 32,768 positions are look-back, candidates only)
     const bool own = mem_ok && p >= olo && p < ohi;
-    if (__builtin_amdgcn_ballot_w64(own) == 0) continue;
+    // (PR: a chunk without own lanes builds nothing and breaks the ring's range -- the
+    // next chunk with own lanes builds the block before it again.  In a window of zeros
+    // that is 512 chunks of look-back skipped for one block rebuilt.)
+    if (__builtin_amdgcn_ballot_w64(own) == 0) {
+      vr = zs_swr_empty();
+      continue;
+    }
     mw0 = k0 - (int)sbud;
     if (MW) mw[k - mw0] = (uint16_t)p;
+    // PR: the lane's record is built once, and its own signature, hash and the
+    // bytes past the signature are taken from it
+    const uint4 rown = PR && mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0);
     Sig S;
-    S.own(win, p);
-    const uint32_t h = sw_hash(sw_word(win, p));
+    if constexpr (PR) {
+      S.a = rown.x;
+      S.b = rown.y;
+      if constexpr (!A7) S.c = rown.z | 0x01000000u;
+    } else {
+      S.own(win, p);
+    }
+    const uint32_t h = PR ? rown.w >> 16 : sw_hash(sw_word(win, p));
     const uint32_t look = n - p;
     const uint32_t maxc = look < ZS_MAX_MATCH ? look : ZS_MAX_MATCH;                 // deflate.ts:1068
     const uint32_t nice = look < (uint32_t)nice_cfg ? look : (uint32_t)nice_cfg;      // deflate.ts:1078-1080
@@ -528,12 +610,21 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     // ring: this chunk's block and the one before it
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    put_rec(k, mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0));
+    if constexpr (PR) {
+      put_blk(cc, rown);
+      vr = zs_swr_push(vr, cc);
+      if (!zs_swr_has(vr, cc - 1)) {  // a run's first chunk, or after a skipped one
+        build_blk(cc - 1, fresh ? qb : fetch(k - 64));
+        vr = zs_swr_extend(vr, cc - 1);
+      }
+    } else {
+      put_rec(k, mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0));
 #if ZS_SW_EXP & 256
-    put_rec(k - 64, make_uint4(qb, qb, qb, 0));  // (timing: the block before without its window reads)
+      put_rec(k - 64, make_uint4(qb, qb, qb, 0));  // (timing: the block before without its window reads)
 #else
-    load_rec_q(k - 64, qb);
+      load_rec_q(k - 64, qb);
 #endif
+    }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
 
@@ -543,7 +634,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     uint32_t bt = 0, bt_s = 0;
     // best long candidate: its length (capped at nice) as lthr = len << 3 | 7, its step
     uint32_t lthr = 7u, lbt = 0, lthr_s = 7u, lbt_s = 0;
-    const uint32_t own_ext = sw_word(win, p + Sig::EXT);  // the lane's bytes past a full signature
+    const uint32_t own_ext = PR && A7 ? rown.z : sw_word(win, p + Sig::EXT);  // the lane's bytes past a full signature
     uint64_t alive_m = 0;
     uint32_t head = 0;  // bit 0: head candidate valid; 0x8000: at exactly MAX_DIST
     // step t of block 0's numbering reads ring slot base - t
@@ -589,10 +680,10 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
             {
 #endif
               // the next four bytes: A7 records carry them (c), else from the window
-              const uint32_t x = (A7 ? R->c[base - t0 - u]
-                                     : sw_word(win, (R->key[base - t0 - u] & 0xffffu) + Sig::EXT)) ^ own_ext;
+              const uint32_t ls = at(base, t0 + u);
+              const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ own_ext;
               uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
-                               : sw_extend(win, p, R->key[base - t0 - u] & 0xffffu, maxc, Sig::EXT + 4u);
+                               : sw_extend(win, p, R->key[ls] & 0xffffu, maxc, Sig::EXT + 4u);
               len = min(min(len, maxc), nice);
               gl = max(gl, (len << 3) | (7u - u));
             }
@@ -613,16 +704,17 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
         snapped = true;
       }
     };
-    const uint32_t base0 = (((uint32_t)(k - 64)) & (ZS_SW_RING - 1)) + 64u;  // block 0: step t at slot base0 - t
+    // block 0: step t at slot at(base0, t)
+    const uint32_t base0 = PR ? zs_swr_base(cc, 0u) + lane : (((uint32_t)(k - 64)) & (ZS_SW_RING - 1)) + 64u;
     // t = 1: the head candidate (deflate.ts:1376)
     {
-      const uint32_t key = R->key[base0 - 1u];
+      const uint32_t key = R->key[at(base0, 1u)];
       bool a1 = false;
       uint32_t sc[1] = {0};
       if (own && key >= khead) {
         a1 = true;
         head = 1u | ((p - (key & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u);
-        sc[0] = score(rmbits(S, base0 - 1u), 0);
+        sc[0] = score(rmbits(S, at(base0, 1u)), 0);
       }
       alive_m = __builtin_amdgcn_ballot_w64(a1);
       fold(sc[0], 1u, sc, 1u, base0);
@@ -646,7 +738,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
       uint32_t sc[3];
       uint64_t lm = 0;
 #pragma unroll
-      for (uint32_t u = 0; u < 3; u++) sc[u] = mstep(base0 - 2u - u, u, lm);
+      for (uint32_t u = 0; u < 3; u++) sc[u] = mstep(at(base0, 2u + u), u, lm);
       alive_m = sw_uniform(lm);  // the lanes live at step 4
       fold(max3(sc[0], sc[1], sc[2]), 2u, sc, 3u, base0);
       snap(4u);
@@ -658,7 +750,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     auto group_fast = [&](uint32_t base, uint32_t t0, auto G, bool live) __attribute__((always_inline)) {
       constexpr uint32_t N = decltype(G)::value;
       // from the group's lowest slot up: one address, immediate offsets
-      const uint32_t lo = base - t0 - (N - 1u);
+      const uint32_t lo = at(base, t0 + (N - 1u));
       const uint2* const A = R->ab + lo;
       const uint32_t* const C = R->c + lo;
       uint32_t sc[N];
@@ -684,14 +776,14 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
       for (uint32_t u = 0; u < 8; u++) {
         sc[u] = 0u;
         if (u < N) {
-          sc[u] = mstep(base - t0 - u, u, lm);
+          sc[u] = mstep(at(base, t0 + u), u, lm);
           last = lm;
         }
       }
       alive_m = sw_uniform(last);  // the lanes live at the group's last step
       fold(max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7]))), t0, sc, N, base);
 #else
-      const uint32_t lo = base - t0 - (N - 1u);
+      const uint32_t lo = at(base, t0 + (N - 1u));
       const uint2* const A = R->ab + lo;
       const uint32_t* const C = R->c + lo;
       const uint32_t* const K = R->key + lo;
@@ -735,12 +827,12 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
       };
       if (ta > tb) return;
       uint32_t t0 = ta, t1 = last_of(ta);
-      uint32_t kl = R->key[base - t1];
+      uint32_t kl = R->key[at(base, t1)];
       while (alive_m) {
         const bool mine = ((alive_m >> lane) & 1u) != 0;
         const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && kl > klim);
         const uint32_t n0 = t1 + 1u, n1 = n0 <= tb ? last_of(n0) : t1;
-        kl = R->key[base - n1];
+        kl = R->key[at(base, n1)];
         if (last_live == alive_m) {
           SW_STAT(1, 1);
           SW_STAT(4, t1 - t0 + 1u);
@@ -762,7 +854,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
         uint32_t t1 = t0 + 7u <= tb ? t0 + 7u : t0 + 3u;
         if (t0 <= budget_s && t1 > budget_s) t1 = budget_s;
         const bool mine = ((alive_m >> lane) & 1u) != 0;
-        const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && R->key[base - t1] > klim);
+        const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && R->key[at(base, t1)] > klim);
 #if ZS_SW_EXP & 4
         if (0) {
 #elif ZS_SW_EXP & 16
@@ -787,17 +879,24 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, SwRing* R, u
     };
     for (uint32_t b = 0; sbud > 4u && alive_m; b++) {
       // block b = steps (64b, 64b + 64]: members k0 - 64b - 64 ... k0 - 64b + 62, i.e. the blocks b and b + 1 back
-      if (b >= 1) {
+      // (PR: only where the ring does not hold it -- a run's first chunk, or after a skipped one)
+      if (b >= 1 && (!PR || !zs_swr_has(vr, cc - (int)b - 1))) {
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
-        load_rec(k - 64 * (int)(b + 1));
+        if constexpr (PR) {
+          build_blk(cc - (int)b - 1, fetch(k - 64 * (int)(b + 1)));
+          vr = zs_swr_extend(vr, cc - (int)b - 1);
+        } else {
+          load_rec(k - 64 * (int)(b + 1));
+        }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
       }
       const uint32_t ta = b == 0 ? 5u : 64u * b + 1u;
       const uint32_t tb = min(64u * b + 64u, sbud);
       // step t of this block at slot base - t
-      const uint32_t base = (((uint32_t)(k - 64 * (int)b - 64)) & (ZS_SW_RING - 1)) + 64u * b + 64u;
+      const uint32_t base = PR ? zs_swr_base(cc, b) + lane
+                               : (((uint32_t)(k - 64 * (int)b - 64)) & (ZS_SW_RING - 1)) + 64u * b + 64u;
       run(base, ta, tb);
       if (tb >= sbud) break;
     }
@@ -881,9 +980,11 @@ __global__ __launch_bounds__(1024) void zs_k_sweep(const uint8_t* __restrict__ i
                                                    const zs_sweep_seg* __restrict__ segs,
                                                    const uint16_t* __restrict__ members, uint2* __restrict__ mres,
                                                    int chain, int nice_cfg) {
-  __shared__ __attribute__((aligned(16))) SwRing ring[16];
+  // the rings (and level 7's member windows), laid over each other: one form runs per launch
+  constexpr uint32_t RING_BYTES = 16u * sizeof(SwRing), MWIN_BYTES = 16u * ZS_SW_MW * sizeof(uint16_t);
+  static_assert(16u * sizeof(SwRingP) <= RING_BYTES + MWIN_BYTES, "the persistent rings must fit the old ones' LDS");
+  __shared__ __attribute__((aligned(16))) uint8_t rmem[RING_BYTES + MWIN_BYTES];
   __shared__ __attribute__((aligned(16))) uint32_t win[ZS_SW_WIN_WORDS];
-  __shared__ uint16_t mwin[16][ZS_SW_MW];
   __shared__ uint32_t next;
   const zs_sweep_seg G = segs[blockIdx.x];
   const int s = (int)G.s;
@@ -921,16 +1022,23 @@ __global__ __launch_bounds__(1024) void zs_k_sweep(const uint8_t* __restrict__ i
   }
   if (threadIdx.x == 0) next = 0;
   const bool a7 = !__syncthreads_or((hi & 0x80808080u) != 0);
-  SwRing* const R = &ring[threadIdx.x >> 6];
+  const uint32_t wave = threadIdx.x >> 6;
   const uint16_t* mem = members + G.mb;
   uint2* out = mres + pos_base[s] + G.base;
-  uint16_t* const mw = mwin[threadIdx.x >> 6];
   const uint32_t olo = G.olo, ohi = G.ohi;
-  if (chain + 64 <= (int)ZS_SW_MW) {
-    if (a7) sw_body<true, true>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
-    else sw_body<false, true>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+  if (chain <= (int)ZS_SWR_MAX_CHAIN) {  // levels 4..6: the persistent ring
+    SwRingP* const R = reinterpret_cast<SwRingP*>(rmem) + wave;
+    if (a7) sw_body<true, false, true>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, false, true>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    return;
+  }
+  SwRing* const R = reinterpret_cast<SwRing*>(rmem) + wave;
+  uint16_t* const mw = reinterpret_cast<uint16_t*>(rmem + RING_BYTES) + wave * ZS_SW_MW;
+  if (chain + 64 <= (int)ZS_SW_MW) {  // level 7
+    if (a7) sw_body<true, true, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, true, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
   } else {  // levels 8, 9: positions from HBM
-    if (a7) sw_body<true, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
-    else sw_body<false, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    if (a7) sw_body<true, false, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, false, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
   }
 }
