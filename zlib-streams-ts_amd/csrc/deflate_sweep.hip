@@ -47,6 +47,7 @@
 #include "zs_common.h"
 #include "zs_kernels.h"
 #include "zs_sweep_ring.h"
+#include "zs_sweep_long.h"
 #include <type_traits>
 
 // the window in LDS: ZS_SEG_WPOS inserted positions, a longest match past the
@@ -641,11 +642,12 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
     auto score = [&](uint32_t mb, uint32_t u) -> uint32_t { return (mb & ~7u) | (7u - u); };  // one v_and_or_b32
     // a group's fold: the longest candidate if longer than the best so far.
     // Long candidates (a full signature match) are rare: when a group holds one
-    // for any lane, those lanes compare the next four bytes of all the group's
-    // long candidates at once (their positions are in the ring), a candidate
-    // matching those too is extended byte-wise (rarer still).  Lengths are
-    // capped at nice: the first nice candidate ends the walk (deflate.ts:1103)
-    // and ties with every later one, so it stays first.
+    // for any lane, those lanes compare the next four bytes of their first long
+    // candidate (its position is in the ring); a candidate matching those too is
+    // extended byte-wise (rarer still).  Which of a group's long candidates a
+    // lane keeps is zs_sweep_long.h's rule: lengths are capped at nice -- the
+    // first nice candidate ends the walk (deflate.ts:1103) and ties with every
+    // later one, so it stays first.
     auto fold = [&](uint32_t gm, uint32_t t0, const uint32_t* sc, uint32_t cnt, uint32_t base)
         __attribute__((always_inline)) {
 #if ZS_SW_EXP & 4096  // (A/B: the step formed per group)
@@ -663,35 +665,71 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
       if (__builtin_expect(__builtin_amdgcn_ballot_w64(gm >= long_m) != 0, 0)) {
 #endif
         SW_STAT(3, 1);
-        if (gm >= long_m && (lthr >> 3) < nice) {
-          uint32_t gl = 0;
-#if ZS_SW_EXP & 1024
-#pragma unroll
-          for (uint32_t u = 0; u < 8; u++) {
-            if (u < cnt && sc[u] >= long_m) {
-#else
-          // the group's long steps as a mask, visited one by one (one to three per lane, typically)
-          uint32_t lm = 0;
+        // the score of the long candidate at place u (zs_sweep_long.h)
+        auto lscore = [&](uint32_t u) -> uint32_t {
+          // the next four bytes: A7 records carry them (c), else from the window
+          const uint32_t ls = at(base, t0 + u);
+          const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ own_ext;
+          const uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
+                                 : sw_extend(win, p, R->key[ls] & 0xffffu, maxc, Sig::EXT + 4u);
+          return zs_swl_score(len, maxc, nice, u);
+        };
+        const bool lg = gm >= long_m && zs_swl_open(lthr, nice);
+#if ZS_SW_EXP & 1024  // (A/B: every lane's long steps as a mask, visited one by one)
+        if (lg) {
+          uint32_t gl = 0, lm = 0;
 #pragma unroll
           for (uint32_t u = 0; u < 8; u++) lm |= (u < cnt && sc[u] >= long_m) ? 1u << u : 0u;
           while (lm) {
-            const uint32_t u = (uint32_t)__builtin_ctz(lm);
+            gl = zs_swl_join(gl, lscore((uint32_t)__builtin_ctz(lm)));
             lm &= lm - 1u;
-            {
+          }
+          zs_swl_fold(gl, t0, &lthr, &lbt);
+        }
+#else
+        // The group's maximum names a lane's first long step; nearly always it is
+        // the lane's only one in the group.  Whether some lane has a second one is
+        // counted per lane from the scores packed four to a word (a score is below
+        // 128, and score + 0x80 - LONG has bit 7 exactly when the step is long),
+        // and only then do those lanes visit their other long steps one by one.
+        // (a lane whose chain ended has gm 0, its steps' scores anything: lg)
+#if ZS_SW_EXP & 8  // (A/B: the steps' lane masks intersected on the scalar unit: 8 VALU, 20 SALU)
+        uint64_t seen = 0, twice = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++)
+          if (u < cnt) {
+            const uint64_t mu = __builtin_amdgcn_ballot_w64(sc[u] >= long_m);
+            twice |= seen & mu;
+            seen |= mu;
+          }
+        twice &= __builtin_amdgcn_ballot_w64(lg);
+#else
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++)
+          if (u < cnt) w[u >> 2] |= sc[u] << (8u * (u & 3u));
+        constexpr uint32_t LB = (0x80u - Sig::LONG) * 0x01010101u;
+        const uint32_t nl = (uint32_t)__builtin_popcount((w[0] + LB) & 0x80808080u) +
+                            (uint32_t)__builtin_popcount((w[1] + LB) & 0x80808080u);
+        const uint64_t twice = __builtin_amdgcn_ballot_w64(lg && nl > 1u);
 #endif
-              // the next four bytes: A7 records carry them (c), else from the window
-              const uint32_t ls = at(base, t0 + u);
-              const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ own_ext;
-              uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
-                               : sw_extend(win, p, R->key[ls] & 0xffffu, maxc, Sig::EXT + 4u);
-              len = min(min(len, maxc), nice);
-              gl = max(gl, (len << 3) | (7u - u));
+        uint32_t gl = 0;
+        const uint32_t u1 = zs_swl_first(gm);
+        if (lg) gl = lscore(u1);
+        if (__builtin_expect(twice != 0, 0)) {
+          if ((twice >> lane) & 1u) {
+            uint32_t lm = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < 8; u++) lm |= (u < cnt && sc[u] >= long_m) ? 1u << u : 0u;
+            lm &= ~(1u << u1);
+            while (lm) {
+              gl = zs_swl_join(gl, lscore((uint32_t)__builtin_ctz(lm)));
+              lm &= lm - 1u;
             }
           }
-          const bool lup = gl > lthr;
-          lthr = max(lthr, gl | 7u);
-          lbt = lup ? t0 + 7u - (gl & 7u) : lbt;
         }
+        zs_swl_fold(gl, t0, &lthr, &lbt);  // (gl 0: no change)
+#endif
       }
     };
     bool snapped = budget_s <= 1u;  // wave-uniform: step chain >> 2 has been folded
@@ -706,8 +744,46 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
     };
     // block 0: step t at slot at(base0, t)
     const uint32_t base0 = PR ? zs_swr_base(cc, 0u) + lane : (((uint32_t)(k - 64)) & (ZS_SW_RING - 1)) + 64u;
-    // t = 1: the head candidate (deflate.ts:1376)
-    {
+    // Steps 1..8 as ONE masked group where the chain >> 2 snapshot is not before
+    // step 8 (levels 5 and up): one address, every load issued before the first
+    // is waited for, one fold.  The head candidate (t = 1, deflate.ts:1376) has
+    // its own liveness rule; the chain steps after it are live while their keys
+    // are (below).  Level 4 (snapshot at step 4) takes the pieces: the head,
+    // steps 2..4, and the blocks' groups from step 5.
+#if ZS_SW_EXP & 2048  // (A/B: the pieces at every level)
+    const bool open8 = false;
+#else
+    const bool open8 = budget_s >= 8u && sbud >= 8u;  // wave-uniform
+#endif
+    if (open8) {
+      const uint32_t lo = at(base0, 8u);
+      const uint2* const A = R->ab + lo;
+      const uint32_t* const C = R->c + lo;
+      const uint32_t* const K = R->key + lo;
+      uint32_t sc[8], key[8];
+      uint2 ab[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        key[u] = K[7u - u];
+        ab[u] = A[7u - u];
+      }
+      const bool a1 = own && key[0] >= khead;
+      head = a1 ? 1u | ((p - (key[0] & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u) : 0u;
+      alive_m = __builtin_amdgcn_ballot_w64(a1);
+      uint64_t lm = alive_m;
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        if (u) {
+          asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key[u]), "v"(klim));
+          lm &= alive_m;
+        }
+        const uint32_t v = score(S.mbits(ab[u].x, ab[u].y, A7 ? 0u : C[7u - u]), u);
+        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(sc[u]) : "v"(v), "s"(lm));
+      }
+      alive_m = sw_uniform(lm);  // the lanes live at step 8
+      fold(max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7]))), 1u, sc, 8u, base0);
+      snap(8u);
+    } else {
       const uint32_t key = R->key[at(base0, 1u)];
       bool a1 = false;
       uint32_t sc[1] = {0};
@@ -734,7 +810,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
       return r;
     };
     // steps 2..4 (masked)
-    if (sbud >= 4u) {
+    if (!open8 && sbud >= 4u) {
       uint32_t sc[3];
       uint64_t lm = 0;
 #pragma unroll
@@ -892,7 +968,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
       }
-      const uint32_t ta = b == 0 ? 5u : 64u * b + 1u;
+      const uint32_t ta = b == 0 ? (open8 ? 9u : 5u) : 64u * b + 1u;
       const uint32_t tb = min(64u * b + 64u, sbud);
       // step t of this block at slot base - t
       const uint32_t base = PR ? zs_swr_base(cc, b) + lane
