@@ -1,5 +1,5 @@
 """CPU check of the L4..L9 match finder's algorithm (tools/emu/emu_bucket_sweep.c
-models zs_k_bucket + zs_k_sweep of deflate_sweep.hip over capi.cpp's windows):
+models zs_k_bucket + zs_k_sweep of deflate_sweep.hip over zs_plan.h's windows):
 the counting sort by (hash, position), the lock-step sweep over bucket predecessors with 12-byte signatures, the liveness keys,
 the chain >> 2 snapshot and the deferred long candidates (with the re-walk
 after a fifth) reproduce a direct longest_match (deflate.ts:1053-1115) at
@@ -74,7 +74,7 @@ def _long_streams():
 
 @pytest.mark.parametrize("level", [4, 7])
 def test_windowed_sweep_model_matches_longest_match(emu, tmp_path, level):
-    """Streams over 65,537 bytes: the sweep's windows (capi.cpp sweep_table -- a first window owning [0, 65520),
+    """Streams over 65,537 bytes: the sweep's windows (zs_plan.h zs_plan_deflate -- a first window owning [0, 65520),
     then 32,752 own positions after a 32,768-position look-back, u16 window-relative members) give every position
     exactly once the result of a direct longest_match over the whole stream's chain."""
     streams = _long_streams()

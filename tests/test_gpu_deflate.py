@@ -84,7 +84,7 @@ def test_sweep_match_table_equals_chain_walk(engine, level):
     inputs.append(bytes(0x41 + (x & 3) for x in corpus.rand(92 + level, 65536)))
     inputs.append(bytes(x & 0x7F for x in corpus.rand(93, 20000)) + corpus.text(94, 45537))
     # streams over 65,537 bytes: the sweep in windows (a first one owning 65,520 positions, then 32,752 own positions
-    # after a 32,768-position look-back each, capi.cpp sweep_table), at and around the window boundaries and up to
+    # after a 32,768-position look-back each, zs_plan.h zs_plan_deflate), at and around the window boundaries and up to
     # 256 KiB
     for n, kind in ((65538, "text"), (98302, "mixed"), (98303, "text"), (130836, "zeros"), (262144, "text"),
                     (200001, "mixed"), (70000, "rand")):

@@ -1,5 +1,5 @@
 // emu_bucket_sweep.c -- CPU model of the L4..L9 match finder (zs_k_bucket +
-// zs_k_sweep, deflate_sweep.hip, over the windows of capi.cpp sweep_table), checked
+// zs_k_sweep, deflate_sweep.hip, over the windows of zs_plan.h zs_plan_deflate), checked
 // position by position against a direct longest_match (deflate.ts:1053-1115)
 // for both budgets the lazy parse asks for (chain, chain >> 2 when
 // prev_length >= good_match, deflate.ts:1075-1077) and for the slide-NIL flag.
@@ -121,7 +121,7 @@ int main(int argc, char** argv) {
       if (head[h] > 0) prev[p] = head[h];
       head[h] = (int32_t)p;
     }
-    for (uint32_t lo = 0; lo < n; lo += lo == 0 ? 65520u : 32752u) {  // capi.cpp sweep_table
+    for (uint32_t lo = 0; lo < n; lo += lo == 0 ? 65520u : 32752u) {  // zs_plan.h zs_plan_deflate
       const uint32_t base = n <= 65537u || lo == 0 ? 0u : lo - 32768u;
       const uint32_t olo = lo - base, ohi = n <= 65537u ? n : lo == 0 ? 65520u : 32768u + 32752u;
       B = buf + base;

@@ -1,6 +1,6 @@
 """Wall-clock profile of zs_k_parse's passes on a C2-shaped batch (build with
 -DZS_PARSE_PROF=1: tools/build_variant.sh pp deflate_parse.hip -DZS_PARSE_PROF=1).
-usage: ZS_LIB=variants/pp/libzsgpu.so python3 tools/parse_prof.py [streams]
+usage: ZS_LIB=variants/pp/libzsgpu.so python3 tools/parse_prof.py [streams [parse_waves]]
 Prints each pass's time summed over waves (wall_clock64 ticks, 100 MHz) per wave."""
 import ctypes, sys
 sys.path.insert(0, "zlib-streams-ts_amd")
@@ -11,8 +11,6 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 e = zsamd.Engine(0)
 if len(sys.argv) > 2:
     e.set_option("parse_waves", int(sys.argv[2]))
-if len(sys.argv) > 3:
-    e.set_option("demand", int(sys.argv[3]))
 buf = bytes(zsamd.corpus("text", 0, n, 65536))
 ins = [buf[i * 65536:(i + 1) * 65536] for i in range(n)]
 e.compress_batch_raw(ins, "deflate-raw", 6)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "zs_plan.h"  // zs_sweep_seg, the windows' and the parse segments' sizes
 
 // Per-block record written by the parse / tree kernels.
 struct zs_block {
@@ -36,20 +37,6 @@ __global__ void zs_k_prev(const uint8_t* in, const uint64_t* in_off, const uint3
                           uint16_t* prevd, uint32_t min_len);
 __global__ void zs_k_match(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                            const uint16_t* prevd, uint2* mres, int chain, int nice, uint32_t min_len);
-// levels 4..9 (deflate_sweep.hip), one workgroup per WINDOW: the inserted
-// positions from `base` up to its own positions' end ohi (at most 65,535; a
-// stream of up to 65,537 bytes is one window, base 0); the window writes the
-// results of its own positions [olo, ohi) (window-relative), members at
-// members + mb (u16, window-relative)
-struct zs_sweep_seg {
-  uint32_t s, base, olo, ohi;
-  uint64_t mb;
-  uint64_t pad;
-};
-#define ZS_SEG_WPOS 65535u   // inserted positions per window at most (u16 members; bucket counts fit 16 bits)
-#define ZS_SEG_FIRST 65520u  // own positions of a long stream's first window ...
-#define ZS_SEG_OWN 32752u    // ... and of its later ones, after a 32,768-position look-back (> MAX_DIST);
-                             // multiples of 16: every window starts 16-byte aligned with its stream
 // zs_k_bucket's workgroup: wave 0 claims, the others scatter (a multiple of 64 dividing 16384: the scan's slices)
 #define ZS_BK_THREADS 512u
 template <bool ORD>
@@ -65,13 +52,6 @@ __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint
 ZS_PARSE_DECL(zs_k_parse)
 ZS_PARSE_DECL(zs_k_parse_2w)  // two waves per stream, ZS_PARSE2W_SEG-position segments
 ZS_PARSE_DECL(zs_k_parse_4w)  // four waves per stream, ZS_PARSE4W_SEG-position segments
-// parse scratch words per 1024-position segment (deflate_parse.hip)
-#define ZS_PARSE_SEG 1024u
-#define ZS_PARSE_SEG_WORDS 3596u
-#define ZS_PARSE2W_SEG 512u
-#define ZS_PARSE2W_SEG_WORDS 2060u
-#define ZS_PARSE4W_SEG 256u
-#define ZS_PARSE4W_SEG_WORDS 1292u
 template <int NW, bool ORD>
 __global__ void zs_k_fast(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                           const uint32_t* blk_base, uint32_t* syms, zs_block* blocks, zs_stream* streams, int chain,

@@ -1,0 +1,372 @@
+// zs_plan.h -- what the host layer (capi.cpp) decides about a batch before it
+// launches anything: each member's route, the kernel instances, the grids and
+// the workspace sizes.  Pure functions of the options and the batch's lengths:
+// no HIP types, no HIP calls, so the host check compiles them with a plain C++
+// compiler (tools/emu/emu_plan.cpp, tests/test_plan_model.py).  capi.cpp runs
+// plan, then the ensure calls, then the uploads and launches.
+#ifndef ZS_PLAN_H
+#define ZS_PLAN_H
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "zs_common.h"
+
+#if defined(__HIPCC__)
+#define ZS_PLAN_FN static __host__ __device__ inline
+#else
+#define ZS_PLAN_FN static inline
+#endif
+
+// ---- constants shared with the kernels
+#define ZS_SPLIT_MAX 64u           // bit ranges searched per member (pieces <= this)
+#define ZS_SEG_LANES 64u    // pieces per span (one lane each)
+#define ZS_SEG_W 1024u      // bits of a lane's start window whose symbol starts it records (the sync bitmaps; 2048 in
+                            // the walk instance for batches of few large members: fewer chains that do not meet)
+#define ZS_SEG_PAD 16u      // u16 values of padding behind each piece's scratch
+#define ZS_SEG_BIG_BITS (1u << 21)  // members with more input bits: block starts from the finder as extra entries
+#define ZS_SEG_SPLIT_BITS (1u << 18)  // deflate64 members with more input bits: the split decode (long copies)
+#define ZS_SEG_BLOCK_BITS 16384u    // span slots per member: one per this many input bits (+ zs_seg_spans' margin)
+#define ZS_SEG_SMAX 8192u           // bits per lane at most (a span's lanes: seg_bits, then from the block before)
+// levels 4..9 (deflate_sweep.hip), one workgroup per WINDOW: the inserted
+// positions from `base` up to its own positions' end ohi (at most 65,535; a
+// stream of up to 65,537 bytes is one window, base 0); the window writes the
+// results of its own positions [olo, ohi) (window-relative), members at
+// members + mb (u16, window-relative)
+struct zs_sweep_seg {
+  uint32_t s, base, olo, ohi;
+  uint64_t mb;
+  uint64_t pad;
+};
+#define ZS_SEG_WPOS 65535u   // inserted positions per window at most (u16 members; bucket counts fit 16 bits)
+#define ZS_SEG_FIRST 65520u  // own positions of a long stream's first window ...
+#define ZS_SEG_OWN 32752u    // ... and of its later ones, after a 32,768-position look-back (> MAX_DIST);
+                             // multiples of 16: every window starts 16-byte aligned with its stream
+// parse scratch words per 1024-position segment (deflate_parse.hip)
+#define ZS_PARSE_SEG 1024u
+#define ZS_PARSE_SEG_WORDS 3596u
+#define ZS_PARSE2W_SEG 512u
+#define ZS_PARSE2W_SEG_WORDS 2060u
+#define ZS_PARSE4W_SEG 256u
+#define ZS_PARSE4W_SEG_WORDS 1292u
+#define ZS_PARSE2W_AUTO 2048u  // batches below this many streams parse with two waves per stream (option parse_waves = 0)
+
+// A member the lane kernel leaves to the large-member paths (the segmented, split
+// or wave decode) when wave_min is set: more input bytes than wave_min, or a high
+// expansion (a cap past 64 KiB and at least 8 bytes of it per input byte: long
+// copies, which one lane makes byte by byte -- deflate64's zeros_100k.deflate64 took a
+// lane 4.3 ms; the wave decoders copy 64 bytes at a time)
+ZS_PLAN_FN bool zs_inf_expands(uint32_t in_len, uint32_t out_cap) {
+  return out_cap > 65536u && out_cap / 8u >= in_len;
+}
+ZS_PLAN_FN bool zs_inf_large(uint32_t in_len, uint32_t out_cap, uint32_t wave_min) {
+  return wave_min && (in_len > wave_min || zs_inf_expands(in_len, out_cap));
+}
+
+// ---- the options that decide routes and instances (zs_set_option)
+struct zs_route_opts {
+  bool inflate_fast = true;
+  bool inflate_ref_wrap = true;  // reproduce the reference's inflate_fast window-wrap copy (inffast.ts:133-147)
+  // split decode of large members (inflate_split.hip): deflate64, or raw deflate without the window-wrap copy
+  bool inflate_split = true;
+  // segmented decode (inflate_seg.hip): a member's blocks cut into lane-sized pieces that synchronise
+  bool inflate_seg = true;
+  uint32_t inflate_wave_min = 32768;  // members with more input bytes decode one per wave (inflate_wave.hip); 0: never
+  uint32_t lane_large_min = 2304;     // this many large members or more: one LANE each (zs_k_inflate_lane<.., true>); 256 KiB members: wave kernel 26.9 / 68.5 / 128 ms at 1024 / 2048 / 4096, lanes 68.6 / 78.3 / 77.7
+  int lane_block = 0;        // members per workgroup of the inflate lane path (0: chosen from the batch size)
+  uint32_t seg_bits = 0;            // input bits per lane of an entry's first block (later ones: from the block before);
+                                    // 0: 4096 for members of 64 KiB of input or more on average, else 2048
+  uint32_t seg_small_batch = 16384; // batches of at most this many members ...
+  uint32_t seg_small_min = 4096;    // ... send members with more input bytes than this to it too
+  bool seg_wide = true;             // the 2048-bit sync window for a batch of few large members
+  int seg_split = 2;                // pieces cut in two at the walk's mid points (0 off, 1 on, 2 auto: small batches)
+  uint32_t seg_big_bits = ZS_SEG_BIG_BITS;  // members with more input bits also walk from the finder's block starts
+  uint64_t seg_scratch_max = 16ull << 30;  // bytes of u16 piece scratch the segmented decode may take per batch
+  uint32_t ncu = 256;               // compute units of the device
+  int parse_waves = 0;       // L4..9 one-wave parse: waves per stream (1, 2; 0: chosen from the batch size)
+  bool match_sweep = true;   // 0: the chain-walk kernels for every stream (a cross-check of the sweep)
+};
+
+// ---- inflate
+// A member's span slots in the segmented decode: one per ZS_SEG_BLOCK_BITS input
+// bits for the blocks, twice the spans of the narrowest lanes, 8 more; its
+// pieces' bound; its u16 scratch elements (each piece 16-byte aligned and padded).
+static inline uint64_t zs_seg_spans(uint32_t in_len) {
+  const uint64_t nbits = 8ull * in_len;
+  return nbits / ZS_SEG_BLOCK_BITS + 2 * nbits / (64ull * ZS_SEG_W) + 8;
+}
+static inline uint32_t zs_seg_pmax(uint32_t in_len) {
+  const uint64_t nbits = 8ull * in_len, spans = zs_seg_spans(in_len);
+  // (x 2: split mode cuts pieces in two)
+  return 2u * (uint32_t)std::min<uint64_t>(spans * ZS_SEG_LANES, nbits / ZS_SEG_W + spans + 1);
+}
+static inline uint64_t zs_seg_scratch_elems(uint32_t in_len, uint32_t out_cap) {
+  return (((uint64_t)out_cap + 7) & ~7ull) + ZS_SEG_PAD * (uint64_t)zs_seg_pmax(in_len) + 16;
+}
+
+// A lane launch: members per workgroup and the root-table instance
+// (zs_k_inflate_lane<rt, ..>; narrow workgroups afford per-lane root tables, inflate_lane.hip)
+struct zs_lane_launch {
+  uint32_t block = 1;
+  int rt = 0;
+};
+
+struct zs_inflate_plan {
+  // the large members (batch indices), by the path that decodes them beside the lane kernel
+  std::vector<uint32_t> seg, split, wave;
+  uint32_t wave_min = 0;  // the lane kernel skips members that are large by this threshold (0: none)
+  zs_lane_launch lane;    // the lane kernel over the whole batch
+  uint32_t piece_cap = 0;   // split path: u16 values per piece
+  uint64_t val_stride = 0;  // u32 values per split member
+  bool wave_refw = false;   // wave list: zs_k_inflate_wave<wave_refw> ...
+  bool wave_lanes = false;  // ... or one lane each, zs_k_inflate_lane<wave_lane.rt, true>
+  zs_lane_launch wave_lane;
+};
+
+// Everything inflate_device decides about a batch with the fast path on
+// (options o, o.inflate_fast set).
+static inline void zs_plan_inflate(const zs_route_opts& o, int wbits, uint32_t n, const uint32_t* in_len,
+                                   const uint32_t* out_cap, zs_inflate_plan& p) {
+  // lane-per-member fast path; anything but a clean end of stream goes to the exact kernel.
+  // A lane's decode is a dependent chain of loads, so the chip wants many
+  // waves more than full ones: up to 16,384 members, thin workgroups (one
+  // wave each) until ~4096 waves; above, 1024 waves of up to 64 members.
+  // Measured (MI355X): 65,536 members want 64 per workgroup (every lane resident at
+  // once, 548 B of LDS each); 8,192 want two (C5-i 29.5 -> 23.7 ms at 8 -> 2: four
+  // waves per SIMD hide each other's waits, with little divergence inside each).
+  uint32_t B = (uint32_t)o.lane_block;
+  if (!B) {
+    if (n <= 16384u)
+      for (B = 1; B < 64 && (n + B - 1) / B > 4608u;) B <<= 1;  // (~4096 waves; a few members over 8,192 keep two per wave)
+    else
+      for (B = 64; B > 8 && (n + B - 1) / B < 1024u;) B >>= 1;
+  }
+  // Large members (more than inflate_wave_min input bytes) decode one per wave
+  // on the side stream, beside the lane kernel: one lane would take the
+  // batch's whole time on such a member.  The wave kernel tracks the
+  // reference's inflate() calls and reproduces their window-wrap copy
+  // (inflate_wave.hip, zs_refcalls); the lane kernel skips exactly these members.
+  p.wave_min = 0;
+  p.seg.clear();
+  p.split.clear();
+  p.wave.clear();
+  // "Large" members decode beside the lane kernel.  With the segmented decode on,
+  // a small batch's members are large from seg_small_min bytes on: one lane each
+  // would leave most of the chip idle (the per-rank shards of the 8-GPU configs).
+  uint32_t big_min = o.inflate_wave_min;
+  if (o.inflate_seg && n <= o.seg_small_batch && o.seg_small_min && (!big_min || o.seg_small_min < big_min))
+    big_min = o.seg_small_min;
+  // Large raw members whose decode carries no call-boundary behaviour
+  // (deflate64; raw deflate without the window-wrap copy) are cut at their
+  // block boundaries and decoded piecewise (inflate_split.hip); the rest of
+  // the large members take the wave kernel.  The pieces' u16 scratch is
+  // bounded: members past kSplitScratch take the wave kernel too.
+  const bool splittable = o.inflate_split && (wbits == -16 || (wbits == -15 && !o.inflate_ref_wrap));
+  p.piece_cap = 0;
+  p.val_stride = 0;
+  if (big_min) {
+    constexpr size_t kSplitScratch = 2ull << 30;
+    constexpr uint32_t kPieceCapMax = 4u << 20;  // values per piece
+    // the segmented decode's u16 scratch (2 bytes per byte of capacity) is
+    // bounded too (option seg_scratch_mb): members past it take the split / wave kernels
+    uint64_t seg_bytes = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      if (!zs_inf_large(in_len[i], out_cap[i], big_min)) continue;
+      // (the segmented decode keeps bit positions in 32 bits; members with long
+      // blocks or long copies -- large deflate64 ones, high expansions -- decode
+      // faster with a wave per block / per member, which copies 64 bytes at a time)
+      const bool longcopies = zs_inf_expands(in_len[i], out_cap[i]) ||
+                              (wbits == -16 && 8ull * in_len[i] > ZS_SEG_SPLIT_BITS);
+      if (o.inflate_seg && in_len[i] < (1u << 29) && !longcopies) {
+        const uint64_t sb = 2 * zs_seg_scratch_elems(in_len[i], out_cap[i]);
+        if (seg_bytes + sb <= o.seg_scratch_max) {
+          seg_bytes += sb;
+          p.seg.push_back(i);
+          continue;
+        }
+      }
+      const uint32_t pc = (std::min(out_cap[i], kPieceCapMax) + 1u) & ~1u;
+      const uint32_t npc = std::max(p.piece_cap, pc);
+      const uint64_t nvs = std::max<uint64_t>(p.val_stride, (out_cap[i] + 3ull) & ~3ull);
+      if (splittable && (2ull * ZS_SPLIT_MAX * npc + 4ull * nvs) * (p.split.size() + 1) <= kSplitScratch) {
+        p.split.push_back(i);
+        p.piece_cap = npc;
+        p.val_stride = nvs;
+      } else {
+        p.wave.push_back(i);
+      }
+    }
+    if (!p.wave.empty() || !p.split.empty() || !p.seg.empty()) p.wave_min = big_min;
+  }
+  // Narrow workgroups with large members beside them (side stream): the
+  // LDS-canon instance, 68 VGPRs, so the side stream's waves find slots on
+  // every SIMD (C5-ii: 34 -> 26 ms); alone, the register instance (C5-i:
+  // 24.4 vs 25.7 ms)
+  p.lane.block = B;
+  p.lane.rt = B > 16 ? 0 : p.wave_min ? 2 : 1;
+  // deflate64 never runs inflate_fast in the reference: no window-wrap copy to reproduce
+  p.wave_refw = o.inflate_ref_wrap && wbits != -16;
+  // Many large members: one lane each (the lane kernel's REFW instance,
+  // the reference's calls tracked per lane) -- a wave per member keeps its
+  // bookkeeping in scalars, and the waves of a CU share one scalar unit
+  // (4,096 x 256 KiB: wave kernel 176 ms)
+  const uint32_t nw = (uint32_t)p.wave.size();
+  p.wave_lanes = p.wave_refw && o.lane_large_min && nw >= o.lane_large_min;
+  for (uint32_t i = 0; p.wave_lanes && i < nw; i++) p.wave_lanes = in_len[p.wave[i]] < (1u << 29);  // 32-bit bit positions
+  // thin workgroups to ~4096 waves (4,096 x 256 KiB: one lane per wave 95 ms, two 110, four 144)
+  uint32_t B2 = 1;
+  while (B2 < 64 && (nw + B2 - 1) / B2 > 4096u) B2 <<= 1;
+  p.wave_lane.block = B2;
+  p.wave_lane.rt = B2 <= 16 ? 2 : 0;
+}
+
+// The segmented decode of the members `list` of a batch (seg_launch): per-member
+// prefix arrays, the big members, and the instances and grids of its kernels.
+struct zs_seg_plan {
+  std::vector<uint32_t> spb, pbase;  // prefix sums per list entry: span slots, pieces
+  std::vector<uint64_t> sbase;       // ... and u16 scratch elements
+  std::vector<uint32_t> big, big_s;  // members over seg_big_bits input bits: list indices, batch indices
+  uint32_t nb = 0;                   // span slots in all
+  uint32_t nwalk = 0;                // the walk's grid: one wave per member, ZS_SPLIT_MAX per big one
+  bool d64 = false, refw = false;    // zs_k_seg_decode<d64, refw>; the fallback zs_k_inflate_wave<refw>
+  bool w2k = false, large = false;   // zs_k_seg_walk<d64, w2k ? 2048 : 1024, large && !d64>
+  uint32_t walk_bits = 0;            // its bits-per-lane argument
+  int split = 0;
+  bool rsmall = false;               // zs_k_seg_resolve<512, 65536> (else <256, 32768>)
+  uint32_t gdec = 0, gfb = 0;        // grids of the decode and of the fallback
+};
+
+static inline void zs_plan_seg(const zs_route_opts& o, int wbits, const std::vector<uint32_t>& list,
+                               const uint32_t* in_len, const uint32_t* out_cap, zs_seg_plan& p) {
+  const uint32_t ng = (uint32_t)list.size();
+  p.d64 = wbits == -16;
+  p.refw = o.inflate_ref_wrap && !p.d64;
+  p.pbase.assign(ng + 1, 0);
+  p.sbase.assign(ng + 1, 0);
+  p.spb.assign(ng + 1, 0);
+  p.big.clear();
+  p.big_s.clear();
+  uint64_t gbits = 0;
+  for (uint32_t k = 0; k < ng; k++) {
+    const uint32_t i = list[k];
+    const uint64_t nbits = 8ull * in_len[i];
+    p.spb[k + 1] = p.spb[k] + 2 * (uint32_t)zs_seg_spans(in_len[i]);  // (x 2: split mode)
+    p.pbase[k + 1] = p.pbase[k] + zs_seg_pmax(in_len[i]);
+    p.sbase[k + 1] = p.sbase[k] + zs_seg_scratch_elems(in_len[i], out_cap[i]);
+    // the big members' list indices for the walk, their stream indices for the finder
+    if (nbits > o.seg_big_bits) {
+      p.big.push_back(k);
+      p.big_s.push_back(i);
+    }
+    gbits += nbits;
+  }
+  p.nb = p.spb[ng];
+  p.nwalk = ng + (uint32_t)p.big.size() * (ZS_SPLIT_MAX - 1u);
+  // The sync window: 2048 bits when the walks all fit the chip at once (the 2048-bit
+  // instance takes 49 KB of LDS: three per CU) and the members are large (blocks
+  // wide enough for lanes of >= 2048 bits), so that fewer neighbours fail to meet
+  // (512 x 256 KiB: 5.3 -> 4.2 ms); otherwise 1024 (occupancy: 1,024 x 256 KiB 7.6 vs 6.6 ms)
+  p.large = gbits >= 65536ull * 8 * ng;  // members of 64 KiB of input or more on average
+  p.w2k = o.seg_wide && p.nwalk <= 3u * o.ncu && p.large;
+  // bits per lane: large members (4,096 x 256 KiB: 17.2 -> 15.9 ms, its 512-member shard 3.70 -> 3.57) walk fewer,
+  // wider spans; 64 KiB members keep 2048 (the 1,024-member gunzip shard: 2.11 vs 2.45 ms, the decode's pieces
+  // too few to fill the chip) -- tools/segbits_ab.sh
+  const uint32_t sbits = o.seg_bits ? o.seg_bits : gbits >= (1ull << 19) * ng ? 4096u : 2048u;
+  p.walk_bits = std::max<uint32_t>(sbits, p.w2k ? 2048u : 0u);
+  // Split mode: the plan cuts each piece in two at the first symbol start past its lane's middle (the walk
+  // records it), so the decode runs twice the pieces, each half as long.  The resolve then takes twice the
+  // rounds (one piece per round) and the plan twice the steps, so it pays only where the decode of few large
+  // members leaves SIMDs idle: a rank's 512 x 256 KiB shard 3.13 -> 2.93 ms (decode 1.36 -> 0.78, plan
+  // 0.08 -> 0.20, resolve 0.30 -> 0.50); 1,024 x 256 KiB 5.07 -> 5.52, C5-i's 1,024 x 64 KiB 1.93 -> 2.09
+  // (profiles/r06/seg/split_*)
+  p.split = o.seg_split == 2 ? (ng <= 2u * o.ncu && p.large ? 1 : 0) : o.seg_split;
+  // one wave per span taken, grid-stride over the work list
+  p.gdec = std::min<uint32_t>(p.nb, 8192u);
+  // the resolve: four members per CU (256 threads, a 32 KiB ring) unless the batch is too small to fill them
+  p.rsmall = ng <= 2u * o.ncu;
+  // (the members the resolve listed: usually none, so a small grid walks the list)
+  p.gfb = std::min<uint32_t>(ng, 256u);
+}
+
+// ---- deflate
+// The L4..9 parse runs two waves per stream (zs_k_parse_2w: 512-position
+// segments, two rounds' speculative passes at once) for a batch of n streams?
+// The whole batch decides (chunks of one batch share the scratch layout).
+static inline int zs_parse_waves_for(const zs_route_opts& o, uint32_t n) {
+  if (o.parse_waves) return o.parse_waves;
+  return n < ZS_PARSE2W_AUTO ? 2 : 1;
+}
+static inline uint32_t zs_parse_seg(int w) {
+  return w == 4 ? ZS_PARSE4W_SEG : w == 2 ? ZS_PARSE2W_SEG : ZS_PARSE_SEG;
+}
+static inline uint32_t zs_parse_seg_words(int w) {
+  return w == 4 ? ZS_PARSE4W_SEG_WORDS : w == 2 ? ZS_PARSE2W_SEG_WORDS : ZS_PARSE_SEG_WORDS;
+}
+
+// The workspace layout of a deflate batch (levels 1..9).  With the sweep (levels
+// 4..9, option match_sweep), every stream is cut into WINDOWS of at most 65,535
+// inserted positions: a stream of up to 65,537 bytes is one; a longer one has a
+// first window owning positions [0, 65520) and then windows owning 32,752
+// positions each after a 32,768-position look-back (more than MAX_DIST: every
+// candidate of an own position is in its window).
+struct zs_deflate_plan {
+  std::vector<uint64_t> pos;       // each stream's base in the per-position tables (8-aligned)
+  std::vector<uint32_t> blk;       // ... and in the block records
+  std::vector<zs_sweep_seg> segs;  // the sweep's windows (batch stream indices); empty without the sweep
+  std::vector<uint32_t> win0;      // each stream's first window (win0[n] = the total)
+  // Members: u16 per position for a stream of one window (pos); 65,536 per window after them for longer ones
+  uint64_t P = 0, members = 0;
+  uint32_t B = 0, max_len = 0, max_blk = 0;
+  int pw = 1;  // waves per stream of the parse (zs_k_parse / _2w / _4w)
+  size_t prevd_bytes = 0, mres_bytes = 0, syms_bytes = 0, pscr_bytes = 0, codes_bytes = 0, hdr_bytes = 0;
+};
+
+static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n, const uint32_t* in_len,
+                                   zs_deflate_plan& p) {
+  const bool sweep = level >= 4 && o.match_sweep;
+  p.pos.resize(n);
+  p.blk.resize(n);
+  p.P = 0;
+  p.B = p.max_len = p.max_blk = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    p.pos[i] = p.P;
+    p.P += ((uint64_t)in_len[i] + 7) & ~7ull;  // per-position tables start 8-aligned (16-B link loads in zs_k_match)
+    p.blk[i] = p.B;
+    const uint32_t nb = in_len[i] / ZS_SYM_END + 2;
+    p.B += nb;
+    p.max_len = std::max(p.max_len, in_len[i]);
+    p.max_blk = std::max(p.max_blk, nb);
+  }
+  p.segs.clear();
+  p.win0.clear();
+  p.members = 0;
+  if (sweep) {
+    uint64_t mb = (p.P + 7) & ~7ull;
+    p.win0.resize(n + 1);
+    for (uint32_t i = 0; i < n; i++) {
+      p.win0[i] = (uint32_t)p.segs.size();
+      const uint32_t len = in_len[i];
+      if (len <= 65537u) {
+        p.segs.push_back({i, 0u, 0u, len, p.pos[i], 0});
+        continue;
+      }
+      for (uint64_t lo = 0; lo < len; mb += 65536) {
+        const uint32_t base = lo == 0 ? 0u : (uint32_t)lo - 32768u;
+        p.segs.push_back({i, base, (uint32_t)lo - base, lo == 0 ? ZS_SEG_FIRST : 32768u + ZS_SEG_OWN, mb, 0});
+        lo += lo == 0 ? ZS_SEG_FIRST : ZS_SEG_OWN;
+      }
+    }
+    p.win0[n] = (uint32_t)p.segs.size();
+    p.members = mb;
+  }
+  p.pw = level >= 4 ? zs_parse_waves_for(o, n) : 1;
+  p.prevd_bytes = 2 * std::max(p.members, p.P) + 128;
+  p.mres_bytes = 8 * p.P + 64;
+  p.syms_bytes = 4 * (p.P + n) + 64;
+  p.pscr_bytes = level >= 4 ? 4ull * zs_parse_seg_words(p.pw) * (p.P / zs_parse_seg(p.pw) + n + 1) : 0;
+  p.codes_bytes = 4ull * (ZS_L_CODES + ZS_D_CODES) * p.B;
+  p.hdr_bytes = 4ull * ZS_HDR_WORDS * p.B;
+}
+
+#endif

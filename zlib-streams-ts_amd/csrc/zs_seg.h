@@ -6,10 +6,8 @@
 #include "zs_inflate.h"
 #include "zs_inftab.h"
 #include "zs_split.h"
+#include "zs_plan.h"  // ZS_SEG_LANES, _W, _PAD, _BIG_BITS, _SPLIT_BITS, _BLOCK_BITS, _SMAX
 
-#define ZS_SEG_LANES 64u    // pieces per span (one lane each)
-#define ZS_SEG_W 1024u      // bits of a lane's start window whose symbol starts it records (the sync bitmaps; 2048 in
-                            // the walk instance for batches of few large members: fewer chains that do not meet)
 #ifndef ZS_SEG_CKB
 // spacing of a lane's (position, output count) checkpoints in its window: 256 bits keeps the
 // 1,024-bit walk at 25 KB of LDS, six walks per CU instead of five (4,096 x 256 KiB decode 14.45 ->
@@ -18,13 +16,8 @@
 #endif
 #define ZS_SEG_NEV 4u       // sub-chunk crossing events a lane records
 #define ZS_SEG_NEOB 4u      // end-of-block codes a lane logs
-#define ZS_SEG_PAD 16u      // u16 values of padding behind each piece's scratch
 #define ZS_SEG_TAB (ENOUGH_LENS + ENOUGH_DISTS_9)  // cached table entries per block
 #define ZS_SEG_NONE 0xffffffffu
-#define ZS_SEG_BIG_BITS (1u << 21)  // members with more input bits: block starts from the finder as extra entries
-#define ZS_SEG_SPLIT_BITS (1u << 18)  // deflate64 members with more input bits: the split decode (long copies)
-#define ZS_SEG_BLOCK_BITS 16384u    // span slots per member: one per this many input bits (+ capi.cpp's margin)
-#define ZS_SEG_SMAX 8192u           // bits per lane at most (a span's lanes: seg_bits, then from the block before)
 
 // span flags
 #define ZS_SEG_B_OK 1u     // header parsed (FIRST), the span's pieces chain from its start to its end

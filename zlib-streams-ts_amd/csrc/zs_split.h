@@ -4,8 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zs_inflate.h"
+#include "zs_plan.h"  // ZS_SPLIT_MAX
 
-#define ZS_SPLIT_MAX 64u           // bit ranges searched per member (pieces <= this)
 #define ZS_SPLIT_MIN_SPAN 16384u   // bits per range at least (2 KiB of input)
 #define ZS_SPLIT_MARK_MAX 65280u   // markers: 255 + k for the byte k before the piece, k <= this
 #define ZS_SPLIT_BAIL 1u
