@@ -176,6 +176,63 @@ int zs_pool_inflate_batch_auto(zs_pool *pool, int wbits, uint32_t n_streams, con
                                int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
                                uint32_t *check);
 
+/* Decompression with preset dictionaries, raw deflate (-15) and zlib (15): each
+ * stream is decoded as if the driver of the z_stream functions called
+ * inflateSetDictionary(strm, dict, dict_len[i]) (inflate.ts:1220-1249) where
+ * zlib's contract calls for it -- for raw deflate right after inflateInit2_, for
+ * zlib when the first inflate() returns Z_NEED_DICT (FDICT set, inflate.ts:594-597),
+ * after which inflate() is called again with the same buffers.  The window keeps a
+ * dictionary's last 32,768 bytes (updatewindow, inflate.ts:282-324).
+ *
+ * The entries take the arguments of their counterparts above plus the
+ * dictionaries: stream i has the dict_len[i] bytes at dict + dict_off[i]
+ * (d_dict: device memory; dict: host memory).  dict_off / dict_len are host
+ * arrays of n_streams entries; entries may alias, so the whole batch can share
+ * one dictionary; a length of 0 means no dictionary; any byte offset is allowed.
+ *  - zlib, FDICT set, adler32(dictionary) != DICTID: ZS_DATA_ERROR, phase
+ *    ZS_PHASE_PROCESS, the empty message, no output (inflate.ts:1235-1241);
+ *  - zlib, FDICT set, dict_len[i] == 0: ZS_NEED_DICT, as the entries above;
+ *  - zlib, FDICT clear: inflateSetDictionary is never called, the dictionary is
+ *    ignored;
+ *  - a distance past dictionary plus output: "invalid distance too far back";
+ *  - check[i] (strm.adler after the stream): zlib the adler32 of the output only
+ *    (the check restarts after DICTID, inflate.ts:592), raw 0;
+ *  - gzip (31: never in DICT mode, inflate.ts:1229) and deflate64-raw (-16) with
+ *    any non-zero dict_len: the call returns ZS_STREAM_ERROR.
+ * (updatewindow indexes its source from end.length rather than from its length
+ * argument; this ABI passes (pointer, length), so dict.length == dictLength
+ * always and that quirk of the reference is unreachable.)  A call whose
+ * dict_len are all 0 is the counterpart's call. */
+/* inflate.ts:1220-1249, :594-597 -- device buffers (as zs_inflate_batch_device_ex) */
+int zs_inflate_batch_dict_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                 int32_t *d_phase, int32_t *d_msg, uint32_t *d_out_len, uint32_t *d_consumed,
+                                 uint32_t *d_check, void *hip_stream, const uint8_t *d_dict,
+                                 const uint64_t *dict_off, const uint32_t *dict_len);
+/* inflate.ts:1220-1249, :594-597 -- host buffers (as zs_inflate_batch_ex) */
+int zs_inflate_batch_dict(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                          const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                          int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
+                          uint32_t *check, const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len);
+/* inflate.ts:1220-1249, :594-597 -- unbounded output (as zs_inflate_batch_auto) */
+int zs_inflate_batch_dict_auto(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                               const uint32_t *in_len, uint8_t **out, uint64_t *out_off, int32_t *status,
+                               int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed, uint32_t *check,
+                               const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len);
+/* inflate.ts:1220-1249, :594-597 -- the pool (as zs_pool_inflate_batch) */
+int zs_pool_inflate_batch_dict(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                               const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                               const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
+                               uint32_t *out_len, uint32_t *consumed, uint32_t *check, const uint8_t *dict,
+                               const uint64_t *dict_off, const uint32_t *dict_len);
+/* inflate.ts:1220-1249, :594-597 -- the pool, unbounded output (as zs_pool_inflate_batch_auto) */
+int zs_pool_inflate_batch_dict_auto(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                                    const uint64_t *in_off, const uint32_t *in_len, uint8_t **out, uint64_t *out_off,
+                                    int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len,
+                                    uint32_t *consumed, uint32_t *check, const uint8_t *dict,
+                                    const uint64_t *dict_off, const uint32_t *dict_len);
+
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);
 

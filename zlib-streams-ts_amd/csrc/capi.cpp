@@ -20,6 +20,7 @@
 #include "zs_split.h"
 #include "zs_seg.h"
 #include "zs_plan.h"
+#include "zs_dict.h"
 
 
 namespace {
@@ -99,6 +100,8 @@ struct zs_ctx {
   hipStream_t side2 = nullptr;        // third: the split decode, beside the segmented decode
   hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
   Buf wlist;
+  Buf dadler, d_dict;  // preset dictionaries: the distinct ones' adler32; the host entries' staging of their bytes
+  zs_dict_set dset;
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
   bool seg_used = false;            // the last inflate batch ran the segmented decode (inflate_seg.hip)
@@ -1082,6 +1085,19 @@ static auto lane_kernel(int rt, bool refw) {
                  : rt == 1 ? zs_k_inflate_lane<1, false>
                            : zs_k_inflate_lane<0, false>);
 }
+// ... and of a batch with dictionaries: the lane launch over the whole batch
+static auto lane_kernel_dict(int rt) {
+  return rt == 2 ? zs_k_inflate_lane<2, false, true> : rt == 1 ? zs_k_inflate_lane<1, false, true>
+                                                               : zs_k_inflate_lane<0, false, true>;
+}
+
+// The preset dictionaries of a batch: the bytes in device memory, host arrays of
+// the members' offsets and lengths (length 0: none)
+struct DictIn {
+  const uint8_t* d_dict;
+  const uint64_t* off;
+  const uint32_t* len;
+};
 
 // The segmented decode of the members in c->ip.seg (inflate_seg.hip; h: the batch's
 // host arrays, b: its device arrays) on the side stream, after the caller's stream
@@ -1228,11 +1244,24 @@ static int split_launch(zs_ctx* c, hipStream_t st, int wbits, const Batch& b, zs
 // capacities with caller_regions = false.
 static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
                           uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
-                          bool caller_regions) {
+                          bool caller_regions, const DictIn* dict = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   // inflateInit2_ / inflateReset2 validation (inflate.ts:138-192) for the stream-layer formats
   if (!(wbits == -15 || wbits == 15 || wbits == 31 || wbits == -16))
     return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15, 31 or -16)");
+  // The members' dictionaries (dict: the _dict entries), the distinct ones found once.
+  // gzip is never in DICT mode (inflateSetDictionary returns Z_STREAM_ERROR, inflate.ts:1229);
+  // the 64 KiB window of deflate64 is not covered.
+  zs_dict_set& ds = c->dset;
+  ds.any = false;
+  if (dict && h.n) {
+    if (!dict->off || !dict->len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
+    zs_dict_distinct(h.n, dict->off, dict->len, ds);
+    if (ds.any && !dict->d_dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
+    if (ds.any && (wbits == 31 || wbits == -16))
+      return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
+  }
+  const bool hasdict = ds.any;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
   HIPCHK(hipSetDevice(c->device));
   const uint32_t n = h.n;
@@ -1245,8 +1274,14 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
       return fail(ZS_STREAM_ERROR, "output offsets/capacities must be multiples of 4");
   const bool fastp = c->o.inflate_fast;
   zs_inflate_plan& p = c->ip;
-  if (fastp) zs_plan_inflate(c->o, wbits, n, h.in_len, h.out_cap, p);
+  if (fastp) zs_plan_inflate(c->o, wbits, n, h.in_len, h.out_cap, p, hasdict ? dict->len : nullptr);
   const MetaLayout ml(n);
+  // behind the batch's metadata: the members' dictionary offsets, lengths and ids, the distinct ones' too
+  const size_t nu = hasdict ? ds.uoff.size() : 0;
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
+               m_uoff = m_did + up256(4ull * n), m_ulen = m_uoff + up256(8ull * nu),
+               m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
   HIPCHK(c->istate.ensure(sizeof(zs_inflate_result) * (size_t)n));
   if (fastp) {
     HIPCHK(c->ltabs.ensure(zs_inflate_lane_scratch_bytes() * (size_t)n));
@@ -1254,7 +1289,28 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     HIPCHK(c->llen.ensure(8ull * n));
   }
   Batch b;
-  if (int r = upload_batch(c, st, ml, ml.bytes, h, &b, [](uint8_t*) {})) return r;
+  if (int r = upload_batch(c, st, ml, m_end, h, &b, [&](uint8_t* hm) {
+        if (!hasdict) return;
+        memcpy(hm + m_doff, dict->off, 8ull * n);
+        memcpy(hm + m_dlen, dict->len, 4ull * n);
+        memcpy(hm + m_did, ds.id.data(), 4ull * n);
+        memcpy(hm + m_uoff, ds.uoff.data(), 8ull * nu);
+        memcpy(hm + m_ulen, ds.ulen.data(), 4ull * nu);
+      }))
+    return r;
+  zs_dict_args dd = {};
+  if (hasdict) {
+    HIPCHK(c->dadler.ensure(4ull * nu));
+    const uint8_t* dm = c->meta.as<uint8_t>();
+    dd = {dict->d_dict, (const uint64_t*)(dm + m_doff), (const uint32_t*)(dm + m_dlen), (const uint32_t*)(dm + m_did),
+          c->dadler.as<uint32_t>()};
+    // DICTID (zlib): the adler32 of each distinct dictionary, once
+    if (wbits == 15) {
+      zs_k_checksum<<<(uint32_t)nu, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + m_uoff),
+                                                 (const uint32_t*)(dm + m_ulen), c->dadler.as<uint32_t>(), 1);
+      HIPCHK(hipGetLastError());
+    }
+  }
   const size_t smem = zs_inflate_smem_bytes(wbits);
   HIPCHK(hipFuncSetAttribute((const void*)zs_k_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   zs_lane_res* const lres = fastp ? c->lres.as<zs_lane_res>() : nullptr;
@@ -1293,7 +1349,8 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
         auto lk2 = lane_kernel(p.wave_lane.rt, true);
         HIPCHK(hipFuncSetAttribute((const void*)lk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsm2));
         lk2<<<(nw + B2 - 1) / B2, B2, lsm2, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, nw, lt,
-                                                       lres, llen, ZS_INF_REF_WRAP, 0u, c->wlist.as<uint32_t>());
+                                                       lres, llen, ZS_INF_REF_WRAP, 0u, c->wlist.as<uint32_t>(),
+                                                       zs_dict_args{});
       } else {
         wave<<<nw, 64, wsm, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits,
                                        c->wlist.as<uint32_t>(), nw, lres, llen, nullptr);
@@ -1304,21 +1361,21 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     }
     const uint32_t B = p.lane.block;
     const size_t lsm = B * zs_inflate_lane_lds_bytes(p.lane.rt != 0);
-    auto lk = lane_kernel(p.lane.rt, false);
+    // (a batch with dictionaries: the dictionary instances, for every member of it)
+    auto lk = p.dict ? lane_kernel_dict(p.lane.rt) : lane_kernel(p.lane.rt, false);
     HIPCHK(hipFuncSetAttribute((const void*)lk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsm));
     lk<<<(n + B - 1) / B, B, lsm, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, n, lt, lres, llen,
-                                        lflags, p.wave_min, nullptr);
+                                        lflags, p.wave_min, nullptr, dd);
     MARK("inflate_lane");
     // Members the single-call instance bailed on whose cap allows more than one
     // inflate() call of the reference (more than 32 KiB of input, or output past
     // 64 KiB): re-run by the call-tracking instance, here, before the exact kernel
     if (c->o.inflate_ref_wrap && wbits != -16) {
       const size_t lsmr = 64 * zs_inflate_lane_lds_bytes(false);
-      HIPCHK(hipFuncSetAttribute((const void*)zs_k_inflate_lane<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lsmr));
-      zs_k_inflate_lane<0, true><<<(n + 63) / 64, 64, lsmr, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap,
-                                                                  wbits, n, lt, lres, llen, ZS_INF_REF_WRAP, p.wave_min,
-                                                                  nullptr);
+      auto lkr = p.dict ? zs_k_inflate_lane<0, true, true> : zs_k_inflate_lane<0, true>;
+      HIPCHK(hipFuncSetAttribute((const void*)lkr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsmr));
+      lkr<<<(n + 63) / 64, 64, lsmr, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, n, lt, lres,
+                                           llen, ZS_INF_REF_WRAP, p.wave_min, nullptr, dd);
       MARK("inflate_long");
     }
     if (p.wave_min) {
@@ -1334,7 +1391,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     }
   }
   zs_k_inflate<<<n, 64, smem, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits,
-                                    c->istate.as<zs_inflate_result>(), lres, lflags);
+                                    c->istate.as<zs_inflate_result>(), lres, lflags, dd);
   MARK("inflate");
   HIPCHK(c->lstat.ensure(16));
   if (!c->keep_counts) HIPCHK(hipMemsetAsync(c->lstat.p, 0, 4, st));
@@ -1397,5 +1454,56 @@ extern "C" int zs_inflate_batch_ex(zs_ctx* c, int wbits, uint32_t n, const uint8
                                              ooff, creq.data() + a},
                                             (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
                                             check ? dr[5] : nullptr, c->stream, false);
+                    });
+}
+
+// ---- preset dictionaries (inflateSetDictionary, inflate.ts:1220-1249; Z_NEED_DICT, inflate.ts:594-597)
+extern "C" int zs_inflate_batch_dict_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
+                                            const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                            const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                            int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
+                                            uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
+                                            const uint8_t* d_dict, const uint64_t* dict_off,
+                                            const uint32_t* dict_len) {
+  const DictIn di = {d_dict, dict_off, dict_len};
+  return inflate_device(c, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_phase, d_msg,
+                        d_out_len, d_consumed, d_check, hip_stream, true, &di);
+}
+
+extern "C" int zs_inflate_batch_dict(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                     const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                     const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                     uint32_t* out_len, uint32_t* consumed, uint32_t* check, const uint8_t* dict,
+                                     const uint64_t* dict_off, const uint32_t* dict_len) {
+  if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  if (!dict_off || !dict_len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them)
+  zs_dict_set ds;
+  zs_dict_distinct(n, dict_off, dict_len, ds);
+  if (ds.any && !dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
+  if (ds.any && (wbits == 31 || wbits == -16))
+    return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
+  std::vector<uint64_t> upos, poff;
+  const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict_len, upos, poff);
+  HIPCHK(c->d_dict.ensure(dbytes + 16));
+  if (dbytes) {
+    std::vector<uint8_t> pack(dbytes);
+    zs_dict_pack(ds, upos, dict, pack.data());
+    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
+  }
+  std::vector<uint32_t> ocap(n), creq(out_cap, out_cap + n);
+  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
+  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
+  return host_batch(c, n, in, in_off, in_len, ocap, 6, res, 3, out, out_off,
+                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
+                        uint32_t** dr) {
+                      const DictIn di = {c->d_dict.as<uint8_t>(), poff.data() + a, dict_len + a};
+                      return inflate_device(c, wbits,
+                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
+                                             ooff, creq.data() + a},
+                                            (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
+                                            check ? dr[5] : nullptr, c->stream, false, &di);
                     });
 }

@@ -97,6 +97,8 @@ struct zs_ist {
   int overflow;
   uint32_t total_in;
   uint32_t ib0;  // input index of ibuf[0]
+  const uint8_t* dict;  // the member's preset dictionary (dict_len = 0: none) and its adler32
+  uint32_t dict_len, dict_adler;
 };
 
 // input byte at absolute index i (i < n), staged 4 KiB at a time through LDS
@@ -189,6 +191,25 @@ static __device__ __forceinline__ void zs_copy(zs_ist& S, uint32_t dist, uint32_
     __builtin_amdgcn_wave_barrier();
   }
   S.total += len;
+}
+
+// inflateSetDictionary's updatewindow(strm, dictionary, dictLength)
+// (inflate.ts:1220-1249, 282-324) on a stream that has produced nothing: the
+// window keeps the dictionary's last w_size bytes, here as the history just
+// below the ring's first output byte, with w_have = min(L, w_size) and
+// w_next = L mod w_size.  (updatewindow indexes from end.length, not from its
+// length argument; the ABI passes (pointer, length), so the two are equal and
+// that quirk of the reference cannot arise.)
+static __device__ void zs_setdict(zs_ist& S) {
+  const uint32_t wsize = 1u << S.w_bits, dl = min(S.dict_len, wsize);
+  for (uint32_t k = threadIdx.x; k < dl; k += 64)
+    S.ring[(S.total - dl + k) & S.rmask] = S.dict[S.dict_len - dl + k];
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+  S.w_size = wsize;
+  S.w_have = dl;
+  S.w_next = dl == wsize ? 0 : dl;
+  S.havedict = 1;
 }
 
 static __device__ void zs_fixedtables(zs_lds& L, zs_ist& S) {  // inflate.ts:218-280
@@ -361,13 +382,19 @@ static __device__ int zs_inflate_call(zs_lds& L, zs_ist& S, uint32_t in0, uint32
         S.mode = DICT;
         [[fallthrough]];
       case DICT:
-        // no dictionary API through the stream layer: Z_NEED_DICT (inflate.ts:594-597)
-        S.hold = hold;
-        S.bits = bits;
-        *consumed = in_start - have;
-        *produced = out_start - left;
-        S.total_in += in_start - have;
-        return ZS_Z_NEED_DICT;
+        if (!S.havedict) {
+          // Z_NEED_DICT (inflate.ts:587-591): the kernel's driver sets the member's
+          // dictionary, if it has one, and calls again
+          S.hold = hold;
+          S.bits = bits;
+          *consumed = in_start - have;
+          *produced = out_start - left;
+          S.total_in += in_start - have;
+          return ZS_Z_NEED_DICT;
+        }
+        S.check = 1;  // the check restarts after DICTID (inflate.ts:592-593)
+        S.mode = TYPE;
+        [[fallthrough]];
       case TYPE:
       case TYPEDO:
         if (S.last) { BYTEBITS(); S.mode = CHECK; break; }
@@ -750,7 +777,8 @@ __global__ __launch_bounds__(64) void zs_k_inflate(const uint8_t* __restrict__ i
                                                    const uint64_t* __restrict__ out_off,
                                                    const uint32_t* __restrict__ out_cap, int wbits,
                                                    zs_inflate_result* __restrict__ res,
-                                                   const zs_lane_res* __restrict__ only, int flags) {
+                                                   const zs_lane_res* __restrict__ only, int flags,
+                                                   zs_dict_args dd) {
   zs_lds& L = *reinterpret_cast<zs_lds*>(zs_inflate_smem);
   const int s = blockIdx.x;
   if (only && only[s].bail == 0) return;  // decoded cleanly by the lane path
@@ -780,6 +808,9 @@ __global__ __launch_bounds__(64) void zs_k_inflate(const uint8_t* __restrict__ i
   S.overflow = 0;
   S.total_in = 0;
   S.ib0 = 0xf0000000u;
+  S.dict_len = dd.dict ? dd.len[s] : 0u;
+  S.dict = S.dict_len ? dd.dict + dd.off[s] : nullptr;
+  S.dict_adler = S.dict_len && S.wrap ? dd.adler[dd.id[s]] : 0u;
   for (uint32_t i = threadIdx.x; i < 256; i += 64) {
     uint32_t c = i;
     for (int k = 0; k < 8; k++) c = (c & 1) ? 0xedb88320u ^ (c >> 1) : c >> 1;
@@ -789,6 +820,8 @@ __global__ __launch_bounds__(64) void zs_k_inflate(const uint8_t* __restrict__ i
 
   int status = ZS_Z_STREAM_END, phase = ZS_PHASE_NONE_;
   bool ended = false;
+  // raw deflate: the dictionary is set right after inflateInit2_, before the first inflate()
+  if (S.dict_len && S.wrap == 0 && !S.d64) zs_setdict(S);
   // transform(): 32 KiB sub-chunks, inflate(Z_NO_FLUSH) while input remains (streams.ts:68-131)
   for (uint32_t off = 0; off < S.n && !ended && phase == ZS_PHASE_NONE_; off += IN_CHUNK) {
     uint32_t pos = off;
@@ -798,6 +831,13 @@ __global__ __launch_bounds__(64) void zs_k_inflate(const uint8_t* __restrict__ i
       const int r = zs_inflate_call(L, S, pos, end - pos, OUT_BUF, false, &used, &produced);
       pos += used;
       if (S.overflow) break;
+      if (r == ZS_Z_NEED_DICT && S.dict_len) {
+        // zlib, FDICT: inflateSetDictionary (Z_DATA_ERROR unless adler32(dict) is the
+        // header's DICTID, inflate.ts:1235-1241), then inflate() again with the same buffers
+        if (S.dict_adler != S.check) { status = ZS_Z_DATA_ERROR; phase = ZS_PHASE_PROCESS_; break; }
+        zs_setdict(S);
+        continue;
+      }
       if (r == ZS_Z_STREAM_END) { ended = true; break; }
       if (r != ZS_Z_OK) { status = r; phase = ZS_PHASE_PROCESS_; break; }
     }

@@ -377,7 +377,21 @@ extern "C" int zs_il_stats(unsigned long long* out) {
 // bookkeeping shares one scalar unit per CU among its waves).
 // RT: 0 no root tables (wide workgroups), 1 root tables, 2 root tables with
 // the canonical limits in LDS too (batches with large members beside them)
-template <int RT, bool REFW>
+// DICT: the instances of a batch in which members have preset dictionaries
+// (inflateSetDictionary, inflate.ts:1220-1249; zs_dict_args).  Bytes before a
+// member's start come from the tail of its dictionary: the last
+// dl = min(dict_len, 32768) bytes, what updatewindow (inflate.ts:282-324) keeps
+// in the window.  (updatewindow indexes its source from end.length, not from the
+// length argument: the two are equal for every caller of this engine, which
+// passes (pointer, length), so that quirk of the reference cannot arise.)  Only
+// single-call dictionary members (zs_inf_dict_single) decode here, in the
+// <., false, true> instances: the reference's one inflate() call then copies
+// from the window by inflate_fast's contiguous branches only
+// (inffast.ts:113-126,149-162), so the bytes are zlib's.  Every other dictionary
+// member bails at once (the exact kernel emulates its calls), the call-tracking
+// instance <., true, true> skips them, and members without a dictionary decode
+// in these instances exactly as in the plain ones.
+template <int RT, bool REFW, bool DICT>
 __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const uint8_t* __restrict__ in,
                                                         const uint64_t* __restrict__ in_off,
                                                         const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
@@ -385,7 +399,8 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
                                                         const uint32_t* __restrict__ out_cap, int wbits, uint32_t n_members,
                                                         zs_lane_tabs* __restrict__ tabs, zs_lane_res* __restrict__ res,
                                                         uint32_t* __restrict__ lens_out, int flags,
-                                                        uint32_t wave_min, const uint32_t* __restrict__ list) {
+                                                        uint32_t wave_min, const uint32_t* __restrict__ list,
+                                                        zs_dict_args dd) {
   extern __shared__ __attribute__((aligned(16))) uint8_t LL[];  // blockDim.x lanes' tables
   constexpr bool ROOT = RT > 0, LCAN = RT == 2;
   constexpr uint32_t lstride = ROOT ? sizeof(zs_lane_lds_root) : sizeof(zs_lane_lds);
@@ -401,8 +416,11 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
       (res[s].bail == 0 || out_cap[s] <= 65536u || zs_inf_large(in_len[s], out_cap[s], wave_min) ||
        in_len[s] >= (1u << 29)))
     return;
+  const uint32_t dlen = DICT ? dd.len[s] : 0u;  // the member's dictionary (0: none)
+  if (DICT && REFW && dlen) return;             // (its result stays the single-call instance's: bailed)
   // a large member: the REFW instance, zs_k_inflate_wave or the split path decodes it
-  if (!REFW && zs_inf_large(in_len[s], out_cap[s], wave_min)) return;
+  // (never a dictionary member: the plan lists none for those paths)
+  if (!REFW && !dlen && zs_inf_large(in_len[s], out_cap[s], wave_min)) return;
   zs_lane_tabs& T = tabs[s];
   zs_lane_lds& F = *reinterpret_cast<zs_lane_lds*>(LL + threadIdx.x * lstride);
   uint16_t* const lroot = ROOT ? reinterpret_cast<zs_lane_lds_root*>(&F)->lroot : nullptr;
@@ -457,6 +475,17 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
   zs_lane_res r = {1u, 0u, 0u, 0u};
   const int wrap = wbits < 0 ? 0 : (wbits >> 4) + 5;  // inflate.ts:152-160
   bool bail = ref_wrap && R.n > 32768u;  // several sub-chunks: the call-tracking instance
+  // DICT: the dictionary's tail that the window keeps, dl bytes, as the aligned
+  // words tw4[0..tlast] (the tail starts tsh bytes into the first)
+  uint32_t dl = min(dlen, 32768u), tsh = 0, tlast = 0;
+  const uint32_t* tw4 = nullptr;
+  if (DICT && dlen) {
+    if (!zs_inf_dict_single(R.n, out_cap[s])) bail = true;  // several calls: the exact kernel
+    const uint8_t* tp = dd.dict + dd.off[s] + (dlen - dl);
+    tsh = (uint32_t)((uintptr_t)tp & 3u);
+    tw4 = reinterpret_cast<const uint32_t*>(tp - tsh);
+    tlast = (tsh + dl - 1u) >> 2;
+  }
   // ---- wrapper header (inflate.ts:377-580): plain zlib / gzip headers only
   if (!bail && wrap) {
     const uint32_t b0 = zs_lr_take(R, 8), b1 = zs_lr_take(R, 8);
@@ -466,7 +495,18 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
       zs_lr_take(R, 16);  // XFL, OS
       if (cm != 8 || flg != 0) bail = true;  // FEXTRA / FNAME / FCOMMENT / FHCRC / reserved: exact path
     } else if (wrap & 1) {
-      if (((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (b1 & 0x20)) bail = true;
+      if (((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (!DICT && (b1 & 0x20))) bail = true;
+      if (DICT && !bail) {
+        if (b1 & 0x20) {
+          // FDICT: DICTID is the adler32 of the dictionary the driver then sets
+          // (inflate.ts:581-593,1220-1249); none given or another one: the exact
+          // kernel reports Z_NEED_DICT / Z_DATA_ERROR
+          const uint32_t id = __builtin_bswap32(zs_lr_take(R, 32));
+          if (!dlen || id != dd.adler[dd.id[s]]) bail = true;
+        } else {
+          dl = 0;  // inflateSetDictionary is never called: the dictionary is ignored
+        }
+      }
     } else {
       bail = true;  // "incorrect header check"
     }
@@ -613,6 +653,30 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
       here = zs_dist_entry(dsym, d64);
       op = C_OP(here);
       const uint32_t dist0 = C_VAL(here) + zs_lr_take(R, op & 15u);
+      if constexpr (DICT && !REFW) {
+        // a copy from before the member's start takes its first bytes from the
+        // dictionary's tail (it may end there, or cross into the output and then
+        // overlap itself): aligned words funnel-shifted into place, 16 bytes a
+        // round, as the far copy below reads HBM; the rest is a copy at the same
+        // distance from the output, whose first byte is now the member's first
+        if (dist0 > total) {
+          const uint32_t back = dist0 - total;
+          if (back > dl || total + len > cap) { bail = true; break; }  // too far back / capacity
+          const uint32_t at = tsh + dl - back, fsh = at & 3u, npre = min(len, back);
+          for (uint32_t i = 0; i < npre; i += 16) {
+            W.room();
+            uint32_t x[5], w[4];
+#pragma unroll
+            for (int k = 0; k < 5; k++) x[k] = IL_LD(tw4[min(((at + i) >> 2) + (uint32_t)k, tlast)]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = __builtin_amdgcn_alignbyte(x[k + 1], x[k], fsh);
+            W.put16(w, min(16u, npre - i));
+          }
+          total += npre;
+          len -= npre;
+          if (len == 0) continue;
+        }
+      }
       if (dist0 > total || total + len > cap) { bail = true; break; }  // too far back / capacity
       // REFW: a copy inflate_fast runs may end with the reference's window-wrap
       // copy -- its last `tail` bytes taken from the current call's first output
@@ -726,13 +790,19 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
 size_t zs_inflate_lane_scratch_bytes() { return sizeof(zs_lane_tabs); }
 size_t zs_inflate_lane_lds_bytes(bool root) { return root ? sizeof(zs_lane_lds_root) : sizeof(zs_lane_lds); }
 
-#define ZS_LANE_INST(R, W)                                                                                           \
-  template __global__ void zs_k_inflate_lane<R, W>(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,       \
-                                                   const uint64_t*, const uint32_t*, int, uint32_t, zs_lane_tabs*,    \
-                                                   zs_lane_res*, uint32_t*, int, uint32_t, const uint32_t*);
-ZS_LANE_INST(0, false)
-ZS_LANE_INST(1, false)
-ZS_LANE_INST(2, false)
-ZS_LANE_INST(0, true)
-ZS_LANE_INST(2, true)
+#define ZS_LANE_INST(R, W, D)                                                                                        \
+  template __global__ void zs_k_inflate_lane<R, W, D>(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,    \
+                                                      const uint64_t*, const uint32_t*, int, uint32_t, zs_lane_tabs*, \
+                                                      zs_lane_res*, uint32_t*, int, uint32_t, const uint32_t*,       \
+                                                      zs_dict_args);
+ZS_LANE_INST(0, false, false)
+ZS_LANE_INST(1, false, false)
+ZS_LANE_INST(2, false, false)
+ZS_LANE_INST(0, true, false)
+ZS_LANE_INST(2, true, false)
+// a batch with dictionaries: the lane launch and the call-tracking retry
+ZS_LANE_INST(0, false, true)
+ZS_LANE_INST(1, false, true)
+ZS_LANE_INST(2, false, true)
+ZS_LANE_INST(0, true, true)
 

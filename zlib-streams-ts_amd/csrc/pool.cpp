@@ -56,10 +56,23 @@ uint32_t first_cap(uint32_t in_len) {
 
 extern "C" void zs_free(void* p) { free(p); }
 
-extern "C" int zs_inflate_batch_auto(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                                     const uint32_t* in_len, uint8_t** out, uint64_t* out_off, int32_t* status,
-                                     int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed,
-                                     uint32_t* check) {
+// One bounded batch of the unbounded decode: with dictionaries when dict_off is given
+static int inflate_bounded(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                           const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                           int32_t* status, int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed,
+                           uint32_t* check, const uint8_t* dict, const uint64_t* dict_off, const uint32_t* dict_len) {
+  if (dict_off)
+    return zs_inflate_batch_dict(c, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, phase, msg, out_len,
+                                 consumed, check, dict, dict_off, dict_len);
+  return zs_inflate_batch_ex(c, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, phase, msg, out_len,
+                             consumed, check);
+}
+
+// zs_inflate_batch_auto, and zs_inflate_batch_dict_auto when dict_off is given
+static int inflate_auto(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                        const uint32_t* in_len, uint8_t** out, uint64_t* out_off, int32_t* status, int32_t* phase,
+                        int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* check, const uint8_t* dict,
+                        const uint64_t* dict_off, const uint32_t* dict_len) {
   if (!out || !out_off) return ZS_STREAM_ERROR;
   *out = nullptr;
   // pass buffers: pass 0 holds every member, later passes the retried ones
@@ -91,8 +104,8 @@ extern "C" int zs_inflate_batch_auto(zs_ctx* c, int wbits, uint32_t n, const uin
       slot[i] = i;
     }
     if (!p.alloc(o + 4)) return ZS_MEM_ERROR;
-    const int r = zs_inflate_batch_ex(c, wbits, n, in, in_off, in_len, p.buf.get(), p.off.data(), p.cap.data(),
-                                      status, phase, msg, out_len, consumed, check);
+    const int r = inflate_bounded(c, wbits, n, in, in_off, in_len, p.buf.get(), p.off.data(), p.cap.data(), status,
+                                  phase, msg, out_len, consumed, check, dict, dict_off, dict_len);
     if (r != ZS_OK) return r;
   }
   for (;;) {
@@ -110,17 +123,21 @@ extern "C" int zs_inflate_batch_auto(zs_ctx* c, int wbits, uint32_t n, const uin
     }
     if (nx.idx.empty()) break;
     const uint32_t m = (uint32_t)nx.idx.size();
-    std::vector<uint64_t> ioff(m);
-    std::vector<uint32_t> ilen(m), cons(m), olen(m), chk(m);
+    std::vector<uint64_t> ioff(m), doff(dict_off ? m : 0);
+    std::vector<uint32_t> ilen(m), cons(m), olen(m), chk(m), dlen(dict_off ? m : 0);
     std::vector<int32_t> st(m), ph(m), ms(m);
     for (uint32_t k = 0; k < m; k++) {
       ioff[k] = in_off[nx.idx[k]];
       ilen[k] = in_len[nx.idx[k]];
+      if (dict_off) {
+        doff[k] = dict_off[nx.idx[k]];
+        dlen[k] = dict_len[nx.idx[k]];
+      }
     }
     if (!nx.alloc(o + 4)) return ZS_MEM_ERROR;
-    const int r = zs_inflate_batch_ex(c, wbits, m, in, ioff.data(), ilen.data(), nx.buf.get(), nx.off.data(),
-                                      nx.cap.data(), st.data(), ph.data(), ms.data(), olen.data(), cons.data(),
-                                      check ? chk.data() : nullptr);
+    const int r = inflate_bounded(c, wbits, m, in, ioff.data(), ilen.data(), nx.buf.get(), nx.off.data(),
+                                  nx.cap.data(), st.data(), ph.data(), ms.data(), olen.data(), cons.data(),
+                                  check ? chk.data() : nullptr, dict, dict_off ? doff.data() : nullptr, dlen.data());
     if (r != ZS_OK) return r;
     for (uint32_t k = 0; k < m; k++) {
       const uint32_t i = nx.idx[k];
@@ -149,6 +166,28 @@ extern "C" int zs_inflate_batch_auto(zs_ctx* c, int wbits, uint32_t n, const uin
     }
   *out = res;
   return ZS_OK;
+}
+
+extern "C" int zs_inflate_batch_auto(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                     const uint32_t* in_len, uint8_t** out, uint64_t* out_off, int32_t* status,
+                                     int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed,
+                                     uint32_t* check) {
+  return inflate_auto(c, wbits, n, in, in_off, in_len, out, out_off, status, phase, msg, out_len, consumed, check,
+                      nullptr, nullptr, nullptr);
+}
+
+// with preset dictionaries (inflateSetDictionary, inflate.ts:1220-1249; Z_NEED_DICT, inflate.ts:594-597)
+extern "C" int zs_inflate_batch_dict_auto(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in,
+                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t** out,
+                                          uint64_t* out_off, int32_t* status, int32_t* phase, int32_t* msg,
+                                          uint32_t* out_len, uint32_t* consumed, uint32_t* check, const uint8_t* dict,
+                                          const uint64_t* dict_off, const uint32_t* dict_len) {
+  if (!dict_off || !dict_len) {
+    zs_set_last_error("null dictionary arrays");
+    return ZS_STREAM_ERROR;
+  }
+  return inflate_auto(c, wbits, n, in, in_off, in_len, out, out_off, status, phase, msg, out_len, consumed, check,
+                      dict, dict_off, dict_len);
 }
 
 // ------------------------------------------------------------------ pool
@@ -288,19 +327,21 @@ extern "C" int zs_pool_inflate_batch(zs_pool* p, int wbits, uint32_t n, const ui
   });
 }
 
-extern "C" int zs_pool_inflate_batch_auto(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,
-                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t** out,
-                                          uint64_t* out_off, int32_t* status, int32_t* phase, int32_t* msg,
-                                          uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+// zs_pool_inflate_batch_auto, and zs_pool_inflate_batch_dict_auto when dict_off is given
+static int pool_inflate_auto(zs_pool* p, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                             const uint32_t* in_len, uint8_t** out, uint64_t* out_off, int32_t* status,
+                             int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* check,
+                             const uint8_t* dict, const uint64_t* dict_off, const uint32_t* dict_len) {
   if (!out || !out_off) return ZS_STREAM_ERROR;
   *out = nullptr;
   const uint32_t G = p ? (uint32_t)p->ctx.size() : 0;
   std::vector<uint8_t*> part(G, nullptr);
   const int r = run_sharded(p, n, [&](uint32_t k, Shard s) {
     if (s.a == s.b) return (int)ZS_OK;
-    return zs_inflate_batch_auto(p->ctx[k], wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, &part[k],
-                                 out_off + s.a, status + s.a, phase + s.a, msg + s.a, out_len + s.a,
-                                 consumed + s.a, check ? check + s.a : nullptr);
+    return inflate_auto(p->ctx[k], wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, &part[k], out_off + s.a,
+                        status + s.a, phase + s.a, msg + s.a, out_len + s.a, consumed + s.a,
+                        check ? check + s.a : nullptr, dict, dict_off ? dict_off + s.a : nullptr,
+                        dict_off ? dict_len + s.a : nullptr);
   });
   if (r == ZS_OK) {  // one buffer: the shards' outputs back to back, offsets rebased
     uint64_t total = 0;
@@ -323,4 +364,47 @@ extern "C" int zs_pool_inflate_batch_auto(zs_pool* p, int wbits, uint32_t n, con
   }
   for (uint8_t* q : part) free(q);
   return r;
+}
+
+extern "C" int zs_pool_inflate_batch_auto(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,
+                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t** out,
+                                          uint64_t* out_off, int32_t* status, int32_t* phase, int32_t* msg,
+                                          uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+  return pool_inflate_auto(p, wbits, n, in, in_off, in_len, out, out_off, status, phase, msg, out_len, consumed, check,
+                           nullptr, nullptr, nullptr);
+}
+
+// The pool entries with preset dictionaries (inflateSetDictionary, inflate.ts:1220-1249; Z_NEED_DICT,
+// inflate.ts:594-597): every shard reads the caller's one dictionary buffer
+extern "C" int zs_pool_inflate_batch_dict(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,
+                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                          const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                          int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed,
+                                          uint32_t* check, const uint8_t* dict, const uint64_t* dict_off,
+                                          const uint32_t* dict_len) {
+  if (!dict_off || !dict_len) {
+    zs_set_last_error("null dictionary arrays");
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_inflate_batch_dict(p->ctx[k], wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, out, out_off + s.a,
+                                 out_cap + s.a, status + s.a, phase + s.a, msg + s.a, out_len + s.a,
+                                 consumed + s.a, check ? check + s.a : nullptr, dict, dict_off + s.a,
+                                 dict_len + s.a);
+  });
+}
+
+extern "C" int zs_pool_inflate_batch_dict_auto(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,
+                                               const uint64_t* in_off, const uint32_t* in_len, uint8_t** out,
+                                               uint64_t* out_off, int32_t* status, int32_t* phase, int32_t* msg,
+                                               uint32_t* out_len, uint32_t* consumed, uint32_t* check,
+                                               const uint8_t* dict, const uint64_t* dict_off,
+                                               const uint32_t* dict_len) {
+  if (!dict_off || !dict_len) {
+    zs_set_last_error("null dictionary arrays");
+    return ZS_STREAM_ERROR;
+  }
+  return pool_inflate_auto(p, wbits, n, in, in_off, in_len, out, out_off, status, phase, msg, out_len, consumed, check,
+                           dict, dict_off, dict_len);
 }

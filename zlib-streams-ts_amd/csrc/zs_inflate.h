@@ -52,15 +52,28 @@ struct zs_lane_res {
   uint32_t want;      // trailer check value (zlib: adler32, gzip: crc32)
 };
 
+// Preset dictionaries of a batch (inflateSetDictionary, inflate.ts:1220-1249), all
+// device memory: member s has the len[s] bytes at dict + off[s] (len[s] = 0: none;
+// members may share one), whose adler32 is adler[id[s]] (zlib members: compared
+// with the header's DICTID).  dict = nullptr: a batch without dictionaries.
+struct zs_dict_args {
+  const uint8_t* dict;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint32_t* id;
+  const uint32_t* adler;
+};
+
 __global__ void zs_k_inflate(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                              const uint64_t* out_off, const uint32_t* out_cap, int wbits, zs_inflate_result* res,
-                             const zs_lane_res* only, int flags);
+                             const zs_lane_res* only, int flags, zs_dict_args dd = {});
 struct zs_lane_tabs;
-template <int RT, bool REFW>
+// DICT: the instances of a batch with dictionaries (dd is read by them only)
+template <int RT, bool REFW, bool DICT = false>
 __global__ void zs_k_inflate_lane(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                   const uint64_t* out_off, const uint32_t* out_cap, int wbits, uint32_t n_members,
                                   zs_lane_tabs* tabs, zs_lane_res* res, uint32_t* lens_out, int flags,
-                                  uint32_t wave_min, const uint32_t* list);
+                                  uint32_t wave_min, const uint32_t* list, zs_dict_args dd = {});
 template <bool REFW>
 __global__ void zs_k_inflate_wave(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                   const uint64_t* out_off, const uint32_t* out_cap, int wbits, const uint32_t* list,

@@ -122,12 +122,27 @@ struct zs_inflate_plan {
   bool wave_refw = false;   // wave list: zs_k_inflate_wave<wave_refw> ...
   bool wave_lanes = false;  // ... or one lane each, zs_k_inflate_lane<wave_lane.rt, true>
   zs_lane_launch wave_lane;
+  // Members with a preset dictionary (dict_len[i] != 0), by their route: the single-call
+  // ones decode in the lane kernel's dictionary instances (zs_k_inflate_lane<.., .., true>,
+  // launched for the whole batch in place of the plain ones), the others in the exact kernel
+  std::vector<uint32_t> dict_lane, dict_exact;
+  bool dict = false;  // any: the dictionary instances
 };
 
+// A dictionary member the lane kernel decodes: one inflate() call of the reference
+// decodes it whole (one 32 KiB input sub-chunk, one 64 KiB output buffer,
+// streams.ts:6-7,78-93), so with the dictionary in the window (w_next = w_have, or 0
+// and a full window) inflate_fast takes only its contiguous window copies
+// (inffast.ts:113-126,149-162) and the bytes are zlib's.
+ZS_PLAN_FN bool zs_inf_dict_single(uint32_t in_len, uint32_t out_cap) {
+  return in_len <= 32768u && out_cap <= 65536u;
+}
+
 // Everything inflate_device decides about a batch with the fast path on
-// (options o, o.inflate_fast set).
+// (options o, o.inflate_fast set).  dict_len: the members' dictionary lengths, or
+// null for a batch without dictionaries.
 static inline void zs_plan_inflate(const zs_route_opts& o, int wbits, uint32_t n, const uint32_t* in_len,
-                                   const uint32_t* out_cap, zs_inflate_plan& p) {
+                                   const uint32_t* out_cap, zs_inflate_plan& p, const uint32_t* dict_len = nullptr) {
   // lane-per-member fast path; anything but a clean end of stream goes to the exact kernel.
   // A lane's decode is a dependent chain of loads, so the chip wants many
   // waves more than full ones: up to 16,384 members, thin workgroups (one
@@ -151,6 +166,13 @@ static inline void zs_plan_inflate(const zs_route_opts& o, int wbits, uint32_t n
   p.seg.clear();
   p.split.clear();
   p.wave.clear();
+  // Dictionary members never go to the segmented, split or wave decoders (none of them
+  // reads a dictionary): the dictionary lane instance or the exact kernel
+  p.dict_lane.clear();
+  p.dict_exact.clear();
+  for (uint32_t i = 0; dict_len && i < n; i++)
+    if (dict_len[i]) (zs_inf_dict_single(in_len[i], out_cap[i]) ? p.dict_lane : p.dict_exact).push_back(i);
+  p.dict = !p.dict_lane.empty() || !p.dict_exact.empty();
   // "Large" members decode beside the lane kernel.  With the segmented decode on,
   // a small batch's members are large from seg_small_min bytes on: one lane each
   // would leave most of the chip idle (the per-rank shards of the 8-GPU configs).
@@ -172,7 +194,7 @@ static inline void zs_plan_inflate(const zs_route_opts& o, int wbits, uint32_t n
     // bounded too (option seg_scratch_mb): members past it take the split / wave kernels
     uint64_t seg_bytes = 0;
     for (uint32_t i = 0; i < n; i++) {
-      if (!zs_inf_large(in_len[i], out_cap[i], big_min)) continue;
+      if (!zs_inf_large(in_len[i], out_cap[i], big_min) || (dict_len && dict_len[i])) continue;
       // (the segmented decode keeps bit positions in 32 bits; members with long
       // blocks or long copies -- large deflate64 ones, high expansions -- decode
       // faster with a wave per block / per member, which copies 64 bytes at a time)

@@ -18,6 +18,10 @@ export interface DecompressBatchOptions extends BatchOptions {
   /** Output cap per stream (bytes), one number for all or one per input.  Default: none -- the
    * output is unbounded, as DecompressionStream's; a stream over a given cap rejects. */
   outCapacity?: number | number[];
+  /** A preset dictionary ("deflate-raw" and "deflate"), as passed to inflateSetDictionary: one view
+   * shared by all inputs, or one per input (null = none).  A "deflate" input with FDICT and the wrong
+   * dictionary fails with "process error: -3", without one with "process error: 2". */
+  dictionary?: ArrayBufferView | (ArrayBufferView | null)[];
 }
 export type Settled<T> = { status: "fulfilled"; value: T } | { status: "rejected"; reason: Error & { zmsg?: string } };
 

@@ -49,6 +49,27 @@ function devicesOf(options) {
   return options.device === undefined ? 0 : options.device;
 }
 
+// options.dictionary of the decompress entries: a preset dictionary, as the z_stream
+// driver would pass to inflateSetDictionary (inflate.ts:1220-1249) -- for "deflate-raw"
+// before the first inflate(), for "deflate" when inflate() returns Z_NEED_DICT.  One
+// ArrayBufferView shared by all inputs, or an array with one per input (null = none).
+// Returns what the addon takes: undefined, or one Uint8Array | null per input.
+function dictionariesOf(options, n) {
+  const d = options.dictionary;
+  if (d === undefined || d === null) return undefined;
+  const view = (x) => {
+    if (x instanceof Uint8Array) return x;
+    if (ArrayBuffer.isView(x)) return new Uint8Array(x.buffer, x.byteOffset, x.byteLength);
+    throw new TypeError("dictionary must be an ArrayBufferView, or an array of ArrayBufferView | null, one per input");
+  };
+  if (Array.isArray(d)) {
+    if (d.length !== n) throw new TypeError("dictionary must be an ArrayBufferView, or an array with one entry per input");
+    return d.map((x) => (x === null || x === undefined ? null : view(x)));
+  }
+  const shared = view(d);
+  return new Array(n).fill(shared);
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
@@ -72,7 +93,9 @@ async function runDecompress(inputs, format, options) {
   const wbits = decompressWbits(format);
   const ins = checkInputs(inputs);
   // no outCapacity: unbounded output, as DecompressionStream (streams.ts:46,132-182); a caller cap is a cap
-  const res = await addon.decompressBatch(ins, wbits, options.outCapacity, devicesOf(options));
+  // (a dictionary for "gzip" / "deflate64-raw" rejects with code "-2": inflateSetDictionary's Z_STREAM_ERROR)
+  const res = await addon.decompressBatch(ins, wbits, options.outCapacity, devicesOf(options),
+                                          dictionariesOf(options, ins.length));
   return res.outputs.map((out, i) => {
     if (res.status[i] === Z_STREAM_END) return out;
     const err = streamError(res.status[i], res.phase[i]);
@@ -120,7 +143,9 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {
   options = options || {};
-  return addon.decompressBatch(checkInputs(inputs), decompressWbits(format), options.outCapacity, devicesOf(options));
+  const ins = checkInputs(inputs);
+  return addon.decompressBatch(ins, decompressWbits(format), options.outCapacity, devicesOf(options),
+                               dictionariesOf(options, ins.length));
 }
 export const engineVersion = () => addon.version();
 export const selfTest = (device = 0) => addon.selfTest(device);

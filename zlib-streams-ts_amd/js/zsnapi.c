@@ -204,6 +204,11 @@ typedef struct {
   uint32_t *in_len, *cap, *olen, *cons, *check;
   int32_t *status, *phase, *msg;
   uint8_t *base;       /* inputs: base + in_off[i] (the job's own copy) */
+  /* decompress with preset dictionaries (zs_pool_inflate_batch_dict*): the job's copy of the
+   * distinct ones, input i's at dict + dict_off[i], dict_len[i] bytes (0: none); NULL: none given */
+  uint8_t *dict;
+  uint64_t *dict_off;
+  uint32_t *dict_len;
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -214,6 +219,7 @@ static void job_free(job *j) {
   if (!j) return;
   free(j->in_off); free(j->out_off); free(j->in_len); free(j->cap); free(j->olen); free(j->cons); free(j->check);
   free(j->status); free(j->phase); free(j->msg); free(j->base);
+  free(j->dict); free(j->dict_off); free(j->dict_len);
   if (!j->out_given) {
     if (j->unbounded) zs_free(j->out);
     else free(j->out);
@@ -248,6 +254,14 @@ static void job_execute(napi_env env, void *data) {
   job *j = (job *)data;
   (void)env;
   if (j->n == 0) j->rc = ZS_OK;
+  else if (j->inflate && j->dict_off && j->unbounded)
+    j->rc = zs_pool_inflate_batch_dict_auto(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, &j->out,
+                                            j->out_off, j->status, j->phase, j->msg, j->olen, j->cons, j->check,
+                                            j->dict, j->dict_off, j->dict_len);
+  else if (j->inflate && j->dict_off)
+    j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
+                                       j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
+                                       j->dict_off, j->dict_len);
   else if (j->inflate && j->unbounded)
     j->rc = zs_pool_inflate_batch_auto(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, &j->out, j->out_off,
                                        j->status, j->phase, j->msg, j->olen, j->cons, j->check);
@@ -395,15 +409,84 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   return queue_job(env, j, "zs.compressBatch");
 }
 
-/* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices) ->
+/* The dictionaries of a decompress job: arr[i] a Uint8Array (input i's preset dictionary) or
+ * null / undefined (none).  Copied like the inputs; an object given for several inputs in a
+ * row (or among the last few distinct ones) is stored once.  0, -1 out of memory, -2 not views. */
+static int copy_dicts(napi_env env, job *j, napi_value arr) {
+  enum { RECENT = 16 };
+  uint32_t len = 0;
+  if (napi_get_array_length(env, arr, &len) != napi_ok || len != j->n) return -2;
+  j->dict_off = (uint64_t *)calloc(j->n + 1, 8);
+  j->dict_len = (uint32_t *)calloc(j->n + 1, 4);
+  view *v = (view *)calloc(j->n + 1, sizeof(view));
+  if (!j->dict_off || !j->dict_len || !v) {
+    free(v);
+    return -1;
+  }
+  view seen[RECENT];
+  uint64_t seen_off[RECENT], tot = 0;
+  uint32_t nseen = 0, next = 0;
+  int rc = 0;
+  for (int pass = 0; pass < 2 && rc == 0; pass++) {
+    /* pass 0: views, offsets, the total; pass 1: the copy */
+    if (pass == 1) {
+      j->dict = (uint8_t *)malloc(tot ? tot : 1);
+      if (!j->dict) rc = -1;
+    }
+    for (uint32_t i = 0; i < j->n && rc == 0; i++) {
+      if (pass == 1) {
+        if (v[i].n) memcpy(j->dict + j->dict_off[i], v[i].p, v[i].n);
+        continue;
+      }
+      napi_value e;
+      napi_valuetype t;
+      if (napi_get_element(env, arr, i, &e) != napi_ok || napi_typeof(env, e, &t) != napi_ok) { rc = -2; break; }
+      if (t == napi_undefined || t == napi_null) continue;
+      bool is_ta = false;
+      napi_typedarray_type tt;
+      size_t n = 0, off = 0;
+      void *data = NULL;
+      napi_value ab;
+      if (napi_is_typedarray(env, e, &is_ta) != napi_ok || !is_ta ||
+          napi_get_typedarray_info(env, e, &tt, &n, &data, &ab, &off) != napi_ok || tt != napi_uint8_array ||
+          n > 0xffffffffull) {
+        rc = -2;
+        break;
+      }
+      if (!n) continue;
+      v[i].p = (const uint8_t *)data;
+      v[i].n = n;
+      j->dict_len[i] = (uint32_t)n;
+      uint32_t k = 0;
+      while (k < nseen && !(seen[k].p == v[i].p && seen[k].n == n)) k++;
+      if (k < nseen) {
+        j->dict_off[i] = seen_off[k];
+        v[i].n = 0; /* (stored already: nothing to copy) */
+      } else {
+        j->dict_off[i] = tot;
+        seen[next % RECENT] = v[i]; /* (once full, the oldest slot is reused) */
+        seen_off[next % RECENT] = tot;
+        next++;
+        if (nseen < RECENT) nseen++;
+        tot += n;
+      }
+    }
+  }
+  free(v);
+  return rc;
+}
+
+/* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,
+ *                 dictionaries: (Uint8Array | null)[] | undefined) ->
  *   Promise<{status, phase: Int32Array, message: string[], outputs: Uint8Array[], consumed: Int32Array,
  *            check: Uint32Array}>
  * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto). */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 5;
+  napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 2) return throw_code(env, ZS_STREAM_ERROR, "decompressBatch(inputs, wbits[, outCapacity[, devices]])");
+  if (argc < 2)
+    return throw_code(env, ZS_STREAM_ERROR, "decompressBatch(inputs, wbits[, outCapacity[, devices[, dictionaries]]])");
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -444,6 +527,18 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
     return throw_code(env, ZS_MEM_ERROR, "out of host memory");
   }
   free(v);
+  napi_valuetype dt = napi_undefined;
+  if (argc > 4) napi_typeof(env, argv[4], &dt);
+  if (dt != napi_undefined && dt != napi_null) {
+    bool is_arr = false;
+    napi_is_array(env, argv[4], &is_arr);
+    const int rc = is_arr ? copy_dicts(env, j, argv[4]) : -2;
+    if (rc != 0) {
+      job_free(j);
+      return rc == -1 ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
+                      : throw_code(env, ZS_STREAM_ERROR, "dictionaries must be (Uint8Array | null)[], one per input");
+    }
+  }
   return queue_job(env, j, "zs.decompressBatch");
 }
 

@@ -102,6 +102,12 @@ def lib():
     _inf_res = [_I32P, _I32P, _I32P, _U32P, _U32P, _U32P]
     L.zs_inflate_batch_ex.argtypes = [_P] + _inf_host + [_P, _U64P, _U32P] + _inf_res
     L.zs_inflate_batch_auto.argtypes = [_P] + _inf_host + [ctypes.POINTER(_P), _U64P] + _inf_res
+    _dict = [ctypes.c_char_p, _U64P, _U32P]
+    if hasattr(L, "zs_inflate_batch_dict"):  # (ZS_LIB may name an older build)
+        L.zs_inflate_batch_dict.argtypes = L.zs_inflate_batch_ex.argtypes + _dict
+        L.zs_inflate_batch_dict_auto.argtypes = L.zs_inflate_batch_auto.argtypes + _dict
+        L.zs_inflate_batch_dict_device.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, _P, _U64P, _U32P, _P, _U64P,
+                                                   _U32P, _P, _P, _P, _P, _P, _P, _P, _P, _U64P, _U32P]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -111,6 +117,9 @@ def lib():
     L.zs_pool_deflate_batch.argtypes = L.zs_deflate_batch_ex.argtypes
     L.zs_pool_inflate_batch.argtypes = L.zs_inflate_batch_ex.argtypes
     L.zs_pool_inflate_batch_auto.argtypes = L.zs_inflate_batch_auto.argtypes
+    if hasattr(L, "zs_pool_inflate_batch_dict"):
+        L.zs_pool_inflate_batch_dict.argtypes = L.zs_inflate_batch_dict.argtypes
+        L.zs_pool_inflate_batch_dict_auto.argtypes = L.zs_inflate_batch_dict_auto.argtypes
     if hasattr(L, "zs_inflate_batch"):
         L.zs_inflate_batch.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, ctypes.c_char_p, _U64P, _U32P, _P, _U64P,
                                        _U32P, _I32P, _I32P, _I32P, _U32P, _U32P]
@@ -257,22 +266,29 @@ class Engine:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                             out_caps: Optional[Sequence[int]] = None):
+                             out_caps: Optional[Sequence[int]] = None, zdict=None):
         """Returns [(status, phase, msg, bytes, consumed)].  out_caps None: unbounded
-        output, as DecompressionStream (zs_inflate_batch_auto); else per-stream caps."""
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps)]
+        output, as DecompressionStream (zs_inflate_batch_auto); else per-stream caps.
+        zdict: a preset dictionary for every input (bytes), or one per input (a
+        list; None = none) -- "deflate-raw" and "deflate" only (zs_inflate_batch_dict*)."""
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                                  out_caps: Optional[Sequence[int]] = None):
+                                  out_caps: Optional[Sequence[int]] = None, zdict=None):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
+        if zdict is not None:
+            d = _dict_layout(zdict, len(inputs))
+            if out_caps is None:
+                return _inflate_host_auto(L, L.zs_inflate_batch_dict_auto, self._ctx, inputs, fmt, self._check, d)
+            return _inflate_host(L, L.zs_inflate_batch_dict, self._ctx, inputs, fmt, out_caps, self._check, d)
         if out_caps is None:
             return _inflate_host_auto(L, L.zs_inflate_batch_auto, self._ctx, inputs, fmt, self._check)
         return _inflate_host(L, L.zs_inflate_batch_ex, self._ctx, inputs, fmt, out_caps, self._check)
 
     def decompress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                         out_caps: Optional[Sequence[int]] = None) -> List[bytes]:
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps))
+                         out_caps: Optional[Sequence[int]] = None, zdict=None) -> List[bytes]:
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict))
 
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
@@ -286,7 +302,18 @@ class Engine:
 
     def decompress_device(self, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                           d_status: int, d_phase: int, d_msg: int, d_out_len: int, d_consumed: int,
-                          hip_stream: int = 0):
+                          hip_stream: int = 0, d_dict: int = 0, dict_off=None, dict_len=None, d_check: int = 0):
+        """d_dict / dict_off / dict_len: preset dictionaries (zs_inflate_batch_dict_device:
+        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none)."""
+        if dict_off is not None:
+            r = self._L.zs_inflate_batch_dict_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
+                                                     _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase),
+                                                     _P(d_msg), _P(d_out_len), _P(d_consumed),
+                                                     _P(d_check) if d_check else None,
+                                                     _P(hip_stream) if hip_stream else None,
+                                                     _P(d_dict) if d_dict else None, dict_off, dict_len)
+            self._check(r, "zs_inflate_batch_dict_device")
+            return
         r = self._L.zs_inflate_batch_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len, _P(d_out),
                                             out_off, out_cap, _P(d_status), _P(d_phase), _P(d_msg), _P(d_out_len),
                                             _P(d_consumed), _P(hip_stream) if hip_stream else None)
@@ -374,7 +401,27 @@ def _inflate_results(L, n, raw, ooffs, status, phase, msg, olen, cons, chk):
              chk[i]) for i in range(n)]
 
 
-def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check):
+def _dict_layout(zdict, n):
+    """(blob, offsets, lengths) of the inputs' preset dictionaries: one bytes-like for
+    all of them, or a sequence with one per input (None / empty = none); equal
+    objects are stored once."""
+    if isinstance(zdict, (bytes, bytearray, memoryview)):
+        zdict = [zdict] * n
+    if len(zdict) != n:
+        raise ValueError("zdict: %d dictionaries for %d inputs" % (len(zdict), n))
+    parts, at, offs, lens, o = [], {}, [], [], 0
+    for d in zdict:
+        d = b"" if d is None else bytes(d)
+        if d and d not in at:
+            at[d] = o
+            parts.append(d)
+            o += len(d)
+        offs.append(at[d] if d else 0)
+        lens.append(len(d))
+    return [b"".join(parts), _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens)]
+
+
+def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check, zdict=()):
     n = len(inputs)
     if n == 0:
         return []
@@ -389,12 +436,12 @@ def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check):
     out = ctypes.create_string_buffer(max(1, oo))
     res = [(ctypes.c_int32 * n)() for _ in range(3)] + [(ctypes.c_uint32 * n)() for _ in range(3)]
     r = fn(handle, decompress_wbits(fmt), n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens), out,
-           _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), *res)
+           _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), *res, *zdict)
     check(r, "inflate batch")
     return _inflate_results(L, n, out.raw, ooffs, *res)
 
 
-def _inflate_host_auto(L, fn, handle, inputs, fmt, check):
+def _inflate_host_auto(L, fn, handle, inputs, fmt, check, zdict=()):
     n = len(inputs)
     if n == 0:
         return []
@@ -403,7 +450,7 @@ def _inflate_host_auto(L, fn, handle, inputs, fmt, check):
     ooffs = (ctypes.c_uint64 * n)()
     outp = _P()
     r = fn(handle, decompress_wbits(fmt), n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
-           ctypes.byref(outp), ooffs, *res)
+           ctypes.byref(outp), ooffs, *res, *zdict)
     check(r, "inflate batch")
     try:
         olen = res[3]
@@ -484,17 +531,22 @@ class Pool:
     def compress_batch(self, inputs, fmt="deflate-raw", level=-1):
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level))
 
-    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None):
+    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
         L = self._L
+        if zdict is not None:
+            d = _dict_layout(zdict, len(inputs))
+            if out_caps is None:
+                return _inflate_host_auto(L, L.zs_pool_inflate_batch_dict_auto, self._pool, inputs, fmt, self._check, d)
+            return _inflate_host(L, L.zs_pool_inflate_batch_dict, self._pool, inputs, fmt, out_caps, self._check, d)
         if out_caps is None:
             return _inflate_host_auto(L, L.zs_pool_inflate_batch_auto, self._pool, inputs, fmt, self._check)
         return _inflate_host(L, L.zs_pool_inflate_batch, self._pool, inputs, fmt, out_caps, self._check)
 
-    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None):
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps)]
+    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict)]
 
-    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None):
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps))
+    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict))
 
 
 _default: Optional[Engine] = None
