@@ -4,6 +4,7 @@
 #include "zs_common.h"
 #include "zs_inflate.h"
 #include "zs_inftab.h"
+#include "zs_lane_reader.h"
 #include "zs_refcalls.h"
 #ifndef ZS_OPAQUE  // (the host stand-in of tools/lane_host defines these away)
 #define ZS_OPAQUE(x) asm("" : "+v"(x))
@@ -39,55 +40,6 @@ extern "C" int zs_il_member_cycles(unsigned long long* out, int n) {
 struct zs_lane_tabs {
   uint16_t lens[320];  // the block's code lengths (lit/len then distance; the header's code-length code first)
 };
-
-struct zs_lane_reader {
-  const uint32_t* w4;  // the aligned words holding the member's bytes
-  uint32_t sh, last;   // the member's offset in its first word; index of the word holding its last byte
-  uint32_t n, pos;  // bytes moved into hold so far
-  uint64_t hold;
-  uint32_t bits;
-  uint32_t pf;      // input bytes [pos, pos + 4), loaded one refill ahead (zero past the end)
-};
-
-// input bytes [at, at + 4), zero past the end: two aligned word loads with
-// clamped indices and a funnel shift -- no branch, so the load stays in flight
-// until the refill that uses it (a branch per byte made the compiler wait on
-// each byte in turn)
-static __device__ __forceinline__ uint32_t zs_lr_load4(const zs_lane_reader& R, uint32_t at) {
-  const uint32_t q = (at + R.sh) >> 2;
-  const uint32_t lo = R.w4[min(q, R.last)], hi = R.w4[min(q + 1u, R.last)];
-  const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, R.sh);
-  const uint32_t valid = at < R.n ? R.n - at : 0u;
-  return valid >= 4u ? v : v & ((1u << (8u * valid)) - 1u);
-}
-// bits < 32 -> bits >= 32: the prefetched word enters hold and the next one is
-// requested, so its latency overlaps the decoding of the bits just added
-static __device__ __forceinline__ void zs_lr_fill(zs_lane_reader& R) {
-  R.hold |= (uint64_t)R.pf << R.bits;
-  R.bits += 32;
-  R.pos += 4;
-  R.pf = zs_lr_load4(R, R.pos);
-}
-// bits consumed so far
-static __device__ __forceinline__ uint64_t zs_lr_bitpos(const zs_lane_reader& R) {
-  return (uint64_t)R.pos * 8u - R.bits;
-}
-// consumed bits beyond the input: a truncated stream (the exact path reports it)
-static __device__ __forceinline__ bool zs_lr_over(const zs_lane_reader& R) {
-  return zs_lr_bitpos(R) > (uint64_t)R.n * 8u;
-}
-static __device__ __forceinline__ uint32_t zs_lr_take(zs_lane_reader& R, uint32_t k) {  // k <= 32
-  if (R.bits < k) zs_lr_fill(R);
-  const uint32_t v = (uint32_t)R.hold & (k == 32 ? 0xffffffffu : ((1u << k) - 1));
-  R.hold >>= k;
-  R.bits -= k;
-  return v;
-}
-static __device__ __forceinline__ void zs_lr_align(zs_lane_reader& R) {
-  const uint32_t d = R.bits & 7u;
-  R.hold >>= d;
-  R.bits -= d;
-}
 
 // Canonical Huffman decoding (RFC 1951 3.2.2) with the code's shape in
 // registers.  lim[l-1] is the end of the length-l codes left-justified to 15
@@ -233,10 +185,6 @@ template <bool LDS>
 static __device__ __forceinline__ uint32_t zs_canon_rank_t(const zs_canon& C, const zs_lane_reader& R, uint32_t& L) {
   if constexpr (LDS) return zs_canon_rank_lds(C, R, L);
   else return zs_canon_rank(C, R, L);
-}
-static __device__ __forceinline__ void zs_lr_drop(zs_lane_reader& R, uint32_t k) {
-  R.hold >>= k;
-  R.bits -= k;
 }
 
 // a root-table symbol as the zlib table entry the decoder consumes (zs_lbase /
@@ -429,18 +377,12 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
   if (s < 65536) zs_il_mcyc[2 * s] = wall_clock64();
 #endif
   zs_lane_reader R;
-  {
-    const uint8_t* src = in + in_off[s];
-    R.n = in_len[s];
-    R.sh = (uint32_t)((uintptr_t)src & 3u);
-    // an empty member reads (and masks off) a word of in_len[] instead: its own address may be past the buffer
-    R.w4 = R.n ? reinterpret_cast<const uint32_t*>(src - R.sh) : in_len;
-    R.last = R.n ? (R.sh + R.n - 1u) >> 2 : 0u;
+  zs_lr_init(R, in + in_off[s], in_len[s]);
+  if (!R.n) {  // an empty member reads (and masks off) a word of in_len[] instead: its own address may be past the buffer
+    R.w4 = in_len;
+    R.last = 0;
   }
-  R.pos = 0;
-  R.hold = 0;
-  R.bits = 0;
-  R.pf = zs_lr_load4(R, 0);
+  zs_lr_rewind(R, 0);
 #if ZS_IL_EXP & 64
   unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long tk0 = clock64();
@@ -608,7 +550,7 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
       st[1] += IL_FIRST();  // wave steps (summed)
 #endif
       uint32_t L, k, sym;
-      const uint32_t b0 = REFW ? R.pos * 8u - R.bits : 0u;  // the symbol's first bit (zs_refcalls)
+      const uint32_t b0 = REFW ? zs_lr_bitpos32(R) : 0u;  // the symbol's first bit (zs_refcalls)
       const uint32_t le = ROOT ? lroot[(uint32_t)R.hold & ((1u << ZS_LROOT) - 1u)] : 0u;
       if (le) {
         L = le >> 12;

@@ -27,7 +27,8 @@
 //  zs_k_split_find  (members over ZS_SEG_BIG_BITS only) candidate block starts,
 //                   one per bit range (inflate_split.hip)
 //  zs_k_seg_walk    one wave per entry (a member's start; a big member's found
-//                   block starts): block after block, header and tables, then
+//                   block starts): block after block, header and tables
+//                   (zs_wr_block_header, zs_wave.h, with the wave-built tables), then
 //                   spans of 64 lanes, lane j decoding from bit sym0 + j S and
 //                   recording the symbol starts of its first ZS_SEG_W bits; it
 //                   stops at the first of its positions (past the next lane's
@@ -51,6 +52,7 @@
 #include "zs_common.h"
 #include "zs_inflate.h"
 #include "zs_inftab.h"
+#include "zs_lane_reader.h"
 #include "zs_wave.h"
 #include "zs_refcalls.h"
 #include "zs_seg.h"
@@ -70,75 +72,13 @@ extern "C" int zs_seg_wdbg_fetch(void* out, unsigned long long bytes) {
 }
 #endif
 
-#if ZS_SEG_EXP & 16
-// header sub-phases, summed over all headers: code-length table, code-length decode, lit/len table, dist table, headers
-__device__ unsigned long long zs_seg_hdbg[8];
-extern "C" int zs_seg_hdbg_fetch(void* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(zs_seg_hdbg), sizeof(zs_seg_hdbg));
-}
-#define HD_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define HD_ADD(i, a, b) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&zs_seg_hdbg[i], (b) - (a)); } while (0)
-#else
-#define HD_T(v) do { } while (0)
-#define HD_ADD(i, a, b) do { } while (0)
-#endif
+// ------------------------------------------------------------- lane decode
+// One lane's symbols, on the lane bit reader (zs_lane_reader.h) started at any
+// bit; member bit positions fit 32 bits (the host sends members under 512 MB here).
 
-// ------------------------------------------------------------- lane reader
-// One lane's bit reader (the lane kernel's scheme: clamped aligned words, one
-// refill ahead, zero past the end), started at any bit; member bit positions
-// fit 32 bits (the host sends members under 512 MB here).
-struct zs_sg_reader {
-  const uint32_t* w4;
-  uint32_t sh, last, n;
-  uint32_t pos;  // bytes moved into hold (a multiple of 4)
-  uint64_t hold;
-  uint32_t bits;
-  uint32_t pf;
-};
-static __device__ __forceinline__ uint32_t zs_sg_load4(const zs_sg_reader& R, uint32_t at) {
-#if ZS_SEG_EXP & 4  // (timing: input words made up in registers instead of loaded -- garbage decodes)
-  return at * 2654435761u;
-#endif
-  const uint32_t q = (at + R.sh) >> 2;
-  const uint32_t lo = R.w4[min(q, R.last)], hi = R.w4[min(q + 1u, R.last)];
-  const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, R.sh);
-  const uint32_t valid = at < R.n ? R.n - at : 0u;
-  return valid >= 4u ? v : v & ((1u << (8u * valid)) - 1u);
-}
-static __device__ __forceinline__ void zs_sg_fill(zs_sg_reader& R) {
-  R.hold |= (uint64_t)R.pf << R.bits;
-  R.bits += 32;
-  R.pos += 4;
-  R.pf = zs_sg_load4(R, R.pos);
-}
-static __device__ __forceinline__ void zs_sg_drop(zs_sg_reader& R, uint32_t k) {
-  R.hold >>= k;
-  R.bits -= k;
-}
-static __device__ __forceinline__ void zs_sg_seek(zs_sg_reader& R, uint32_t bit) {
-  R.pos = (bit >> 5) << 2;
-  R.hold = 0;
-  R.bits = 0;
-  R.pf = zs_sg_load4(R, R.pos);
-  zs_sg_fill(R);
-  zs_sg_drop(R, bit & 31u);
-}
-static __device__ __forceinline__ uint32_t zs_sg_bitpos(const zs_sg_reader& R) { return R.pos * 8u - R.bits; }
-static __device__ __forceinline__ uint32_t zs_sg_take(zs_sg_reader& R, uint32_t k) {  // k <= 32
-  if (R.bits < k) zs_sg_fill(R);
-  const uint32_t v = (uint32_t)R.hold & (k == 32 ? 0xffffffffu : ((1u << k) - 1u));
-  zs_sg_drop(R, k);
-  return v;
-}
-static __device__ __forceinline__ void zs_sg_init(zs_sg_reader& R, const uint8_t* src, uint32_t n) {
-  R.n = n;
-  R.sh = (uint32_t)((uintptr_t)src & 3u);
-  R.w4 = reinterpret_cast<const uint32_t*>(src - R.sh);
-  R.last = (R.sh + n - 1u) >> 2;
-}
 // a code from a zlib table (second level included); nb: its bits
 template <typename TT>
-static __device__ __forceinline__ zcode zs_sg_code(zs_sg_reader& R, const TT& t, uint32_t mask, uint32_t& nb) {
+static __device__ __forceinline__ zcode zs_sg_code(zs_lane_reader& R, const TT& t, uint32_t mask, uint32_t& nb) {
   zcode here = t[(uint32_t)R.hold & mask];
   uint32_t b = C_BITS(here);
   if (C_OP(here) && (C_OP(here) & 0xf0) == 0) {
@@ -146,7 +86,7 @@ static __device__ __forceinline__ zcode zs_sg_code(zs_sg_reader& R, const TT& t,
     here = t[C_VAL(here) + (((uint32_t)R.hold & ((1u << (rb + C_OP(here))) - 1u)) >> rb)];
     b = rb + C_BITS(here);
   }
-  zs_sg_drop(R, b);
+  zs_lr_drop(R, b);
   nb = b;
   return here;
 }
@@ -160,10 +100,10 @@ struct zs_sg_sym {
   uint32_t l1, e1, l2, e2;  // the bit fields (zs_refcalls)
 };
 template <typename TD>
-static __device__ __forceinline__ zs_sg_sym zs_sg_decode(zs_sg_reader& R, const zcode* lt, uint32_t lmask,
+static __device__ __forceinline__ zs_sg_sym zs_sg_decode(zs_lane_reader& R, const zcode* lt, uint32_t lmask,
                                                         const TD& dt, uint32_t dmask, uint32_t emask) {
   zs_sg_sym y = {ZS_SG_BAD, 0u, 0u, 0u, 0u, 0u, 0u};
-  if (R.bits < 32) zs_sg_fill(R);
+  if (R.bits < 32) zs_lr_fill(R);
   zcode here = zs_sg_code(R, lt, lmask, y.l1);
   uint32_t op = C_OP(here);
   if (op == 0) {
@@ -178,121 +118,15 @@ static __device__ __forceinline__ zs_sg_sym zs_sg_decode(zs_sg_reader& R, const 
   }
   if (op & 64) return y;  // "invalid literal/length code"
   y.e1 = op & emask;
-  y.len = C_VAL(here) + zs_sg_take(R, y.e1);
-  if (R.bits < 32) zs_sg_fill(R);
+  y.len = C_VAL(here) + zs_lr_take(R, y.e1);
+  if (R.bits < 32) zs_lr_fill(R);
   here = zs_sg_code(R, dt, dmask, y.l2);
   op = C_OP(here);
   if (op & 64) return y;  // "invalid distance code"
   y.e2 = op & 15u;
-  y.val = C_VAL(here) + zs_sg_take(R, y.e2);
+  y.val = C_VAL(here) + zs_lr_take(R, y.e2);
   y.kind = ZS_SG_COPY;
   return y;
-}
-
-// The block header at the wave reader's position (inflate.ts:600-836) into
-// zlib's tables (inflate_table) in LDS, as zs_k_inflate_wave; a stored block's
-// length (inflate.ts:631-672: LEN and NLEN at the next byte boundary, the reader
-// left at its first byte) in slen, else ZS_SEG_NONE; false for anything invalid
-// (the member then takes the other paths).
-static __device__ bool zs_sg_header(zs_wave_reader& R, zcode* codes, uint16_t* lens, uint16_t* work, bool d64,
-                                    uint32_t& last, uint32_t& lbits, uint32_t& dbits, uint32_t& dofs,
-                                    uint32_t& ntab, uint32_t& slen) {
-  last = zs_wr_take(R, 1);
-  const uint32_t type = zs_wr_take(R, 2);
-  uint32_t lused = 0, dused = 0;
-  slen = ZS_SEG_NONE;
-  if (type == 0) {
-    zs_wr_align(R);
-    const uint32_t len = zs_wr_take(R, 16), nlen = zs_wr_take(R, 16);
-    if (len != (nlen ^ 0xffffu) || zs_wr_over(R)) return false;  // "invalid stored block lengths", or past the input
-    slen = len;
-    return true;
-  }
-  if (type == 1) {  // fixed tables (inflate.ts:218-280)
-    uint32_t sym;
-    for (sym = 0; sym < 144; sym++) lens[sym] = 8;
-    for (; sym < 256; sym++) lens[sym] = 9;
-    for (; sym < 280; sym++) lens[sym] = 7;
-    for (; sym < 288; sym++) lens[sym] = 8;
-    lbits = 9;
-    zs_inflate_table_wave<false>(LENS, lens, 288, codes, &lbits, work, d64, &lused);
-    for (sym = 0; sym < 32; sym++) lens[sym] = 5;
-    dbits = 5;
-    zs_inflate_table_wave<false>(DISTS, lens, 32, codes + lused, &dbits, work, d64, &dused);
-  } else if (type == 2) {  // dynamic (inflate.ts:662-836)
-    const uint32_t nlen = zs_wr_take(R, 5) + 257, ndist = zs_wr_take(R, 5) + 1, ncode = zs_wr_take(R, 4) + 4;
-    if (nlen > 286 || (!d64 && ndist > 30)) return false;
-    uint32_t i;
-    for (i = 0; i < ncode; i++) lens[ZS_BL_ORDER[i]] = (uint16_t)zs_wr_take(R, 3);
-    for (; i < 19; i++) lens[ZS_BL_ORDER[i]] = 0;
-    uint32_t cbits = 7, used;
-    HD_T(t0);
-    if (zs_inflate_table_wave<false>(CODES, lens, 19, codes, &cbits, work, d64, &used)) return false;
-    HD_T(t1);
-    // The code lengths (inflate.ts:702-778), one symbol at a time but with no
-    // memory round trip per symbol: the code-length code's table (<= 128
-    // entries of bits << 8 | symbol) sits in a VGPR, lane l holding entries l
-    // and l + 64, read with v_readlane at the input's next cbits bits; a repeat
-    // is stored by up to 138 lanes at once; the previous length stays in a
-    // register.  (Was an LDS lookup and readfirstlane per symbol and a store
-    // per repeated length: ~44k core cycles per header, profiles/r06/hdr/.)
-    const uint32_t lane = threadIdx.x & 63u, csz = 1u << cbits, cmask = csz - 1u, N = nlen + ndist;
-    const zcode c0 = lane < csz ? codes[lane] : 0u, c1 = lane + 64u < csz ? codes[lane + 64u] : 0u;
-    const uint32_t tv = ((C_BITS(c0) << 8) | C_VAL(c0)) | (((C_BITS(c1) << 8) | C_VAL(c1)) << 16);
-    uint32_t prev = 0;
-    i = 0;
-    while (i < N) {
-      if (R.bits < 32) zs_wr_fill(R);
-      const uint32_t idx = (uint32_t)R.hold & cmask;
-      const uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)tv, (int)(idx & 63u));
-      const uint32_t e = (idx & 64u) ? e2 >> 16 : e2 & 0xffffu;
-      const uint32_t nb = e >> 8, v = e & 0xffu;
-      R.hold >>= nb;
-      R.bits -= nb;
-      if (v < 16) {
-        lens[i++] = (uint16_t)v;
-        prev = v;
-        continue;
-      }
-      uint32_t rep, val = 0;
-      if (v == 16) {
-        if (i == 0) return false;
-        val = prev;
-        rep = 3 + zs_wr_take(R, 2);
-      } else if (v == 17) {
-        rep = 3 + zs_wr_take(R, 3);
-      } else {
-        rep = 11 + zs_wr_take(R, 7);
-      }
-      if (i + rep > N) return false;
-      for (uint32_t j = lane; j < rep; j += 64u) lens[i + j] = (uint16_t)val;
-      i += rep;
-      prev = val;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // (the lengths visible to this wave's table builds)
-    __builtin_amdgcn_wave_barrier();
-    if (zs_wr_over(R) || zs_u(lens[256]) == 0) return false;
-    HD_T(t2);
-    lbits = 9;
-    if (zs_inflate_table_wave<false>(LENS, lens, nlen, codes, &lbits, work, d64, &lused)) return false;
-    HD_T(t3);
-    dbits = 6;
-    if (zs_inflate_table_wave<false>(DISTS, lens + nlen, ndist, codes + lused, &dbits, work, d64, &dused)) return false;
-    HD_T(t4);
-    HD_ADD(0, t0, t1);
-    HD_ADD(1, t1, t2);
-    HD_ADD(2, t2, t3);
-    HD_ADD(3, t3, t4);
-    HD_ADD(4, 0ull, 1ull);
-    HD_ADD(5, 0ull, (unsigned long long)(nlen + ndist));
-  } else {
-    return false;  // "invalid block type"
-  }
-  lbits = zs_u(lbits);
-  dbits = zs_u(dbits);
-  dofs = zs_u(lused);
-  ntab = zs_u(lused + dused);
-  return true;
 }
 
 // ------------------------------------------------------------------- walk
@@ -391,9 +225,9 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
   lds_vu32* const vown_next = (lds_vu32*)(lane + 1u < nl ? L.s.own[lane + 1u] : L.s.own[lane]);
   bool left_own = false;
   // ---- 1. the lane's own decode
-  zs_sg_reader G;
-  zs_sg_init(G, src, n);
-  if (on) zs_sg_seek(G, q);
+  zs_lane_reader G;
+  zs_lr_init(G, src, n);
+  if (on) zs_lr_seek(G, q);
   uint32_t pos = q, cum = 0, last_len = 0;
   uint32_t pe = lane == 0 ? pe0 : q;  // the end of the symbol before (events)
   uint32_t nev = 0, ev_k[ZS_SEG_NEV], ev_sb[ZS_SEG_NEV], ev_c[ZS_SEG_NEV];
@@ -455,7 +289,7 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
         const uint32_t fend = fe - 64u;
         bool stay;
         do {
-          if (G.bits < 32) zs_sg_fill(G);
+          if (G.bits < 32) zs_lr_fill(G);
           uint32_t nb;
           zcode here = zs_sg_code(G, lt, lmask, nb);
           uint32_t op = C_OP(here), len = 1u;
@@ -466,16 +300,16 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
             } else {
               const uint32_t e1 = op & emask;
               len = C_VAL(here) + ((uint32_t)G.hold & ((1u << e1) - 1u));
-              zs_sg_drop(G, e1);
-              if (G.bits < 32) zs_sg_fill(G);
+              zs_lr_drop(G, e1);
+              if (G.bits < 32) zs_lr_fill(G);
               here = zs_sg_code(G, dt, dmask, nb);
               op = C_OP(here);
               stop = (op & 64u) != 0;  // invalid distance
-              zs_sg_drop(G, op & 15u);
+              zs_lr_drop(G, op & 15u);
             }
           }
           if (stop) {
-            zs_sg_seek(G, pos);
+            zs_lr_seek(G, pos);
             nofast = true;
           } else {
 #if ZS_SEG_EXP & 2
@@ -483,7 +317,7 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
 #endif
             cum += len;
             last_len = len;
-            pos = zs_sg_bitpos(G);
+            pos = zs_lr_bitpos32(G);
           }
           stay = !stop && pos < fend;
         } while (__builtin_amdgcn_ballot_w64(stay) == run);
@@ -540,12 +374,12 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
         xbad = sb;
       }
       pos = sb + 1u;
-      zs_sg_seek(G, pos);
+      zs_lr_seek(G, pos);
       pe = pos;
       last_len = 0;
       continue;
     }
-    const uint32_t se = zs_sg_bitpos(G);
+    const uint32_t se = zs_lr_bitpos32(G);
     // sub-chunk crossing events: boundaries 262144 k (k >= 1) with pe <= b < se
     uint32_t bd = (pe + 262143u) & ~262143u;
     if (bd == 0) bd = 262144u;
@@ -684,18 +518,18 @@ static __device__ uint32_t zs_sg_span(zs_sg_walk_lds<W>& L, const uint8_t* src, 
       if (pass == 1 && !redo_end) break;
       uint32_t p = pass ? tp : cp, c = pass ? tc : cc, lp = 0;
       const uint32_t to = pass ? end : start;
-      zs_sg_seek(G, p);
+      zs_lr_seek(G, p);
       while (p < to) {
         const zs_sg_sym y = zs_sg_decode(G, lt, lmask, dt, dmask, emask);
         if (y.kind == ZS_SG_BAD) {
           p = p + 1u;
-          zs_sg_seek(G, p);
+          zs_lr_seek(G, p);
           lp = 0;
           continue;
         }
         lp = y.kind == ZS_SG_EOB ? 0u : y.len;
         c += lp;
-        p = zs_sg_bitpos(G);
+        p = zs_lr_bitpos32(G);
       }
       bad |= p != to;
       if (pass) {
@@ -804,29 +638,11 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
   const uint32_t sb0 = spb[m], cap = spb[m + 1] - sb0;
   zs_seg_mem& M = mem[m];
   zs_wave_reader R;
-  R.n = n;
-  R.sh = (uint32_t)((uintptr_t)src & 3u);
-  R.w4 = reinterpret_cast<const uint32_t*>(src - R.sh);
-  R.last = (R.sh + n - 1u) >> 2;
-  R.inw = L.h.inw;
-  zs_wr_stage(R, ((start >> 3) + R.sh) >> 2);
-  zs_wr_seek(R, start >> 3);
-  zs_wr_take(R, start & 7u);
-  bool good = true;
+  zs_wr_init(R, src, n, L.h.inw);
+  zs_wr_start(R, start);
   const int wrap = wbits < 0 ? 0 : (wbits >> 4) + 5;  // inflate.ts:152-160
-  if (e == 0 && wrap) {  // plain zlib / gzip headers only (inflate.ts:377-580), as the lane path
-    const uint32_t b0 = zs_wr_take(R, 8), b1 = zs_wr_take(R, 8);
-    if ((wrap & 2) && b0 == 0x1f && b1 == 0x8b) {
-      const uint32_t cm = zs_wr_take(R, 8), flg = zs_wr_take(R, 8);
-      zs_wr_take(R, 32);
-      zs_wr_take(R, 16);
-      good = cm == 8 && flg == 0;
-    } else if (wrap & 1) {
-      good = !(((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (b1 & 0x20));
-    } else {
-      good = false;
-    }
-  }
+  bool good = true;
+  if (e == 0 && wrap) good = zs_wr_wrapper_header(R, wrap);  // plain zlib / gzip headers only, as the lane path
   uint32_t hdr = (uint32_t)zs_wr_bitpos(R);
   uint32_t pe0 = e == 0 ? 0u : start;  // sub-chunk events before the first symbol go to it
   uint32_t prevb = ZS_SEG_NONE;       // the entry's last span
@@ -841,28 +657,24 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
 #endif
   while (good) {
     // ---- a block: its header (wave-uniform) and tables
-    if (prevb != ZS_SEG_NONE || hdr != (uint32_t)zs_wr_bitpos(R)) {  // (a span has reused the staging LDS)
-      zs_wr_stage(R, ((hdr >> 3) + R.sh) >> 2);
-      zs_wr_seek(R, hdr >> 3);
-      zs_wr_take(R, hdr & 7u);
-    }
-    uint32_t last = 0, lbits = 0, dbits = 0, dofs = 0, ntab = 0, slen = ZS_SEG_NONE;
+    if (prevb != ZS_SEG_NONE || hdr != (uint32_t)zs_wr_bitpos(R)) zs_wr_start(R, hdr);  // (a span has reused the staging LDS)
+    uint32_t last = 0, lbits = 0, dbits = 0, dofs = 0, ntab = 0, slen = ZS_WR_CODED;
 #if ZS_SEG_EXP & 2
     const unsigned long long wd_h = __builtin_readcyclecounter();
 #endif
-    good = zs_sg_header(R, L.codes, L.h.lens, L.h.work, D64, last, lbits, dbits, dofs, ntab, slen);
+    good = zs_wr_block_header<true>(R, L.codes, L.h.lens, L.h.work, D64, last, lbits, dbits, dofs, ntab, slen);
 #if ZS_SEG_EXP & 2
     wd[0] += __builtin_readcyclecounter() - wd_h;
     wd[3]++;
 #endif
     const uint32_t sym0 = (uint32_t)zs_wr_bitpos(R);
     if (good && sym0 > nbits) good = false;
-    if (good && slen != ZS_SEG_NONE && (uint64_t)sym0 + 8ull * slen > nbits) good = false;  // (the exact path reports it)
+    if (good && slen != ZS_WR_CODED && (uint64_t)sym0 + 8ull * slen > nbits) good = false;  // (the exact path reports it)
     if (!good) break;
     __syncthreads();
     uint32_t tab = ZS_SEG_NONE, cur = sym0;
     bool first = true;
-    if (slen != ZS_SEG_NONE) {
+    if (slen != ZS_WR_CODED) {
       // ---- a stored block: one span of one piece (lane 0), the bytes at sym0 / 8
       uint32_t b = 0;
       if (lane == 0) b = atomicAdd(&M.nalloc, 1u);
@@ -902,7 +714,7 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
       prevb = b;
       pe0 = cur;
     }
-    while (slen == ZS_SEG_NONE) {  // (a coded block's spans; left by break)
+    while (slen == ZS_WR_CODED) {  // (a coded block's spans; left by break)
       // ---- a span
       // (split mode: two slots, the second for the pieces' second halves, which the plan writes)
       const uint32_t nsl = split ? 2u : 1u;
@@ -983,7 +795,7 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
     }
     if (!good) break;
     // ---- the block ended at cur: the final one, or at a later entry's start
-    if (slen == ZS_SEG_NONE) S = min(ZS_SEG_SMAX, max(W, (cur - hdr) / 60u));
+    if (slen == ZS_WR_CODED) S = min(ZS_SEG_SMAX, max(W, (cur - hdr) / 60u));
     hdr = cur;
     if (last) {
       flags_e = 3u;
@@ -1562,9 +1374,9 @@ __global__ __launch_bounds__(64) void zs_k_seg_decode(const uint8_t* __restrict_
   const uint32_t dofs = zs_u(Bk.dofs);
   const zs_sg_dtab dt = {(const zs_l_zc*)(codes + dofs), (const zs_g_zc*)(tcache + (size_t)tab * ZS_SEG_TAB + dofs),
                          ZS_SEG_TAB_DEC - dofs};
-  zs_sg_reader G;
-  zs_sg_init(G, in + in_off[s], in_len[s]);
-  zs_sg_seek(G, p.start);
+  zs_lane_reader G;
+  zs_lr_init(G, in + in_off[s], in_len[s]);
+  zs_lr_seek(G, p.start);
   zs_sg_out W;
   W.dst = (zs_g_u16*)(scratch + sbase[m] + p.off);
   W.ring = (zs_l_u16*)ring[lane];
@@ -1611,13 +1423,13 @@ __global__ __launch_bounds__(64) void zs_k_seg_decode(const uint8_t* __restrict_
       }
     } else if (y.kind == ZS_SG_EOB) {
       if (REFW) C.symbol(sb, o, 0u, y.l1, 0u, 0u, 0u, true);
-      bad = zs_sg_bitpos(G) != dend;  // only the block's last piece ends with its end of block
+      bad = zs_lr_bitpos32(G) != dend;  // only the block's last piece ends with its end of block
       break;
     } else {
       bad = true;
       break;
     }
-    sb = zs_sg_bitpos(G);
+    sb = zs_lr_bitpos32(G);
   }
   bad |= sb > dend || W.P != p.dcnt || W.ovf;
   if (!bad) W.finish();

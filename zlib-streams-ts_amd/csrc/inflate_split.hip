@@ -16,7 +16,7 @@
 //     missed boundary), and keeps the first.
 //  2. zs_k_split_decode: one workgroup per found start (a "piece"; the first
 //     piece starts at bit 0) decodes blocks wave-uniformly, like
-//     zs_k_inflate_wave, until it closes a block at or past the next piece's
+//     zs_k_inflate_wave (reader, block header and tables: zs_wave.h), until it closes a block at or past the next piece's
 //     start.  The history before a piece's start is unknown: a copy reaching
 //     back before it produces MARKERS -- the ring and the piece's output hold
 //     u16 values, a byte below 256, and 255 + k for "the byte k positions
@@ -343,14 +343,8 @@ static __device__ __forceinline__ uint32_t zs_split_starts(const uint64_t* found
 }
 
 // ----------------------------------------------------------------- decoder
-// u16 history ring (the window: 32 KiB; deflate64 64 KiB) first in the dynamic LDS
-struct zs_split_tabs {
-  uint32_t inw[ZS_WIN_IN];
-  zcode codes[ENOUGH_LENS + ENOUGH_DISTS_9];
-  uint16_t lens[320];
-  uint16_t work[288];
-};
-
+// u16 history ring (the window: 32 KiB; deflate64 64 KiB) first in the dynamic
+// LDS, then the staged input and zlib's tables (zs_wave_tabs)
 __global__ __launch_bounds__(64) void zs_k_split_decode(const uint8_t* __restrict__ in,
                                                        const uint64_t* __restrict__ in_off,
                                                        const uint32_t* __restrict__ in_len,
@@ -363,7 +357,7 @@ __global__ __launch_bounds__(64) void zs_k_split_decode(const uint8_t* __restric
   const uint32_t wsize = d64 ? 65536u : 32768u;
   const uint32_t rmask = wsize - 1u;
   uint16_t* ring = reinterpret_cast<uint16_t*>(zs_ssm);
-  zs_split_tabs& W = *reinterpret_cast<zs_split_tabs*>(zs_ssm + 2u * wsize);
+  zs_wave_tabs& W = *reinterpret_cast<zs_wave_tabs*>(zs_ssm + 2u * wsize);
   const uint32_t m = blockIdx.x / ZS_SPLIT_MAX, k = blockIdx.x % ZS_SPLIT_MAX;
   const uint32_t lane = threadIdx.x;
   const uint32_t s = zs_u(list[m]);
@@ -376,22 +370,16 @@ __global__ __launch_bounds__(64) void zs_k_split_decode(const uint8_t* __restric
   const uint64_t start = starts[k];
   const uint8_t* src = in + in_off[s];
   zs_wave_reader R;
-  R.n = n;
-  R.sh = (uint32_t)((uintptr_t)src & 3u);
-  R.w4 = reinterpret_cast<const uint32_t*>(src - R.sh);
-  R.last = (R.sh + n - 1u) >> 2;
-  R.inw = W.inw;
-  const uint32_t at0 = (uint32_t)(start >> 3);
-  zs_wr_stage(R, (at0 + R.sh) >> 2);
-  zs_wr_seek(R, at0);
-  zs_wr_take(R, (uint32_t)(start & 7u));
+  zs_wr_init(R, src, n, W.inw);
+  zs_wr_start(R, start);
   uint16_t* dst = scratch + (size_t)blockIdx.x * piece_cap;
   uint32_t* dstw = reinterpret_cast<uint32_t*>(dst);
   const uint32_t* ringw = reinterpret_cast<const uint32_t*>(ring);
   const uint32_t lmask = d64 ? 31u : 15u;
   const bool first = k == 0;
   uint32_t total = 0, flushed = 0, next = ZS_SPLIT_MAX, nblk = 0;
-  bool bail = false, last = false;
+  uint32_t last = 0;
+  bool bail = false;
   // output leaves the ring 128 entries (one dword per lane) at a time
   auto flush = [&]() {
     while (total - flushed >= 128u) {
@@ -416,14 +404,15 @@ __global__ __launch_bounds__(64) void zs_k_split_decode(const uint8_t* __restric
       while (q < npieces && starts[q] < b) q++;
       if (q < npieces && starts[q] == b) { next = q; break; }
     }
-    last = zs_wr_take(R, 1) != 0;
-    const uint32_t type = zs_wr_take(R, 2);
-    uint32_t lbits, dbits, lused;
-    if (type == 0) {  // stored
-      zs_wr_align(R);
-      const uint32_t len = zs_wr_take(R, 16), nlen = zs_wr_take(R, 16);
+    // the header and zlib's tables (zs_wr_block_header, the serial inflate_table)
+    uint32_t lbits, dbits, dofs, ntab, len;
+    if (!zs_wr_block_header<false>(R, W.codes, W.lens, W.work, d64, last, lbits, dbits, dofs, ntab, len)) {
+      bail = true;
+      break;
+    }
+    if (len != ZS_WR_CODED) {  // stored
       const uint32_t at = (uint32_t)(zs_wr_bitpos(R) >> 3);
-      if (len != (nlen ^ 0xffffu) || zs_wr_over(R) || at + len > R.n || total + len > piece_cap) { bail = true; break; }
+      if (at + len > R.n || total + len > piece_cap) { bail = true; break; }
       for (uint32_t i = 0; i < len; i += 64) {
         const uint32_t j = i + lane;
         if (j < len) ring[(total + lane) & rmask] = src[at + j];
@@ -433,60 +422,8 @@ __global__ __launch_bounds__(64) void zs_k_split_decode(const uint8_t* __restric
       zs_wr_seek(R, at + len);
       continue;
     }
-    if (type == 1) {
-      uint32_t sym;
-      for (sym = 0; sym < 144; sym++) W.lens[sym] = 8;
-      for (; sym < 256; sym++) W.lens[sym] = 9;
-      for (; sym < 280; sym++) W.lens[sym] = 7;
-      for (; sym < 288; sym++) W.lens[sym] = 8;
-      lbits = 9;
-      zs_inflate_table(LENS, W.lens, 288, W.codes, &lbits, W.work, d64, &lused);
-      for (sym = 0; sym < 32; sym++) W.lens[sym] = 5;
-      dbits = 5;
-      zs_inflate_table(DISTS, W.lens, 32, W.codes + lused, &dbits, W.work, d64, &sym);
-    } else if (type == 2) {
-      const uint32_t nlen = zs_wr_take(R, 5) + 257, ndist = zs_wr_take(R, 5) + 1, ncode = zs_wr_take(R, 4) + 4;
-      if (nlen > 286 || (!d64 && ndist > 30)) { bail = true; break; }
-      uint32_t i;
-      for (i = 0; i < ncode; i++) W.lens[ZS_BL_ORDER[i]] = (uint16_t)zs_wr_take(R, 3);
-      for (; i < 19; i++) W.lens[ZS_BL_ORDER[i]] = 0;
-      uint32_t cbits = 7, used;
-      if (zs_inflate_table(CODES, W.lens, 19, W.codes, &cbits, W.work, d64, &used)) { bail = true; break; }
-      i = 0;
-      while (i < nlen + ndist) {
-        const zcode here = zs_wr_decode(R, W.codes, cbits);
-        const uint32_t v = C_VAL(here);
-        if (v < 16) { W.lens[i++] = (uint16_t)v; continue; }
-        uint32_t rep, val = 0;
-        if (v == 16) {
-          if (i == 0) { bail = true; break; }
-          val = zs_u(W.lens[i - 1]);
-          rep = 3 + zs_wr_take(R, 2);
-        } else if (v == 17) {
-          rep = 3 + zs_wr_take(R, 3);
-        } else {
-          rep = 11 + zs_wr_take(R, 7);
-        }
-        if (i + rep > nlen + ndist) { bail = true; break; }
-        while (rep--) W.lens[i++] = (uint16_t)val;
-      }
-      if (bail || zs_wr_over(R) || zs_u(W.lens[256]) == 0) { bail = true; break; }
-      lbits = 9;
-      uint32_t dused;
-      if (zs_inflate_table(LENS, W.lens, nlen, W.codes, &lbits, W.work, d64, &lused)) { bail = true; break; }
-      dbits = 6;
-      if (zs_inflate_table(DISTS, W.lens + nlen, ndist, W.codes + lused, &dbits, W.work, d64, &dused)) {
-        bail = true;
-        break;
-      }
-    } else {
-      bail = true;
-      break;
-    }
-    lbits = zs_u(lbits);
-    dbits = zs_u(dbits);
     const zcode* lt = W.codes;
-    const zcode* dt = W.codes + zs_u(lused);
+    const zcode* dt = W.codes + dofs;
     for (;;) {
       zcode here = zs_wr_decode(R, lt, lbits);
       uint32_t op = C_OP(here);
@@ -669,4 +606,4 @@ __global__ void zs_k_split_final(const uint32_t* __restrict__ list, uint32_t n_l
   lens_out[list[m]] = r.out_len;
 }
 
-size_t zs_split_lds_bytes(bool d64) { return (d64 ? 131072u : 65536u) + sizeof(zs_split_tabs); }
+size_t zs_split_lds_bytes(bool d64) { return (d64 ? 131072u : 65536u) + sizeof(zs_wave_tabs); }

@@ -15,7 +15,9 @@
 //    a period < 64 copy stored from one read per lane -- and every byte is also
 //    stored to HBM, never read back;
 //  * zlib's own tables (inflate_table, zs_inftab.h) in LDS, built by all lanes
-//    on identical values.
+//    on identical values; the reader, the wrapper header and the block header
+//    parse are the ones of zs_wave.h, shared with the split decode and the
+//    segmented walk.
 // Outcome contract = the lane path's (zs_lane_res): any condition that is not a
 // clean end of stream sets bail and the exact kernel (zs_k_inflate) redecodes
 // the member, so statuses, phases and messages come from the exact state
@@ -31,14 +33,8 @@
 #include "zs_wave.h"
 
 // history ring: the window (32 KiB; deflate64 64 KiB), at the start of the
-// dynamic LDS; then the staged input and zlib's tables.  Deflate: 40,792 B, four
-// workgroups per CU; deflate64: 73,560 B, two.
-struct zs_wave_tabs {
-  uint32_t inw[ZS_WIN_IN];
-  zcode codes[ENOUGH_LENS + ENOUGH_DISTS_9];
-  uint16_t lens[320];
-  uint16_t work[288];
-};
+// dynamic LDS; then the staged input and zlib's tables (zs_wave_tabs).  Deflate:
+// 40,792 B, four workgroups per CU; deflate64: 73,560 B, two.
 static __host__ __device__ inline uint32_t zs_wave_ring_bytes(bool d64) { return d64 ? 65536u : 32768u; }
 
 // REFW: a deflate / zlib / gzip member with the reference's window-wrap copy
@@ -60,16 +56,12 @@ static __device__ __forceinline__ void zs_wave_member(uint8_t* zs_wsm, const uin
   const uint32_t lane = threadIdx.x;
   const uint8_t* src = in + in_off[s];
   zs_wave_reader R;
-  R.n = zs_u(in_len[s]);
-  R.sh = (uint32_t)((uintptr_t)src & 3u);
-  R.w4 = R.n ? reinterpret_cast<const uint32_t*>(src - R.sh) : in_len;  // an empty member reads (and masks) in_len[]
-  R.last = R.n ? (R.sh + R.n - 1u) >> 2 : 0u;
-  R.inw = W.inw;
-  zs_wr_stage(R, 0);
-  R.pos = 0;
-  R.hold = 0;
-  R.bits = 0;
-  R.pf = zs_wr_load4(R, 0);
+  zs_wr_init(R, src, zs_u(in_len[s]), W.inw);
+  if (!R.n) {  // an empty member reads (and masks) in_len[], never its own address
+    R.w4 = in_len;
+    R.last = 0;
+  }
+  zs_wr_start(R, 0);
   uint8_t* dst = out + out_off[s];
   uint32_t* dstw = reinterpret_cast<uint32_t*>(dst);  // out_off is 4-aligned
   const uint32_t* ringw = reinterpret_cast<const uint32_t*>(ring);
@@ -91,29 +83,18 @@ static __device__ __forceinline__ void zs_wave_member(uint8_t* zs_wsm, const uin
     }
   };
   // ---- wrapper header (inflate.ts:377-580): plain zlib / gzip headers only, as the lane path
-  if (wrap) {
-    const uint32_t b0 = zs_wr_take(R, 8), b1 = zs_wr_take(R, 8);
-    if ((wrap & 2) && b0 == 0x1f && b1 == 0x8b) {
-      const uint32_t cm = zs_wr_take(R, 8), flg = zs_wr_take(R, 8);
-      zs_wr_take(R, 32);  // MTIME
-      zs_wr_take(R, 16);  // XFL, OS
-      if (cm != 8 || flg != 0) bail = true;
-    } else if (wrap & 1) {
-      if (((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (b1 & 0x20)) bail = true;
-    } else {
-      bail = true;
-    }
-  }
-  bool last = false;
+  if (wrap && !zs_wr_wrapper_header(R, wrap)) bail = true;
+  uint32_t last = 0;
   while (!bail && !last) {
-    last = zs_wr_take(R, 1) != 0;
-    const uint32_t type = zs_wr_take(R, 2);
-    uint32_t lbits, dbits, lused;
-    if (type == 0) {  // stored (inflate.ts:615-660): bytes straight from the input, 64 per step
-      zs_wr_align(R);
-      const uint32_t len = zs_wr_take(R, 16), nlen = zs_wr_take(R, 16);
+    // the header and zlib's tables (zs_wr_block_header, the serial inflate_table)
+    uint32_t lbits, dbits, dofs, ntab, len;
+    if (!zs_wr_block_header<false>(R, W.codes, W.lens, W.work, d64, last, lbits, dbits, dofs, ntab, len)) {
+      bail = true;
+      break;
+    }
+    if (len != ZS_WR_CODED) {  // stored (inflate.ts:615-660): bytes straight from the input, 64 per step
       const uint32_t at = (uint32_t)(zs_wr_bitpos(R) >> 3);
-      if (len != (nlen ^ 0xffffu) || zs_wr_over(R) || at + len > R.n || total + len > cap) { bail = true; break; }
+      if (at + len > R.n || total + len > cap) { bail = true; break; }
       if (refw) C.stored(at, total, len);
       for (uint32_t i = 0; i < len; i += 64) {
         const uint32_t k = i + lane;
@@ -124,60 +105,8 @@ static __device__ __forceinline__ void zs_wave_member(uint8_t* zs_wsm, const uin
       zs_wr_seek(R, at + len);
       continue;
     }
-    if (type == 1) {  // fixed tables (inflate.ts:218-280)
-      uint32_t sym;
-      for (sym = 0; sym < 144; sym++) W.lens[sym] = 8;
-      for (; sym < 256; sym++) W.lens[sym] = 9;
-      for (; sym < 280; sym++) W.lens[sym] = 7;
-      for (; sym < 288; sym++) W.lens[sym] = 8;
-      lbits = 9;
-      zs_inflate_table(LENS, W.lens, 288, W.codes, &lbits, W.work, d64, &lused);
-      for (sym = 0; sym < 32; sym++) W.lens[sym] = 5;
-      dbits = 5;
-      zs_inflate_table(DISTS, W.lens, 32, W.codes + lused, &dbits, W.work, d64, &sym);
-    } else if (type == 2) {  // dynamic (inflate.ts:662-836)
-      const uint32_t nlen = zs_wr_take(R, 5) + 257, ndist = zs_wr_take(R, 5) + 1, ncode = zs_wr_take(R, 4) + 4;
-      if (nlen > 286 || (!d64 && ndist > 30)) { bail = true; break; }
-      uint32_t i;
-      for (i = 0; i < ncode; i++) W.lens[ZS_BL_ORDER[i]] = (uint16_t)zs_wr_take(R, 3);
-      for (; i < 19; i++) W.lens[ZS_BL_ORDER[i]] = 0;
-      uint32_t cbits = 7, used;
-      if (zs_inflate_table(CODES, W.lens, 19, W.codes, &cbits, W.work, d64, &used)) { bail = true; break; }
-      i = 0;
-      while (i < nlen + ndist) {
-        const zcode here = zs_wr_decode(R, W.codes, cbits);
-        const uint32_t v = C_VAL(here);
-        if (v < 16) { W.lens[i++] = (uint16_t)v; continue; }
-        uint32_t rep, val = 0;
-        if (v == 16) {
-          if (i == 0) { bail = true; break; }
-          val = zs_u(W.lens[i - 1]);
-          rep = 3 + zs_wr_take(R, 2);
-        } else if (v == 17) {
-          rep = 3 + zs_wr_take(R, 3);
-        } else {
-          rep = 11 + zs_wr_take(R, 7);
-        }
-        if (i + rep > nlen + ndist) { bail = true; break; }
-        while (rep--) W.lens[i++] = (uint16_t)val;
-      }
-      if (bail || zs_wr_over(R) || zs_u(W.lens[256]) == 0) { bail = true; break; }
-      lbits = 9;
-      uint32_t dused;
-      if (zs_inflate_table(LENS, W.lens, nlen, W.codes, &lbits, W.work, d64, &lused)) { bail = true; break; }
-      dbits = 6;
-      if (zs_inflate_table(DISTS, W.lens + nlen, ndist, W.codes + lused, &dbits, W.work, d64, &dused)) {
-        bail = true;
-        break;
-      }
-    } else {
-      bail = true;  // "invalid block type"
-      break;
-    }
-    lbits = zs_u(lbits);
-    dbits = zs_u(dbits);
     const zcode* lt = W.codes;
-    const zcode* dt = W.codes + zs_u(lused);
+    const zcode* dt = W.codes + dofs;
     // symbols (inffast.ts:5-228 semantics; the reference's call boundaries tracked by C)
     for (;;) {
       const uint64_t b0 = zs_wr_bitpos(R);

@@ -1,7 +1,8 @@
 // zs_inftab.h -- zlib's decoding tables for the inflate kernels: inflate_table
 // (inftrees.ts:62-279) and the length / distance bases (inflate/constants.ts:8-45),
-// shared by the exact stream-layer kernel (inflate.hip) and the lane-per-member
-// path (inflate_lane.hip).
+// shared by the exact stream-layer kernel (inflate.hip), the lane-per-member
+// path (inflate_lane.hip) and, through the block header parse of zs_wave.h, the
+// wave, split and segmented decoders.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -163,16 +164,16 @@ static __device__ __attribute__((unused)) int zs_inflate_table(int type, const u
 #ifndef ZS_HOST_BUILD  // (tools/lane_host compiles the serial form on the CPU: no waves there)
 // zs_inflate_table_wave: inflate_table's exact output (same return value, root
 // bits, size and entries) built by the 64 lanes of one wave together, for the
-// segmented walk's block headers (inflate_seg.hip; the wave and split decoders
-// keep the serial form: with both forms inlined they lose occupancy, 7 -> 3
-// waves per SIMD for zs_k_split_decode).  Requires all 64 lanes active and
+// segmented walk's block headers (zs_wr_block_header<true>, zs_wave.h; the wave
+// and split decoders keep the serial form, that function's <false>: with both
+// forms inlined they lose occupancy, 7 -> 3 waves per SIMD for zs_k_split_decode).  Requires all 64 lanes active and
 // wave-uniform arguments.
 //
 // Why: the serial form makes one pass per symbol and per table entry, each a
 // chain of dependent LDS round trips for ONE lane's worth of work -- measured in
 // the segmented walk at ~214k core cycles for a literal/length table and ~72k
 // for a distance table per dynamic header, against ~43k for decoding the ~300
-// code lengths themselves (tools/dbg/seg_hdr_clock.py, profiles/r06/hdr/).
+// code lengths themselves (profiles/r06/hdr/).
 //
 // How (RFC 1951 3.2.2 canonical codes, which is what inflate_table lays out):
 //  * per-length values live across the lanes: lane k holds count[k], the first
