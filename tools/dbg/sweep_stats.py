@@ -1,3 +1,6 @@
+"""Counters of zs_k_sweep per 64-member chunk on the C2 batch (a counter build:
+tools/build_variant.sh swprof deflate_sweep.hip -DZS_SW_PROF=1, then
+ZS_LIB=variants/swprof/libzsgpu.so python3 tools/dbg/sweep_stats.py)."""
 import ctypes, os, sys
 sys.path.insert(0, "zlib-streams-ts_amd")
 import torch; torch.cuda.init()

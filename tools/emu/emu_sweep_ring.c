@@ -40,7 +40,7 @@ static int g_break_mirror;
 static unsigned long long g_reads, g_bad, g_builds;
 static uint32_t g_next, g_run_id;
 
-static void build_block(wave_t* w, int32_t b) {  // put_blk for the 64 lanes
+static void build_block(wave_t* w, int32_t b) {  // SwRingP::put for the 64 lanes
   g_builds++;
   for (int lane = 0; lane < 64; lane++) {
     const int32_t j = 64 * b + lane;
@@ -63,7 +63,7 @@ static void check(const wave_t* w, uint32_t slot, int32_t want, const char* what
   }
 }
 
-// sw_body's run(): steps [ta, tb] in groups of 8, or 4 where the range or the chain >> 2 snapshot cuts them
+// SwWave::run(): steps [ta, tb] in groups of 8, or 4 where the range or the chain >> 2 snapshot cuts them
 static void sweep_range(const wave_t* w, int32_t k, uint32_t base, uint32_t ta, uint32_t tb, uint32_t budget_s) {
   for (uint32_t t0 = ta; t0 <= tb;) {
     uint32_t t1 = t0 + 7u <= tb ? t0 + 7u : t0 + 3u;

@@ -54,12 +54,10 @@
 // last of them (258 bytes) and the 16-byte overreach of the word compares
 #define ZS_SW_WIN_WORDS ((ZS_SEG_WPOS + 258u + 20u + 3u) / 4u + 2u)
 #define ZS_SW_RING 128u  // records per wave (two blocks of 64 members), stored twice (mirror)
-#ifndef ZS_SW_EXP
-#define ZS_SW_EXP 0  // experiments (timing A/B only; 0 in the product)
-#endif
 #define ZS_SW_MW 320u    // per-wave LDS window of member positions (chain + 64 <= ZS_SW_MW: level 7)
-// chunks per run of the persistent ring (levels 4..6); bits 16..20 of ZS_SW_EXP override it (timing A/B)
-#define ZS_SW_RUN_CAP ((((ZS_SW_EXP) >> 16) & 31u) ? (((ZS_SW_EXP) >> 16) & 31u) : 16u)
+#ifndef ZS_SW_RUN_CAP
+#define ZS_SW_RUN_CAP 16u  // chunks per run of the persistent ring at most (levels 4..6; 1, 4, 8, 16: DESIGN 4.2)
+#endif
 
 typedef __attribute__((address_space(3))) uint32_t zs_sw_lds_u32;
 static __device__ __forceinline__ uint32_t sw_lds_addr(const void* p) {
@@ -353,12 +351,7 @@ struct SwSig<false> {
   static constexpr uint32_t LONG = 88u;  // all 11 bytes: the exact length needs the window
   static constexpr uint32_t THR0 = 23u;  // sigma 2 (B << 3 | 7): no match yet
   static constexpr uint32_t EXT = 11u;   // a long candidate's known bytes
-  uint32_t a, b, c;
-  __device__ __forceinline__ void own(const uint32_t* win, uint32_t p) {
-    a = sw_word(win, p);
-    b = sw_word(win, p + 4);
-    c = (sw_word(win, p + 8) & 0x00ffffffu) | 0x01000000u;
-  }
+  uint32_t a, b, c;  // the lane's own signature: its record's words, c with the sentinel (SwWave::start)
   static __device__ __forceinline__ uint4 rec(const uint32_t* win, uint32_t q, uint32_t w0) {
     return make_uint4(w0, sw_word(win, q + 4), sw_word(win, q + 8) & 0x00ffffffu, 0u);
   }
@@ -377,11 +370,7 @@ struct SwSig<true> {
   static constexpr uint32_t LONG = 64u;  // all 8 signature bytes: a match of >= 10 bytes
   static constexpr uint32_t THR0 = 7u;   // sigma 0
   static constexpr uint32_t EXT = 10u;
-  uint32_t a, b;
-  __device__ __forceinline__ void own(const uint32_t* win, uint32_t p) {
-    a = sw_x7(sw_word(win, p)) | (sw_word(win, p + 3) << 8);
-    b = sw_word(win, p + 6);
-  }
+  uint32_t a, b;  // the lane's own signature: its record's words
   // (the record's third word: the four bytes past the signature, which a long
   // candidate's first extension step compares -- from the ring, not the window)
   static __device__ __forceinline__ uint4 rec(const uint32_t* win, uint32_t q, uint32_t w0) {
@@ -401,11 +390,30 @@ struct SwSig<true> {
 // 0..1 (8 B), word 2 (the 11-byte form only) and the liveness key
 // hash << 16 | q.  Member j's record lives in slot j mod 128 and again 128
 // slots later, so that a block's 64 steps read slots base .. base + 63 without
-// wrapping.
+// wrapping.  A chunk builds every block it reads; the members' positions are
+// not kept past two blocks (level 7 keeps them in a window of its own, mw).
+//
+// Both layouts number the members in blocks of 64 (block b = members 64 b ..
+// 64 b + 63, chunk c's own block is c) and provide
+//   put(b, lane, r)   this lane's record r of block b (b wave-uniform),
+//   base(c, s, lane)  for chunk c's steps (64 s, 64 s + 64] -- members of the
+//                     blocks c - s - 1 and c - s: step t reads slot base - t.
 struct SwRing {
   uint2 ab[2 * ZS_SW_RING];
   uint32_t c[2 * ZS_SW_RING];
   uint32_t key[2 * ZS_SW_RING];
+  __device__ __forceinline__ void put(int b, uint32_t lane, uint4 r) {
+    const uint32_t i = (uint32_t)(64 * b + (int)lane) & (ZS_SW_RING - 1);
+    ab[i] = make_uint2(r.x, r.y);
+    ab[i + ZS_SW_RING] = make_uint2(r.x, r.y);
+    c[i] = r.z;  // (A7: the bytes past the signature)
+    c[i + ZS_SW_RING] = r.z;
+    key[i] = r.w;
+    key[i + ZS_SW_RING] = r.w;
+  }
+  static __device__ __forceinline__ uint32_t base(int c, uint32_t s, uint32_t lane) {
+    return ((uint32_t)(64 * (c - (int)s - 1) + (int)lane) & (ZS_SW_RING - 1)) + 64u * s + 64u;
+  }
 };
 // The persistent ring of levels 4..6 (chain <= 128, zs_sweep_ring.h): three
 // blocks of 64 members, block b at slots 64 (b mod 3), which a wave keeps
@@ -413,11 +421,27 @@ struct SwRing {
 // the blocks before it are the previous chunks' -- and slots 0..63 again at
 // 192..255, so that the 64 steps of a block read upwards from one wave-uniform
 // base without wrapping, as they do in SwRing.  The key array doubles as the
-// window of member positions (SwRing's mwin).
+// window of member positions: pos(c, lane, t) is the position of member
+// 64 c + lane - t for a step t of chunk c that was swept.
 struct SwRingP {
   uint2 ab[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
   uint32_t c[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
   uint32_t key[ZS_SWR_SLOTS + ZS_SWR_MIRROR];
+  __device__ __forceinline__ void put(int b, uint32_t lane, uint4 r) {
+    const uint32_t i = zs_swr_block_slot(b) + lane;
+    ab[i] = make_uint2(r.x, r.y);
+    c[i] = r.z;
+    key[i] = r.w;
+    if (zs_swr_mirrored(b)) {  // a block at slot 0 is written twice (the mirror)
+      ab[i + ZS_SWR_SLOTS] = make_uint2(r.x, r.y);
+      c[i + ZS_SWR_SLOTS] = r.z;
+      key[i + ZS_SWR_SLOTS] = r.w;
+    }
+  }
+  static __device__ __forceinline__ uint32_t base(int c, uint32_t s, uint32_t lane) { return zs_swr_base(c, s) + lane; }
+  __device__ __forceinline__ uint32_t pos(int c, uint32_t lane, uint32_t t) const {
+    return key[zs_swr_member_slot(c, lane, t)] & 0xffffu;
+  }
 };
 
 // The lock-step sweep of one stream (the workgroup), for signature form A7.
@@ -444,7 +468,10 @@ struct SwRingP {
 // such a block runs with the exec mask of the live lanes and no per-step test.
 // A block in which some lane's chain ends runs the masked form (the step's
 // ballot of `key > klim` ands into the live mask, a dead lane's score is 0).
-#if ZS_SW_EXP & 64  // instrumentation (timing experiments only)
+#ifndef ZS_SW_PROF
+#define ZS_SW_PROF 0  // instrumentation: counts of chunks, groups, long branches and wave steps (0 in the product)
+#endif
+#if ZS_SW_PROF
 __device__ unsigned long long zs_sw_stat[8];  // chunks, fast groups, masked groups, long branches, wave steps
 #define SW_STAT(i, v) do { if ((threadIdx.x & 63u) == __builtin_ctzll(__builtin_amdgcn_read_exec())) atomicAdd(&zs_sw_stat[i], (unsigned long long)(v)); } while (0)
 extern "C" int zs_sw_stats(unsigned long long* out) {
@@ -454,82 +481,407 @@ extern "C" int zs_sw_stats(unsigned long long* out) {
 #define SW_STAT(i, v) do { } while (0)
 #endif
 
+static __device__ __forceinline__ uint32_t sw_score(uint32_t mb, uint32_t u) { return (mb & ~7u) | (7u - u); }  // one v_and_or_b32
+template <uint32_t N>  // the maximum of a group's N scores
+static __device__ __forceinline__ uint32_t sw_gmax(const uint32_t* sc) {
+  static_assert(N == 8 || N == 4 || N == 3 || N == 1, "group sizes");
+  if constexpr (N == 8) return max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7])));
+  else if constexpr (N == 4) return max3(sc[0], sc[1], max(sc[2], sc[3]));
+  else if constexpr (N == 3) return max3(sc[0], sc[1], sc[2]);
+  else return sc[0];
+}
+
+// One lane's state while its chunk is swept: its position, the limits of its
+// walk, and its best candidates so far.
+template <bool A7>
+struct SwLane {
+  SwSig<A7> S;           // the position's own signature
+  uint32_t p;            // the position (0 past the members)
+  bool own;              // ... is one of the window's own: it gets a result
+  uint32_t maxc, nice;   // deflate.ts:1068, 1078-1080
+  uint32_t khead, klim;  // liveness: the head needs key >= khead, a chain step key > klim
+  uint32_t long_m;       // a score at or above it is a long candidate (a tail lane records none)
+  uint32_t own_ext;      // the lane's bytes past a full signature
+  // the best short candidate: its group's maximum score (matched bits, 7 - its place in the group) and the
+  // group's first step (0: none) -- the step itself, bt + 7 - (thr & 7), is formed once at the end
+  uint32_t thr, bt, thr_s, bt_s;
+  // best long candidate: its length (capped at nice) as lthr = len << 3 | 7, its step
+  uint32_t lthr, lbt, lthr_s, lbt_s;
+  uint64_t alive_m;  // (wave-uniform) the lanes whose chain has not ended
+  uint32_t head;     // bit 0: head candidate valid; 0x8000: at exactly MAX_DIST
+  bool snapped;      // (wave-uniform) step chain >> 2 has been folded
+  __device__ __forceinline__ bool tail() const { return maxc <= 12u; }  // exact re-walk after the sweep
+  __device__ __forceinline__ void snap() {  // the chain >> 2 result (deflate.ts:1075-1077)
+    thr_s = thr;
+    bt_s = bt;
+    lthr_s = lthr;
+    lbt_s = lbt;
+    snapped = true;
+  }
+};
+
+// One wave's sweep of a window: what its chunks share, and the pieces of one
+// chunk's work -- start (the lanes' state), build (the ring's blocks), sweep
+// (the chain steps) and settle (the results).  sw_body drives them.
 template <bool A7, bool MW, bool PR>  // PR: the persistent ring (chain <= ZS_SWR_MAX_CHAIN; MW is then unused)
-static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp, uint16_t* mw, uint32_t* next,
-                                               uint32_t n, uint32_t m, uint32_t olo, uint32_t ohi,
-                                               const uint16_t* mem, uint2* out, int chain, int nice_cfg) {
-  // n: bytes from the window's start to the stream's end; m: the window's
-  // members (inserted positions); results for the own positions [olo, ohi)
+struct SwWave {
   using Sig = SwSig<A7>;
+  using Lane = SwLane<A7>;
   using Ring = std::conditional_t<PR, SwRingP, SwRing>;
-  Ring* const R = (Ring*)ringp;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t budget = (uint32_t)chain, budget_s = (uint32_t)chain >> 2;
+  const uint32_t* win;
+  Ring* R;
+  uint16_t* mw;
+  const uint16_t* mem;
+  // n: bytes from the window's start to the stream's end; m: the window's members (inserted positions)
+  uint32_t n, m, lane;
   // the steps swept: the full chain (a demand-driven variant that swept chain >> 2
   // steps and left the rest to the parse lost: DESIGN 4.2, tools/variants/r05_paths.patch)
-#if ZS_SW_EXP & 128
-  const uint32_t sbud = 4u;  // (timing: the per-chunk cost without chain steps past 4)
-#else
-  const uint32_t sbud = budget;
-#endif
-  const uint32_t nchunks = (m + 63) / 64;
-  auto put_rec = [&](int j, uint4 r) {
-    const uint32_t i = (uint32_t)j & (ZS_SW_RING - 1);
-    R->ab[i] = make_uint2(r.x, r.y);
-    R->ab[i + ZS_SW_RING] = make_uint2(r.x, r.y);
-    R->c[i] = r.z;  // (A7: the bytes past the signature)
-    R->c[i + ZS_SW_RING] = r.z;
-    R->key[i] = r.w;
-    R->key[i + ZS_SW_RING] = r.w;
-  };
-  // PR: this lane's record of block blk (wave-uniform); a block at slot 0 is written twice (the mirror)
-  auto put_blk = [&](int blk, uint4 r) {
-    const uint32_t i = zs_swr_block_slot(blk) + lane;
-    R->ab[i] = make_uint2(r.x, r.y);
-    R->c[i] = r.z;
-    R->key[i] = r.w;
-    if (zs_swr_mirrored(blk)) {
-      R->ab[i + ZS_SWR_SLOTS] = make_uint2(r.x, r.y);
-      R->c[i + ZS_SWR_SLOTS] = r.z;
-      R->key[i + ZS_SWR_SLOTS] = r.w;
-    }
-  };
-  // the slot of step t, from the base of its 64 steps (below)
-  auto at = [&](uint32_t base, uint32_t t) -> uint32_t { return base - t; };
-  auto make_rec = [&](uint32_t q) -> uint4 {
+  uint32_t budget, budget_s, nice_cfg;
+  int cc;           // the chunk swept (wave-uniform); the lane's member is k()
+  zs_swr_range vr;  // PR: the blocks the ring holds
+  // MW: the members k0 - budget .. k0 + 63 of the current chunk are kept in a
+  // per-wave LDS window as their records are built, so the distances after
+  // the sweep read positions from LDS instead of HBM (chain + 64 <= ZS_SW_MW)
+  int mw0;  // member index of mw[0] (k0 - budget)
+
+  __device__ __forceinline__ int k() const { return 64 * cc + (int)lane; }
+  __device__ __forceinline__ uint32_t fetch(int j) const { return j >= 0 && (uint32_t)j < m ? (uint32_t)mem[j] : 0u; }
+  __device__ __forceinline__ uint4 make_rec(uint32_t q) const {
     const uint32_t w0 = sw_word(win, q);
     uint4 r = Sig::rec(win, q, w0);
     r.w = (sw_hash(w0) << 16) | q;
     return r;
-  };
-  // MW: the members k0 - budget .. k0 + 63 of the current chunk are kept in a
-  // per-wave LDS window as their records are built, so the distances after
-  // the sweep read positions from LDS instead of HBM (chain + 64 <= ZS_SW_MW)
-  int mw0 = 0;  // member index of mw[0] (k0 - budget)
-  auto load_rec_q = [&](int j, uint32_t q) {  // key 0 = no member: fails every liveness test
+  }
+  // block blk from its members' positions q (0: no member; key 0 fails every liveness test)
+  __device__ __forceinline__ void build_blk(int blk, uint32_t q) {
+    const int j = 64 * blk + (int)lane;
     const bool in = j >= 0 && (uint32_t)j < m;
     if (MW && (uint32_t)(j - mw0) < ZS_SW_MW) mw[j - mw0] = (uint16_t)q;  // (block 1 back reaches below k0 - budget when budget < 64)
-    put_rec(j, in ? make_rec(q) : make_uint4(0, 0, 0, 0));
-  };
-  auto fetch = [&](int j) -> uint32_t { return j >= 0 && (uint32_t)j < m ? (uint32_t)mem[j] : 0u; };
-  auto load_rec = [&](int j) { load_rec_q(j, fetch(j)); };
-  int cc = 0;  // the chunk swept (wave-uniform)
-  auto build_blk = [&](int blk, uint32_t q) {  // PR: block blk from its members' positions (0: no member)
-    const int j = 64 * blk + (int)lane;
-    put_blk(blk, j >= 0 && (uint32_t)j < m ? make_rec(q) : make_uint4(0, 0, 0, 0));
-  };
-  auto member = [&](int j) -> uint32_t {  // j = k - t for a step t that was swept: its block is in the ring
-    if constexpr (PR) return R->key[zs_swr_member_slot(cc, lane, 64u * (uint32_t)cc + lane - (uint32_t)j)] & 0xffffu;
+    R->put(blk, lane, in ? make_rec(q) : make_uint4(0, 0, 0, 0));
+    if constexpr (PR) vr = zs_swr_extend(vr, blk);
+  }
+  // PR builds on demand: only a block the ring does not hold (a run's first chunk, or after a skipped one)
+  __device__ __forceinline__ bool missing(int blk) const { return !PR || !zs_swr_has(vr, blk); }
+  // the position of member k - t for a step t that was swept: its block is in the ring
+  __device__ __forceinline__ uint32_t member(uint32_t t) const {
+    if constexpr (PR) return R->pos(cc, lane, t);
+    const int j = k() - (int)t;
     return MW ? (uint32_t)mw[j - mw0] : (uint32_t)mem[j];
-  };
-  auto rmbits = [&](const Sig& S, uint32_t slot) -> uint32_t {  // a ring record's matched bits
-    const uint2 ab = R->ab[slot];
-    return S.mbits(ab.x, ab.y, A7 ? 0u : R->c[slot]);
-  };
-  // chunks are claimed one ahead: the next chunk's members (its own and the
-  // block before) are loaded while this one is swept.  PR: a wave claims runs
-  // [c, ce) of consecutive chunks, the next run during the last chunk of this
-  // one; only a run's first chunk needs the members of the block before.
+  }
+
+  // start: the state of the lane at position p before the first step; returns its record
+  __device__ __forceinline__ uint4 start(Lane& L, uint32_t p, bool mem_ok, bool own) const {
+    // the lane's record is built once, and its own signature, hash and the
+    // bytes past the signature are taken from it
+    const uint4 rown = mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0);
+    L.S.a = rown.x;
+    L.S.b = rown.y;
+    if constexpr (!A7) L.S.c = rown.z | 0x01000000u;
+    L.own_ext = A7 ? rown.z : sw_word(win, p + Sig::EXT);
+    L.p = p;
+    L.own = own;
+    const uint32_t h = rown.w >> 16;
+    const uint32_t look = n - p;
+    L.maxc = look < ZS_MAX_MATCH ? look : ZS_MAX_MATCH;  // deflate.ts:1068
+    L.nice = look < nice_cfg ? look : nice_cfg;          // deflate.ts:1078-1080
+    L.long_m = L.tail() ? 0xffffu : Sig::LONG;
+    const uint32_t limit = p > ZS_MAX_DIST ? p - ZS_MAX_DIST : 0u;  // deflate.ts:1060
+    L.khead = (h << 16) | (limit > 1u ? limit : 1u);
+    L.klim = (h << 16) | limit;
+    L.thr = L.thr_s = Sig::THR0;
+    L.bt = L.bt_s = 0;
+    L.lthr = L.lthr_s = ZS_SWL_NONE;
+    L.lbt = L.lbt_s = 0;
+    L.alive_m = 0;
+    L.head = 0;
+    L.snapped = budget_s <= 1u;
+    return rown;
+  }
+
+  // build: the ring's blocks for chunk cc -- its own (from the lanes' records)
+  // and the one before it (positions qb where they were loaded ahead)
+  __device__ __forceinline__ void build(uint4 rown, uint32_t p, uint32_t qb, bool have_qb) {
+    mw0 = 64 * cc - (int)budget;
+    if (MW) mw[k() - mw0] = (uint16_t)p;
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    R->put(cc, lane, rown);
+    if constexpr (PR) vr = zs_swr_push(vr, cc);
+    if (missing(cc - 1)) build_blk(cc - 1, have_qb ? qb : fetch(k() - 64));
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+  }
+
+  // A group's fold: the longest candidate if longer than the best so far.
+  // Long candidates (a full signature match) are rare: when a group holds one
+  // for any lane, those lanes compare the next four bytes of their first long
+  // candidate (its position is in the ring); a candidate matching those too is
+  // extended byte-wise (rarer still).  Which of a group's long candidates a
+  // lane keeps is zs_sweep_long.h's rule: lengths are capped at nice -- the
+  // first nice candidate ends the walk (deflate.ts:1103) and ties with every
+  // later one, so it stays first.
+  // (gm: the maximum of the group's cnt scores sc, 0 for a lane that takes
+  // none; its steps are t0 .. t0 + cnt - 1, step t at slot base - t)
+  __device__ __forceinline__ void fold(Lane& L, uint32_t gm, uint32_t t0, const uint32_t* sc, uint32_t cnt,
+                                       uint32_t base) const {
+    const bool up = gm > (L.thr | 7u);  // longer than the best so far
+    L.thr = up ? gm : L.thr;
+    L.bt = up ? t0 : L.bt;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(gm >= L.long_m) != 0, 0)) {
+      SW_STAT(3, 1);
+      // the score of the long candidate at place u (zs_sweep_long.h)
+      auto lscore = [&](uint32_t u) -> uint32_t {
+        // the next four bytes: A7 records carry them (c), else from the window
+        const uint32_t ls = base - (t0 + u);
+        const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ L.own_ext;
+        const uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
+                               : sw_extend(win, L.p, R->key[ls] & 0xffffu, L.maxc, Sig::EXT + 4u);
+        return zs_swl_score(len, L.maxc, L.nice, u);
+      };
+      const bool lg = gm >= L.long_m && zs_swl_open(L.lthr, L.nice);
+      // The group's maximum names a lane's first long step; nearly always it is
+      // the lane's only one in the group.  Whether some lane has a second one is
+      // counted per lane from the scores packed four to a word (a score is below
+      // 128, and score + 0x80 - LONG has bit 7 exactly when the step is long),
+      // and only then do those lanes visit their other long steps one by one.
+      // (a lane whose chain ended has gm 0, its steps' scores anything: lg)
+      uint32_t w[2] = {0, 0};
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++)
+        if (u < cnt) w[u >> 2] |= sc[u] << (8u * (u & 3u));
+      constexpr uint32_t LB = (0x80u - Sig::LONG) * 0x01010101u;
+      const uint32_t nl = (uint32_t)__builtin_popcount((w[0] + LB) & 0x80808080u) +
+                          (uint32_t)__builtin_popcount((w[1] + LB) & 0x80808080u);
+      const uint64_t twice = __builtin_amdgcn_ballot_w64(lg && nl > 1u);
+      uint32_t gl = 0;
+      const uint32_t u1 = zs_swl_first(gm);
+      if (lg) gl = lscore(u1);
+      if (__builtin_expect(twice != 0, 0)) {
+        if ((twice >> lane) & 1u) {
+          uint32_t lm = 0;
+#pragma unroll
+          for (uint32_t u = 0; u < 8; u++) lm |= (u < cnt && sc[u] >= L.long_m) ? 1u << u : 0u;
+          lm &= ~(1u << u1);
+          while (lm) {
+            gl = zs_swl_join(gl, lscore((uint32_t)__builtin_ctz(lm)));
+            lm &= lm - 1u;
+          }
+        }
+      }
+      zs_swl_fold(gl, t0, &L.lthr, &L.lbt);  // (gl 0: no change)
+    }
+  }
+
+  // Steps t0 .. t0 + N - 1 as one group: step t reads slot base - t, one
+  // address per group (its lowest slot), immediate offsets inside.
+  // Unmasked, for a group in which every live lane is live throughout.
+  // (every lane runs it -- no divergent region, whose join costs register moves --
+  // and a lane whose chain has ended folds nothing)
+  template <uint32_t N>
+  __device__ __forceinline__ void group_fast(Lane& L, uint32_t base, uint32_t t0, bool live) const {
+    const uint32_t lo = base - (t0 + (N - 1u));
+    const uint2* const A = R->ab + lo;
+    const uint32_t* const C = R->c + lo;
+    uint32_t sc[N];
+#pragma unroll
+    for (uint32_t u = 0; u < N; u++) {
+      const uint2 ab = A[N - 1u - u];
+      sc[u] = sw_score(L.S.mbits(ab.x, ab.y, A7 ? 0u : C[N - 1u - u]), u);
+    }
+    fold(L, live ? sw_gmax<N>(sc) : 0u, t0, sc, N, base);
+  }
+  // Masked, for a group in which a chain ends: liveness is monotone in t (keys
+  // fall with the member index), so a step is live iff its own key is (and the
+  // lane was live when the group began); a dead lane's score is 0.  Every load
+  // is issued before the first is waited for.
+  // HEAD: the group begins the walk.  The head candidate (t0 = 1,
+  // deflate.ts:1376) has its own liveness rule, key >= khead, and it starts
+  // alive_m; the chain steps after it are live while their keys are.
+  template <uint32_t N, bool HEAD>
+  __device__ __forceinline__ void group_masked(Lane& L, uint32_t base, uint32_t t0) const {
+    const uint32_t lo = base - (t0 + (N - 1u));
+    const uint2* const A = R->ab + lo;
+    const uint32_t* const C = R->c + lo;
+    const uint32_t* const K = R->key + lo;
+    uint32_t sc[N], key[N];
+    uint2 ab[N];
+#pragma unroll
+    for (uint32_t u = 0; u < N; u++) {
+      key[u] = K[N - 1u - u];
+      ab[u] = A[N - 1u - u];
+    }
+    if constexpr (HEAD) {
+      const bool a1 = L.own && key[0] >= L.khead;
+      L.head = a1 ? 1u | ((L.p - (key[0] & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u) : 0u;
+      L.alive_m = __builtin_amdgcn_ballot_w64(a1);
+    }
+    uint64_t lm = L.alive_m;  // the live lanes
+#pragma unroll
+    for (uint32_t u = 0; u < N; u++) {
+      if (!HEAD || u) {
+        asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key[u]), "v"(L.klim));
+        lm &= L.alive_m;
+      }
+      const uint32_t v = sw_score(L.S.mbits(ab[u].x, ab[u].y, A7 ? 0u : C[N - 1u - u]), u);
+      asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(sc[u]) : "v"(v), "s"(lm));
+    }
+    L.alive_m = sw_uniform(lm);  // the lanes live at the group's last step
+    fold(L, sw_gmax<N>(sc), t0, sc, N, base);
+  }
+
+  // Steps [ta, tb] of a block (ta = 1 mod 4, tb = 0 mod 4, wave-uniform) in
+  // groups of 8 (4 where the range or the snapshot cuts them).  A group in
+  // which every live lane is still live at its last step runs unmasked with
+  // the exec mask of the live lanes; otherwise masked.
+  __device__ __forceinline__ void run(Lane& L, uint32_t base, uint32_t ta, uint32_t tb) const {
+    // the next group's last key is read with this group's records: the fast-or-masked test waits on no load
+    auto last_of = [&](uint32_t t0) __attribute__((always_inline)) {
+      uint32_t t1 = t0 + 7u <= tb ? t0 + 7u : t0 + 3u;
+      if (t0 <= budget_s && t1 > budget_s) t1 = budget_s;
+      return t1;
+    };
+    if (ta > tb) return;
+    uint32_t t0 = ta, t1 = last_of(ta);
+    uint32_t kl = R->key[base - t1];
+    while (L.alive_m) {
+      const bool mine = ((L.alive_m >> lane) & 1u) != 0;
+      const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && kl > L.klim);
+      const uint32_t n0 = t1 + 1u, n1 = n0 <= tb ? last_of(n0) : t1;
+      kl = R->key[base - n1];
+      SW_STAT(last_live == L.alive_m ? 1 : 2, 1);
+      SW_STAT(4, t1 - t0 + 1u);
+      if (last_live == L.alive_m) {
+        if (t1 - t0 == 7u) group_fast<8>(L, base, t0, mine);
+        else group_fast<4>(L, base, t0, mine);
+      } else {
+        if (t1 - t0 == 7u) group_masked<8, false>(L, base, t0);
+        else group_masked<4, false>(L, base, t0);
+      }
+      if (t1 == budget_s) L.snap();
+      if (n0 > tb) break;
+      t0 = n0;
+      t1 = n1;
+    }
+  }
+
+  // sweep: the chain steps 1 .. budget of chunk cc, while a lane's chain lasts
+  __device__ __forceinline__ void sweep(Lane& L) {
+    // Steps 1..8 as ONE masked group where the chain >> 2 snapshot is not before
+    // step 8 (levels 5 and up): one address, one fold.  Level 4 (snapshot at
+    // step 4) takes the pieces: the head, steps 2..4, and the blocks' groups
+    // from step 5.
+    const uint32_t base0 = Ring::base(cc, 0u, lane);
+    const bool open8 = budget_s >= 8u && budget >= 8u;  // wave-uniform
+    if (open8) {
+      group_masked<8, true>(L, base0, 1u);
+      if (budget_s == 8u) L.snap();
+    } else {
+      group_masked<1, true>(L, base0, 1u);
+      if (budget_s == 1u) L.snap();
+      if (budget >= 4u) {
+        group_masked<3, false>(L, base0, 2u);
+        if (budget_s == 4u) L.snap();
+      }
+    }
+    for (uint32_t b = 0; budget > 4u && L.alive_m; b++) {
+      // block b = steps (64b, 64b + 64]: members k0 - 64b - 64 ... k0 - 64b + 62, i.e. the blocks b and b + 1 back
+      const int blk = cc - (int)b - 1;
+      if (b >= 1 && missing(blk)) {
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        build_blk(blk, fetch(64 * blk + (int)lane));
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+      }
+      const uint32_t ta = b == 0 ? (open8 ? 9u : 5u) : 64u * b + 1u;
+      const uint32_t tb = min(64u * b + 64u, budget);
+      run(L, Ring::base(cc, b, lane), ta, tb);
+      if (tb >= budget) break;
+    }
+    if (!L.snapped) L.snap();  // every chain ended before step chain >> 2
+  }
+
+  // settle: the lane's result from its bests -- lengths from the scores,
+  // distances from the members' positions
+  __device__ __forceinline__ void settle(const Lane& L, uint2* out) const {
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    if (!L.own) return;
+    const uint32_t p = L.p;
+    uint32_t rx = 0, ry = 0;
+    if (L.head) {
+      uint32_t len = 2, dist = 0, len_s = 2, dist_s = 0;
+      if (L.tail()) {  // maxc <= 12: min(lcp, maxc) exactly, first maximum in chain order (deflate.ts:1082-1105)
+        const int k = this->k();
+        uint32_t b = 2u << 16, bs = 2u << 16;
+        for (uint32_t t = 1; t <= budget && (int)t <= k; t++) {
+          const uint32_t q = member(t);
+          const uint32_t key = (sw_hash(sw_word(win, q)) << 16) | q;
+          if (t == 1u ? key < L.khead : key <= L.klim) break;
+          // (three straight word compares.  sw_extend(win, p, q, maxc, 0) gives the same min(lcp, maxc), but its
+          // loop inside this serial walk of up to chain steps cost 0.2 ms of level 6's sweep: DESIGN 4.2)
+          uint32_t len = 12;
+          for (uint32_t o = 0; o < 12u; o += 4) {
+            const uint32_t y = sw_word(win, q + o) ^ sw_word(win, p + o);
+            if (y) { len = o + (uint32_t)(__builtin_ctz(y) >> 3); break; }
+          }
+          const uint32_t sc = ((len < L.maxc ? len : L.maxc) << 16) | (0xffffu - t);
+          b = max(b, sc);
+          if (t <= budget_s) bs = max(bs, sc);
+        }
+        len = b >> 16;
+        dist = len > 2u ? p - (uint32_t)mem[k - (int)(0xffffu - (b & 0xffffu))] : 0u;
+        len_s = bs >> 16;
+        dist_s = len_s > 2u ? p - (uint32_t)mem[k - (int)(0xffffu - (bs & 0xffffu))] : 0u;
+      } else {
+        const uint32_t tb = L.bt + 7u - (L.thr & 7u), tb_s = L.bt_s + 7u - (L.thr_s & 7u);  // the steps
+        if (L.bt) {
+          len = Sig::len(L.thr >> 3);
+          dist = p - member(tb);
+        }
+        if (L.bt_s) {
+          len_s = Sig::len(L.thr_s >> 3);
+          dist_s = tb_s == tb ? dist : p - member(tb_s);
+        }
+        // long candidates beat every short one; a nice one's length was capped: measure it
+        auto long_of = [&](uint32_t lt, uint32_t t, uint32_t& ln, uint32_t& ds) {
+          const uint32_t q = member(t);
+          ln = lt >> 3;
+          if (ln >= L.nice) ln = sw_extend(win, p, q, L.maxc, Sig::EXT);
+          ds = p - q;
+        };
+        if (L.lbt) long_of(L.lthr, L.lbt, len, dist);
+        if (L.lbt_s) {
+          if (L.lbt_s == L.lbt) {
+            len_s = len;
+            dist_s = dist;
+          } else {
+            long_of(L.lthr_s, L.lbt_s, len_s, dist_s);
+          }
+        }
+      }
+      rx = (len << 16) | (len > 2u ? dist : 0u) | (L.head & 0x8000u);
+      ry = (len_s << 16) | (len_s > 2u ? dist_s : 0u);
+    }
+    out[p] = make_uint2(rx, ry);
+  }
+};
+
+// The sweep of one window by one wave: results for the own positions
+// [olo, ohi) of its members.  Chunks are claimed one ahead: the next chunk's
+// members (its own and the block before) are loaded while this one is swept.
+// PR: a wave claims runs [c, ce) of consecutive chunks, the next run during
+// the last chunk of this one; only a run's first chunk needs the members of
+// the block before.
+template <bool A7, bool MW, bool PR>
+static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp, uint16_t* mw, uint32_t* next,
+                                               uint32_t n, uint32_t m, uint32_t olo, uint32_t ohi,
+                                               const uint16_t* mem, uint2* out, int chain, int nice_cfg) {
+  using Wave = SwWave<A7, MW, PR>;
+  const uint32_t lane = threadIdx.x & 63u;
+  Wave W{win, (typename Wave::Ring*)ringp, mw, mem, n, m, lane, (uint32_t)chain, (uint32_t)chain >> 2,
+         (uint32_t)nice_cfg, 0, zs_swr_empty(), 0};
+  const uint32_t nchunks = (m + 63) / 64;
   auto claim = [&]() -> uint32_t {
     uint32_t c = 0;
     if (lane == 0) c = atomicAdd(next, 1u);
@@ -549,9 +901,8 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
   uint32_t c, ce = 0;
   if constexpr (PR) claim_run(c, ce);
   else c = claim();
-  uint32_t pf_p = fetch((int)(64 * c + lane)), pf_b = fetch((int)(64 * c + lane) - 64);
-  zs_swr_range vr = zs_swr_empty();  // PR: the blocks the ring holds
-  bool fresh_n = true;               // PR: the next chunk starts a run
+  uint32_t pf_p = W.fetch((int)(64 * c + lane)), pf_b = W.fetch((int)(64 * c + lane) - 64);
+  bool fresh_n = true;  // PR: the next chunk starts a run
   for (;;) {
     if (c >= nchunks) break;
     const bool fresh = fresh_n;  // (wave-uniform) a run's first chunk: pf_b was loaded, the ring holds nothing
@@ -560,19 +911,17 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
       cn = c + 1u;
       fresh_n = cn >= ce;
       if (fresh_n) claim_run(cn, cen);
-      if (fresh) vr = zs_swr_empty();
+      if (fresh) W.vr = zs_swr_empty();
     } else {
       cn = claim();
     }
-    cc = (int)c;
-    const int k0 = (int)(64 * c);
-    const int k = k0 + (int)lane;
-    const bool mem_ok = (uint32_t)k < m;
+    W.cc = (int)c;
+    const bool mem_ok = (uint32_t)W.k() < m;
     SW_STAT(0, 1);
     const uint32_t p = pf_p, qb = pf_b;  // (0 past the members)
     if (cn < nchunks) {
-      pf_p = fetch((int)(64 * cn + lane));
-      if (!PR || fresh_n) pf_b = fetch((int)(64 * cn + lane) - 64);
+      pf_p = W.fetch((int)(64 * cn + lane));
+      if (!PR || fresh_n) pf_b = W.fetch((int)(64 * cn + lane) - 64);
     }
     c = cn;
     ce = cen;
@@ -583,470 +932,14 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
     // next chunk with own lanes builds the block before it again.  In a window of zeros
     // that is 512 chunks of look-back skipped for one block rebuilt.)
     if (__builtin_amdgcn_ballot_w64(own) == 0) {
-      vr = zs_swr_empty();
+      W.vr = zs_swr_empty();
       continue;
     }
-    mw0 = k0 - (int)sbud;
-    if (MW) mw[k - mw0] = (uint16_t)p;
-    // PR: the lane's record is built once, and its own signature, hash and the
-    // bytes past the signature are taken from it
-    const uint4 rown = PR && mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0);
-    Sig S;
-    if constexpr (PR) {
-      S.a = rown.x;
-      S.b = rown.y;
-      if constexpr (!A7) S.c = rown.z | 0x01000000u;
-    } else {
-      S.own(win, p);
-    }
-    const uint32_t h = PR ? rown.w >> 16 : sw_hash(sw_word(win, p));
-    const uint32_t look = n - p;
-    const uint32_t maxc = look < ZS_MAX_MATCH ? look : ZS_MAX_MATCH;                 // deflate.ts:1068
-    const uint32_t nice = look < (uint32_t)nice_cfg ? look : (uint32_t)nice_cfg;      // deflate.ts:1078-1080
-    const bool tail = maxc <= 12u;  // exact re-walk after the sweep
-    const uint32_t long_m = tail ? 0xffffu : Sig::LONG;  // a tail lane records no long candidates
-    const uint32_t limit = p > ZS_MAX_DIST ? p - ZS_MAX_DIST : 0u;                   // deflate.ts:1060
-    const uint32_t khead = (h << 16) | (limit > 1u ? limit : 1u);
-    const uint32_t klim = (h << 16) | limit;
-    // ring: this chunk's block and the one before it
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if constexpr (PR) {
-      put_blk(cc, rown);
-      vr = zs_swr_push(vr, cc);
-      if (!zs_swr_has(vr, cc - 1)) {  // a run's first chunk, or after a skipped one
-        build_blk(cc - 1, fresh ? qb : fetch(k - 64));
-        vr = zs_swr_extend(vr, cc - 1);
-      }
-    } else {
-      put_rec(k, mem_ok ? make_rec(p) : make_uint4(0, 0, 0, 0));
-#if ZS_SW_EXP & 256
-      put_rec(k - 64, make_uint4(qb, qb, qb, 0));  // (timing: the block before without its window reads)
-#else
-      load_rec_q(k - 64, qb);
-#endif
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-
-    // the best short candidate: its group's maximum score (matched bits, 7 - its place in the group) and the
-    // group's first step (0: none) -- the step itself, t0 + 7 - (score & 7), is formed once at the end
-    uint32_t thr = Sig::THR0, thr_s = Sig::THR0;
-    uint32_t bt = 0, bt_s = 0;
-    // best long candidate: its length (capped at nice) as lthr = len << 3 | 7, its step
-    uint32_t lthr = 7u, lbt = 0, lthr_s = 7u, lbt_s = 0;
-    const uint32_t own_ext = PR && A7 ? rown.z : sw_word(win, p + Sig::EXT);  // the lane's bytes past a full signature
-    uint64_t alive_m = 0;
-    uint32_t head = 0;  // bit 0: head candidate valid; 0x8000: at exactly MAX_DIST
-    // step t of block 0's numbering reads ring slot base - t
-    auto score = [&](uint32_t mb, uint32_t u) -> uint32_t { return (mb & ~7u) | (7u - u); };  // one v_and_or_b32
-    // a group's fold: the longest candidate if longer than the best so far.
-    // Long candidates (a full signature match) are rare: when a group holds one
-    // for any lane, those lanes compare the next four bytes of their first long
-    // candidate (its position is in the ring); a candidate matching those too is
-    // extended byte-wise (rarer still).  Which of a group's long candidates a
-    // lane keeps is zs_sweep_long.h's rule: lengths are capped at nice -- the
-    // first nice candidate ends the walk (deflate.ts:1103) and ties with every
-    // later one, so it stays first.
-    auto fold = [&](uint32_t gm, uint32_t t0, const uint32_t* sc, uint32_t cnt, uint32_t base)
-        __attribute__((always_inline)) {
-#if ZS_SW_EXP & 4096  // (A/B: the step formed per group)
-      const bool up = gm > thr;
-      thr = max(thr, gm | 7u);
-      bt = up ? t0 + 7u - (gm & 7u) : bt;
-#else
-      const bool up = gm > (thr | 7u);  // longer than the best so far
-      thr = up ? gm : thr;
-      bt = up ? t0 : bt;
-#endif
-#if ZS_SW_EXP & 32
-      if (0) {
-#else
-      if (__builtin_expect(__builtin_amdgcn_ballot_w64(gm >= long_m) != 0, 0)) {
-#endif
-        SW_STAT(3, 1);
-        // the score of the long candidate at place u (zs_sweep_long.h)
-        auto lscore = [&](uint32_t u) -> uint32_t {
-          // the next four bytes: A7 records carry them (c), else from the window
-          const uint32_t ls = at(base, t0 + u);
-          const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ own_ext;
-          const uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
-                                 : sw_extend(win, p, R->key[ls] & 0xffffu, maxc, Sig::EXT + 4u);
-          return zs_swl_score(len, maxc, nice, u);
-        };
-        const bool lg = gm >= long_m && zs_swl_open(lthr, nice);
-#if ZS_SW_EXP & 1024  // (A/B: every lane's long steps as a mask, visited one by one)
-        if (lg) {
-          uint32_t gl = 0, lm = 0;
-#pragma unroll
-          for (uint32_t u = 0; u < 8; u++) lm |= (u < cnt && sc[u] >= long_m) ? 1u << u : 0u;
-          while (lm) {
-            gl = zs_swl_join(gl, lscore((uint32_t)__builtin_ctz(lm)));
-            lm &= lm - 1u;
-          }
-          zs_swl_fold(gl, t0, &lthr, &lbt);
-        }
-#else
-        // The group's maximum names a lane's first long step; nearly always it is
-        // the lane's only one in the group.  Whether some lane has a second one is
-        // counted per lane from the scores packed four to a word (a score is below
-        // 128, and score + 0x80 - LONG has bit 7 exactly when the step is long),
-        // and only then do those lanes visit their other long steps one by one.
-        // (a lane whose chain ended has gm 0, its steps' scores anything: lg)
-#if ZS_SW_EXP & 8  // (A/B: the steps' lane masks intersected on the scalar unit: 8 VALU, 20 SALU)
-        uint64_t seen = 0, twice = 0;
-#pragma unroll
-        for (uint32_t u = 0; u < 8; u++)
-          if (u < cnt) {
-            const uint64_t mu = __builtin_amdgcn_ballot_w64(sc[u] >= long_m);
-            twice |= seen & mu;
-            seen |= mu;
-          }
-        twice &= __builtin_amdgcn_ballot_w64(lg);
-#else
-        uint32_t w[2] = {0, 0};
-#pragma unroll
-        for (uint32_t u = 0; u < 8; u++)
-          if (u < cnt) w[u >> 2] |= sc[u] << (8u * (u & 3u));
-        constexpr uint32_t LB = (0x80u - Sig::LONG) * 0x01010101u;
-        const uint32_t nl = (uint32_t)__builtin_popcount((w[0] + LB) & 0x80808080u) +
-                            (uint32_t)__builtin_popcount((w[1] + LB) & 0x80808080u);
-        const uint64_t twice = __builtin_amdgcn_ballot_w64(lg && nl > 1u);
-#endif
-        uint32_t gl = 0;
-        const uint32_t u1 = zs_swl_first(gm);
-        if (lg) gl = lscore(u1);
-        if (__builtin_expect(twice != 0, 0)) {
-          if ((twice >> lane) & 1u) {
-            uint32_t lm = 0;
-#pragma unroll
-            for (uint32_t u = 0; u < 8; u++) lm |= (u < cnt && sc[u] >= long_m) ? 1u << u : 0u;
-            lm &= ~(1u << u1);
-            while (lm) {
-              gl = zs_swl_join(gl, lscore((uint32_t)__builtin_ctz(lm)));
-              lm &= lm - 1u;
-            }
-          }
-        }
-        zs_swl_fold(gl, t0, &lthr, &lbt);  // (gl 0: no change)
-#endif
-      }
-    };
-    bool snapped = budget_s <= 1u;  // wave-uniform: step chain >> 2 has been folded
-    auto snap = [&](uint32_t t1) __attribute__((always_inline)) {
-      if (t1 == budget_s) {  // the chain >> 2 result (deflate.ts:1075-1077)
-        thr_s = thr;
-        bt_s = bt;
-        lthr_s = lthr;
-        lbt_s = lbt;
-        snapped = true;
-      }
-    };
-    // block 0: step t at slot at(base0, t)
-    const uint32_t base0 = PR ? zs_swr_base(cc, 0u) + lane : (((uint32_t)(k - 64)) & (ZS_SW_RING - 1)) + 64u;
-    // Steps 1..8 as ONE masked group where the chain >> 2 snapshot is not before
-    // step 8 (levels 5 and up): one address, every load issued before the first
-    // is waited for, one fold.  The head candidate (t = 1, deflate.ts:1376) has
-    // its own liveness rule; the chain steps after it are live while their keys
-    // are (below).  Level 4 (snapshot at step 4) takes the pieces: the head,
-    // steps 2..4, and the blocks' groups from step 5.
-#if ZS_SW_EXP & 2048  // (A/B: the pieces at every level)
-    const bool open8 = false;
-#else
-    const bool open8 = budget_s >= 8u && sbud >= 8u;  // wave-uniform
-#endif
-    if (open8) {
-      const uint32_t lo = at(base0, 8u);
-      const uint2* const A = R->ab + lo;
-      const uint32_t* const C = R->c + lo;
-      const uint32_t* const K = R->key + lo;
-      uint32_t sc[8], key[8];
-      uint2 ab[8];
-#pragma unroll
-      for (uint32_t u = 0; u < 8; u++) {
-        key[u] = K[7u - u];
-        ab[u] = A[7u - u];
-      }
-      const bool a1 = own && key[0] >= khead;
-      head = a1 ? 1u | ((p - (key[0] & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u) : 0u;
-      alive_m = __builtin_amdgcn_ballot_w64(a1);
-      uint64_t lm = alive_m;
-#pragma unroll
-      for (uint32_t u = 0; u < 8; u++) {
-        if (u) {
-          asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key[u]), "v"(klim));
-          lm &= alive_m;
-        }
-        const uint32_t v = score(S.mbits(ab[u].x, ab[u].y, A7 ? 0u : C[7u - u]), u);
-        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(sc[u]) : "v"(v), "s"(lm));
-      }
-      alive_m = sw_uniform(lm);  // the lanes live at step 8
-      fold(max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7]))), 1u, sc, 8u, base0);
-      snap(8u);
-    } else {
-      const uint32_t key = R->key[at(base0, 1u)];
-      bool a1 = false;
-      uint32_t sc[1] = {0};
-      if (own && key >= khead) {
-        a1 = true;
-        head = 1u | ((p - (key & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u);
-        sc[0] = score(rmbits(S, at(base0, 1u)), 0);
-      }
-      alive_m = __builtin_amdgcn_ballot_w64(a1);
-      fold(sc[0], 1u, sc, 1u, base0);
-      snap(1u);
-    }
-    // masked step (blocks in which a chain ends): 0 for a lane whose chain ended
-    // masked step (groups in which a chain ends): liveness is monotone in t
-    // (keys fall with the member index), so a step is live iff its own key is
-    // (and the lane was live when the group began); lm = the live lanes
-    auto mstep = [&](uint32_t slot, uint32_t u, uint64_t& lm) -> uint32_t {
-      const uint32_t key = R->key[slot];
-      asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key), "v"(klim));
-      lm &= alive_m;
-      const uint32_t v = score(rmbits(S, slot), u);
-      uint32_t r;
-      asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(v), "s"(lm));
-      return r;
-    };
-    // steps 2..4 (masked)
-    if (!open8 && sbud >= 4u) {
-      uint32_t sc[3];
-      uint64_t lm = 0;
-#pragma unroll
-      for (uint32_t u = 0; u < 3; u++) sc[u] = mstep(at(base0, 2u + u), u, lm);
-      alive_m = sw_uniform(lm);  // the lanes live at step 4
-      fold(max3(sc[0], sc[1], sc[2]), 2u, sc, 3u, base0);
-      snap(4u);
-    }
-    // Steps [ta, tb] of block b (ta = 1 mod 4, tb = 0 mod 4, wave-uniform):
-    // step t reads slot base - t, one address per group, immediate offsets inside.
-    // (every lane runs it -- no divergent region, whose join costs register moves --
-    // and a lane whose chain has ended folds nothing)
-    auto group_fast = [&](uint32_t base, uint32_t t0, auto G, bool live) __attribute__((always_inline)) {
-      constexpr uint32_t N = decltype(G)::value;
-      // from the group's lowest slot up: one address, immediate offsets
-      const uint32_t lo = at(base, t0 + (N - 1u));
-      const uint2* const A = R->ab + lo;
-      const uint32_t* const C = R->c + lo;
-      uint32_t sc[N];
-#pragma unroll
-      for (uint32_t u = 0; u < N; u++) {
-        const uint2 ab = A[N - 1u - u];
-        sc[u] = score(S.mbits(ab.x, ab.y, A7 ? 0u : C[N - 1u - u]), u);
-      }
-      uint32_t gm;
-      if constexpr (N == 8)
-        gm = max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7])));
-      else
-        gm = max3(sc[0], sc[1], max(sc[2], sc[3]));
-      fold(live ? gm : 0u, t0, sc, N, base);
-    };
-    // (like group_fast: one address, immediate offsets, every load issued before the first is waited for)
-    auto group_masked = [&](uint32_t base, uint32_t t0, auto G) __attribute__((always_inline)) {
-      constexpr uint32_t N = decltype(G)::value;
-#if ZS_SW_EXP & 8192  // (A/B: step by step, an address and a wait each)
-      uint32_t sc[8];
-      uint64_t lm = 0, last = 0;
-#pragma unroll
-      for (uint32_t u = 0; u < 8; u++) {
-        sc[u] = 0u;
-        if (u < N) {
-          sc[u] = mstep(at(base, t0 + u), u, lm);
-          last = lm;
-        }
-      }
-      alive_m = sw_uniform(last);  // the lanes live at the group's last step
-      fold(max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7]))), t0, sc, N, base);
-#else
-      const uint32_t lo = at(base, t0 + (N - 1u));
-      const uint2* const A = R->ab + lo;
-      const uint32_t* const C = R->c + lo;
-      const uint32_t* const K = R->key + lo;
-      uint32_t sc[N], key[N];
-      uint2 ab[N];
-#pragma unroll
-      for (uint32_t u = 0; u < N; u++) {
-        key[u] = K[N - 1u - u];
-        ab[u] = A[N - 1u - u];
-      }
-      uint64_t lm = 0;
-#pragma unroll
-      for (uint32_t u = 0; u < N; u++) {
-        asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key[u]), "v"(klim));
-        lm &= alive_m;
-        const uint32_t v = score(S.mbits(ab[u].x, ab[u].y, A7 ? 0u : C[N - 1u - u]), u);
-        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(sc[u]) : "v"(v), "s"(lm));
-      }
-      alive_m = sw_uniform(lm);  // the lanes live at the group's last step
-      uint32_t gm;
-      if constexpr (N == 8)
-        gm = max(max3(sc[0], sc[1], sc[2]), max3(sc[3], sc[4], max3(sc[5], sc[6], sc[7])));
-      else
-        gm = max3(sc[0], sc[1], max(sc[2], sc[3]));
-      fold(gm, t0, sc, N, base);
-#endif
-    };
-    using G8 = std::integral_constant<uint32_t, 8>;
-    using G4 = std::integral_constant<uint32_t, 4>;
-    // Steps [ta, tb] of a block in groups of 8 (4 where the range or the
-    // snapshot cuts them).  A group in which every live lane is still live at
-    // its last step runs unmasked with the exec mask of the live lanes;
-    // otherwise masked.
-    auto run = [&](uint32_t base, uint32_t ta, uint32_t tb) __attribute__((always_inline)) {
-#if !(ZS_SW_EXP & 16384)
-      // the next group's last key is read with this group's records: the fast-or-masked test waits on no load
-      auto last_of = [&](uint32_t t0) __attribute__((always_inline)) {
-        uint32_t t1 = t0 + 7u <= tb ? t0 + 7u : t0 + 3u;
-        if (t0 <= budget_s && t1 > budget_s) t1 = budget_s;
-        return t1;
-      };
-      if (ta > tb) return;
-      uint32_t t0 = ta, t1 = last_of(ta);
-      uint32_t kl = R->key[at(base, t1)];
-      while (alive_m) {
-        const bool mine = ((alive_m >> lane) & 1u) != 0;
-        const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && kl > klim);
-        const uint32_t n0 = t1 + 1u, n1 = n0 <= tb ? last_of(n0) : t1;
-        kl = R->key[at(base, n1)];
-        if (last_live == alive_m) {
-          SW_STAT(1, 1);
-          SW_STAT(4, t1 - t0 + 1u);
-          if (t1 - t0 == 7u) group_fast(base, t0, G8{}, mine);
-          else group_fast(base, t0, G4{}, mine);
-        } else {
-          SW_STAT(2, 1);
-          SW_STAT(4, t1 - t0 + 1u);
-          if (t1 - t0 == 7u) group_masked(base, t0, G8{});
-          else group_masked(base, t0, G4{});
-        }
-        snap(t1);
-        if (n0 > tb) break;
-        t0 = n0;
-        t1 = n1;
-      }
-#else
-      for (uint32_t t0 = ta; t0 <= tb && alive_m;) {
-        uint32_t t1 = t0 + 7u <= tb ? t0 + 7u : t0 + 3u;
-        if (t0 <= budget_s && t1 > budget_s) t1 = budget_s;
-        const bool mine = ((alive_m >> lane) & 1u) != 0;
-        const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && R->key[at(base, t1)] > klim);
-#if ZS_SW_EXP & 4
-        if (0) {
-#elif ZS_SW_EXP & 16
-        if (1) {
-#else
-        if (last_live == alive_m) {
-#endif
-          SW_STAT(1, 1);
-          SW_STAT(4, t1 - t0 + 1u);
-          if (t1 - t0 == 7u) group_fast(base, t0, G8{}, mine);
-          else group_fast(base, t0, G4{}, mine);
-        } else {
-          SW_STAT(2, 1);
-          SW_STAT(4, t1 - t0 + 1u);
-          if (t1 - t0 == 7u) group_masked(base, t0, G8{});
-          else group_masked(base, t0, G4{});
-        }
-        snap(t1);  // (every lane: one whose chain ended has its final best already)
-        t0 = t1 + 1u;
-      }
-#endif
-    };
-    for (uint32_t b = 0; sbud > 4u && alive_m; b++) {
-      // block b = steps (64b, 64b + 64]: members k0 - 64b - 64 ... k0 - 64b + 62, i.e. the blocks b and b + 1 back
-      // (PR: only where the ring does not hold it -- a run's first chunk, or after a skipped one)
-      if (b >= 1 && (!PR || !zs_swr_has(vr, cc - (int)b - 1))) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-        if constexpr (PR) {
-          build_blk(cc - (int)b - 1, fetch(k - 64 * (int)(b + 1)));
-          vr = zs_swr_extend(vr, cc - (int)b - 1);
-        } else {
-          load_rec(k - 64 * (int)(b + 1));
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-      }
-      const uint32_t ta = b == 0 ? (open8 ? 9u : 5u) : 64u * b + 1u;
-      const uint32_t tb = min(64u * b + 64u, sbud);
-      // step t of this block at slot base - t
-      const uint32_t base = PR ? zs_swr_base(cc, b) + lane
-                               : (((uint32_t)(k - 64 * (int)b - 64)) & (ZS_SW_RING - 1)) + 64u * b + 64u;
-      run(base, ta, tb);
-      if (tb >= sbud) break;
-    }
-    if (!snapped) {  // every chain ended before step chain >> 2
-      thr_s = thr;
-      bt_s = bt;
-      lthr_s = lthr;
-      lbt_s = lbt;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (own) {
-      uint32_t rx = 0, ry = 0;
-      if (head) {
-        uint32_t L = 2, D = 0, Ls = 2, Ds = 0;
-        if (tail) {  // maxc <= 12: min(lcp, maxc) exactly, first maximum in chain order (deflate.ts:1082-1105)
-          uint32_t b = 2u << 16, bs = 2u << 16;
-          for (uint32_t t = 1; t <= budget && (int)t <= k; t++) {
-            const uint32_t q = t <= sbud ? member(k - (int)t) : (uint32_t)mem[k - (int)t];
-            const uint32_t key = (sw_hash(sw_word(win, q)) << 16) | q;
-            if (t == 1u ? key < khead : key <= klim) break;
-            uint32_t len = 12;
-            for (uint32_t o = 0; o < 12u; o += 4) {
-              const uint32_t y = sw_word(win, q + o) ^ sw_word(win, p + o);
-              if (y) { len = o + (uint32_t)(__builtin_ctz(y) >> 3); break; }
-            }
-            const uint32_t sc = ((len < maxc ? len : maxc) << 16) | (0xffffu - t);
-            b = max(b, sc);
-            if (t <= budget_s) bs = max(bs, sc);
-          }
-          L = b >> 16;
-          D = L > 2u ? p - (uint32_t)mem[k - (int)(0xffffu - (b & 0xffffu))] : 0u;
-          Ls = bs >> 16;
-          Ds = Ls > 2u ? p - (uint32_t)mem[k - (int)(0xffffu - (bs & 0xffffu))] : 0u;
-        } else {
-#if ZS_SW_EXP & 4096
-          const uint32_t tb = bt, tb_s = bt_s;
-#else
-          const uint32_t tb = bt + 7u - (thr & 7u), tb_s = bt_s + 7u - (thr_s & 7u);  // the steps
-#endif
-          if (bt) {
-            L = Sig::len(thr >> 3);
-            D = p - member(k - (int)tb);
-          }
-          if (bt_s) {
-            Ls = Sig::len(thr_s >> 3);
-            Ds = tb_s == tb ? D : p - member(k - (int)tb_s);
-          }
-          // long candidates beat every short one; a nice one's length was capped: measure it
-          auto long_of = [&](uint32_t lt, uint32_t t, uint32_t& len, uint32_t& dist) {
-            const uint32_t q = member(k - (int)t);
-            len = lt >> 3;
-            if (len >= nice) len = sw_extend(win, p, q, maxc, Sig::EXT);
-            dist = p - q;
-          };
-          if (lbt) long_of(lthr, lbt, L, D);
-          if (lbt_s) {
-            if (lbt_s == lbt) {
-              Ls = L;
-              Ds = D;
-            } else {
-              long_of(lthr_s, lbt_s, Ls, Ds);
-            }
-          }
-        }
-        rx = (L << 16) | (L > 2u ? D : 0u) | (head & 0x8000u);
-        ry = (Ls << 16) | (Ls > 2u ? Ds : 0u);
-      }
-#if ZS_SW_EXP & 512
-      if (rx == 0x12345678u) out[p] = make_uint2(rx, ry);  // (timing: without the result stores)
-#else
-      out[p] = make_uint2(rx, ry);
-#endif
-    }
+    typename Wave::Lane L;
+    const uint4 rown = W.start(L, p, mem_ok, own);
+    W.build(rown, p, qb, fresh);
+    W.sweep(L);
+    W.settle(L, out);
   }
 }
 
