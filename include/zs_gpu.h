@@ -233,6 +233,48 @@ int zs_pool_inflate_batch_dict_auto(zs_pool *pool, int wbits, uint32_t n_streams
                                     uint32_t *consumed, uint32_t *check, const uint8_t *dict,
                                     const uint64_t *dict_off, const uint32_t *dict_len);
 
+/* Compression against preset dictionaries, raw deflate (-15) and zlib (15): stream
+ * i is the bytes of deflateInit2_(level, Z_DEFLATED, wbits, 8, Z_DEFAULT_STRATEGY),
+ * then deflateSetDictionary(strm, dict, dict_len[i]) (deflate.ts:367-424) when
+ * dict_len[i] > 0, then the stream layer's one write() + close() as in the
+ * entries above.  The window takes a dictionary's last 32,768 bytes (deflate.ts:383-392).
+ *
+ * The entries take the arguments of their _ex counterparts plus the dictionaries,
+ * with the conventions of the zs_inflate_batch_dict* entries: dict_off / dict_len
+ * are host arrays of n_streams entries, entries may alias, a length of 0 means no
+ * dictionary (that stream's bytes are the plain entries'), any byte offset.
+ *  - zlib: FDICT is set, FCHECK taken with it, and DICTID -- the adler32 of ALL
+ *    dict_len[i] bytes -- follows the header (deflate.ts:767-778); the trailer and
+ *    check[i] are the adler32 of the data alone (the check restarts at 1);
+ *  - raw: no header; check[i] stays 1;
+ *  - gzip (31; deflateSetDictionary returns Z_STREAM_ERROR for wrap 2,
+ *    deflate.ts:373) with any non-zero dict_len: the call returns ZS_STREAM_ERROR;
+ *  - level 0 with any non-zero dict_len: the call returns ZS_STREAM_ERROR (not
+ *    built: deflate_stored's block cuts after a dictionary depend on the stream
+ *    layer's buffer sizes, which no available yardstick reproduces);
+ *  - invalid level, short capacity (Z_BUF_ERROR), statuses and messages as the
+ *    plain entries.  Size outputs with zs_deflate_bound_dict.
+ * A call whose dict_len are all 0 is the counterpart's call. */
+/* deflateBound after deflateSetDictionary (deflate.ts:633: four more bytes for
+ * DICTID in a zlib stream): zs_deflate_bound, plus 4 for wbits 15 and dict_len > 0. */
+uint64_t zs_deflate_bound_dict(uint64_t source_len, int wbits, uint64_t dict_len);
+/* deflate.ts:367-424, :767-778 -- device buffers (as zs_deflate_batch_device_ex) */
+int zs_deflate_batch_dict_device(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                 uint32_t *d_out_len, uint32_t *d_check, void *hip_stream, const uint8_t *d_dict,
+                                 const uint64_t *dict_off, const uint32_t *dict_len);
+/* deflate.ts:367-424, :767-778 -- host buffers (as zs_deflate_batch_ex) */
+int zs_deflate_batch_dict(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                          const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                          const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
+                          const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len);
+/* deflate.ts:367-424, :767-778 -- the pool (as zs_pool_deflate_batch) */
+int zs_pool_deflate_batch_dict(zs_pool *pool, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                               const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                               const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
+                               const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len);
+
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);
 

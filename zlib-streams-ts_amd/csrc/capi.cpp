@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zs_gpu.h"
@@ -101,6 +102,7 @@ struct zs_ctx {
   hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
   Buf wlist;
   Buf dadler, d_dict;  // preset dictionaries: the distinct ones' adler32; the host entries' staging of their bytes
+  Buf djoin;           // deflate with dictionaries: the joined streams (zs_k_dict_join)
   zs_dict_set dset;
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
@@ -370,6 +372,10 @@ uint64_t zs_deflate_bound(uint64_t n, int wbits) {  // deflate.ts:615-674, memLe
   return b;  // (output capacities must still be multiples of 4: round up when allocating)
 }
 
+uint64_t zs_deflate_bound_dict(uint64_t n, int wbits, uint64_t dict_len) {  // deflate.ts:633: DICTID (zlib, strstart != 0)
+  return zs_deflate_bound(n, wbits) + (wbits == 15 && dict_len ? 4u : 0u);
+}
+
 }  // extern "C"
 
 // Device metadata block: in_off | in_len | out_off | out_cap | pos_base | blk_base
@@ -400,6 +406,14 @@ struct Batch {
   uint8_t* out;
   const uint64_t* out_off;
   const uint32_t* out_cap;
+};
+
+// The preset dictionaries of a batch: the bytes in device memory, host arrays of
+// the members' offsets and lengths (length 0: none)
+struct DictIn {
+  const uint8_t* d_dict;
+  const uint64_t* off;
+  const uint32_t* len;
 };
 
 // Fills the host copy of the metadata block (`bytes` of it) from h's host arrays
@@ -467,8 +481,15 @@ static int deflate_stored_batch(zs_ctx* c, int wrap, const Batch& h, int32_t* d_
 // (1..3); then trees, layout, emit, wrapper, statuses.  (A pipeline of chunks of
 // streams -- chunk j's parse .. emit on a side stream beside chunk j + 1's sweep
 // -- measured slower twice: DESIGN 5, tools/variants/r05_paths.patch.)
+// A batch with preset dictionaries (dd): b holds the JOINED streams (dictionary tail + data,
+// DESIGN 4.6), dd->data the caller's data (the check values are over the data alone); the
+// parse starts at dd->start[s], the zlib wrapper carries FDICT / DICTID.
+struct DeflDict {
+  const Batch* data;
+  const uint32_t *start, *did, *dadler;
+};
 static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const zs_level_cfg& cfg, const Batch& b,
-                          const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len) {
+                          const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len, const DeflDict* dd = nullptr) {
   const zs_deflate_plan& p = c->dp;
   const uint32_t n = b.n;
   const uint8_t* dm = c->meta.as<uint8_t>();
@@ -482,7 +503,8 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
   const int nthreads_s = 256, nblocks_s = (int)((n + 255) / 256);
   MARK("start");
   if (wrap) {
-    zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
+    const Batch& d = dd ? *dd->data : b;
+    zs_k_checksum<<<n, 64, 0, st>>>(d.in, d.in_off, d.in_len, check, wrap == 1 ? 1 : 2);
     zs_k_copy_check<<<nblocks_s, nthreads_s, 0, st>>>(check, d_st, (int)n);
     MARK("checksum");
   }
@@ -507,30 +529,46 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
   }
   if (level >= 4) {
     const int pw = p.pw;  // waves per stream of the lazy parse (deflate_parse.hip)
-    auto parse = pw == 4 ? zs_k_parse_4w : pw == 2 ? zs_k_parse_2w : zs_k_parse;
-    parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
-                                 c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
+    if (dd) {
+      auto parse = pw == 4 ? zs_k_parse_4w_dict : pw == 2 ? zs_k_parse_2w_dict : zs_k_parse_dict;
+      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
+                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, dd->start);
+    } else {
+      auto parse = pw == 4 ? zs_k_parse_4w : pw == 2 ? zs_k_parse_2w : zs_k_parse;
+      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
+                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
+    }
     MARK("parse");
   } else {
     const int fast_smem = 2 * 32768 * 2 + 32768;  // head[] + prev[] (u16 x 32 K each) + the 32 KiB input ring
-    // levels 1..3: the group-speculative replay (default) or the step-by-step one (fast_group = 0)
-    auto fast = !c->fast_group ? zs_k_fast_serial
-                : c->lane_order   ? (cfg.nice <= 8 ? zs_k_fast<2, true> : cfg.nice <= 16 ? zs_k_fast<4, true> : zs_k_fast<8, true>)
-                                  : (cfg.nice <= 8 ? zs_k_fast<2, false> : cfg.nice <= 16 ? zs_k_fast<4, false> : zs_k_fast<8, false>);
+    // levels 1..3: the group-speculative replay (default) or the step-by-step one (fast_group = 0);
+    // the DICT instances for a batch with dictionaries
+    auto pick = [&](auto D) {
+      constexpr bool DICT = decltype(D)::value;
+      return !c->fast_group ? zs_k_fast_serial<DICT>
+             : c->lane_order ? (cfg.nice <= 8 ? zs_k_fast<2, true, DICT> : cfg.nice <= 16 ? zs_k_fast<4, true, DICT> : zs_k_fast<8, true, DICT>)
+                             : (cfg.nice <= 8 ? zs_k_fast<2, false, DICT> : cfg.nice <= 16 ? zs_k_fast<4, false, DICT> : zs_k_fast<8, false, DICT>);
+    };
+    auto fast = dd ? pick(std::true_type{}) : pick(std::false_type{});
     HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, fast_smem));
-    fast<<<n, 64, fast_smem, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st,
-                                        cfg.chain, cfg.lazy, cfg.nice);
+    fast<<<n, 64, fast_smem, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                   cfg.nice, dd ? dd->start : nullptr);
     MARK("fast");
   }
   zs_k_trees<<<dim3(p.max_blk, n), 64, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
                                                 c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n);
   MARK("trees");
-  zs_k_layout<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n);
+  if (dd) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
+                                                             dd->start);
+  else zs_k_layout<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n);
   MARK("layout");
   zs_k_emit<<<dim3(p.max_blk, n), 256, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
                                                 c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), b.out, b.out_off, wrap);
   MARK("emit");
-  if (wrap) zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n);
+  if (wrap && dd)
+    zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, dd->start,
+                                                     dd->did, dd->dadler);
+  else if (wrap) zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n);
   zs_k_finish<<<nblocks_s, nthreads_s, 0, st>>>(d_st, d_status, d_out_len, (int)n);
   MARK("finish");
   return ZS_OK;
@@ -552,8 +590,10 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
 // `caller_regions` (the public device entries): the regions are the caller's
 // buffers, so capacities must be multiples of 4; the host entries stage in
 // regions of the capacities rounded up and pass the exact capacities.
+// `dict` (the _dict entries): the streams' preset dictionaries; a batch with none
+// of them set is the plain batch.
 static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                          uint32_t* d_check, void* hip_stream, bool caller_regions) {
+                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION, deflate.ts:268-270
   int wrap;
@@ -562,6 +602,21 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   else if (wbits == 31) wrap = 2;
   else return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15 or 31)");
   if (level < 0 || level > 9) return fail(ZS_STREAM_ERROR, "invalid level");  // deflate.ts:281-294
+  // The streams' dictionaries (dict: the _dict entries), the distinct ones found once.
+  // deflateSetDictionary refuses gzip (wrap == 2, deflate.ts:373); level 0 is not built.
+  zs_dict_set& ds = c->dset;
+  ds.any = false;
+  if (dict && h.n) {
+    if (!dict->off || !dict->len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
+    zs_dict_distinct(h.n, dict->off, dict->len, ds);
+    if (ds.any && !dict->d_dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
+    if (ds.any && wrap == 2) return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
+    if (ds.any && level == 0) return fail(ZS_STREAM_ERROR, "level 0 with a preset dictionary is not built");
+    for (uint32_t i = 0; ds.any && i < h.n; i++)
+      if (dict->len[i] && h.in_len[i] > 0xffffffffu - ZS_W_SIZE)
+        return fail(ZS_STREAM_ERROR, "stream too long for a preset dictionary");
+  }
+  const bool hasdict = ds.any;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
   HIPCHK(hipSetDevice(c->device));
   const uint32_t n = h.n;
@@ -579,8 +634,20 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   }
   // host-side layout: workspace bases (and the sweep's windows, levels 4..9)
   zs_deflate_plan& p = c->dp;
-  zs_plan_deflate(c->o, level, n, h.in_len, p);
+  zs_plan_deflate(c->o, level, n, h.in_len, p, hasdict ? dict->len : nullptr);
   const MetaLayout ml(n, (uint32_t)p.segs.size());
+  // behind the batch's metadata: the streams' dictionary offsets, lengths, ids and parse starts, the
+  // joined streams' offsets and lengths, the distinct dictionaries' offsets and lengths
+  const size_t nu = hasdict ? ds.uoff.size() : 0;
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
+               m_start = m_did + up256(4ull * n), m_joff = m_start + up256(4ull * n),
+               m_jlen = m_joff + up256(8ull * n), m_uoff = m_jlen + up256(4ull * n),
+               m_ulen = m_uoff + up256(8ull * nu), m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
+  if (hasdict) {
+    HIPCHK(c->djoin.ensure(p.J + 16));
+    HIPCHK(c->dadler.ensure(4ull * nu));
+  }
   HIPCHK(c->prevd.ensure(p.prevd_bytes));
   HIPCHK(c->mres.ensure(p.mres_bytes));
   HIPCHK(c->syms.ensure(p.syms_bytes));
@@ -591,12 +658,42 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   HIPCHK(c->hdr.ensure(p.hdr_bytes));
   HIPCHK(c->check.ensure(4ull * n));
   Batch b;
-  int r = upload_batch(c, st, ml, ml.bytes, h, &b, [&](uint8_t* hm) {
+  int r = upload_batch(c, st, ml, m_end, h, &b, [&](uint8_t* hm) {
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * n);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * n);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
+    if (!hasdict) return;
+    memcpy(hm + m_doff, dict->off, 8ull * n);
+    memcpy(hm + m_dlen, dict->len, 4ull * n);
+    memcpy(hm + m_did, ds.id.data(), 4ull * n);
+    memcpy(hm + m_start, p.start.data(), 4ull * n);
+    memcpy(hm + m_joff, p.joff.data(), 8ull * n);
+    uint32_t* jl = (uint32_t*)(hm + m_jlen);
+    for (uint32_t i = 0; i < n; i++) jl[i] = p.start[i] + h.in_len[i];
+    memcpy(hm + m_uoff, ds.uoff.data(), 8ull * nu);
+    memcpy(hm + m_ulen, ds.ulen.data(), 4ull * nu);
   });
-  if (r == ZS_OK) r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len);
+  if (r == ZS_OK && hasdict) {
+    const uint8_t* dm = c->meta.as<uint8_t>();
+    const uint32_t* d_start = (const uint32_t*)(dm + m_start);
+    const uint64_t* d_joff = (const uint64_t*)(dm + m_joff);
+    MARK("start");
+    // DICTID (zlib): the adler32 of each distinct dictionary, once
+    if (wrap == 1)
+      zs_k_checksum<<<(uint32_t)nu, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + m_uoff),
+                                                 (const uint32_t*)(dm + m_ulen), c->dadler.as<uint32_t>(), 1);
+    // the joined streams: 4 KiB per workgroup
+    zs_k_dict_join<<<dim3(std::max(1u, (uint32_t)(((uint64_t)p.max_len + 4095) / 4096)), n), 256, 0, st>>>(
+        b.in, b.in_off, b.in_len, dict->d_dict, (const uint64_t*)(dm + m_doff), (const uint32_t*)(dm + m_dlen),
+        d_start, c->djoin.as<uint8_t>(), d_joff);
+    MARK("dict_join");
+    HIPCHK(hipGetLastError());
+    const Batch bj = {n, c->djoin.as<uint8_t>(), d_joff, (const uint32_t*)(dm + m_jlen), b.out, b.out_off, b.out_cap};
+    const DeflDict dd = {&b, d_start, (const uint32_t*)(dm + m_did), c->dadler.as<uint32_t>()};
+    r = deflate_launch(c, st, level, wrap, kLevels[level], bj, ml, d_status, d_out_len, &dd);
+  } else if (r == ZS_OK) {
+    r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len);
+  }
   if (r != ZS_OK) return r;
   if (d_check)
     zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), wrap, d_check, (int)n);
@@ -837,6 +934,57 @@ extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, 
                     });  // out_len is 0 for failed streams
 }
 
+// ---- preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778)
+extern "C" int zs_deflate_batch_dict_device(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
+                                            const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                            const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                            uint32_t* d_out_len, uint32_t* d_check, void* hip_stream,
+                                            const uint8_t* d_dict, const uint64_t* dict_off,
+                                            const uint32_t* dict_len) {
+  const DictIn di = {d_dict, dict_off, dict_len};
+  return deflate_device(c, level, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len,
+                        d_check, hip_stream, true, &di);
+}
+
+extern "C" int zs_deflate_batch_dict(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
+                                     const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                     const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                     uint32_t* out_len, uint32_t* check, const uint8_t* dict,
+                                     const uint64_t* dict_off, const uint32_t* dict_len) {
+  if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  if (!dict_off || !dict_len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them)
+  zs_dict_set ds;
+  zs_dict_distinct(n, dict_off, dict_len, ds);
+  if (!ds.any)
+    return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check);
+  if (!dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
+  if (wbits == 31) return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
+  if (level == 0) return fail(ZS_STREAM_ERROR, "level 0 with a preset dictionary is not built");
+  std::vector<uint64_t> upos, poff;
+  const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict_len, upos, poff);
+  HIPCHK(c->d_dict.ensure(dbytes + 16));
+  {
+    std::vector<uint8_t> pack(dbytes);
+    zs_dict_pack(ds, upos, dict, pack.data());
+    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
+  }
+  std::vector<uint32_t> ocap(n);
+  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
+  uint32_t* res[3] = {(uint32_t*)status, out_len, check};
+  return host_batch(c, n, in, in_off, in_len, ocap, 3, res, 1, out, out_off,
+                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
+                        uint32_t** dr) {
+                      const DictIn di = {c->d_dict.as<uint8_t>(), poff.data() + a, dict_len + a};
+                      return deflate_device(c, level, wbits,
+                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
+                                             ooff, out_cap + a},
+                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false, &di);
+                    });
+}
+
 static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
                           const uint32_t* in_len, const uint32_t* seeds, uint32_t* d_check, void* hip_stream) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
@@ -995,6 +1143,7 @@ extern "C" uint64_t zs_debug_fetch(zs_ctx* c, int what, uint32_t s, void* dst, u
   pos_base = ((const uint64_t*)(hm + m2.pos_base))[s];
   blk_base = ((const uint32_t*)(hm + m2.blk_base))[s];
   n = ((const uint32_t*)(hm + m2.in_len))[s];
+  if (s < c->dp.start.size()) n += c->dp.start[s];  // a batch with dictionaries: the joined stream's positions
   const void* src = nullptr;
   uint64_t bytes = 0;
   switch (what) {
@@ -1090,14 +1239,6 @@ static auto lane_kernel_dict(int rt) {
   return rt == 2 ? zs_k_inflate_lane<2, false, true> : rt == 1 ? zs_k_inflate_lane<1, false, true>
                                                                : zs_k_inflate_lane<0, false, true>;
 }
-
-// The preset dictionaries of a batch: the bytes in device memory, host arrays of
-// the members' offsets and lengths (length 0: none)
-struct DictIn {
-  const uint8_t* d_dict;
-  const uint64_t* off;
-  const uint32_t* len;
-};
 
 // The segmented decode of the members in c->ip.seg (inflate_seg.hip; h: the batch's
 // host arrays, b: its device arrays) on the side stream, after the caller's stream

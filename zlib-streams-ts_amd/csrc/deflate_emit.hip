@@ -677,13 +677,19 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
 }
 
 // --------------------------------------------------------------- layout
-__global__ void zs_k_layout(const uint32_t* __restrict__ blk_base, zs_block* __restrict__ blocks,
+// DICT: a zlib stream compressed against a preset dictionary (dstart[s] != 0) carries the
+// four DICTID bytes behind its header (deflate.ts:767-778)
+template <bool DICT>
+static __device__ __forceinline__ void zs_layout_body(const uint32_t* __restrict__ blk_base, zs_block* __restrict__ blocks,
                             zs_stream* __restrict__ streams, const uint32_t* __restrict__ out_cap,
-                            uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off, int wrap, int nstreams) {
+                            uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off, int wrap, int nstreams,
+                            const uint32_t* __restrict__ dstart) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nstreams) return;
   zs_stream st = streams[s];
-  const uint32_t hl = wrap == 1 ? 2u : wrap == 2 ? 10u : 0u, tl = wrap == 1 ? 4u : wrap == 2 ? 8u : 0u;
+  uint32_t hl = wrap == 1 ? 2u : wrap == 2 ? 10u : 0u;
+  const uint32_t tl = wrap == 1 ? 4u : wrap == 2 ? 8u : 0u;
+  if (DICT && wrap == 1 && dstart[s]) hl += 4u;
   uint64_t off = (uint64_t)hl * 8;
   zs_block* blk = blocks + blk_base[s];
   int bad = 0;
@@ -718,6 +724,17 @@ __global__ void zs_k_layout(const uint32_t* __restrict__ blk_base, zs_block* __r
   }
   const uint64_t tb = off / 8;
   for (uint64_t by = tb > 0 ? tb - 1 : 0; by < (out_len + 3) / 4 * 4; by += 4) ow[by >> 2] = 0;
+}
+__global__ void zs_k_layout(const uint32_t* __restrict__ blk_base, zs_block* __restrict__ blocks,
+                            zs_stream* __restrict__ streams, const uint32_t* __restrict__ out_cap,
+                            uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off, int wrap, int nstreams) {
+  zs_layout_body<false>(blk_base, blocks, streams, out_cap, out, out_off, wrap, nstreams, nullptr);
+}
+__global__ void zs_k_layout_dict(const uint32_t* __restrict__ blk_base, zs_block* __restrict__ blocks,
+                                 zs_stream* __restrict__ streams, const uint32_t* __restrict__ out_cap,
+                                 uint8_t* __restrict__ out, const uint64_t* __restrict__ out_off, int wrap, int nstreams,
+                                 const uint32_t* __restrict__ dstart) {
+  zs_layout_body<true>(blk_base, blocks, streams, out_cap, out, out_off, wrap, nstreams, dstart);
 }
 
 // -------------------------------------------------------------------- emit
@@ -930,9 +947,14 @@ __global__ __launch_bounds__(ZS_EMIT_THREADS) void zs_k_emit(
 }
 
 // -------------------------------------------------------------------- wrap
-__global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
+// DICT (zlib only): a stream with a preset dictionary (dstart[s] != 0) sets FDICT, takes its
+// FCHECK with it and puts DICTID = dadler[did[s]], the adler32 of the whole dictionary, behind
+// the header (deflate.ts:767-778); in_len is unused (no gzip with a dictionary, deflate.ts:373)
+template <bool DICT>
+static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
-                          int level, int nstreams) {
+                          int level, int nstreams, const uint32_t* __restrict__ dstart,
+                          const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nstreams || wrap == 0) return;
   const zs_stream st = streams[s];
@@ -944,9 +966,15 @@ __global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __rest
     uint32_t header = (8u + ((15u - 8u) << 4)) << 8;
     const uint32_t lf = level < 2 ? 0u : level < 6 ? 1u : level == 6 ? 2u : 3u;
     header |= lf << 6;
+    const bool fdict = DICT && dstart[s] != 0u;
+    if (fdict) header |= 0x20u;  // PRESET_DICT
     header += 31 - (header % 31);
     put_byte(0, header >> 8);
     put_byte(1, header);
+    if (fdict) {
+      const uint32_t id = dadler[did[s]];
+      for (int i = 0; i < 4; i++) put_byte(2 + i, id >> (24 - 8 * i));
+    }
     for (int i = 0; i < 4; i++) put_byte(tb + i, st.check >> (24 - 8 * i));
   } else {  // gzip: deflate.ts:787-806, 971-979
     const uint32_t xfl = level == 9 ? 2u : level < 2 ? 4u : 0u;
@@ -954,6 +982,47 @@ __global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __rest
     for (int i = 0; i < 10; i++) put_byte(i, h[i]);
     for (int i = 0; i < 4; i++) put_byte(tb + i, st.check >> (8 * i));
     for (int i = 0; i < 4; i++) put_byte(tb + 4 + i, in_len[s] >> (8 * i));
+  }
+}
+__global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
+                          const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
+                          int level, int nstreams) {
+  zs_wrap_body<false>(streams, out, out_off, in_len, wrap, level, nstreams, nullptr, nullptr, nullptr);
+}
+__global__ void zs_k_wrap_dict(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
+                               const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
+                               int level, int nstreams, const uint32_t* __restrict__ dstart,
+                               const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler) {
+  zs_wrap_body<true>(streams, out, out_off, in_len, wrap, level, nstreams, dstart, did, dadler);
+}
+
+// --------------------------------------------------------------- dictionary join
+// The joined stream of a stream with a preset dictionary: the last dstart[s]
+// bytes of the dictionary (deflate.ts:383-392), then the data.  256 threads x 4 words per
+// workgroup, blockIdx.y the stream; joined + joff[s] is 16-aligned, the bytes up to the next
+// multiple of 4 past the joined length are zeroed.  Dictionaries and inputs at any byte offset.
+__global__ __launch_bounds__(256) void zs_k_dict_join(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                      const uint32_t* __restrict__ in_len,
+                                                      const uint8_t* __restrict__ dict,
+                                                      const uint64_t* __restrict__ dict_off,
+                                                      const uint32_t* __restrict__ dict_len,
+                                                      const uint32_t* __restrict__ dstart, uint8_t* __restrict__ joined,
+                                                      const uint64_t* __restrict__ joff) {
+  const int s = blockIdx.y;
+  const uint32_t lp = dstart[s], n = in_len[s];
+  const uint64_t nv = (uint64_t)lp + n;
+  const uint8_t* d = lp ? dict + dict_off[s] + (dict_len[s] - lp) : dict;
+  const uint8_t* src = in + in_off[s];
+  uint32_t* dst = reinterpret_cast<uint32_t*>(joined + joff[s]);
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint64_t w = ((uint64_t)blockIdx.x * 4 + k) * 256 + threadIdx.x;
+    if (4 * w >= nv) return;
+    uint32_t v = 0;
+    for (uint32_t j = 0; j < 4; j++) {
+      const uint64_t b = 4 * w + j;
+      if (b < nv) v |= (uint32_t)(b < lp ? d[b] : src[b - lp]) << (8 * j);
+    }
+    dst[w] = v;
   }
 }
 

@@ -32,12 +32,16 @@ struct zs_fast_lds {
   uint32_t ring[8192];  // input byte x (x < 256 c) at byte (x & 32767)
 };
 
+// DICT: the stream is a joined one (a preset dictionary's tail, then the data):
+// positions below p0 = dstart[s] are inserted as deflateSetDictionary and the next
+// fill_window insert them (deflate.ts:400-412, 198-213), the parse starts at p0.
+template <bool DICT>
 __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                 const uint32_t* __restrict__ in_len,
                                                 const uint64_t* __restrict__ pos_base,
                                                 const uint32_t* __restrict__ blk_base, uint32_t* __restrict__ syms,
                                                 zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
-                                                int chain, int lazy, int nice_cfg) {
+                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart) {
   extern __shared__ __attribute__((aligned(16))) uint8_t zs_fast_smem[];
   zs_fast_lds& L = *reinterpret_cast<zs_fast_lds*>(zs_fast_smem);
   const int s = blockIdx.x;
@@ -93,6 +97,7 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   uint32_t nsym = 0, in_blk = 0, nflush = 0, blk_start = 0;
   uint32_t ml = 0, ms_rel = 0;  // match_length / match_start (window-relative)
   uint32_t p = 0;
+  const uint32_t p0 = DICT ? dstart[s] : 0u;
   auto insert = [&](uint32_t q) -> uint32_t {  // INSERT_STRING (deflate.ts:113-118), window-relative
     const uint32_t h = hash_at(q);
     const uint32_t rel = q - base;
@@ -131,6 +136,13 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
     blk_start = end;
   };
 
+  if (DICT) {
+    for (uint32_t q = 0; q < p0 && q + 2 < n; q++) {
+      advance_to(q);
+      insert(q);
+    }
+    p = blk_start = p0;
+  }
   while (p < n) {
     advance_to(p);
     // fill_window slide (deflate.ts:180-190): same schedule as deflate_slow
@@ -204,6 +216,13 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   }
 }
 
+template __global__ void zs_k_fast_serial<false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
+                                                 const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int,
+                                                 const uint32_t*);
+template __global__ void zs_k_fast_serial<true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
+                                                const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int,
+                                                const uint32_t*);
+
 // ---------------------------------------------------------------- zs_k_fast
 // The group-speculative replay (CPU model: tools/emu/emu_fast_group.c,
 // tests/test_emu_fast.py).  One wave per stream keeps the reference's exact
@@ -261,13 +280,16 @@ static __device__ __forceinline__ uint32_t zs_fg_mskor(uint32_t addr, uint32_t m
 // links the lane-ordered exchanges hand out come from zs_wave_match instead --
 // the highest lower lane of the same hash, else head[h] -- and the last lane of
 // each hash stores head[h] with a plain half-word store.
-template <int NW, bool ORD>
+// DICT: the stream is a joined one (a preset dictionary's tail, then the data):
+// the positions below p0 = dstart[s] enter head[] / prev[] as groups of truly inserted
+// positions without parse steps (step 4 alone), then the parse starts at p0.
+template <int NW, bool ORD, bool DICT>
 __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                 const uint32_t* __restrict__ in_len,
                                                 const uint64_t* __restrict__ pos_base,
                                                 const uint32_t* __restrict__ blk_base, uint32_t* __restrict__ syms,
                                                 zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
-                                                int chain, int lazy, int nice_cfg) {
+                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart) {
   extern __shared__ __attribute__((aligned(16))) uint8_t zs_fastg_smem[];
   zs_fastg_lds& L = *reinterpret_cast<zs_fastg_lds*>(zs_fastg_smem);
   const int s = blockIdx.x;
@@ -300,6 +322,8 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
 
   uint32_t base = 0, p = 0;
   uint32_t nsym = 0, in_blk = 0, nflush = 0, blk_start = 0;
+  const uint32_t p0 = DICT ? dstart[s] : 0u;
+  if (DICT) blk_start = p0;
 #ifdef ZS_FG_PROF
   unsigned long long fg_acc[5] = {0, 0, 0, 0, 0}, fg_last = __builtin_readcyclecounter();
   uint32_t fg_rw = 0, fg_lg = 0;
@@ -360,6 +384,33 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
       continue;  // re-evaluate the group bounds against the new base
     }
     FG_T(0);
+    if (DICT && p < p0) {
+      // a group of dictionary positions (p0 <= 32768: no slide is due, base = 0): those with
+      // three bytes to hash are inserted in lane order, as step 4 inserts a group's
+      const uint32_t g0 = p;
+      fill_to(g0 + 160u);
+      const uint32_t q = g0 + lane;
+      const bool ins = q < p0 && q + 2 < n;
+      const uint32_t hw = rword(q);
+      const uint32_t h = (((hw & 0xffu) << 10) ^ (((hw >> 8) & 0xffu) << 5) ^ ((hw >> 16) & 0xffu)) & ZS_HASH_MASK;
+      const uint32_t ha = zs_fg_addr(&L.head[h >> 1]), sh = 16u * (h & 1u);
+      uint32_t tp;
+      if (ORD) {
+        tp = (zs_fg_mskor(ha, ins ? 0xffffu << sh : 0u, ins ? q << sh : 0u) >> sh) & 0xffffu;
+      } else {
+        const uint64_t im = zs_wave_match(h, ins);
+        const int pl = zs_lane_below(im, lane);
+        tp = pl >= 0 ? g0 + (uint32_t)pl : (L.head[h >> 1] >> sh) & 0xffffu;
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        if (ins && (im >> lane) == 1ull) reinterpret_cast<uint16_t*>(L.head)[h] = (uint16_t)q;
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+      }
+      if (ins) L.prev[q & 0x7fffu] = (uint16_t)tp;
+      p = min(g0 + 64u, p0);
+      continue;
+    }
     const uint32_t g0 = p, rg0 = g0 - base;
     uint32_t tslide = base + ZS_SLIDE_AT;
     if (m >= ZS_MIN_LOOKAHEAD - 1 && m - (ZS_MIN_LOOKAHEAD - 1) > tslide) tslide = m - (ZS_MIN_LOOKAHEAD - 1);
@@ -621,15 +672,19 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
   }
 }
 
-template __global__ void zs_k_fast<2, true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
-template __global__ void zs_k_fast<4, true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
-template __global__ void zs_k_fast<8, true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
-template __global__ void zs_k_fast<2, false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
-template __global__ void zs_k_fast<4, false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
-template __global__ void zs_k_fast<8, false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, const uint32_t*,
-                                      uint32_t*, zs_block*, zs_stream*, int, int, int);
+#define ZS_FAST_INST(NW, ORD, DICT)                                                                              \
+  template __global__ void zs_k_fast<NW, ORD, DICT>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, \
+                                                    const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int, \
+                                                    const uint32_t*);
+ZS_FAST_INST(2, true, false)
+ZS_FAST_INST(4, true, false)
+ZS_FAST_INST(8, true, false)
+ZS_FAST_INST(2, false, false)
+ZS_FAST_INST(4, false, false)
+ZS_FAST_INST(8, false, false)
+ZS_FAST_INST(2, true, true)
+ZS_FAST_INST(4, true, true)
+ZS_FAST_INST(8, true, true)
+ZS_FAST_INST(2, false, true)
+ZS_FAST_INST(4, false, true)
+ZS_FAST_INST(8, false, true)

@@ -132,7 +132,10 @@ extern "C" int zs_parse_stats(unsigned long long* out) {
 #endif
 
 
-template <uint32_t WIN, uint32_t SEG, uint32_t NWV>
+// DICT: the stream is a joined one (a preset dictionary's tail, then the data):
+// the parse starts at p0 = dstart[s] in the no-pending-match state deflateSetDictionary leaves
+// (deflate.ts:413-418), the segments, the symbols and the blocks cover [p0, n).
+template <uint32_t WIN, uint32_t SEG, uint32_t NWV, bool DICT>
 static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_seg_tab& T, zs_round_state& RS,
                                                      const uint8_t* __restrict__ in,
                                                      const uint64_t* __restrict__ in_off,
@@ -141,21 +144,23 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
                                                      const uint32_t* __restrict__ blk_base,
                                                      const uint2* __restrict__ mres, uint32_t* __restrict__ syms,
                                                      zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
-                                                     uint32_t* __restrict__ scratch, int good, int lazy) {
+                                                     uint32_t* __restrict__ scratch, int good, int lazy,
+                                                     const uint32_t* __restrict__ dstart) {
   using CF = zs_seg_cfg<SEG>;
   const int s = blockIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t n = in_len[s];
+  const uint32_t p0 = DICT ? dstart[s] : 0u;
   const uint8_t* src = in + in_off[s];
   const uint2* M = mres + pos_base[s];
   uint32_t* sy = syms + pos_base[s] + s;  // each stream owns n+1 symbol slots
   // this wave's 64 segment slots (a stream owns >= min(nseg, 64 NWV) slots)
   uint32_t* scr = scratch + (size_t)CF::WORDS * (pos_base[s] / SEG + s + 64u * wave);
   zs_block* blk = blocks + blk_base[s];
-  const uint32_t nseg = (n + SEG - 1) / SEG;
+  const uint32_t nseg = (n - p0 + SEG - 1) / SEG;
   const bool aligned = ((uintptr_t)src & 3u) == 0;
 
-  zs_pstate t = {0, 0, ZS_MIN_MATCH - 1, 0};  // the true parse state entering the round (wave-uniform)
+  zs_pstate t = {p0, 0, ZS_MIN_MATCH - 1, 0};  // the true parse state entering the round (wave-uniform)
   uint32_t total = 0;     // symbols written (wave-uniform)
   uint32_t last_sym = 0;  // the last symbol written (wave-uniform)
   if (NWV > 1) {
@@ -170,7 +175,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     const uint32_t r0 = sr + 64u * wave;
     const uint32_t nr = r0 < nseg ? min(64u, nseg - r0) : 0u;
     const bool mine = lane < nr;  // lane owns segment r0 + lane
-    const uint32_t a = mine ? (r0 + lane) * SEG : n, b = mine ? min(n, a + SEG) : n;
+    const uint32_t a = mine ? p0 + (r0 + lane) * SEG : n, b = mine ? min(n, a + SEG) : n;
     uint32_t* spec = scr + (size_t)lane * CF::WORDS;
     uint32_t* sync = spec + CF::SPEC;
     uint32_t* fix = sync + CF::SYNC;
@@ -451,7 +456,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     const uint32_t b = b0 + lane;
     zs_block k;
     if (b <= nflush) {
-      const uint32_t in_start = b == 0 ? 0u : blk[b - 1].in_end;
+      const uint32_t in_start = b == 0 ? p0 : blk[b - 1].in_end;
       const uint32_t in_end = b < nflush ? blk[b].in_end : n;
       const uint32_t slides = b < nflush ? blk[b].pad : final_slides;
       k.sym_start = b * ZS_SYM_END;
@@ -485,8 +490,19 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
     __shared__ zs_round_state RS;                                                                                   \
     const uint32_t w_ = threadIdx.x >> 6;                                                                           \
-    zs_parse_body<WIN, SEG, NWV>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms, blocks,  \
-                                 streams, scratch, good, lazy);                                                     \
+    zs_parse_body<WIN, SEG, NWV, false>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms,   \
+                                        blocks, streams, scratch, good, lazy, nullptr);                             \
+  }                                                                                                                  \
+  __global__ __launch_bounds__(64 * NWV) void name##_dict(                                                           \
+      const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,     \
+      const uint64_t* __restrict__ pos_base, const uint32_t* __restrict__ blk_base, const uint2* __restrict__ mres,  \
+      uint32_t* __restrict__ syms, zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,                  \
+      uint32_t* __restrict__ scratch, int good, int lazy, const uint32_t* __restrict__ dstart) {                    \
+    __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
+    __shared__ zs_round_state RS;                                                                                   \
+    const uint32_t w_ = threadIdx.x >> 6;                                                                           \
+    zs_parse_body<WIN, SEG, NWV, true>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms,    \
+                                       blocks, streams, scratch, good, lazy, dstart);                               \
   }
 ZS_PARSE_KERNEL(zs_k_parse, ZS_PARSE_WIN, ZS_PARSE_SEG, 1)
 // two waves per stream, 512-position segments: half the speculative pass per lane (small batches)

@@ -315,6 +315,25 @@ extern "C" int zs_pool_deflate_batch(zs_pool* p, int level, int wbits, uint32_t 
   });
 }
 
+// with preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778):
+// every shard reads the caller's one dictionary buffer
+extern "C" int zs_pool_deflate_batch_dict(zs_pool* p, int level, int wbits, uint32_t n, const uint8_t* in,
+                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                          const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                          uint32_t* out_len, uint32_t* check, const uint8_t* dict,
+                                          const uint64_t* dict_off, const uint32_t* dict_len) {
+  if (!dict_off || !dict_len) {
+    zs_set_last_error("null dictionary arrays");
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_deflate_batch_dict(p->ctx[k], level, wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, out,
+                                 out_off + s.a, out_cap + s.a, status + s.a, out_len + s.a,
+                                 check ? check + s.a : nullptr, dict, dict_off + s.a, dict_len + s.a);
+  });
+}
+
 extern "C" int zs_pool_inflate_batch(zs_pool* p, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
                                      const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                                      const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,

@@ -44,26 +44,45 @@ __global__ void zs_k_bucket(const uint8_t* in, const uint64_t* in_off, const uin
                             const zs_sweep_seg* segs, uint16_t* members, uint2* mres);
 __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                            const zs_sweep_seg* segs, const uint16_t* members, uint2* mres, int chain, int nice);
-// the lazy parse (deflate_parse.hip): pass A stages 32 match-table entries per lane in LDS
+// the lazy parse (deflate_parse.hip): pass A stages 32 match-table entries per lane in LDS; the
+// _dict instances parse joined streams (dictionary tail + data) from dstart[s] on
 #define ZS_PARSE_DECL(name)                                                                                        \
   __global__ void name(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base, \
                        const uint32_t* blk_base, const uint2* mres, uint32_t* syms, zs_block* blocks,              \
-                       zs_stream* streams, uint32_t* scratch, int good, int lazy);
+                       zs_stream* streams, uint32_t* scratch, int good, int lazy);                                 \
+  __global__ void name##_dict(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,                   \
+                              const uint64_t* pos_base, const uint32_t* blk_base, const uint2* mres, uint32_t* syms, \
+                              zs_block* blocks, zs_stream* streams, uint32_t* scratch, int good, int lazy,         \
+                              const uint32_t* dstart);
 ZS_PARSE_DECL(zs_k_parse)
 ZS_PARSE_DECL(zs_k_parse_2w)  // two waves per stream, ZS_PARSE2W_SEG-position segments
 ZS_PARSE_DECL(zs_k_parse_4w)  // four waves per stream, ZS_PARSE4W_SEG-position segments
-template <int NW, bool ORD>
+// DICT: joined streams (dictionary tail + data): the positions below dstart[s] are inserted, the
+// parse starts there; else dstart is unused (null)
+template <int NW, bool ORD, bool DICT>
 __global__ void zs_k_fast(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                           const uint32_t* blk_base, uint32_t* syms, zs_block* blocks, zs_stream* streams, int chain,
-                          int lazy, int nice);
+                          int lazy, int nice, const uint32_t* dstart);
+template <bool DICT>
 __global__ void zs_k_fast_serial(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                                  const uint64_t* pos_base, const uint32_t* blk_base, uint32_t* syms, zs_block* blocks,
-                                 zs_stream* streams, int chain, int lazy, int nice);
+                                 zs_stream* streams, int chain, int lazy, int nice, const uint32_t* dstart);
+// A batch with preset dictionaries: stream s's joined stream at joined + joff[s] is the last
+// dstart[s] bytes of its dictionary (dict + dict_off[s], dict_len[s] bytes), then its data
+__global__ void zs_k_dict_join(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* dict,
+                               const uint64_t* dict_off, const uint32_t* dict_len, const uint32_t* dstart,
+                               uint8_t* joined, const uint64_t* joff);
 __global__ void zs_k_trees(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base, const uint32_t* blk_base,
                            const uint32_t* syms, zs_block* blocks, const zs_stream* streams, uint32_t* codes,
                            uint32_t* hdr, int nstreams);
 __global__ void zs_k_layout(const uint32_t* blk_base, zs_block* blocks, zs_stream* streams, const uint32_t* out_cap,
                             uint8_t* out, const uint64_t* out_off, int wrap, int nstreams);
+// zlib streams with a preset dictionary (dstart[s] != 0): FDICT and DICTID (deflate.ts:767-778)
+__global__ void zs_k_layout_dict(const uint32_t* blk_base, zs_block* blocks, zs_stream* streams, const uint32_t* out_cap,
+                                 uint8_t* out, const uint64_t* out_off, int wrap, int nstreams, const uint32_t* dstart);
+__global__ void zs_k_wrap_dict(const zs_stream* streams, uint8_t* out, const uint64_t* out_off, const uint32_t* in_len,
+                               int wrap, int level, int nstreams, const uint32_t* dstart, const uint32_t* did,
+                               const uint32_t* dadler);
 __global__ void zs_k_emit(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base, const uint32_t* blk_base,
                           const uint32_t* syms, const zs_block* blocks, const zs_stream* streams, const uint32_t* codes,
                           const uint32_t* hdr, uint8_t* out, const uint64_t* out_off, int wrap);

@@ -341,23 +341,50 @@ struct zs_deflate_plan {
   uint64_t P = 0, members = 0;
   uint32_t B = 0, max_len = 0, max_blk = 0;
   int pw = 1;  // waves per stream of the parse (zs_k_parse / _2w / _4w)
+  // A batch with preset dictionaries (else empty / 0): each stream's parse start L' in its
+  // joined stream, the joined streams' offsets in the join buffer, and that buffer's bytes
+  std::vector<uint32_t> start;
+  std::vector<uint64_t> joff;
+  uint64_t J = 0;
   size_t prevd_bytes = 0, mres_bytes = 0, syms_bytes = 0, pscr_bytes = 0, codes_bytes = 0, hdr_bytes = 0;
 };
 
+// The part of a preset dictionary that enters the window (deflate.ts:383-392: its last w_size bytes)
+ZS_PLAN_FN uint32_t zs_dict_tail(uint32_t dict_len) { return dict_len < ZS_W_SIZE ? dict_len : ZS_W_SIZE; }
+
+// dict_len: the streams' preset-dictionary lengths, or null for a batch without
+// dictionaries.  A stream with one is planned as its JOINED stream -- the
+// dictionary's tail of L' = zs_dict_tail bytes, then the data: the
+// per-position tables, the windows and max_len follow nv = L' + n, the windows'
+// own positions start at L' (p.start), the block records follow n.
 static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n, const uint32_t* in_len,
-                                   zs_deflate_plan& p) {
+                                   zs_deflate_plan& p, const uint32_t* dict_len = nullptr) {
   const bool sweep = level >= 4 && o.match_sweep;
   p.pos.resize(n);
   p.blk.resize(n);
   p.P = 0;
   p.B = p.max_len = p.max_blk = 0;
+  p.start.clear();
+  p.joff.clear();
+  p.J = 0;
+  if (dict_len) {
+    p.start.resize(n);
+    p.joff.resize(n);
+  }
   for (uint32_t i = 0; i < n; i++) {
+    const uint32_t lp = dict_len ? zs_dict_tail(dict_len[i]) : 0u;
+    const uint64_t nv = (uint64_t)lp + in_len[i];
+    if (dict_len) {
+      p.start[i] = lp;
+      p.joff[i] = p.J;
+      p.J += (nv + 15) & ~15ull;  // joined streams start 16-aligned (the sweep's 16-byte window loads)
+    }
     p.pos[i] = p.P;
-    p.P += ((uint64_t)in_len[i] + 7) & ~7ull;  // per-position tables start 8-aligned (16-B link loads in zs_k_match)
+    p.P += (nv + 7) & ~7ull;  // per-position tables start 8-aligned (16-B link loads in zs_k_match)
     p.blk[i] = p.B;
     const uint32_t nb = in_len[i] / ZS_SYM_END + 2;
     p.B += nb;
-    p.max_len = std::max(p.max_len, in_len[i]);
+    p.max_len = std::max(p.max_len, (uint32_t)std::min<uint64_t>(nv, 0xffffffffull));
     p.max_blk = std::max(p.max_blk, nb);
   }
   p.segs.clear();
@@ -368,14 +395,15 @@ static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n
     p.win0.resize(n + 1);
     for (uint32_t i = 0; i < n; i++) {
       p.win0[i] = (uint32_t)p.segs.size();
-      const uint32_t len = in_len[i];
+      const uint32_t lp = dict_len ? p.start[i] : 0u;  // the first window's own positions start behind the dictionary
+      const uint32_t len = lp + in_len[i];
       if (len <= 65537u) {
-        p.segs.push_back({i, 0u, 0u, len, p.pos[i], 0});
+        p.segs.push_back({i, 0u, lp, len, p.pos[i], 0});
         continue;
       }
       for (uint64_t lo = 0; lo < len; mb += 65536) {
         const uint32_t base = lo == 0 ? 0u : (uint32_t)lo - 32768u;
-        p.segs.push_back({i, base, (uint32_t)lo - base, lo == 0 ? ZS_SEG_FIRST : 32768u + ZS_SEG_OWN, mb, 0});
+        p.segs.push_back({i, base, lo == 0 ? lp : (uint32_t)lo - base, lo == 0 ? ZS_SEG_FIRST : 32768u + ZS_SEG_OWN, mb, 0});
         lo += lo == 0 ? ZS_SEG_FIRST : ZS_SEG_OWN;
       }
     }

@@ -13,6 +13,10 @@ export interface BatchOptions {
 export interface CompressBatchOptions extends BatchOptions {
   /** 0..9, or -1 / any non-number for the default (6), as CompressionStream's {level} (streams.ts:221). */
   level?: number;
+  /** A preset dictionary ("deflate-raw" and "deflate", levels 1..9), as passed to deflateSetDictionary
+   * right after deflateInit2_: one view shared by all inputs, or one per input (null = none).  "deflate"
+   * outputs carry FDICT and DICTID.  With "gzip", or with level 0, the call fails with "init failed: -2". */
+  dictionary?: ArrayBufferView | (ArrayBufferView | null)[];
 }
 export interface DecompressBatchOptions extends BatchOptions {
   /** Output cap per stream (bytes), one number for all or one per input.  Default: none -- the

@@ -49,9 +49,11 @@ function devicesOf(options) {
   return options.device === undefined ? 0 : options.device;
 }
 
-// options.dictionary of the decompress entries: a preset dictionary, as the z_stream
-// driver would pass to inflateSetDictionary (inflate.ts:1220-1249) -- for "deflate-raw"
-// before the first inflate(), for "deflate" when inflate() returns Z_NEED_DICT.  One
+// options.dictionary: a preset dictionary.  The decompress entries use it as the z_stream
+// driver would pass it to inflateSetDictionary (inflate.ts:1220-1249) -- for "deflate-raw"
+// before the first inflate(), for "deflate" when inflate() returns Z_NEED_DICT; the compress
+// entries as deflateSetDictionary right after deflateInit2_ (deflate.ts:367-424; "deflate-raw"
+// and "deflate", levels 1..9: "gzip" or level 0 with one fail with "init failed: -2").  One
 // ArrayBufferView shared by all inputs, or an array with one per input (null = none).
 // Returns what the addon takes: undefined, or one Uint8Array | null per input.
 function dictionariesOf(options, n) {
@@ -79,7 +81,8 @@ async function runCompress(inputs, format, options) {
   const level = typeof options.level == "number" ? options.level : -1;
   let res;
   try {
-    res = await addon.compressBatch(checkInputs(inputs), wbits, level, devicesOf(options));
+    const ins = checkInputs(inputs);
+    res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length));
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -138,7 +141,8 @@ export const deflateBound = (length, format = "deflate") => addon.deflateBound(l
 export async function compressBatchDetailed(inputs, format = "deflate", options = {}) {
   options = options || {};
   const level = typeof options.level == "number" ? options.level : -1;
-  return addon.compressBatch(checkInputs(inputs), compressWbits(format), level, devicesOf(options));
+  const ins = checkInputs(inputs);
+  return addon.compressBatch(ins, compressWbits(format), level, devicesOf(options), dictionariesOf(options, ins.length));
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

@@ -204,7 +204,7 @@ typedef struct {
   uint32_t *in_len, *cap, *olen, *cons, *check;
   int32_t *status, *phase, *msg;
   uint8_t *base;       /* inputs: base + in_off[i] (the job's own copy) */
-  /* decompress with preset dictionaries (zs_pool_inflate_batch_dict*): the job's copy of the
+  /* preset dictionaries (zs_pool_inflate_batch_dict*, zs_pool_deflate_batch_dict): the job's copy of the
    * distinct ones, input i's at dict + dict_off[i], dict_len[i] bytes (0: none); NULL: none given */
   uint8_t *dict;
   uint64_t *dict_off;
@@ -268,6 +268,10 @@ static void job_execute(napi_env env, void *data) {
   else if (j->inflate)
     j->rc = zs_pool_inflate_batch(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off, j->cap,
                                   j->status, j->phase, j->msg, j->olen, j->cons, j->check);
+  else if (j->dict_off)
+    j->rc = zs_pool_deflate_batch_dict(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
+                                       j->out_off, j->cap, j->status, j->olen, j->check, j->dict, j->dict_off,
+                                       j->dict_len);
   else
     j->rc = zs_pool_deflate_batch(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                   j->out_off, j->cap, j->status, j->olen, j->check);
@@ -371,45 +375,7 @@ static napi_value queue_job(napi_env env, job *j, const char *name) {
   return promise;
 }
 
-/* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[]) ->
- *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
-static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 3) return throw_code(env, ZS_STREAM_ERROR, "compressBatch(inputs, wbits, level[, devices])");
-  view *v = NULL;
-  uint32_t n = 0;
-  if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
-  napi_value undef;
-  napi_get_undefined(env, &undef);
-  const uint64_t mask = device_mask(env, argc > 3 ? argv[3] : undef);
-  zs_pool *pool = mask ? pool_for(env, mask) : NULL;
-  job *j = pool ? job_new(n) : NULL;
-  if (!j) {
-    free(v);
-    return pool ? throw_code(env, ZS_MEM_ERROR, "out of host memory") : NULL;
-  }
-  j->pool = pool;
-  j->wbits = arg_i32(env, argv[1], -15);
-  j->level = arg_i32(env, argv[2], -1);
-  uint64_t tout = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    j->out_off[i] = tout;
-    j->cap[i] = (uint32_t)((zs_deflate_bound(v[i].n, j->wbits) + 3) & ~3ull);
-    tout += j->cap[i];
-  }
-  j->out = (uint8_t *)malloc(tout ? tout : 1);  /* (uninitialised: only the outputs are written) */
-  if (!j->out || copy_inputs(j, v) != 0) {
-    free(v);
-    job_free(j);
-    return throw_code(env, ZS_MEM_ERROR, "out of host memory");
-  }
-  free(v);
-  return queue_job(env, j, "zs.compressBatch");
-}
-
-/* The dictionaries of a decompress job: arr[i] a Uint8Array (input i's preset dictionary) or
+/* The dictionaries of a job: arr[i] a Uint8Array (input i's preset dictionary) or
  * null / undefined (none).  Copied like the inputs; an object given for several inputs in a
  * row (or among the last few distinct ones) is stored once.  0, -1 out of memory, -2 not views. */
 static int copy_dicts(napi_env env, job *j, napi_value arr) {
@@ -474,6 +440,58 @@ static int copy_dicts(napi_env env, job *j, napi_value arr) {
   }
   free(v);
   return rc;
+}
+
+/* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
+ *               dictionaries: (Uint8Array | null)[] | undefined) ->
+ *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
+static napi_value CompressBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) return throw_code(env, ZS_STREAM_ERROR, "compressBatch(inputs, wbits, level[, devices[, dictionaries]])");
+  view *v = NULL;
+  uint32_t n = 0;
+  if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
+  napi_value undef;
+  napi_get_undefined(env, &undef);
+  const uint64_t mask = device_mask(env, argc > 3 ? argv[3] : undef);
+  zs_pool *pool = mask ? pool_for(env, mask) : NULL;
+  job *j = pool ? job_new(n) : NULL;
+  if (!j) {
+    free(v);
+    return pool ? throw_code(env, ZS_MEM_ERROR, "out of host memory") : NULL;
+  }
+  j->pool = pool;
+  j->wbits = arg_i32(env, argv[1], -15);
+  j->level = arg_i32(env, argv[2], -1);
+  napi_valuetype dt = napi_undefined;
+  if (argc > 4) napi_typeof(env, argv[4], &dt);
+  if (dt != napi_undefined && dt != napi_null) {
+    bool is_arr = false;
+    napi_is_array(env, argv[4], &is_arr);
+    const int rc = is_arr ? copy_dicts(env, j, argv[4]) : -2;
+    if (rc != 0) {
+      free(v);
+      job_free(j);
+      return rc == -1 ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
+                      : throw_code(env, ZS_STREAM_ERROR, "dictionaries must be (Uint8Array | null)[], one per input");
+    }
+  }
+  uint64_t tout = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    j->out_off[i] = tout;
+    j->cap[i] = (uint32_t)((zs_deflate_bound_dict(v[i].n, j->wbits, j->dict_len ? j->dict_len[i] : 0) + 3) & ~3ull);
+    tout += j->cap[i];
+  }
+  j->out = (uint8_t *)malloc(tout ? tout : 1);  /* (uninitialised: only the outputs are written) */
+  if (!j->out || copy_inputs(j, v) != 0) {
+    free(v);
+    job_free(j);
+    return throw_code(env, ZS_MEM_ERROR, "out of host memory");
+  }
+  free(v);
+  return queue_job(env, j, "zs.compressBatch");
 }
 
 /* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,

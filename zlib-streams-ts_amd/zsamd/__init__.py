@@ -108,6 +108,11 @@ def lib():
         L.zs_inflate_batch_dict_auto.argtypes = L.zs_inflate_batch_auto.argtypes + _dict
         L.zs_inflate_batch_dict_device.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, _P, _U64P, _U32P, _P, _U64P,
                                                    _U32P, _P, _P, _P, _P, _P, _P, _P, _P, _U64P, _U32P]
+    if hasattr(L, "zs_deflate_batch_dict"):
+        L.zs_deflate_bound_dict.restype = ctypes.c_uint64
+        L.zs_deflate_bound_dict.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
+        L.zs_deflate_batch_dict.argtypes = L.zs_deflate_batch_ex.argtypes + _dict
+        L.zs_deflate_batch_dict_device.argtypes = L.zs_deflate_batch_device_ex.argtypes + [_P, _U64P, _U32P]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -120,6 +125,8 @@ def lib():
     if hasattr(L, "zs_pool_inflate_batch_dict"):
         L.zs_pool_inflate_batch_dict.argtypes = L.zs_inflate_batch_dict.argtypes
         L.zs_pool_inflate_batch_dict_auto.argtypes = L.zs_inflate_batch_dict_auto.argtypes
+    if hasattr(L, "zs_pool_deflate_batch_dict"):
+        L.zs_pool_deflate_batch_dict.argtypes = L.zs_deflate_batch_dict.argtypes
     if hasattr(L, "zs_inflate_batch"):
         L.zs_inflate_batch.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, ctypes.c_char_p, _U64P, _U32P, _P, _U64P,
                                        _U32P, _I32P, _I32P, _I32P, _U32P, _U32P]
@@ -171,14 +178,17 @@ def _arr(ctype, values):
     return a
 
 
-def deflate_bound(n: int, fmt: str = "deflate-raw") -> int:
-    """deflateBound (deflate.ts:615-674) for a fresh stream, memLevel 8."""
+def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0) -> int:
+    """deflateBound (deflate.ts:615-674) for a fresh stream, memLevel 8; dict_len: the
+    length of its preset dictionary (zs_deflate_bound_dict: DICTID, deflate.ts:633)."""
+    if dict_len:
+        return int(lib().zs_deflate_bound_dict(n, compress_wbits(fmt), dict_len))
     return int(lib().zs_deflate_bound(n, compress_wbits(fmt)))
 
 
-def deflate_capacity(n: int, fmt: str = "deflate-raw") -> int:
+def deflate_capacity(n: int, fmt: str = "deflate-raw", dict_len: int = 0) -> int:
     """deflate_bound rounded up to the engine's 4-byte output granularity."""
-    return (deflate_bound(n, fmt) + 3) & ~3
+    return (deflate_bound(n, fmt, dict_len) + 3) & ~3
 
 
 class Engine:
@@ -251,19 +261,26 @@ class Engine:
             raise ZsUnavailable("%s failed (%d): %s" % (what, r, msg))
 
     # ---------------------------------------------------------- host buffers
-    def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1
+    def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
                            ) -> List[Tuple[int, bytes]]:
-        """Returns [(status, bytes)] -- status Z_STREAM_END on success."""
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level)]
+        """Returns [(status, bytes)] -- status Z_STREAM_END on success.
+        zdict: a preset dictionary for every input (bytes), or one per input (a
+        list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
+        (zs_deflate_batch_dict: deflateSetDictionary, deflate.ts:367-424)."""
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict)]
 
-    def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1
+    def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
                                 ) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
+        if zdict is not None:
+            return _deflate_host(self._L, self._L.zs_deflate_batch_dict, self._ctx, inputs, fmt, level, self._check,
+                                 _dict_layout(zdict, len(inputs)))
         return _deflate_host(self._L, self._L.zs_deflate_batch_ex, self._ctx, inputs, fmt, level, self._check)
 
-    def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1) -> List[bytes]:
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level))
+    def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
+                       ) -> List[bytes]:
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None):
@@ -292,8 +309,19 @@ class Engine:
 
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
-                        d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0):
-        """Device pointers (ints) + host layout arrays (ctypes arrays)."""
+                        d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
+                        dict_off=None, dict_len=None):
+        """Device pointers (ints) + host layout arrays (ctypes arrays).
+        d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
+        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none)."""
+        if dict_off is not None:
+            r = self._L.zs_deflate_batch_dict_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
+                                                     _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
+                                                     _P(d_status), _P(d_out_len), _P(d_check) if d_check else None,
+                                                     _P(hip_stream) if hip_stream else None,
+                                                     _P(d_dict) if d_dict else None, dict_off, dict_len)
+            self._check(r, "zs_deflate_batch_dict_device")
+            return
         r = self._L.zs_deflate_batch_device_ex(self._ctx, compress_level(level), compress_wbits(fmt), n, _P(d_in),
                                                in_off, in_len, _P(d_out), out_off, out_cap, _P(d_status),
                                                _P(d_out_len), _P(d_check) if d_check else None,
@@ -376,13 +404,16 @@ def _layout(inputs):
     return b"".join(inputs), offs, lens
 
 
-def _deflate_host(L, fn, handle, inputs, fmt, level, check):
+def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=()):
     n = len(inputs)
     if n == 0:
         return []
     wbits = compress_wbits(fmt)
     blob, offs, lens = _layout(inputs)
-    caps = [(int(L.zs_deflate_bound(len(b), wbits)) + 3) & ~3 for b in inputs]
+    if zdict:
+        caps = [(int(L.zs_deflate_bound_dict(len(b), wbits, zdict[2][i])) + 3) & ~3 for i, b in enumerate(inputs)]
+    else:
+        caps = [(int(L.zs_deflate_bound(len(b), wbits)) + 3) & ~3 for b in inputs]
     ooffs, oo = [], 0
     for c in caps:
         ooffs.append(oo)
@@ -390,7 +421,7 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check):
     out = ctypes.create_string_buffer(max(1, oo))
     status, olen, chk = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
     r = fn(handle, compress_level(level), wbits, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
-           out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk)
+           out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk, *zdict)
     check(r, "deflate batch")
     raw = out.raw
     return [(status[i], raw[ooffs[i]: ooffs[i] + olen[i]], chk[i]) for i in range(n)]
@@ -522,14 +553,17 @@ class Pool:
     def _check(self, r: int, what: str):
         Engine._check(self, r, what)
 
-    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1):
+    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
+        if zdict is not None:
+            return _deflate_host(self._L, self._L.zs_pool_deflate_batch_dict, self._pool, inputs, fmt, level,
+                                 self._check, _dict_layout(zdict, len(inputs)))
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
-    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1):
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level)]
+    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict)]
 
-    def compress_batch(self, inputs, fmt="deflate-raw", level=-1):
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level))
+    def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
         L = self._L
