@@ -21,6 +21,7 @@
 #include "zs_split.h"
 #include "zs_seg.h"
 #include "zs_plan.h"
+#include "zs_sweep_ring.h"
 #include "zs_dict.h"
 
 
@@ -514,8 +515,9 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
     (c->lane_order ? zs_k_bucket<true> : zs_k_bucket<false>)<<<nw, ZS_BK_THREADS, 0, st>>>(
         b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(), c->mres.as<uint2>());
     MARK("bucket");
-    zs_k_sweep<<<nw, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(),
-                                    c->mres.as<uint2>(), cfg.chain, cfg.nice);
+    // (a chain budget that is not all groups of eight falls back to the general walk)
+    (zs_sweep_uniform8(cfg.chain) ? zs_k_sweep<true> : zs_k_sweep<false>)<<<nw, 1024, 0, st>>>(
+        b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(), c->mres.as<uint2>(), cfg.chain, cfg.nice);
     MARK("sweep");
   } else if (level >= 4) {
     // cross-check (option match_sweep = 0): the chain-walk kernels for every stream

@@ -49,6 +49,7 @@
 #include "zs_sweep_ring.h"
 #include "zs_sweep_long.h"
 #include <type_traits>
+#include <utility>
 
 // the window in LDS: ZS_SEG_WPOS inserted positions, a longest match past the
 // last of them (258 bytes) and the 16-byte overreach of the word compares
@@ -310,13 +311,6 @@ static __device__ __forceinline__ uint32_t sw_extend(const uint32_t* win, uint32
   return k < maxc ? k : maxc;
 }
 
-// a wave-uniform 64-bit value kept in SGPRs (lane masks updated in loops with divergent bodies)
-static __device__ __forceinline__ uint64_t sw_uniform(uint64_t x) {
-  // (readfirstlane returns int: widen through uint32_t, not by sign extension)
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)x);
-}
-
 static __device__ __forceinline__ uint32_t max3(uint32_t a, uint32_t b, uint32_t c) {
   return max(max(a, b), c);  // one v_max3_u32
 }
@@ -363,6 +357,16 @@ struct SwSig<false> {
     // ffbl(0) = ~0 and the clamped add keep "no difference" at ~0; f2 <= 88 (the sentinel)
     return min(min(f0, f1), f2);
   }
+  template <uint32_t U>
+  __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t z) const {
+    return (mbits(x, y, z) & ~7u) | (7u - U);  // one v_and_or_b32
+  }
+  template <uint32_t U>
+  __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t z, uint64_t lm) const {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(step<U>(x, y, z)), "s"(lm));
+    return r;
+  }
   static __device__ __forceinline__ uint32_t len(uint32_t sigma) { return sigma; }
 };
 template <>
@@ -381,6 +385,43 @@ struct SwSig<true> {
     asm("v_ffbl_b32 %0, %1" : "=v"(f0) : "v"(x ^ a));
     asm("v_ffbl_b32 %0, %1\n\tv_add_u32_e64 %0, %0, 32 clamp" : "=&v"(f1) : "v"(y ^ b));
     return min(min(f0, f1), 64u);  // one v_min3_u32
+  }
+  // the whole step -- mbits(x, y, .) with its low three bits replaced by 7 - U, the step's score at
+  // place U of its group (SwWave) -- as ONE asm block of the same seven VALU.  The
+  // compiler cannot see into an asm block and assumes that it writes its results with a destination
+  // select; gfx950 wants one wait state between such a write and a VALU that reads it (the dst_sel
+  // forwarding hazard), so a plain instruction that consumes a block's result straight behind it gets
+  // an s_nop 0 in front.  With the min3 and the and_or inside, a step's result is first read by the
+  // group's max tree, after the other steps.
+  // (in place in the registers of the record's words: a block that wrote a register of the block
+  // before it would meet the same rule)
+  template <uint32_t U>
+  __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t) const {
+    asm("v_xor_b32_e32 %0, %0, %2\n\t"
+        "v_xor_b32_e32 %1, %1, %3\n\t"
+        "v_ffbl_b32 %0, %0\n\t"
+        "v_ffbl_b32 %1, %1\n\t"
+        "v_add_u32_e64 %1, %1, 32 clamp\n\t"
+        "v_min3_u32 %0, %0, %1, 64\n\t"
+        "v_and_or_b32 %0, %0, -8, %4"
+        : "+v"(x), "+v"(y)
+        : "v"(a), "v"(b), "n"(7u - U));
+    return x;
+  }
+  // ... and 0 for a lane outside lm (the masked groups' select)
+  template <uint32_t U>
+  __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t, uint64_t lm) const {
+    asm("v_xor_b32_e32 %0, %0, %2\n\t"
+        "v_xor_b32_e32 %1, %1, %3\n\t"
+        "v_ffbl_b32 %0, %0\n\t"
+        "v_ffbl_b32 %1, %1\n\t"
+        "v_add_u32_e64 %1, %1, 32 clamp\n\t"
+        "v_min3_u32 %0, %0, %1, 64\n\t"
+        "v_and_or_b32 %0, %0, -8, %4\n\t"
+        "v_cndmask_b32_e64 %0, 0, %0, %5"
+        : "+v"(x), "+v"(y)
+        : "v"(a), "v"(b), "n"(7u - U), "s"(lm));
+    return x;
   }
   static __device__ __forceinline__ uint32_t len(uint32_t sigma) { return sigma ? sigma + 2u : 2u; }
 };
@@ -481,7 +522,15 @@ extern "C" int zs_sw_stats(unsigned long long* out) {
 #define SW_STAT(i, v) do { } while (0)
 #endif
 
-static __device__ __forceinline__ uint32_t sw_score(uint32_t mb, uint32_t u) { return (mb & ~7u) | (7u - u); }  // one v_and_or_b32
+// f(integral_constant<uint32_t, u>) for u = 0 .. N - 1: a group's steps, each with its place as a constant
+template <class F, uint32_t... U>
+static __device__ __forceinline__ void sw_each_(F&& f, std::integer_sequence<uint32_t, U...>) {
+  (f(std::integral_constant<uint32_t, U>{}), ...);
+}
+template <uint32_t N, class F>
+static __device__ __forceinline__ void sw_each(F&& f) {
+  sw_each_(f, std::make_integer_sequence<uint32_t, N>{});
+}
 template <uint32_t N>  // the maximum of a group's N scores
 static __device__ __forceinline__ uint32_t sw_gmax(const uint32_t* sc) {
   static_assert(N == 8 || N == 4 || N == 3 || N == 1, "group sizes");
@@ -523,7 +572,12 @@ struct SwLane {
 // One wave's sweep of a window: what its chunks share, and the pieces of one
 // chunk's work -- start (the lanes' state), build (the ring's blocks), sweep
 // (the chain steps) and settle (the results).  sw_body drives them.
-template <bool A7, bool MW, bool PR>  // PR: the persistent ring (chain <= ZS_SWR_MAX_CHAIN; MW is then unused)
+// PR: the persistent ring (chain <= ZS_SWR_MAX_CHAIN; MW is then unused).
+// U8: the chain budget and its quarter are multiples of 8 (zs_sweep_uniform8,
+// levels 5..9), so after the opening group of steps 1..8 every group is
+// exactly eight steps and the chain >> 2 snapshot falls on a group's end: the
+// walk (run8) needs no group bounds and no 4-step forms.
+template <bool A7, bool MW, bool PR, bool U8>
 struct SwWave {
   using Sig = SwSig<A7>;
   using Lane = SwLane<A7>;
@@ -621,9 +675,10 @@ struct SwWave {
   // first nice candidate ends the walk (deflate.ts:1103) and ties with every
   // later one, so it stays first.
   // (gm: the maximum of the group's cnt scores sc, 0 for a lane that takes
-  // none; its steps are t0 .. t0 + cnt - 1, step t at slot base - t)
+  // none; its steps are t0 .. t0 + cnt - 1, and step t0 + u's record is
+  // element cnt - 1 - u of the group's part gc, gk of the ring's c and key)
   __device__ __forceinline__ void fold(Lane& L, uint32_t gm, uint32_t t0, const uint32_t* sc, uint32_t cnt,
-                                       uint32_t base) const {
+                                       const uint32_t* gc, const uint32_t* gk) const {
     const bool up = gm > (L.thr | 7u);  // longer than the best so far
     L.thr = up ? gm : L.thr;
     L.bt = up ? t0 : L.bt;
@@ -632,10 +687,10 @@ struct SwWave {
       // the score of the long candidate at place u (zs_sweep_long.h)
       auto lscore = [&](uint32_t u) -> uint32_t {
         // the next four bytes: A7 records carry them (c), else from the window
-        const uint32_t ls = base - (t0 + u);
-        const uint32_t x = (A7 ? R->c[ls] : sw_word(win, (R->key[ls] & 0xffffu) + Sig::EXT)) ^ L.own_ext;
+        const uint32_t ls = cnt - 1u - u;
+        const uint32_t x = (A7 ? gc[ls] : sw_word(win, (gk[ls] & 0xffffu) + Sig::EXT)) ^ L.own_ext;
         const uint32_t len = x ? Sig::EXT + ((uint32_t)__builtin_ctz(x) >> 3)
-                               : sw_extend(win, L.p, R->key[ls] & 0xffffu, L.maxc, Sig::EXT + 4u);
+                               : sw_extend(win, L.p, gk[ls] & 0xffffu, L.maxc, Sig::EXT + 4u);
         return zs_swl_score(len, L.maxc, L.nice, u);
       };
       const bool lg = gm >= L.long_m && zs_swl_open(L.lthr, L.nice);
@@ -673,22 +728,36 @@ struct SwWave {
   }
 
   // Steps t0 .. t0 + N - 1 as one group: step t reads slot base - t, one
-  // address per group (its lowest slot), immediate offsets inside.
+  // address per ring array for the group (its lowest slot: at()), immediate
+  // offsets inside.
+  struct Grp {
+    const uint2* A;
+    const uint32_t *C, *K;
+  };
+  template <uint32_t N>
+  __device__ __forceinline__ Grp at(uint32_t base, uint32_t t0) const {
+    const uint32_t lo = base - (t0 + (N - 1u));
+    return Grp{R->ab + lo, R->c + lo, R->key + lo};
+  }
+  // (A7: the group's part of c, from the address of its part of ab)
+  __device__ __forceinline__ const uint32_t* c_of(const Grp& g) const {
+    if constexpr (A7) return R->c + ((sw_lds_addr(g.A) - sw_lds_addr(R->ab)) >> 3);
+    else return g.C;
+  }
   // Unmasked, for a group in which every live lane is live throughout.
   // (every lane runs it -- no divergent region, whose join costs register moves --
-  // and a lane whose chain has ended folds nothing)
+  // and a lane whose chain has ended folds nothing: its maximum is selected to
+  // 0 on the alive_m pair itself)
   template <uint32_t N>
-  __device__ __forceinline__ void group_fast(Lane& L, uint32_t base, uint32_t t0, bool live) const {
-    const uint32_t lo = base - (t0 + (N - 1u));
-    const uint2* const A = R->ab + lo;
-    const uint32_t* const C = R->c + lo;
+  __device__ __forceinline__ void group_fast(Lane& L, const Grp& g, uint32_t t0) const {
     uint32_t sc[N];
-#pragma unroll
-    for (uint32_t u = 0; u < N; u++) {
-      const uint2 ab = A[N - 1u - u];
-      sc[u] = sw_score(L.S.mbits(ab.x, ab.y, A7 ? 0u : C[N - 1u - u]), u);
-    }
-    fold(L, live ? sw_gmax<N>(sc) : 0u, t0, sc, N, base);
+    sw_each<N>([&](auto uc) __attribute__((always_inline)) {
+      constexpr uint32_t u = decltype(uc)::value;
+      const uint2 ab = g.A[N - 1u - u];
+      sc[u] = L.S.template step<u>(ab.x, ab.y, A7 ? 0u : g.C[N - 1u - u]);
+    });
+    const uint32_t gm = __builtin_amdgcn_inverse_ballot_w64(L.alive_m) ? sw_gmax<N>(sc) : 0u;
+    fold(L, gm, t0, sc, N, c_of(g), g.K);
   }
   // Masked, for a group in which a chain ends: liveness is monotone in t (keys
   // fall with the member index), so a step is live iff its own key is (and the
@@ -698,17 +767,13 @@ struct SwWave {
   // deflate.ts:1376) has its own liveness rule, key >= khead, and it starts
   // alive_m; the chain steps after it are live while their keys are.
   template <uint32_t N, bool HEAD>
-  __device__ __forceinline__ void group_masked(Lane& L, uint32_t base, uint32_t t0) const {
-    const uint32_t lo = base - (t0 + (N - 1u));
-    const uint2* const A = R->ab + lo;
-    const uint32_t* const C = R->c + lo;
-    const uint32_t* const K = R->key + lo;
+  __device__ __forceinline__ void group_masked(Lane& L, const Grp& g, uint32_t t0) const {
     uint32_t sc[N], key[N];
     uint2 ab[N];
 #pragma unroll
     for (uint32_t u = 0; u < N; u++) {
-      key[u] = K[N - 1u - u];
-      ab[u] = A[N - 1u - u];
+      key[u] = g.K[N - 1u - u];
+      ab[u] = g.A[N - 1u - u];
     }
     if constexpr (HEAD) {
       const bool a1 = L.own && key[0] >= L.khead;
@@ -716,17 +781,19 @@ struct SwWave {
       L.alive_m = __builtin_amdgcn_ballot_w64(a1);
     }
     uint64_t lm = L.alive_m;  // the live lanes
-#pragma unroll
-    for (uint32_t u = 0; u < N; u++) {
+    sw_each<N>([&](auto uc) __attribute__((always_inline)) {
+      constexpr uint32_t u = decltype(uc)::value;
+      // (asm results go through locals: an asm operand cannot name a captured variable)
       if (!HEAD || u) {
-        asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(lm) : "v"(key[u]), "v"(L.klim));
-        lm &= L.alive_m;
+        uint64_t gt;
+        const uint32_t ku = key[u], klim = L.klim;
+        asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(gt) : "v"(ku), "v"(klim));
+        lm = gt & L.alive_m;
       }
-      const uint32_t v = sw_score(L.S.mbits(ab[u].x, ab[u].y, A7 ? 0u : C[N - 1u - u]), u);
-      asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(sc[u]) : "v"(v), "s"(lm));
-    }
-    L.alive_m = sw_uniform(lm);  // the lanes live at the group's last step
-    fold(L, sw_gmax<N>(sc), t0, sc, N, base);
+      sc[u] = L.S.template step<u>(ab[u].x, ab[u].y, A7 ? 0u : g.C[N - 1u - u], lm);
+    });
+    L.alive_m = lm;  // the lanes live at the group's last step (an SGPR pair: the asm's, and-ed with one)
+    fold(L, sw_gmax<N>(sc), t0, sc, N, c_of(g), g.K);
   }
 
   // Steps [ta, tb] of a block (ta = 1 mod 4, tb = 0 mod 4, wave-uniform) in
@@ -744,24 +811,88 @@ struct SwWave {
     uint32_t t0 = ta, t1 = last_of(ta);
     uint32_t kl = R->key[base - t1];
     while (L.alive_m) {
-      const bool mine = ((L.alive_m >> lane) & 1u) != 0;
-      const uint64_t last_live = __builtin_amdgcn_ballot_w64(mine && kl > L.klim);
+      const uint64_t last_live = __builtin_amdgcn_ballot_w64(kl > L.klim) & L.alive_m;
       const uint32_t n0 = t1 + 1u, n1 = n0 <= tb ? last_of(n0) : t1;
       kl = R->key[base - n1];
       SW_STAT(last_live == L.alive_m ? 1 : 2, 1);
       SW_STAT(4, t1 - t0 + 1u);
       if (last_live == L.alive_m) {
-        if (t1 - t0 == 7u) group_fast<8>(L, base, t0, mine);
-        else group_fast<4>(L, base, t0, mine);
+        if (t1 - t0 == 7u) group_fast<8>(L, at<8>(base, t0), t0);
+        else group_fast<4>(L, at<4>(base, t0), t0);
       } else {
-        if (t1 - t0 == 7u) group_masked<8, false>(L, base, t0);
-        else group_masked<4, false>(L, base, t0);
+        if (t1 - t0 == 7u) group_masked<8, false>(L, at<8>(base, t0), t0);
+        else group_masked<4, false>(L, at<4>(base, t0), t0);
       }
       if (t1 == budget_s) L.snap();
       if (n0 > tb) break;
       t0 = n0;
       t1 = n1;
     }
+  }
+
+  // U8: steps [ta, te] (ta = 1 mod 8, te = 0 mod 8) in groups of exactly eight.
+  // The groups' addresses run down the ring, one subtraction per array and
+  // group, and the next group's last key is this group's at an immediate offset
+  // (for the range's last group that is a slot below the range, inside the
+  // ring's arrays or the array before them: read, never used).
+  __device__ __forceinline__ void run8(Lane& L, uint32_t base, uint32_t ta, uint32_t te) const {
+    // (one name for the mask from here on: the loops around this one carry it in several copies that the
+    // compiler cannot tell are equal, and each copy would be an SGPR-pair move per group)
+    asm("" : "+s"(L.alive_m));
+    Grp g = at<8>(base, ta);
+    // (the key address runs eight slots below its group: the look-ahead key at offset 0, the group's above it)
+    const zs_sw_lds_u32* k8 = (const zs_sw_lds_u32*)(g.K - 8);
+    uint32_t kl = g.K[0];
+    if (!L.alive_m) return;
+    uint32_t t0 = ta;
+    do {
+      const uint64_t last_live = __builtin_amdgcn_ballot_w64(kl > L.klim) & L.alive_m;
+      kl = k8[0];
+      g.K = (const uint32_t*)(k8 + 8);
+      SW_STAT(last_live == L.alive_m ? 1 : 2, 1);
+      SW_STAT(4, 8u);
+      // The steps run unmasked.  A group in which a chain ends loads the steps' keys with the
+      // records and, behind the steps, zeroes step by step the scores of the lanes whose key is no
+      // longer live: group_masked's liveness rule.  (Two conditional pieces around one copy of the
+      // steps, the max tree and the fold -- not group_fast and group_masked joined: the join of the
+      // two forms cost register moves and flag tests in both, and the long branch stood twice.)
+      const uint64_t a0 = L.alive_m;  // the lanes live when the group begins
+      const bool ends = last_live != a0;
+      uint32_t sc[8], key[8];
+      if (ends) {  // (the keys' loads go out with the records')
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) key[u] = g.K[7u - u];
+      }
+      sw_each<8>([&](auto uc) __attribute__((always_inline)) {
+        constexpr uint32_t u = decltype(uc)::value;
+        const uint2 ab = g.A[7u - u];
+        sc[u] = L.S.template step<u>(ab.x, ab.y, A7 ? 0u : g.C[7u - u]);
+      });
+      if (ends) {
+        uint64_t lm = a0;
+        sw_each<8>([&](auto uc) __attribute__((always_inline)) {
+          constexpr uint32_t u = decltype(uc)::value;
+          uint64_t gt;
+          const uint32_t ku = key[u], klim = L.klim;
+          asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(gt) : "v"(ku), "v"(klim));
+          lm = gt & a0;
+          const uint64_t lmu = lm;
+          uint32_t v = sc[u];
+          asm("v_cndmask_b32_e64 %0, 0, %0, %1" : "+v"(v) : "s"(lmu));
+          sc[u] = v;
+        });
+        L.alive_m = lm;  // the lanes live at the group's last step
+      }
+      const uint32_t gm = __builtin_amdgcn_inverse_ballot_w64(a0) ? sw_gmax<8>(sc) : 0u;
+      fold(L, gm, t0, sc, 8u, c_of(g), g.K);
+      t0 += 8u;
+      g.A -= 8;
+      if (!A7) g.C -= 8;  // (A7 reads c in the long branch only: from A's slot)
+      k8 -= 8;
+      // (empty asm: the key address is the one the loop carries -- otherwise it is re-based so that
+      // the look-ahead costs a subtraction and a move)
+      asm("" : "+v"(k8));
+    } while (t0 <= te && L.alive_m);
   }
 
   // sweep: the chain steps 1 .. budget of chunk cc, while a lane's chain lasts
@@ -771,15 +902,15 @@ struct SwWave {
     // step 4) takes the pieces: the head, steps 2..4, and the blocks' groups
     // from step 5.
     const uint32_t base0 = Ring::base(cc, 0u, lane);
-    const bool open8 = budget_s >= 8u && budget >= 8u;  // wave-uniform
+    const bool open8 = U8 || (budget_s >= 8u && budget >= 8u);  // wave-uniform
     if (open8) {
-      group_masked<8, true>(L, base0, 1u);
+      group_masked<8, true>(L, at<8>(base0, 1u), 1u);
       if (budget_s == 8u) L.snap();
-    } else {
-      group_masked<1, true>(L, base0, 1u);
+    } else if constexpr (!U8) {
+      group_masked<1, true>(L, at<1>(base0, 1u), 1u);
       if (budget_s == 1u) L.snap();
       if (budget >= 4u) {
-        group_masked<3, false>(L, base0, 2u);
+        group_masked<3, false>(L, at<3>(base0, 2u), 2u);
         if (budget_s == 4u) L.snap();
       }
     }
@@ -793,9 +924,21 @@ struct SwWave {
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
       }
-      const uint32_t ta = b == 0 ? (open8 ? 9u : 5u) : 64u * b + 1u;
+      uint32_t ta = b == 0 ? (open8 ? 9u : 5u) : 64u * b + 1u;
       const uint32_t tb = min(64u * b + 64u, budget);
-      run(L, Ring::base(cc, b, lane), ta, tb);
+      const uint32_t base = Ring::base(cc, b, lane);
+      if constexpr (U8) {
+        // the snapshot is a group's end: the block's groups are walked up to it, and on from it
+        while (ta <= tb && L.alive_m) {
+          const bool cut = !L.snapped && budget_s <= tb;  // (budget_s >= ta: the steps before ta are done)
+          const uint32_t te = cut ? budget_s : tb;
+          run8(L, base, ta, te);
+          if (cut) L.snap();
+          ta = te + 1u;
+        }
+      } else {
+        run(L, base, ta, tb);
+      }
       if (tb >= budget) break;
     }
     if (!L.snapped) L.snap();  // every chain ended before step chain >> 2
@@ -873,11 +1016,11 @@ struct SwWave {
 // PR: a wave claims runs [c, ce) of consecutive chunks, the next run during
 // the last chunk of this one; only a run's first chunk needs the members of
 // the block before.
-template <bool A7, bool MW, bool PR>
+template <bool A7, bool MW, bool PR, bool U8>
 static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp, uint16_t* mw, uint32_t* next,
                                                uint32_t n, uint32_t m, uint32_t olo, uint32_t ohi,
                                                const uint16_t* mem, uint2* out, int chain, int nice_cfg) {
-  using Wave = SwWave<A7, MW, PR>;
+  using Wave = SwWave<A7, MW, PR, U8>;
   const uint32_t lane = threadIdx.x & 63u;
   Wave W{win, (typename Wave::Ring*)ringp, mw, mem, n, m, lane, (uint32_t)chain, (uint32_t)chain >> 2,
          (uint32_t)nice_cfg, 0, zs_swr_empty(), 0};
@@ -943,6 +1086,7 @@ static __device__ __forceinline__ void sw_body(const uint32_t* win, void* ringp,
   }
 }
 
+template <bool U8>  // the host picks the instance from the level's chain (zs_sweep_uniform8)
 __global__ __launch_bounds__(1024) void zs_k_sweep(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                    const uint32_t* __restrict__ in_len,
                                                    const uint64_t* __restrict__ pos_base,
@@ -997,17 +1141,21 @@ __global__ __launch_bounds__(1024) void zs_k_sweep(const uint8_t* __restrict__ i
   const uint32_t olo = G.olo, ohi = G.ohi;
   if (chain <= (int)ZS_SWR_MAX_CHAIN) {  // levels 4..6: the persistent ring
     SwRingP* const R = reinterpret_cast<SwRingP*>(rmem) + wave;
-    if (a7) sw_body<true, false, true>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
-    else sw_body<false, false, true>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    if (a7) sw_body<true, false, true, U8>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, false, true, U8>(win, R, nullptr, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
     return;
   }
   SwRing* const R = reinterpret_cast<SwRing*>(rmem) + wave;
   uint16_t* const mw = reinterpret_cast<uint16_t*>(rmem + RING_BYTES) + wave * ZS_SW_MW;
   if (chain + 64 <= (int)ZS_SW_MW) {  // level 7
-    if (a7) sw_body<true, true, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
-    else sw_body<false, true, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    if (a7) sw_body<true, true, false, U8>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, true, false, U8>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
   } else {  // levels 8, 9: positions from HBM
-    if (a7) sw_body<true, false, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
-    else sw_body<false, false, false>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    if (a7) sw_body<true, false, false, U8>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
+    else sw_body<false, false, false, U8>(win, R, mw, &next, n, m, olo, ohi, mem, out, chain, nice_cfg);
   }
 }
+template __global__ void zs_k_sweep<true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
+                                          const zs_sweep_seg*, const uint16_t*, uint2*, int, int);
+template __global__ void zs_k_sweep<false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
+                                           const zs_sweep_seg*, const uint16_t*, uint2*, int, int);

@@ -42,6 +42,8 @@ __global__ void zs_k_match(const uint8_t* in, const uint64_t* in_off, const uint
 template <bool ORD>
 __global__ void zs_k_bucket(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                             const zs_sweep_seg* segs, uint16_t* members, uint2* mres);
+// U8: zs_sweep_uniform8(chain) holds -- the instance whose groups after the opening one are all eight steps
+template <bool U8>
 __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                            const zs_sweep_seg* segs, const uint16_t* members, uint2* mres, int chain, int nice);
 // the lazy parse (deflate_parse.hip): pass A stages 32 match-table entries per lane in LDS; the

@@ -92,4 +92,15 @@ ZS_SWR_FN uint32_t zs_swr_run_len(uint32_t left, uint32_t cap) {
   return r < 1u ? 1u : (r > cap ? cap : r);
 }
 
+// zs_k_sweep<true>'s condition on a level's chain budget: it and its quarter
+// (the budget when prev_length >= good_match, deflate.ts:1075-1077) are
+// multiples of 8 and at least 8.  The sweep's blocks are 64 steps and steps
+// 1..8 are its opening group, so every later group is then exactly eight
+// steps, t0 = 1 mod 8, and the quarter's snapshot falls on a group's end.
+// (levels 5..9: 32, 128, 256, 1024, 4096; level 4's 16 / 4 does not qualify
+// and takes zs_k_sweep<false>, whose groups are cut where they must be)
+ZS_SWR_FN int zs_sweep_uniform8(int32_t chain) {
+  return chain >= 8 && chain % 8 == 0 && (chain >> 2) >= 8 && (chain >> 2) % 8 == 0;
+}
+
 #endif
