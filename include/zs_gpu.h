@@ -275,6 +275,47 @@ int zs_pool_deflate_batch_dict(zs_pool *pool, int level, int wbits, uint32_t n_s
                                const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
                                const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len);
 
+/* Compression strategies: stream i is the bytes of deflateInit2_(level, Z_DEFLATED,
+ * wbits, 8, strategy) and the stream layer's one write() + close(), for every strategy
+ * the reference validates (deflate.ts:289-290) and dispatches on (deflate.ts:923-931). */
+#define ZS_DEFAULT_STRATEGY 0 /* deflate.ts:923-931: the level's own deflate_fast / deflate_slow */
+#define ZS_FILTERED 1         /* deflate.ts:1381-1387: deflate_slow drops a new match of at most 5 bytes */
+#define ZS_HUFFMAN_ONLY 2     /* deflate.ts:1525-1565: deflate_huff, every byte a literal */
+#define ZS_RLE 3              /* deflate.ts:1450-1523: deflate_rle (see option rle_ref) */
+#define ZS_FIXED 4            /* trees.ts:567: no dynamic trees (stored blocks are still chosen, trees.ts:574) */
+/* The entries take the arguments of zs_deflate_batch_device_ex / zs_deflate_batch_ex /
+ * zs_pool_deflate_batch with `strategy` behind `level`.
+ *  - strategy below 0 or above 4: the call returns ZS_STREAM_ERROR (deflate.ts:289-290,
+ *    "init failed: -2");
+ *  - ZS_DEFAULT_STRATEGY is the counterpart's call;
+ *  - level 0 with any strategy is the plain level-0 path (deflate.ts:925 picks deflate_stored
+ *    first; both wrappers already read "level < 2");
+ *  - ZS_FILTERED at levels 1..3 is strategy 0's bytes (deflate_fast has no filtered branch);
+ *  - ZS_HUFFMAN_ONLY and above clear the zlib header's level bits (deflate.ts:757) and set
+ *    gzip's XFL to 4 below level 9 (deflate.ts:798);
+ *  - ZS_RLE follows option rle_ref: 1 (default) the reference, whose scan compares the
+ *    previous byte's value with the scan index (deflate.ts:1469-1481) and so never finds a
+ *    run -- the bytes are ZS_HUFFMAN_ONLY's; 0 zlib's deflate_rle (matches at distance 1).
+ *    The pool's contexts keep the default;
+ *  - preset dictionaries are not built with a strategy: there are no _dict forms of these
+ *    entries;
+ *  - statuses, check values, Z_BUF_ERROR and zs_deflate_bound (deflateBound does not look
+ *    at the strategy) as the plain entries. */
+/* deflate.ts:289-290, :923-931 -- device buffers (as zs_deflate_batch_device_ex) */
+int zs_deflate_batch_strategy_device(zs_ctx *ctx, int level, int strategy, int wbits, uint32_t n_streams,
+                                     const uint8_t *d_in, const uint64_t *in_off, const uint32_t *in_len,
+                                     uint8_t *d_out, const uint64_t *out_off, const uint32_t *out_cap,
+                                     int32_t *d_status, uint32_t *d_out_len, uint32_t *d_check, void *hip_stream);
+/* deflate.ts:289-290, :923-931 -- host buffers (as zs_deflate_batch_ex) */
+int zs_deflate_batch_strategy(zs_ctx *ctx, int level, int strategy, int wbits, uint32_t n_streams, const uint8_t *in,
+                              const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                              const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check);
+/* deflate.ts:289-290, :923-931 -- the pool (as zs_pool_deflate_batch) */
+int zs_pool_deflate_batch_strategy(zs_pool *pool, int level, int strategy, int wbits, uint32_t n_streams,
+                                   const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                                   const uint64_t *out_off, const uint32_t *out_cap, int32_t *status,
+                                   uint32_t *out_len, uint32_t *check);
+
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);
 
@@ -361,7 +402,10 @@ void zs_set_timing(zs_ctx *ctx, int on);
  * does: 1 reproduces the reference's inflate_fast window-wrap copy
  * (inffast.ts:133-147), which changes the output of members whose match
  * crosses the reference's window wrap between inflate() calls; 0 decodes with
- * zlib semantics (the bytes the compressor was given). */
+ * zlib semantics (the bytes the compressor was given).  "rle_ref" (default 1)
+ * does too, for ZS_RLE alone: 1 reproduces the reference's deflate_rle, which
+ * finds no run (deflate.ts:1469-1481) and so writes ZS_HUFFMAN_ONLY's bytes; 0
+ * compresses as zlib's deflate_rle does (greedy matches at distance 1). */
 int zs_set_option(zs_ctx *ctx, const char *name, int value);
 
 /* Introspection for tests: copy an intermediate array of stream s of the last

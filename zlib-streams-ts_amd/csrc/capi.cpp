@@ -90,6 +90,7 @@ struct zs_ctx {
   zs_deflate_plan dp;
   zs_inflate_plan ip;
   zs_seg_plan gp;
+  std::vector<zs_huff_chunk> hchunks;  // zs_k_huff_tally's (stream, block) list
   // workspace
   Buf meta, prevd, mres, syms, blocks, streams, codes, hdr, check, istate, pscr, ltabs, lres, llen, lstat;
   bool fast_group = true;    // L1..3: zs_k_fast (group-speculative) instead of zs_k_fast_serial
@@ -216,6 +217,7 @@ static const Option kOptions[] = {
     OPT_FLAG("inflate_ref_wrap", o.inflate_ref_wrap),
     OPT_FLAG("check_phases", check_phases),
     OPT_FLAG("match_sweep", o.match_sweep),
+    OPT_FLAG("rle_ref", o.rle_ref),
     OPT_FLAG("fast_group", fast_group),
     {"lane_order", [](zs_ctx* c, int v) { c->lane_order = v != 0; },
      [](const zs_ctx* c, int v) { return !v || c->lane_order_ok; },
@@ -489,8 +491,10 @@ struct DeflDict {
   const Batch* data;
   const uint32_t *start, *did, *dadler;
 };
+// sp: the strategy's routes (zs_plan_strategy); d_chunks: zs_k_huff_tally's list (c->hchunks, uploaded).
 static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const zs_level_cfg& cfg, const Batch& b,
-                          const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len, const DeflDict* dd = nullptr) {
+                          const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len, const DeflDict* dd = nullptr,
+                          const zs_strategy_plan& sp = zs_strategy_plan(), const zs_huff_chunk* d_chunks = nullptr) {
   const zs_deflate_plan& p = c->dp;
   const uint32_t n = b.n;
   const uint8_t* dm = c->meta.as<uint8_t>();
@@ -509,7 +513,14 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
     zs_k_copy_check<<<nblocks_s, nthreads_s, 0, st>>>(check, d_st, (int)n);
     MARK("checksum");
   }
-  if (level >= 4 && c->o.match_sweep) {
+  if (sp.tally == ZS_TALLY_HUFF) {
+    zs_k_huff_tally<<<(uint32_t)c->hchunks.size(), 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, d_chunks, syms,
+                                                                 d_bk, d_st);
+    MARK("huff_tally");
+  } else if (sp.tally == ZS_TALLY_RLE) {
+    zs_k_rle_tally<<<n, 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st);
+    MARK("rle_tally");
+  } else if (level >= 4 && c->o.match_sweep) {
     const uint32_t nw = (uint32_t)p.segs.size();
     // a window: counting sort by hash + lock-step sweep (deflate_sweep.hip)
     (c->lane_order ? zs_k_bucket<true> : zs_k_bucket<false>)<<<nw, ZS_BK_THREADS, 0, st>>>(
@@ -529,14 +540,17 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
                                                    c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u);
     MARK("match");
   }
-  if (level >= 4) {
+  if (sp.tally != ZS_TALLY_LEVEL) {
+    // (the tally kernels wrote the symbols and the block records)
+  } else if (level >= 4) {
     const int pw = p.pw;  // waves per stream of the lazy parse (deflate_parse.hip)
     if (dd) {
       auto parse = pw == 4 ? zs_k_parse_4w_dict : pw == 2 ? zs_k_parse_2w_dict : zs_k_parse_dict;
       parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
                                    c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, dd->start);
     } else {
-      auto parse = pw == 4 ? zs_k_parse_4w : pw == 2 ? zs_k_parse_2w : zs_k_parse;
+      auto parse = sp.filtered ? (pw == 4 ? zs_k_parse_4w_filt : pw == 2 ? zs_k_parse_2w_filt : zs_k_parse_filt)
+                               : (pw == 4 ? zs_k_parse_4w : pw == 2 ? zs_k_parse_2w : zs_k_parse);
       parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
                                    c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
     }
@@ -558,7 +572,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
     MARK("fast");
   }
   zs_k_trees<<<dim3(p.max_blk, n), 64, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
-                                                c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n);
+                                                c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n, sp.fixed ? 1 : 0);
   MARK("trees");
   if (dd) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
                                                              dd->start);
@@ -570,7 +584,8 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
   if (wrap && dd)
     zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, dd->start,
                                                      dd->did, dd->dadler);
-  else if (wrap) zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n);
+  else if (wrap)
+    zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, sp.wrap_strategy);
   zs_k_finish<<<nblocks_s, nthreads_s, 0, st>>>(d_st, d_status, d_out_len, (int)n);
   MARK("finish");
   return ZS_OK;
@@ -595,7 +610,8 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
 // `dict` (the _dict entries): the streams' preset dictionaries; a batch with none
 // of them set is the plain batch.
 static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict = nullptr) {
+                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict = nullptr,
+                          int strategy = ZS_DEFAULT_STRATEGY) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION, deflate.ts:268-270
   int wrap;
@@ -604,6 +620,8 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   else if (wbits == 31) wrap = 2;
   else return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15 or 31)");
   if (level < 0 || level > 9) return fail(ZS_STREAM_ERROR, "invalid level");  // deflate.ts:281-294
+  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
+  const zs_strategy_plan sp = zs_plan_strategy(c->o, level, strategy);
   // The streams' dictionaries (dict: the _dict entries), the distinct ones found once.
   // deflateSetDictionary refuses gzip (wrap == 2, deflate.ts:373); level 0 is not built.
   zs_dict_set& ds = c->dset;
@@ -636,8 +654,13 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   }
   // host-side layout: workspace bases (and the sweep's windows, levels 4..9)
   zs_deflate_plan& p = c->dp;
-  zs_plan_deflate(c->o, level, n, h.in_len, p, hasdict ? dict->len : nullptr);
+  zs_plan_deflate(c->o, sp.plan_level, n, h.in_len, p, hasdict ? dict->len : nullptr);
   const MetaLayout ml(n, (uint32_t)p.segs.size());
+  if (sp.tally == ZS_TALLY_HUFF) zs_plan_huff_chunks(n, h.in_len, c->hchunks);
+  else c->hchunks.clear();
+  if (sp.tally == ZS_TALLY_RLE)  // (zs_k_rle_tally's 32-bit positions run 4,416 past a stream's end)
+    for (uint32_t i = 0; i < n; i++)
+      if (h.in_len[i] > 0xffff0000u) return fail(ZS_STREAM_ERROR, "stream too long for Z_RLE");
   // behind the batch's metadata: the streams' dictionary offsets, lengths, ids and parse starts, the
   // joined streams' offsets and lengths, the distinct dictionaries' offsets and lengths
   const size_t nu = hasdict ? ds.uoff.size() : 0;
@@ -645,13 +668,16 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
                m_start = m_did + up256(4ull * n), m_joff = m_start + up256(4ull * n),
                m_jlen = m_joff + up256(8ull * n), m_uoff = m_jlen + up256(4ull * n),
-               m_ulen = m_uoff + up256(8ull * nu), m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
+               m_ulen = m_uoff + up256(8ull * nu), m_chunks = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes,
+               m_end = m_chunks + up256(sizeof(zs_huff_chunk) * c->hchunks.size());  // zs_k_huff_tally's list last
   if (hasdict) {
     HIPCHK(c->djoin.ensure(p.J + 16));
     HIPCHK(c->dadler.ensure(4ull * nu));
   }
-  HIPCHK(c->prevd.ensure(p.prevd_bytes));
-  HIPCHK(c->mres.ensure(p.mres_bytes));
+  if (sp.tally == ZS_TALLY_LEVEL) {  // (the tallies search no matches)
+    HIPCHK(c->prevd.ensure(p.prevd_bytes));
+    HIPCHK(c->mres.ensure(p.mres_bytes));
+  }
   HIPCHK(c->syms.ensure(p.syms_bytes));
   HIPCHK(c->pscr.ensure(p.pscr_bytes));
   HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
@@ -664,6 +690,7 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * n);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * n);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
+    if (!c->hchunks.empty()) memcpy(hm + m_chunks, c->hchunks.data(), sizeof(zs_huff_chunk) * c->hchunks.size());
     if (!hasdict) return;
     memcpy(hm + m_doff, dict->off, 8ull * n);
     memcpy(hm + m_dlen, dict->len, 4ull * n);
@@ -694,7 +721,8 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
     const DeflDict dd = {&b, d_start, (const uint32_t*)(dm + m_did), c->dadler.as<uint32_t>()};
     r = deflate_launch(c, st, level, wrap, kLevels[level], bj, ml, d_status, d_out_len, &dd);
   } else if (r == ZS_OK) {
-    r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len);
+    r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len, nullptr, sp,
+                       (const zs_huff_chunk*)(c->meta.as<uint8_t>() + m_chunks));
   }
   if (r != ZS_OK) return r;
   if (d_check)
@@ -914,10 +942,10 @@ extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, con
   return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, nullptr);
 }
 
-extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
-                                   const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                                   const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
-                                   uint32_t* out_len, uint32_t* check) {
+// The host compress: zs_deflate_batch_ex (strategy 0) and zs_deflate_batch_strategy
+static int deflate_host(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
+                        const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                        const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
@@ -932,8 +960,36 @@ extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, 
                       return deflate_device(c, level, wbits,
                                             {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
                                              ooff, out_cap + a},
-                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false);
+                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false, nullptr,
+                                            strategy);
                     });  // out_len is 0 for failed streams
+}
+
+extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
+                                   const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                   const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                   uint32_t* out_len, uint32_t* check) {
+  return deflate_host(c, level, ZS_DEFAULT_STRATEGY, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len,
+                      check);
+}
+
+// ---- compression strategies (deflateInit2_'s strategy: validation deflate.ts:289-290, dispatch :923-931)
+extern "C" int zs_deflate_batch_strategy_device(zs_ctx* c, int level, int strategy, int wbits, uint32_t n,
+                                                const uint8_t* d_in, const uint64_t* in_off, const uint32_t* in_len,
+                                                uint8_t* d_out, const uint64_t* out_off, const uint32_t* out_cap,
+                                                int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check,
+                                                void* hip_stream) {
+  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
+  return deflate_device(c, level, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len,
+                        d_check, hip_stream, true, nullptr, strategy);
+}
+
+extern "C" int zs_deflate_batch_strategy(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
+                                         const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                         const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                         uint32_t* out_len, uint32_t* check) {
+  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
+  return deflate_host(c, level, strategy, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check);
 }
 
 // ---- preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778)
@@ -1148,6 +1204,8 @@ extern "C" uint64_t zs_debug_fetch(zs_ctx* c, int what, uint32_t s, void* dst, u
   if (s < c->dp.start.size()) n += c->dp.start[s];  // a batch with dictionaries: the joined stream's positions
   const void* src = nullptr;
   uint64_t bytes = 0;
+  // (a batch of the tally kernels -- Z_HUFFMAN_ONLY, Z_RLE -- searches no matches: the tables may not be there)
+  if ((what == 0 && 2ull * (pos_base + n) > c->prevd.cap) || (what == 1 && 8ull * (pos_base + n) > c->mres.cap)) return 0;
   switch (what) {
     case 0: src = c->prevd.as<uint16_t>() + pos_base; bytes = 2ull * n; break;
     case 1: src = c->mres.as<uint2>() + pos_base; bytes = 8ull * n; break;

@@ -482,7 +482,7 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
                                                  const uint32_t* __restrict__ blk_base,
                                                  const uint32_t* __restrict__ syms, zs_block* __restrict__ blocks,
                                                  const zs_stream* __restrict__ streams, uint32_t* __restrict__ codes,
-                                                 uint32_t* __restrict__ hdr, int nstreams) {
+                                                 uint32_t* __restrict__ hdr, int nstreams, int fixed) {
   __shared__ zs_tw w;
   const int s = blockIdx.y;
   const uint32_t b = blockIdx.x;
@@ -621,7 +621,7 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
     t.opt_len += 3u * ((uint32_t)max_blindex + 1) + 5 + 5 + 4;
     uint32_t opt_lenb = (t.opt_len + 3 + 7) >> 3;
     const uint32_t static_lenb = (t.static_len + 3 + 7) >> 3;
-    if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
+    if (static_lenb <= opt_lenb || fixed) opt_lenb = static_lenb;  // trees.ts:567 (fixed: Z_FIXED)
     const uint32_t stored_len = blk.in_end - blk.in_start;
     uint32_t type;
     if (stored_len + 4 <= opt_lenb) type = 0;
@@ -954,9 +954,10 @@ template <bool DICT>
 static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
                           int level, int nstreams, const uint32_t* __restrict__ dstart,
-                          const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler) {
+                          const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler, int strategy) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nstreams || wrap == 0) return;
+  const bool hs = strategy >= 2;  // Z_HUFFMAN_ONLY and above: the "fastest" wrapper bits (deflate.ts:757,798)
   const zs_stream st = streams[s];
   if (st.status != ZS_Z_STREAM_END) return;
   uint32_t* ow = (uint32_t*)(out + out_off[s]);
@@ -964,7 +965,7 @@ static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict_
   const uint64_t tb = st.total_bits / 8;
   if (wrap == 1) {  // zlib: deflate.ts:753-786, 980-983
     uint32_t header = (8u + ((15u - 8u) << 4)) << 8;
-    const uint32_t lf = level < 2 ? 0u : level < 6 ? 1u : level == 6 ? 2u : 3u;
+    const uint32_t lf = (hs || level < 2) ? 0u : level < 6 ? 1u : level == 6 ? 2u : 3u;
     header |= lf << 6;
     const bool fdict = DICT && dstart[s] != 0u;
     if (fdict) header |= 0x20u;  // PRESET_DICT
@@ -977,7 +978,7 @@ static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict_
     }
     for (int i = 0; i < 4; i++) put_byte(tb + i, st.check >> (24 - 8 * i));
   } else {  // gzip: deflate.ts:787-806, 971-979
-    const uint32_t xfl = level == 9 ? 2u : level < 2 ? 4u : 0u;
+    const uint32_t xfl = level == 9 ? 2u : (hs || level < 2) ? 4u : 0u;
     const uint8_t h[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)xfl, 255};
     for (int i = 0; i < 10; i++) put_byte(i, h[i]);
     for (int i = 0; i < 4; i++) put_byte(tb + i, st.check >> (8 * i));
@@ -986,14 +987,14 @@ static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict_
 }
 __global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
-                          int level, int nstreams) {
-  zs_wrap_body<false>(streams, out, out_off, in_len, wrap, level, nstreams, nullptr, nullptr, nullptr);
+                          int level, int nstreams, int strategy) {
+  zs_wrap_body<false>(streams, out, out_off, in_len, wrap, level, nstreams, nullptr, nullptr, nullptr, strategy);
 }
 __global__ void zs_k_wrap_dict(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                                const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
                                int level, int nstreams, const uint32_t* __restrict__ dstart,
                                const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler) {
-  zs_wrap_body<true>(streams, out, out_off, in_len, wrap, level, nstreams, dstart, did, dadler);
+  zs_wrap_body<true>(streams, out, out_off, in_len, wrap, level, nstreams, dstart, did, dadler, 0);
 }
 
 // --------------------------------------------------------------- dictionary join

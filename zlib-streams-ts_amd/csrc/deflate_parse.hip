@@ -135,7 +135,8 @@ extern "C" int zs_parse_stats(unsigned long long* out) {
 // DICT: the stream is a joined one (a preset dictionary's tail, then the data):
 // the parse starts at p0 = dstart[s] in the no-pending-match state deflateSetDictionary leaves
 // (deflate.ts:413-418), the segments, the symbols and the blocks cover [p0, n).
-template <uint32_t WIN, uint32_t SEG, uint32_t NWV, bool DICT>
+// FILT: Z_FILTERED's step (zs_parse.h); the sync argument above holds for it unchanged.
+template <uint32_t WIN, uint32_t SEG, uint32_t NWV, bool DICT, bool FILT>
 static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_seg_tab& T, zs_round_state& RS,
                                                      const uint8_t* __restrict__ in,
                                                      const uint64_t* __restrict__ in_off,
@@ -200,7 +201,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
           yacc.w = m == 3 ? y : yacc.w;
           if (++nsync % 4 == 0) *reinterpret_cast<uint4*>(sync + nsync - 4) = yacc;
         }
-        const uint32_t v = zs_parse_step(st, e, lit, n, good, lazy);
+        const uint32_t v = zs_parse_step<FILT>(st, e, lit, n, good, lazy);
         if (v != ZS_NONE) {
           const uint32_t m = cnt & 3u;
           sacc.x = m == 0 ? v : sacc.x;
@@ -313,7 +314,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
           if ((sv >> 16) == key) { from = sv & 0xffffu; break; }
         }
         const uint32_t p = c.p;
-        const uint32_t v = zs_parse_step(c, M[p], p > 0 ? src[p - 1] : 0u, n, good, lazy);
+        const uint32_t v = zs_parse_step<FILT>(c, M[p], p > 0 ? src[p - 1] : 0u, n, good, lazy);
         if (v != ZS_NONE) {  // gathered four at a time (see pass A)
           const uint32_t m = nf & 3u;
           facc.x = m == 0 ? v : facc.x;
@@ -490,7 +491,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
     __shared__ zs_round_state RS;                                                                                   \
     const uint32_t w_ = threadIdx.x >> 6;                                                                           \
-    zs_parse_body<WIN, SEG, NWV, false>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms,   \
+    zs_parse_body<WIN, SEG, NWV, false, false>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms,   \
                                         blocks, streams, scratch, good, lazy, nullptr);                             \
   }                                                                                                                  \
   __global__ __launch_bounds__(64 * NWV) void name##_dict(                                                           \
@@ -501,8 +502,19 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
     __shared__ zs_round_state RS;                                                                                   \
     const uint32_t w_ = threadIdx.x >> 6;                                                                           \
-    zs_parse_body<WIN, SEG, NWV, true>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres, syms,    \
-                                       blocks, streams, scratch, good, lazy, dstart);                               \
+    zs_parse_body<WIN, SEG, NWV, true, false>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres,  \
+                                              syms, blocks, streams, scratch, good, lazy, dstart);                  \
+  }                                                                                                                  \
+  __global__ __launch_bounds__(64 * NWV) void name##_filt(                                                           \
+      const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,     \
+      const uint64_t* __restrict__ pos_base, const uint32_t* __restrict__ blk_base, const uint2* __restrict__ mres,  \
+      uint32_t* __restrict__ syms, zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,                  \
+      uint32_t* __restrict__ scratch, int good, int lazy) {                                                         \
+    __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
+    __shared__ zs_round_state RS;                                                                                   \
+    const uint32_t w_ = threadIdx.x >> 6;                                                                           \
+    zs_parse_body<WIN, SEG, NWV, false, true>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres,  \
+                                              syms, blocks, streams, scratch, good, lazy, nullptr);                 \
   }
 ZS_PARSE_KERNEL(zs_k_parse, ZS_PARSE_WIN, ZS_PARSE_SEG, 1)
 // two waves per stream, 512-position segments: half the speculative pass per lane (small batches)

@@ -315,6 +315,23 @@ extern "C" int zs_pool_deflate_batch(zs_pool* p, int level, int wbits, uint32_t 
   });
 }
 
+// with a compression strategy (deflate.ts:289-290, :923-931)
+extern "C" int zs_pool_deflate_batch_strategy(zs_pool* p, int level, int strategy, int wbits, uint32_t n,
+                                              const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                              uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                              int32_t* status, uint32_t* out_len, uint32_t* check) {
+  if (strategy < 0 || strategy > ZS_FIXED) {
+    zs_set_last_error("invalid strategy");
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_deflate_batch_strategy(p->ctx[k], level, strategy, wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, out,
+                                     out_off + s.a, out_cap + s.a, status + s.a, out_len + s.a,
+                                     check ? check + s.a : nullptr);
+  });
+}
+
 // with preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778):
 // every shard reads the caller's one dictionary buffer
 extern "C" int zs_pool_deflate_batch_dict(zs_pool* p, int level, int wbits, uint32_t n, const uint8_t* in,

@@ -47,7 +47,8 @@ template <bool U8>
 __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                            const zs_sweep_seg* segs, const uint16_t* members, uint2* mres, int chain, int nice);
 // the lazy parse (deflate_parse.hip): pass A stages 32 match-table entries per lane in LDS; the
-// _dict instances parse joined streams (dictionary tail + data) from dstart[s] on
+// _dict instances parse joined streams (dictionary tail + data) from dstart[s] on; the _filt
+// instances are Z_FILTERED's (a new match of at most 5 bytes is dropped, deflate.ts:1381-1387)
 #define ZS_PARSE_DECL(name)                                                                                        \
   __global__ void name(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base, \
                        const uint32_t* blk_base, const uint2* mres, uint32_t* syms, zs_block* blocks,              \
@@ -55,7 +56,10 @@ __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint
   __global__ void name##_dict(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,                   \
                               const uint64_t* pos_base, const uint32_t* blk_base, const uint2* mres, uint32_t* syms, \
                               zs_block* blocks, zs_stream* streams, uint32_t* scratch, int good, int lazy,         \
-                              const uint32_t* dstart);
+                              const uint32_t* dstart);                                                           \
+  __global__ void name##_filt(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,                   \
+                              const uint64_t* pos_base, const uint32_t* blk_base, const uint2* mres, uint32_t* syms, \
+                              zs_block* blocks, zs_stream* streams, uint32_t* scratch, int good, int lazy);
 ZS_PARSE_DECL(zs_k_parse)
 ZS_PARSE_DECL(zs_k_parse_2w)  // two waves per stream, ZS_PARSE2W_SEG-position segments
 ZS_PARSE_DECL(zs_k_parse_4w)  // four waves per stream, ZS_PARSE4W_SEG-position segments
@@ -74,9 +78,17 @@ __global__ void zs_k_fast_serial(const uint8_t* in, const uint64_t* in_off, cons
 __global__ void zs_k_dict_join(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint8_t* dict,
                                const uint64_t* dict_off, const uint32_t* dict_len, const uint32_t* dstart,
                                uint8_t* joined, const uint64_t* joff);
+// fixed: Z_FIXED (trees.ts:567: the static trees' length is taken whatever the dynamic ones')
 __global__ void zs_k_trees(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base, const uint32_t* blk_base,
                            const uint32_t* syms, zs_block* blocks, const zs_stream* streams, uint32_t* codes,
-                           uint32_t* hdr, int nstreams);
+                           uint32_t* hdr, int nstreams, int fixed);
+// the tallies of Z_HUFFMAN_ONLY and of zlib's Z_RLE (deflate_strategy.hip): symbols, block records, nsym / nblk
+__global__ void zs_k_huff_tally(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                const uint64_t* pos_base, const uint32_t* blk_base, const zs_huff_chunk* chunks,
+                                uint32_t* syms, zs_block* blocks, zs_stream* streams);
+__global__ void zs_k_rle_tally(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                               const uint64_t* pos_base, const uint32_t* blk_base, uint32_t* syms, zs_block* blocks,
+                               zs_stream* streams);
 __global__ void zs_k_layout(const uint32_t* blk_base, zs_block* blocks, zs_stream* streams, const uint32_t* out_cap,
                             uint8_t* out, const uint64_t* out_off, int wrap, int nstreams);
 // zlib streams with a preset dictionary (dstart[s] != 0): FDICT and DICTID (deflate.ts:767-778)
@@ -92,7 +104,7 @@ __global__ void zs_k_stored(const uint8_t* in, const uint64_t* in_off, const uin
                             const uint64_t* out_off, const uint32_t* out_cap, const uint32_t* check, int wrap,
                             int32_t* status, uint32_t* out_len_res);
 __global__ void zs_k_wrap(const zs_stream* streams, uint8_t* out, const uint64_t* out_off, const uint32_t* in_len,
-                          int wrap, int level, int nstreams);
+                          int wrap, int level, int nstreams, int strategy);
 __global__ void zs_k_checksum(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* check,
                               int kind, const uint32_t* seeds = nullptr);
 __global__ void zs_k_selftest(uint32_t* bad, int rounds);

@@ -19,6 +19,8 @@ struct zs_pstate {
 // Written without branches (selects only): the lanes of a wave stand at
 // different points of their parses, and a branchy step costs every lane all
 // paths plus the exec-mask bookkeeping.
+// FILT: Z_FILTERED -- a new match of at most 5 bytes is dropped like a too-far one.
+template <bool FILT = false>
 static __device__ __forceinline__ uint32_t zs_parse_step(zs_pstate& st, uint2 e, uint32_t lit, uint32_t n, int good,
                                                          int lazy) {
   const uint32_t p = st.p, pl = st.ml, pm = st.ms;
@@ -31,7 +33,7 @@ static __device__ __forceinline__ uint32_t zs_parse_step(zs_pstate& st, uint2 e,
   const uint32_t L = (u >> 16) & 0x1ffu, D = u & 0x7fffu;
   const bool take = search & (L > pl);
   const uint32_t ms = take ? p - D : pm;
-  const bool too_far = (L == ZS_MIN_MATCH) & (D > ZS_TOO_FAR);  // deflate.ts:1381-1387
+  const bool too_far = FILT ? L <= 5u : (L == ZS_MIN_MATCH) & (D > ZS_TOO_FAR);  // deflate.ts:1381-1387
   const uint32_t ml = (take & !too_far) ? L : ZS_MIN_MATCH - 1;
   const bool emit = (pl >= ZS_MIN_MATCH) & (ml <= pl);  // emit the previous match (deflate.ts:1389-1411)
   const uint32_t sym = 0x80000000u | ((pl - ZS_MIN_MATCH) << 16) | (p - 1 - pm);

@@ -86,6 +86,9 @@ struct zs_route_opts {
   uint32_t ncu = 256;               // compute units of the device
   int parse_waves = 0;       // L4..9 one-wave parse: waves per stream (1, 2; 0: chosen from the batch size)
   bool match_sweep = true;   // 0: the chain-walk kernels for every stream (a cross-check of the sweep)
+  // Z_RLE: 1 reproduces the reference's deflate_rle, whose scan compares the previous byte's value
+  // with the scan index (deflate.ts:1469-1481) and so finds no run: deflate_huff's tally; 0: zlib's
+  bool rle_ref = true;
 };
 
 // ---- inflate
@@ -324,6 +327,51 @@ static inline uint32_t zs_parse_seg(int w) {
 }
 static inline uint32_t zs_parse_seg_words(int w) {
   return w == 4 ? ZS_PARSE4W_SEG_WORDS : w == 2 ? ZS_PARSE2W_SEG_WORDS : ZS_PARSE_SEG_WORDS;
+}
+
+// ---- compression strategies (deflateInit2_'s strategy, deflate.ts:289-290; dispatch :923-931)
+#define ZS_STRAT_DEFAULT 0
+#define ZS_STRAT_FILTERED 1
+#define ZS_STRAT_HUFFMAN_ONLY 2
+#define ZS_STRAT_RLE 3
+#define ZS_STRAT_FIXED 4
+// who tallies the symbols of a batch
+#define ZS_TALLY_LEVEL 0  // the level's own path: deflate_fast (1..3) or the match search + lazy parse (4..9)
+#define ZS_TALLY_HUFF 1   // zs_k_huff_tally: every byte a literal (deflate_huff, deflate.ts:1525-1565)
+#define ZS_TALLY_RLE 2    // zs_k_rle_tally: zlib's deflate_rle, matches at distance 1
+struct zs_strategy_plan {
+  bool stored = false;    // level 0: deflate_stored whatever the strategy (deflate.ts:925)
+  int tally = ZS_TALLY_LEVEL;
+  bool filtered = false;  // the lazy parse's _filt instances (levels 4..9; deflate_fast has no filtered branch)
+  bool fixed = false;     // zs_k_trees takes the static trees' length (trees.ts:567)
+  int wrap_strategy = 0;  // zs_k_wrap: >= 2 clears the zlib level bits and sets gzip XFL 4 below level 9 (deflate.ts:757,798)
+  int plan_level = 0;     // the level zs_plan_deflate lays the workspace out for (1 for the tallies: no windows, no parse scratch)
+};
+// level: 0..9; strategy: 0..4 (validated by the caller)
+static inline zs_strategy_plan zs_plan_strategy(const zs_route_opts& o, int level, int strategy) {
+  zs_strategy_plan sp;
+  sp.plan_level = level;
+  if (level == 0) {
+    sp.stored = true;
+    return sp;
+  }
+  sp.wrap_strategy = strategy;
+  if (strategy == ZS_STRAT_FILTERED) sp.filtered = level >= 4;
+  else if (strategy == ZS_STRAT_HUFFMAN_ONLY) sp.tally = ZS_TALLY_HUFF;
+  else if (strategy == ZS_STRAT_RLE) sp.tally = o.rle_ref ? ZS_TALLY_HUFF : ZS_TALLY_RLE;
+  else if (strategy == ZS_STRAT_FIXED) sp.fixed = true;
+  if (sp.tally != ZS_TALLY_LEVEL) sp.plan_level = 1;
+  return sp;
+}
+// zs_k_huff_tally's grid: one workgroup per (stream, block of 16,383 bytes); a stream of n
+// bytes has n / 16383 + 1 blocks (the last one final, possibly empty)
+struct zs_huff_chunk {
+  uint32_t s, b;
+};
+static inline void zs_plan_huff_chunks(uint32_t n, const uint32_t* in_len, std::vector<zs_huff_chunk>& chunks) {
+  chunks.clear();
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t b = 0; b <= in_len[i] / ZS_SYM_END; b++) chunks.push_back({i, b});
 }
 
 // The workspace layout of a deflate batch (levels 1..9).  With the sweep (levels

@@ -17,7 +17,17 @@ export interface CompressBatchOptions extends BatchOptions {
    * right after deflateInit2_: one view shared by all inputs, or one per input (null = none).  "deflate"
    * outputs carry FDICT and DICTID.  With "gzip", or with level 0, the call fails with "init failed: -2". */
   dictionary?: ArrayBufferView | (ArrayBufferView | null)[];
+  /** deflateInit2_'s strategy (deflate.ts:289-290, :923-931): 0 Z_DEFAULT_STRATEGY (any non-number),
+   * 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE (the reference's, which finds no run: Z_HUFFMAN_ONLY's bytes),
+   * 4 Z_FIXED.  A number out of range fails with "init failed: -2" (code "-2" from the detailed entry);
+   * together with `dictionary` it is a TypeError. */
+  strategy?: number;
 }
+export const Z_DEFAULT_STRATEGY: 0;
+export const Z_FILTERED: 1;
+export const Z_HUFFMAN_ONLY: 2;
+export const Z_RLE: 3;
+export const Z_FIXED: 4;
 export interface DecompressBatchOptions extends BatchOptions {
   /** Output cap per stream (bytes), one number for all or one per input.  Default: none -- the
    * output is unbounded, as DecompressionStream's; a stream over a given cap rejects. */

@@ -72,6 +72,18 @@ function dictionariesOf(options, n) {
   return new Array(n).fill(shared);
 }
 
+// options.strategy: deflateInit2_'s strategy (deflate.ts:289-290, :923-931), 0 Z_DEFAULT_STRATEGY ..
+// 4 Z_FIXED.  A strategy that is not a number means 0 (the rule of `level`, streams.ts:221); a
+// number out of range fails with "init failed: -2"; together with a dictionary it is a TypeError
+// (no dictionaries with a strategy: zs_gpu.h).
+export const Z_DEFAULT_STRATEGY = 0, Z_FILTERED = 1, Z_HUFFMAN_ONLY = 2, Z_RLE = 3, Z_FIXED = 4;
+function strategyOf(options) {
+  const s = typeof options.strategy == "number" ? options.strategy : 0;
+  if (s !== 0 && options.dictionary !== undefined && options.dictionary !== null)
+    throw new TypeError("strategy and dictionary cannot be combined");
+  return s;
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
@@ -82,7 +94,8 @@ async function runCompress(inputs, format, options) {
   let res;
   try {
     const ins = checkInputs(inputs);
-    res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length));
+    res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
+                                    strategyOf(options));
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -142,7 +155,8 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
   options = options || {};
   const level = typeof options.level == "number" ? options.level : -1;
   const ins = checkInputs(inputs);
-  return addon.compressBatch(ins, compressWbits(format), level, devicesOf(options), dictionariesOf(options, ins.length));
+  return addon.compressBatch(ins, compressWbits(format), level, devicesOf(options), dictionariesOf(options, ins.length),
+                             strategyOf(options));
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

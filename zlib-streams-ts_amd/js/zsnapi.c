@@ -198,6 +198,7 @@ typedef struct {
   int inflate;   /* 0 compress, 1 decompress */
   int unbounded; /* decompress without a caller capacity: zs_pool_inflate_batch_auto */
   int wbits, level;
+  int strategy;  /* compress: deflateInit2_'s strategy (zs_pool_deflate_batch_strategy when not 0) */
   uint32_t n;
   zs_pool *pool;
   uint64_t *in_off, *out_off;
@@ -272,6 +273,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_deflate_batch_dict(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                        j->out_off, j->cap, j->status, j->olen, j->check, j->dict, j->dict_off,
                                        j->dict_len);
+  else if (j->strategy)
+    j->rc = zs_pool_deflate_batch_strategy(j->pool, j->level, j->strategy, j->wbits, j->n, j->base, j->in_off, j->in_len,
+                                           j->out, j->out_off, j->cap, j->status, j->olen, j->check);
   else
     j->rc = zs_pool_deflate_batch(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                   j->out_off, j->cap, j->status, j->olen, j->check);
@@ -443,13 +447,22 @@ static int copy_dicts(napi_env env, job *j, napi_value arr) {
 }
 
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
- *               dictionaries: (Uint8Array | null)[] | undefined) ->
+ *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined) ->
+ * strategy: 0..4 (a non-number means 0); out of range, or not 0 together with dictionaries, throws code "-2"
+ * (deflate.ts:289-290; no dictionaries with a strategy, zs_gpu.h) before any device is touched ->
  *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
 static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 6;
+  napi_value argv[6];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 3) return throw_code(env, ZS_STREAM_ERROR, "compressBatch(inputs, wbits, level[, devices[, dictionaries]])");
+  if (argc < 3)
+    return throw_code(env, ZS_STREAM_ERROR, "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy]]])");
+  const int32_t strategy = argc > 5 ? arg_i32(env, argv[5], 0) : 0;
+  if (strategy < 0 || strategy > ZS_FIXED) return throw_code(env, ZS_STREAM_ERROR, "invalid strategy");
+  napi_valuetype dt = napi_undefined;
+  if (argc > 4) napi_typeof(env, argv[4], &dt);
+  if (strategy && dt != napi_undefined && dt != napi_null)
+    return throw_code(env, ZS_STREAM_ERROR, "a strategy with preset dictionaries is not built");
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -465,8 +478,7 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   j->pool = pool;
   j->wbits = arg_i32(env, argv[1], -15);
   j->level = arg_i32(env, argv[2], -1);
-  napi_valuetype dt = napi_undefined;
-  if (argc > 4) napi_typeof(env, argv[4], &dt);
+  j->strategy = strategy;
   if (dt != napi_undefined && dt != napi_null) {
     bool is_arr = false;
     napi_is_array(env, argv[4], &is_arr);

@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("ZS_LIB") or os.path.join(os.path.dirname(_HERE), "lib
 Z_OK, Z_STREAM_END, Z_NEED_DICT = 0, 1, 2
 Z_STREAM_ERROR, Z_DATA_ERROR, Z_MEM_ERROR, Z_BUF_ERROR = -2, -3, -4, -5
 PHASE_NONE, PHASE_INIT, PHASE_PROCESS, PHASE_FINISH = 0, 1, 2, 3
+# deflateInit2_'s strategy (deflate.ts:289-290, :923-931; ZS_* in zs_gpu.h)
+Z_DEFAULT_STRATEGY, Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED = 0, 1, 2, 3, 4
 
 # format -> windowBits, streams.ts:220 (compression) and :233 (decompression).
 # Unknown strings fall through to 15 there ("deflate"); the same here.
@@ -60,6 +62,18 @@ def compress_level(level) -> int:
     if isinstance(level, bool) or not isinstance(level, int):
         return -1
     return level
+
+
+def compress_strategy(strategy, zdict=None) -> int:
+    """The `strategy` keyword of the compress entries: 0..4 (Z_DEFAULT_STRATEGY .. Z_FIXED);
+    anything else is deflateInit2_'s Z_STREAM_ERROR (deflate.ts:289-290), reported as the
+    stream layer does ("init failed: -2", streams.ts:53).  A strategy other than 0 together
+    with a preset dictionary is not built (zs_gpu.h): ValueError, before any call."""
+    if isinstance(strategy, bool) or not isinstance(strategy, int) or not 0 <= strategy <= Z_FIXED:
+        raise ZsError("init failed: %d" % Z_STREAM_ERROR, Z_STREAM_ERROR, PHASE_INIT, "invalid strategy")
+    if strategy and zdict is not None:
+        raise ValueError("strategy %d with a preset dictionary is not built" % strategy)
+    return strategy
 
 
 def stream_error_text(status: int, phase: int) -> str:
@@ -113,6 +127,11 @@ def lib():
         L.zs_deflate_bound_dict.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
         L.zs_deflate_batch_dict.argtypes = L.zs_deflate_batch_ex.argtypes + _dict
         L.zs_deflate_batch_dict_device.argtypes = L.zs_deflate_batch_device_ex.argtypes + [_P, _U64P, _U32P]
+    if hasattr(L, "zs_deflate_batch_strategy"):  # `strategy` behind `level`
+        _with = lambda a: a[:2] + [ctypes.c_int] + a[2:]
+        L.zs_deflate_batch_strategy.argtypes = _with(L.zs_deflate_batch_ex.argtypes)
+        L.zs_deflate_batch_strategy_device.argtypes = _with(L.zs_deflate_batch_device_ex.argtypes)
+        L.zs_pool_deflate_batch_strategy.argtypes = _with(L.zs_deflate_batch_ex.argtypes)
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -261,26 +280,30 @@ class Engine:
             raise ZsUnavailable("%s failed (%d): %s" % (what, r, msg))
 
     # ---------------------------------------------------------- host buffers
-    def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
-                           ) -> List[Tuple[int, bytes]]:
+    def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
+                           strategy: int = 0) -> List[Tuple[int, bytes]]:
         """Returns [(status, bytes)] -- status Z_STREAM_END on success.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
-        (zs_deflate_batch_dict: deflateSetDictionary, deflate.ts:367-424)."""
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict)]
+        (zs_deflate_batch_dict: deflateSetDictionary, deflate.ts:367-424).
+        strategy: Z_DEFAULT_STRATEGY .. Z_FIXED (zs_deflate_batch_strategy; not with zdict)."""
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy)]
 
-    def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
-                                ) -> List[Tuple[int, bytes, int]]:
+    def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
+                                strategy: int = 0) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
+        if compress_strategy(strategy, zdict):
+            return _deflate_host(self._L, self._L.zs_deflate_batch_strategy, self._ctx, inputs, fmt, level,
+                                 self._check, strategy=strategy)
         if zdict is not None:
             return _deflate_host(self._L, self._L.zs_deflate_batch_dict, self._ctx, inputs, fmt, level, self._check,
                                  _dict_layout(zdict, len(inputs)))
         return _deflate_host(self._L, self._L.zs_deflate_batch_ex, self._ctx, inputs, fmt, level, self._check)
 
-    def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None
-                       ) -> List[bytes]:
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict))
+    def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
+                       strategy: int = 0) -> List[bytes]:
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None):
@@ -310,10 +333,19 @@ class Engine:
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                         d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
-                        dict_off=None, dict_len=None):
+                        dict_off=None, dict_len=None, strategy: int = 0):
         """Device pointers (ints) + host layout arrays (ctypes arrays).
         d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
-        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none)."""
+        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
+        strategy: zs_deflate_batch_strategy_device (not with dictionaries)."""
+        if compress_strategy(strategy, dict_off):
+            r = self._L.zs_deflate_batch_strategy_device(self._ctx, compress_level(level), strategy,
+                                                         compress_wbits(fmt), n, _P(d_in), in_off, in_len, _P(d_out),
+                                                         out_off, out_cap, _P(d_status), _P(d_out_len),
+                                                         _P(d_check) if d_check else None,
+                                                         _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_deflate_batch_strategy_device")
+            return
         if dict_off is not None:
             r = self._L.zs_deflate_batch_dict_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
                                                      _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
@@ -348,9 +380,16 @@ class Engine:
         self._check(r, "zs_inflate_batch_device")
 
     def compress_host(self, level: int, fmt: str, n: int, h_in: int, in_off, in_len, h_out: int, out_off, out_cap,
-                      status, out_len):
+                      status, out_len, strategy: int = 0):
         """zs_deflate_batch on caller-owned host memory (pointers as ints,
-        layout/result arrays as ctypes arrays): the end-to-end host->host path."""
+        layout/result arrays as ctypes arrays): the end-to-end host->host path
+        (strategy: zs_deflate_batch_strategy)."""
+        if compress_strategy(strategy):
+            r = self._L.zs_deflate_batch_strategy(self._ctx, level, strategy, compress_wbits(fmt), n,
+                                                  ctypes.cast(h_in, ctypes.c_char_p), in_off, in_len, _P(h_out),
+                                                  out_off, out_cap, status, out_len, None)
+            self._check(r, "zs_deflate_batch_strategy")
+            return
         r = self._L.zs_deflate_batch(self._ctx, level, compress_wbits(fmt), n, ctypes.cast(h_in, ctypes.c_char_p),
                                      in_off, in_len, _P(h_out), out_off, out_cap, status, out_len)
         self._check(r, "zs_deflate_batch")
@@ -404,7 +443,7 @@ def _layout(inputs):
     return b"".join(inputs), offs, lens
 
 
-def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=()):
+def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None):
     n = len(inputs)
     if n == 0:
         return []
@@ -420,7 +459,8 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=()):
         oo += c
     out = ctypes.create_string_buffer(max(1, oo))
     status, olen, chk = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
-    r = fn(handle, compress_level(level), wbits, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
+    lead = (compress_level(level),) if strategy is None else (compress_level(level), strategy)  # (fn: a _strategy entry)
+    r = fn(handle, *lead, wbits, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
            out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk, *zdict)
     check(r, "deflate batch")
     raw = out.raw
@@ -553,17 +593,20 @@ class Pool:
     def _check(self, r: int, what: str):
         Engine._check(self, r, what)
 
-    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
+    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
+        if compress_strategy(strategy, zdict):
+            return _deflate_host(self._L, self._L.zs_pool_deflate_batch_strategy, self._pool, inputs, fmt, level,
+                                 self._check, strategy=strategy)
         if zdict is not None:
             return _deflate_host(self._L, self._L.zs_pool_deflate_batch_dict, self._pool, inputs, fmt, level,
                                  self._check, _dict_layout(zdict, len(inputs)))
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
-    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict)]
+    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy)]
 
-    def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None):
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict))
+    def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
         L = self._L
