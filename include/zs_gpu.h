@@ -316,6 +316,49 @@ int zs_pool_deflate_batch_strategy(zs_pool *pool, int level, int strategy, int w
                                    const uint64_t *out_off, const uint32_t *out_cap, int32_t *status,
                                    uint32_t *out_len, uint32_t *check);
 
+/* windowBits and memLevel: stream i is the bytes of deflateInit2_(level, Z_DEFLATED, wbits,
+ * mem_level, Z_DEFAULT_STRATEGY) (deflate.ts:253-343) and the stream layer's one write() +
+ * close(), for the whole range of both arguments.  The window is w_size = 1 << windowBits
+ * bytes (a decoder with that much window can inflate the stream), the hash has mem_level + 7
+ * bits, and a block closes after (1 << (mem_level + 6)) - 1 symbols (deflate.ts:295-336).
+ * The entries take the arguments of zs_deflate_batch_device_ex / zs_deflate_batch_ex /
+ * zs_pool_deflate_batch with `mem_level` behind `wbits`.
+ *  - wbits: -9..-15 raw deflate, 8..15 zlib, 25..31 gzip.  8 runs as 9 and writes CINFO 1
+ *    (deflate.ts:295-297); the zlib header's CINFO is windowBits - 8 and FCHECK follows it
+ *    (deflate.ts:754-770); the gzip header does not change;
+ *  - -8, 24, any other wbits: the call returns ZS_STREAM_ERROR, zs_last_error() "invalid window
+ *    bits"; mem_level outside 1..9: ZS_STREAM_ERROR, "invalid memLevel" (deflate.ts:281-294,
+ *    "init failed: -2").  Both are checked before the context is looked at;
+ *  - wbits -15, 15 or 31 with mem_level 8 is the counterpart's call: the same plan, kernels
+ *    and bytes;
+ *  - level 0 with any other parameters: ZS_STREAM_ERROR (not built: deflate_stored's cuts then
+ *    depend on w_size, pending_buf_size and the stream layer's output buffers, which no
+ *    available yardstick reproduces);
+ *  - preset dictionaries and strategies are not built with these parameters: there are no
+ *    _dict or _strategy forms of these entries;
+ *  - statuses, check values, Z_BUF_ERROR and the 4-byte alignment rule of the device form as
+ *    the plain entries.  Size outputs with zs_deflate_bound_params. */
+/* deflateBound (deflate.ts:619-673) for deflateInit2_'s windowBits (as above) and mem_level: with
+ * w_bits != 15 or hash_bits != 15 it is (w_bits <= hash_bits && level ? fixedlen : storelen) +
+ * wraplen (deflate.ts:669-671), fixedlen = n + (n >> 3) + (n >> 8) + (n >> 9) + 4, storelen =
+ * n + (n >> 5) + (n >> 7) + (n >> 11) + 7; otherwise zs_deflate_bound's formula.  0 for
+ * parameters the entries refuse. */
+uint64_t zs_deflate_bound_params(uint64_t source_len, int wbits, int mem_level, int level);
+/* deflate.ts:253-343 -- device buffers (as zs_deflate_batch_device_ex) */
+int zs_deflate_batch_params_device(zs_ctx *ctx, int level, int wbits, int mem_level, uint32_t n_streams,
+                                   const uint8_t *d_in, const uint64_t *in_off, const uint32_t *in_len,
+                                   uint8_t *d_out, const uint64_t *out_off, const uint32_t *out_cap,
+                                   int32_t *d_status, uint32_t *d_out_len, uint32_t *d_check, void *hip_stream);
+/* deflate.ts:253-343 -- host buffers (as zs_deflate_batch_ex) */
+int zs_deflate_batch_params(zs_ctx *ctx, int level, int wbits, int mem_level, uint32_t n_streams, const uint8_t *in,
+                            const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                            const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check);
+/* deflate.ts:253-343 -- the pool (as zs_pool_deflate_batch) */
+int zs_pool_deflate_batch_params(zs_pool *pool, int level, int wbits, int mem_level, uint32_t n_streams,
+                                 const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *status,
+                                 uint32_t *out_len, uint32_t *check);
+
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);
 

@@ -105,6 +105,7 @@ struct zs_ctx {
   Buf wlist;
   Buf dadler, d_dict;  // preset dictionaries: the distinct ones' adler32; the host entries' staging of their bytes
   Buf djoin;           // deflate with dictionaries: the joined streams (zs_k_dict_join)
+  Buf ghead;           // levels 1..3 at memLevel 9 and a large window: head[] per stream (zs_plan_fast_params)
   zs_dict_set dset;
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
@@ -375,6 +376,21 @@ uint64_t zs_deflate_bound(uint64_t n, int wbits) {  // deflate.ts:615-674, memLe
   return b;  // (output capacities must still be multiples of 4: round up when allocating)
 }
 
+// deflate.ts:619-673 for deflateInit2_'s windowBits and memLevel
+uint64_t zs_deflate_bound_params(uint64_t n, int wbits, int mem_level, int level) {
+  int wrap;
+  const int wb = zs_wbits_split(wbits, &wrap);
+  if (!wb || mem_level < 1 || mem_level > 9) return 0;
+  const zs_deflate_params q = zs_make_params(wb, mem_level);
+  const uint64_t wraplen = wrap == 0 ? 0 : wrap == 1 ? 6 : 18;
+  if (q.w_bits != 15 || q.hash_bits != 8 + 7) {  // deflate.ts:669-671
+    const uint64_t fixedlen = n + (n >> 3) + (n >> 8) + (n >> 9) + 4;
+    const uint64_t storelen = n + (n >> 5) + (n >> 7) + (n >> 11) + 7;
+    return (q.w_bits <= q.hash_bits && level ? fixedlen : storelen) + wraplen;
+  }
+  return zs_deflate_bound(n, wrap == 0 ? -15 : wrap == 1 ? 15 : 31);
+}
+
 uint64_t zs_deflate_bound_dict(uint64_t n, int wbits, uint64_t dict_len) {  // deflate.ts:633: DICTID (zlib, strstart != 0)
   return zs_deflate_bound(n, wbits) + (wbits == 15 && dict_len ? 4u : 0u);
 }
@@ -494,8 +510,12 @@ struct DeflDict {
 // sp: the strategy's routes (zs_plan_strategy); d_chunks: zs_k_huff_tally's list (c->hchunks, uploaded).
 static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const zs_level_cfg& cfg, const Batch& b,
                           const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len, const DeflDict* dd = nullptr,
-                          const zs_strategy_plan& sp = zs_strategy_plan(), const zs_huff_chunk* d_chunks = nullptr) {
+                          const zs_strategy_plan& sp = zs_strategy_plan(), const zs_huff_chunk* d_chunks = nullptr,
+                          const zs_deflate_params& q = zs_deflate_params()) {
   const zs_deflate_plan& p = c->dp;
+  // non-default windowBits / memLevel (never with dd or a strategy): the *_par instances
+  const bool par = !q.is_default();
+  const zs_kpar kp = q.kpar();
   const uint32_t n = b.n;
   const uint8_t* dm = c->meta.as<uint8_t>();
   const uint64_t* d_pos = (const uint64_t*)(dm + ml.pos_base);
@@ -520,7 +540,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
   } else if (sp.tally == ZS_TALLY_RLE) {
     zs_k_rle_tally<<<n, 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st);
     MARK("rle_tally");
-  } else if (level >= 4 && c->o.match_sweep) {
+  } else if (level >= 4 && p.sweep) {
     const uint32_t nw = (uint32_t)p.segs.size();
     // a window: counting sort by hash + lock-step sweep (deflate_sweep.hip)
     (c->lane_order ? zs_k_bucket<true> : zs_k_bucket<false>)<<<nw, ZS_BK_THREADS, 0, st>>>(
@@ -530,6 +550,15 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
     (zs_sweep_uniform8(cfg.chain) ? zs_k_sweep<true> : zs_k_sweep<false>)<<<nw, 1024, 0, st>>>(
         b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(), c->mres.as<uint2>(), cfg.chain, cfg.nice);
     MARK("sweep");
+  } else if (level >= 4 && par) {
+    // the chain-walk kernels with the runtime window and hash (they follow prev[] links whatever the hash)
+    const dim3 g((p.max_len + 8191) / 8192, n);
+    (c->lane_order ? zs_k_prev_par<true> : zs_k_prev_par<false>)<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_pos,
+                                                                                   c->prevd.as<uint16_t>(), 0u, kp);
+    MARK("prev");
+    if (p.max_len) zs_k_match_par<<<g, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, c->prevd.as<uint16_t>(),
+                                                       c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u, kp);
+    MARK("match");
   } else if (level >= 4) {
     // cross-check (option match_sweep = 0): the chain-walk kernels for every stream
     const dim3 g((p.max_len + 8191) / 8192, n);
@@ -544,7 +573,11 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
     // (the tally kernels wrote the symbols and the block records)
   } else if (level >= 4) {
     const int pw = p.pw;  // waves per stream of the lazy parse (deflate_parse.hip)
-    if (dd) {
+    if (par) {
+      auto parse = pw == 4 ? zs_k_parse_4w_par : pw == 2 ? zs_k_parse_2w_par : zs_k_parse_par;
+      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
+                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, kp);
+    } else if (dd) {
       auto parse = pw == 4 ? zs_k_parse_4w_dict : pw == 2 ? zs_k_parse_2w_dict : zs_k_parse_dict;
       parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
                                    c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, dd->start);
@@ -555,6 +588,23 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
                                    c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
     }
     MARK("parse");
+  } else if (par) {
+    // levels 1..3: the instance and its LDS by the tables' sizes (zs_plan_fast_params)
+    const zs_fast_plan f = zs_plan_fast_params(q, c->fast_group, n);
+    uint16_t* gh = f.route == ZS_FAST_SERIAL_GHEAD ? c->ghead.as<uint16_t>() : nullptr;
+    if (f.route == ZS_FAST_GROUP) {
+      auto fast = c->lane_order ? (cfg.nice <= 8 ? zs_k_fast_par<2, true, false> : cfg.nice <= 16 ? zs_k_fast_par<4, true, false> : zs_k_fast_par<8, true, false>)
+                                : (cfg.nice <= 8 ? zs_k_fast_par<2, false, false> : cfg.nice <= 16 ? zs_k_fast_par<4, false, false> : zs_k_fast_par<8, false, false>);
+      HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
+      fast<<<n, 64, f.lds_bytes, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                       cfg.nice, nullptr, kp);
+    } else {
+      auto fast = gh ? zs_k_fast_serial_par<false, true> : zs_k_fast_serial_par<false, false>;
+      HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
+      fast<<<n, 64, f.lds_bytes, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                       cfg.nice, nullptr, kp, gh);
+    }
+    MARK("fast");
   } else {
     const int fast_smem = 2 * 32768 * 2 + 32768;  // head[] + prev[] (u16 x 32 K each) + the 32 KiB input ring
     // levels 1..3: the group-speculative replay (default) or the step-by-step one (fast_group = 0);
@@ -571,8 +621,9 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
                                    cfg.nice, dd ? dd->start : nullptr);
     MARK("fast");
   }
-  zs_k_trees<<<dim3(p.max_blk, n), 64, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
-                                                c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n, sp.fixed ? 1 : 0);
+  (par ? zs_k_trees_par : zs_k_trees)<<<dim3(p.max_blk, n), 64, 0, st>>>(
+      b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st, c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n,
+      sp.fixed ? 1 : 0);
   MARK("trees");
   if (dd) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
                                                              dd->start);
@@ -584,6 +635,9 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const 
   if (wrap && dd)
     zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, dd->start,
                                                      dd->did, dd->dadler);
+  else if (wrap && par)
+    zs_k_wrap_par<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n,
+                                                    sp.wrap_strategy, q.w_bits);
   else if (wrap)
     zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, sp.wrap_strategy);
   zs_k_finish<<<nblocks_s, nthreads_s, 0, st>>>(d_st, d_status, d_out_len, (int)n);
@@ -611,7 +665,7 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
 // of them set is the plain batch.
 static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
                           uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict = nullptr,
-                          int strategy = ZS_DEFAULT_STRATEGY) {
+                          int strategy = ZS_DEFAULT_STRATEGY, const zs_deflate_params& q = zs_deflate_params()) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION, deflate.ts:268-270
   int wrap;
@@ -644,6 +698,8 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   for (uint32_t i = 0; i < n; i++)
     if ((h.out_off[i] & 3) || (caller_regions && (h.out_cap[i] & 3)))
       return fail(ZS_STREAM_ERROR, "output offsets/capacities must be multiples of 4");
+  if (level == 0 && !q.is_default())
+    return fail(ZS_STREAM_ERROR, "level 0 with non-default windowBits / memLevel is not built");
   if (level == 0) {
     const int r = deflate_stored_batch(c, wrap, h, d_status, d_out_len, st);
     if (r == ZS_OK && d_check) {
@@ -654,7 +710,8 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
   }
   // host-side layout: workspace bases (and the sweep's windows, levels 4..9)
   zs_deflate_plan& p = c->dp;
-  zs_plan_deflate(c->o, sp.plan_level, n, h.in_len, p, hasdict ? dict->len : nullptr);
+  zs_plan_deflate(c->o, sp.plan_level, n, h.in_len, p, hasdict ? dict->len : nullptr, q);
+  if (!q.is_default() && level <= 3) HIPCHK(c->ghead.ensure(zs_plan_fast_params(q, c->fast_group, n).ghead_bytes));
   const MetaLayout ml(n, (uint32_t)p.segs.size());
   if (sp.tally == ZS_TALLY_HUFF) zs_plan_huff_chunks(n, h.in_len, c->hchunks);
   else c->hchunks.clear();
@@ -722,7 +779,7 @@ static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32
     r = deflate_launch(c, st, level, wrap, kLevels[level], bj, ml, d_status, d_out_len, &dd);
   } else if (r == ZS_OK) {
     r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len, nullptr, sp,
-                       (const zs_huff_chunk*)(c->meta.as<uint8_t>() + m_chunks));
+                       (const zs_huff_chunk*)(c->meta.as<uint8_t>() + m_chunks), q);
   }
   if (r != ZS_OK) return r;
   if (d_check)
@@ -945,7 +1002,8 @@ extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, con
 // The host compress: zs_deflate_batch_ex (strategy 0) and zs_deflate_batch_strategy
 static int deflate_host(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
                         const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
-                        const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check) {
+                        const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check,
+                        const zs_deflate_params& q = zs_deflate_params()) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
@@ -961,7 +1019,7 @@ static int deflate_host(zs_ctx* c, int level, int strategy, int wbits, uint32_t 
                                             {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
                                              ooff, out_cap + a},
                                             (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false, nullptr,
-                                            strategy);
+                                            strategy, q);
                     });  // out_len is 0 for failed streams
 }
 
@@ -990,6 +1048,40 @@ extern "C" int zs_deflate_batch_strategy(zs_ctx* c, int level, int strategy, int
                                          uint32_t* out_len, uint32_t* check) {
   if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
   return deflate_host(c, level, strategy, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check);
+}
+
+// ---- windowBits and memLevel (deflateInit2_, deflate.ts:253-343; validation :281-294)
+// wbits -> the plain entries' code (-15 / 15 / 31) and the parameters; an error before the context is looked at
+static int params_split(int wbits, int mem_level, int* plain_wbits, zs_deflate_params* q) {
+  int wrap;
+  const int wb = zs_wbits_split(wbits, &wrap);
+  if (!wb) return fail(ZS_STREAM_ERROR, "invalid window bits");
+  if (mem_level < 1 || mem_level > 9) return fail(ZS_STREAM_ERROR, "invalid memLevel");
+  *q = zs_make_params(wb, mem_level);
+  *plain_wbits = wrap == 0 ? -15 : wrap == 1 ? 15 : 31;
+  return ZS_OK;
+}
+extern "C" int zs_deflate_batch_params_device(zs_ctx* c, int level, int wbits, int mem_level, uint32_t n,
+                                              const uint8_t* d_in, const uint64_t* in_off, const uint32_t* in_len,
+                                              uint8_t* d_out, const uint64_t* out_off, const uint32_t* out_cap,
+                                              int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check,
+                                              void* hip_stream) {
+  int pw;
+  zs_deflate_params q;
+  if (int r = params_split(wbits, mem_level, &pw, &q)) return r;
+  return deflate_device(c, level, pw, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, nullptr, ZS_DEFAULT_STRATEGY, q);
+}
+
+extern "C" int zs_deflate_batch_params(zs_ctx* c, int level, int wbits, int mem_level, uint32_t n, const uint8_t* in,
+                                       const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                       const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                       uint32_t* out_len, uint32_t* check) {
+  int pw;
+  zs_deflate_params q;
+  if (int r = params_split(wbits, mem_level, &pw, &q)) return r;
+  return deflate_host(c, level, ZS_DEFAULT_STRATEGY, pw, n, in, in_off, in_len, out, out_off, out_cap, status, out_len,
+                      check, q);
 }
 
 // ---- preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778)

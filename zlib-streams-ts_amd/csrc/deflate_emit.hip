@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "zs_common.h"
 #include "zs_kernels.h"
+#include "zs_par.h"  // compiled twice: the plain kernels, and zs_k_trees_par / zs_k_wrap_par for non-default windowBits / memLevel
 
 // ------------------------------------------------------------ tree building
 static constexpr int ZS_EXTRA_BLBITS[ZS_BL_CODES] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 3, 7};
@@ -67,8 +68,16 @@ struct zs_tstate {
 // entry carries its own key -- freq << 17 | depth << 10 | node, so the order is
 // the order of (entry >> 10) -- and a sift step costs one LDS read of the two
 // children instead of a dependent chain through the freq and depth arrays.
-// Widths: a block's total frequency is at most 16,384 (ZS_SYM_END symbols +
-// end-of-block), below 2^15; depths stay far below 2^7; nodes below 2^10.
+// Widths: the frequency field holds 15 bits.  A block's total frequency is at most
+// 16,384 at memLevel 8 (ZS_SYM_END symbols + end-of-block) and stays below 2^15 up to
+// memLevel 9 -- except that a memLevel 9 block of 32,767 literals and lengths plus
+// end-of-block totals exactly 32,768 = 2^15, one past the field.  Only the literal/length
+// tree's ROOT can carry that sum (every other node's is smaller), and the root's key is
+// never compared: zs_build_tree makes it in its last round, when the heap holds that one
+// entry (heap_len == 1: zs_pqdownheap_v's loop does not run), and then reads only its
+// node bits (the low 10, which the overflow leaves intact); d.freq[] takes the sum itself,
+// which fits 16 bits.  So the key stays 32 bits wide.  Depths stay far below 2^7; nodes
+// below 2^10.
 static __device__ __forceinline__ uint32_t zs_hkey(uint32_t e) { return e >> 10; }
 
 // pqdownheap (trees.ts:167-185), two levels per LDS round trip: the children
@@ -477,7 +486,15 @@ extern "C" int zs_trees_stats(unsigned long long* out) {
 #else
 #define TR_MARK(i) do { } while (0)
 #endif
-__global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+// zs_k_trees_par (non-default windowBits / memLevel, zs_par.h): a block whose start has slid out
+// of the window (blk.last bit 1) is never stored -- the reference passes no buffer for it
+// (block_start < 0, deflate.ts:1120-1124; trees.ts:574) and codes it with the static or dynamic trees.
+#if ZS_PAR_BUILD
+#define ZS_TR_MAY_STORE(blk) (((blk).last & 2u) == 0u)
+#else
+#define ZS_TR_MAY_STORE(blk) true
+#endif
+__global__ __launch_bounds__(64) void ZS_PN(zs_k_trees)(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                  const uint64_t* __restrict__ pos_base,
                                                  const uint32_t* __restrict__ blk_base,
                                                  const uint32_t* __restrict__ syms, zs_block* __restrict__ blocks,
@@ -531,7 +548,7 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
   }
   __syncthreads();
   // init_block (trees.ts:90-103) + tally counts
-  for (uint32_t i = lane; i < ZS_L_CODES + ZS_D_CODES; i += 64) w.tally[i] = (uint16_t)hist[i];  // <= 16,383
+  for (uint32_t i = lane; i < ZS_L_CODES + ZS_D_CODES; i += 64) w.tally[i] = (uint16_t)hist[i];  // <= 32,767 (memLevel 9)
   for (uint32_t i = lane; i < ZS_L_CODES; i += 64) w.lfreq[i] = i == ZS_END_BLOCK ? 1 : (uint16_t)hist[i];
   for (uint32_t i = lane; i < ZS_D_CODES; i += 64) w.dfreq[i] = (uint16_t)hist[ZS_L_CODES + i];
   if (lane < ZS_BL_CODES) w.bfreq[lane] = 0;
@@ -624,7 +641,7 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
     if (static_lenb <= opt_lenb || fixed) opt_lenb = static_lenb;  // trees.ts:567 (fixed: Z_FIXED)
     const uint32_t stored_len = blk.in_end - blk.in_start;
     uint32_t type;
-    if (stored_len + 4 <= opt_lenb) type = 0;
+    if (stored_len + 4 <= opt_lenb && ZS_TR_MAY_STORE(blk)) type = 0;
     else if (static_lenb == opt_lenb) type = 1;
     else type = 2;
     if (type == 2) {
@@ -676,6 +693,7 @@ __global__ __launch_bounds__(64) void zs_k_trees(const uint8_t* __restrict__ in,
   TR_MARK(5);
 }
 
+#if !ZS_PAR_BUILD
 // --------------------------------------------------------------- layout
 // DICT: a zlib stream compressed against a preset dictionary (dstart[s] != 0) carries the
 // four DICTID bytes behind its header (deflate.ts:767-778)
@@ -946,15 +964,28 @@ __global__ __launch_bounds__(ZS_EMIT_THREADS) void zs_k_emit(
   }
 }
 
+#endif  // !ZS_PAR_BUILD
 // -------------------------------------------------------------------- wrap
 // DICT (zlib only): a stream with a preset dictionary (dstart[s] != 0) sets FDICT, takes its
 // FCHECK with it and puts DICTID = dadler[did[s]], the adler32 of the whole dictionary, behind
 // the header (deflate.ts:767-778); in_len is unused (no gzip with a dictionary, deflate.ts:373)
+// zs_k_wrap_par (non-default windowBits): CMF carries CINFO = w_bits - 8 and FCHECK follows it
+// (deflate.ts:754-770); gzip is unchanged
+#if ZS_PAR_BUILD
+#define ZS_WRAP_ARG , uint32_t w_bits
+#define ZS_WRAP_PASS , w_bits
+#define ZS_WRAP_WBITS w_bits
+#else
+#define ZS_WRAP_ARG
+#define ZS_WRAP_PASS
+#define ZS_WRAP_WBITS 15u
+#endif
 template <bool DICT>
 static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
                           int level, int nstreams, const uint32_t* __restrict__ dstart,
-                          const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler, int strategy) {
+                          const uint32_t* __restrict__ did, const uint32_t* __restrict__ dadler, int strategy
+                          ZS_WRAP_ARG) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nstreams || wrap == 0) return;
   const bool hs = strategy >= 2;  // Z_HUFFMAN_ONLY and above: the "fastest" wrapper bits (deflate.ts:757,798)
@@ -964,7 +995,7 @@ static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict_
   auto put_byte = [&](uint64_t at, uint32_t c) { atomicOr(&ow[at >> 2], (c & 0xffu) << (8 * (at & 3))); };
   const uint64_t tb = st.total_bits / 8;
   if (wrap == 1) {  // zlib: deflate.ts:753-786, 980-983
-    uint32_t header = (8u + ((15u - 8u) << 4)) << 8;
+    uint32_t header = (8u + ((ZS_WRAP_WBITS - 8u) << 4)) << 8;
     const uint32_t lf = (hs || level < 2) ? 0u : level < 6 ? 1u : level == 6 ? 2u : 3u;
     header |= lf << 6;
     const bool fdict = DICT && dstart[s] != 0u;
@@ -985,11 +1016,13 @@ static __device__ __forceinline__ void zs_wrap_body(const zs_stream* __restrict_
     for (int i = 0; i < 4; i++) put_byte(tb + 4 + i, in_len[s] >> (8 * i));
   }
 }
-__global__ void zs_k_wrap(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
+__global__ void ZS_PN(zs_k_wrap)(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
-                          int level, int nstreams, int strategy) {
-  zs_wrap_body<false>(streams, out, out_off, in_len, wrap, level, nstreams, nullptr, nullptr, nullptr, strategy);
+                          int level, int nstreams, int strategy ZS_WRAP_ARG) {
+  zs_wrap_body<false>(streams, out, out_off, in_len, wrap, level, nstreams, nullptr, nullptr, nullptr, strategy
+                      ZS_WRAP_PASS);
 }
+#if !ZS_PAR_BUILD
 __global__ void zs_k_wrap_dict(const zs_stream* __restrict__ streams, uint8_t* __restrict__ out,
                                const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ in_len, int wrap,
                                int level, int nstreams, const uint32_t* __restrict__ dstart,
@@ -1091,3 +1124,4 @@ __global__ __launch_bounds__(256) void zs_k_stored(const uint8_t* __restrict__ i
     ow[w] = word;
   }
 }
+#endif  // !ZS_PAR_BUILD

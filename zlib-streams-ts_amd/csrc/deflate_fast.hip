@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "zs_common.h"
 #include "zs_kernels.h"
+#include "zs_par.h"  // compiled twice: the plain kernels, and the *_par ones for non-default windowBits / memLevel
 
 struct zs_fast_lds {
   uint16_t head[32768];
@@ -32,25 +33,64 @@ struct zs_fast_lds {
   uint32_t ring[8192];  // input byte x (x < 256 c) at byte (x & 32767)
 };
 
+#if ZS_PAR_BUILD
+#define ZS_FS_RMASK (kp.w_size - 1u)  // the ring's bytes
+#else
+#define ZS_FS_RMASK 32767u
+#endif
 // DICT: the stream is a joined one (a preset dictionary's tail, then the data):
 // positions below p0 = dstart[s] are inserted as deflateSetDictionary and the next
 // fill_window insert them (deflate.ts:400-412, 198-213), the parse starts at p0.
+// zs_k_fast_serial_par (non-default windowBits / memLevel, zs_par.h): head[] has 1 << hash_bits
+// entries, prev[] w_size (indexed by position & (w_size - 1), as the reference's, so a slide
+// moves nothing), the ring w_size bytes (every candidate starts at most MAX_DIST = w_size - 262
+// below the parse position), carved from the dynamic LDS in that order; the hash, MAX_DIST, the
+// slide test and step and the block length are kp's.
+// GH: head[] does not fit beside them (memLevel 9 at w_bits 14, 15; zs_plan_fast_params): it is
+// stream s's 65,536 u16 of the global workspace ghead (128 KiB, resident in L2); the wave's
+// stores to it are fenced before its next loads.
+#if ZS_PAR_BUILD
+template <bool DICT, bool GH>
+#else
 template <bool DICT>
-__global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+#endif
+__global__ __launch_bounds__(64) void ZS_PN(zs_k_fast_serial)(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                 const uint32_t* __restrict__ in_len,
                                                 const uint64_t* __restrict__ pos_base,
                                                 const uint32_t* __restrict__ blk_base, uint32_t* __restrict__ syms,
                                                 zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
-                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart) {
+                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart
+#if ZS_PAR_BUILD
+                                                , zs_kpar kp, uint16_t* __restrict__ ghead
+#endif
+                                                ) {
   extern __shared__ __attribute__((aligned(16))) uint8_t zs_fast_smem[];
+#if ZS_PAR_BUILD
+  struct {
+    uint16_t *head, *prev;
+    uint32_t* ring;
+  } L;
+  const uint32_t nhead = kp.hash_mask + 1u;
+  L.head = GH ? ghead + (size_t)blockIdx.x * nhead : reinterpret_cast<uint16_t*>(zs_fast_smem);
+  L.prev = reinterpret_cast<uint16_t*>(zs_fast_smem) + (GH ? 0u : nhead);
+  L.ring = reinterpret_cast<uint32_t*>(L.prev + kp.w_size);
+#define ZS_FS_HEAD_FENCE() do { if (GH) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); } while (0)
+#else
   zs_fast_lds& L = *reinterpret_cast<zs_fast_lds*>(zs_fast_smem);
+#define ZS_FS_HEAD_FENCE() do { } while (0)
+#endif
   const int s = blockIdx.x;
   const uint32_t lane = threadIdx.x;
   const uint32_t n = in_len[s];
   const uint8_t* src = in + in_off[s];
   uint32_t* sy = syms + pos_base[s] + s;
   zs_block* blk = blocks + blk_base[s];
+#if ZS_PAR_BUILD
+  for (uint32_t i = lane; i < nhead; i += 64) L.head[i] = 0;
+  for (uint32_t i = lane; i < kp.w_size; i += 64) L.prev[i] = 0;
+#else
   for (uint32_t i = lane; i < 32768; i += 64) { L.head[i] = 0; L.prev[i] = 0; }  // CLEAR_HASH (deflate.ts:120-123)
+#endif
   __syncthreads();
 
   // chunk window: r0 = input bytes [256 c + 4 lane, +4), r1 = the next chunk's
@@ -59,7 +99,7 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   uint8_t* const ringb = reinterpret_cast<uint8_t*>(L.ring);
   auto advance_to = [&](uint32_t q) {  // make the window's first chunk the one holding q
     while (q >= 256u * (c + 1)) {
-      L.ring[((256u * c) & 32767u) / 4 + lane] = r0;  // chunk c leaves the registers for the ring
+      L.ring[((256u * c) & ZS_FS_RMASK) / 4 + lane] = r0;  // chunk c leaves the registers for the ring
       r0 = r1;
       r1 = zs_load_word(src, n, 256u * (c + 2) + 4 * lane);
       c++;
@@ -79,7 +119,7 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
     const int from = (int)(((o >> 2) & 63u) * 4u);
     const uint32_t w0 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)r0);
     const uint32_t w1 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)r1);
-    const uint32_t rb = ringb[y & 32767u];
+    const uint32_t rb = ringb[y & ZS_FS_RMASK];
     const uint32_t wb = ((o & 256u) ? w1 : w0) >> (8 * (o & 3));
     return y < 256u * c ? rb : wb & 0xffu;
   };
@@ -87,8 +127,8 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   // at a time over consecutive positions as UPDATE_HASH does (deflate.ts:109-111)
   uint32_t hq = 0xfffffff0u, hv = 0;  // hq + 1 never equals a position
   auto hash_at = [&](uint32_t q) -> uint32_t {
-    hv = q == hq + 1 ? ((hv << 5) ^ win_byte(q + 2)) & ZS_HASH_MASK
-                     : ((win_byte(q) << 10) ^ (win_byte(q + 1) << 5) ^ win_byte(q + 2)) & ZS_HASH_MASK;
+    hv = q == hq + 1 ? ((hv << ZS_P_HSHIFT) ^ win_byte(q + 2)) & ZS_P_HMASK
+                     : ((win_byte(q) << (2 * ZS_P_HSHIFT)) ^ (win_byte(q + 1) << ZS_P_HSHIFT) ^ win_byte(q + 2)) & ZS_P_HMASK;
     hq = q;
     return hv;
   };
@@ -103,7 +143,8 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
     const uint32_t rel = q - base;
     const uint32_t hh = L.head[h];
     // lane 0 writes; the wave's later LDS reads are ordered behind these writes
-    if (lane == 0) { L.prev[rel & 0x7fffu] = (uint16_t)hh; L.head[h] = (uint16_t)rel; }
+    if (lane == 0) { L.prev[rel & ZS_P_WMASK] = (uint16_t)hh; L.head[h] = (uint16_t)rel; }
+    ZS_FS_HEAD_FENCE();
     return hh;
   };
   // Symbols are held one per lane (lane nsym % 64) and stored 64 at a time: a
@@ -146,26 +187,37 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   while (p < n) {
     advance_to(p);
     // fill_window slide (deflate.ts:180-190): same schedule as deflate_slow
-    if (p - base >= ZS_SLIDE_AT && min(n, base + 65536u) - p < ZS_MIN_LOOKAHEAD) {
+    if (p - base >= ZS_P_SLIDE_AT && min(n, base + ZS_P_2W) - p < ZS_MIN_LOOKAHEAD) {
+#if ZS_PAR_BUILD
+      for (uint32_t i = lane; i < nhead; i += 64) {
+        const uint32_t a = L.head[i];
+        L.head[i] = (uint16_t)(a >= kp.w_size ? a - kp.w_size : 0u);
+      }
+      for (uint32_t i = lane; i < kp.w_size; i += 64) {
+        const uint32_t b = L.prev[i];
+        L.prev[i] = (uint16_t)(b >= kp.w_size ? b - kp.w_size : 0u);
+      }
+#else
       for (uint32_t i = lane; i < 32768; i += 64) {
         const uint32_t a = L.head[i], b = L.prev[i];
         L.head[i] = (uint16_t)(a >= 32768u ? a - 32768u : 0u);
         L.prev[i] = (uint16_t)(b >= 32768u ? b - 32768u : 0u);
       }
+#endif
       __syncthreads();
-      base += 32768u;
-      ms_rel -= 32768u;
+      base += ZS_P_W;
+      ms_rel -= ZS_P_W;
     }
     const uint32_t look = n - p;
     uint32_t hash_head = 0;
     if (look >= ZS_MIN_MATCH) hash_head = insert(p);
     const uint32_t srel = p - base;
-    if (hash_head != 0 && srel - hash_head <= ZS_MAX_DIST) {
+    if (hash_head != 0 && srel - hash_head <= ZS_P_MAX_DIST) {
       // longest_match with prev_length = MIN_MATCH - 1 (deflate_fast never sets it), deflate.ts:1053-1115
       uint32_t chain_length = (uint32_t)chain;
       const uint32_t maxc = look < ZS_MAX_MATCH ? look : ZS_MAX_MATCH;
       const uint32_t nice = look < (uint32_t)nice_cfg ? look : (uint32_t)nice_cfg;
-      const uint32_t limit = srel > ZS_MAX_DIST ? srel - ZS_MAX_DIST : 0;
+      const uint32_t limit = srel > ZS_P_MAX_DIST ? srel - ZS_P_MAX_DIST : 0;
       uint32_t best = ZS_MIN_MATCH - 1, cur = hash_head;
       // lane_byte reads other lanes' registers: every lane runs it, then masks
       const uint32_t sbv = lane_byte(p + lane);
@@ -190,7 +242,7 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
           best = len;
           if (len >= nice) break;
         }
-        cur = L.prev[cur & 0x7fffu];
+        cur = L.prev[cur & ZS_P_WMASK];
       } while (cur > limit && --chain_length != 0);
       ml = best <= look ? best : look;
     }
@@ -206,7 +258,7 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
       emit(win_byte(p));
       p++;
     }
-    if (in_blk == ZS_SYM_END) close_block(p, 0);
+    if (in_blk == ZS_P_SYM_END) close_block(p, 0);
   }
   close_block(n, 1);
   drain();
@@ -216,12 +268,24 @@ __global__ __launch_bounds__(64) void zs_k_fast_serial(const uint8_t* __restrict
   }
 }
 
+#if ZS_PAR_BUILD
+// (no dictionaries with these parameters: DICT = false alone)
+template __global__ void zs_k_fast_serial_par<false, false>(const uint8_t*, const uint64_t*, const uint32_t*,
+                                                            const uint64_t*, const uint32_t*, uint32_t*, zs_block*,
+                                                            zs_stream*, int, int, int, const uint32_t*, zs_kpar,
+                                                            uint16_t*);
+template __global__ void zs_k_fast_serial_par<false, true>(const uint8_t*, const uint64_t*, const uint32_t*,
+                                                           const uint64_t*, const uint32_t*, uint32_t*, zs_block*,
+                                                           zs_stream*, int, int, int, const uint32_t*, zs_kpar,
+                                                           uint16_t*);
+#else
 template __global__ void zs_k_fast_serial<false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
                                                  const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int,
                                                  const uint32_t*);
 template __global__ void zs_k_fast_serial<true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*,
                                                 const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int,
                                                 const uint32_t*);
+#endif
 
 // ---------------------------------------------------------------- zs_k_fast
 // The group-speculative replay (CPU model: tools/emu/emu_fast_group.c,
@@ -283,22 +347,44 @@ static __device__ __forceinline__ uint32_t zs_fg_mskor(uint32_t addr, uint32_t m
 // DICT: the stream is a joined one (a preset dictionary's tail, then the data):
 // the positions below p0 = dstart[s] enter head[] / prev[] as groups of truly inserted
 // positions without parse steps (step 4 alone), then the parse starts at p0.
+// zs_k_fast_par (non-default windowBits / memLevel with at most 15 hash bits, zs_par.h): head[]
+// has 1 << hash_bits half-words and prev[] w_size (indexed by position & (w_size - 1), as the
+// reference's), carved from the dynamic LDS in front of the 32 KiB ring, which stays (a superset
+// of every window); the hash, MAX_DIST, the slide test and step and the block length are kp's.
 template <int NW, bool ORD, bool DICT>
-__global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+__global__ __launch_bounds__(64) void ZS_PN(zs_k_fast)(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                 const uint32_t* __restrict__ in_len,
                                                 const uint64_t* __restrict__ pos_base,
                                                 const uint32_t* __restrict__ blk_base, uint32_t* __restrict__ syms,
                                                 zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
-                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart) {
+                                                int chain, int lazy, int nice_cfg, const uint32_t* __restrict__ dstart
+                                                ZS_PAR_ARG) {
   extern __shared__ __attribute__((aligned(16))) uint8_t zs_fastg_smem[];
+#if ZS_PAR_BUILD
+  struct {
+    uint32_t* head;
+    uint16_t* prev;
+    uint32_t* ring;
+  } L;
+  const uint32_t nheadw = (kp.hash_mask + 1u) / 2u;  // head[] words
+  L.head = reinterpret_cast<uint32_t*>(zs_fastg_smem);
+  L.prev = reinterpret_cast<uint16_t*>(L.head + nheadw);
+  L.ring = reinterpret_cast<uint32_t*>(L.prev + kp.w_size);
+#else
   zs_fastg_lds& L = *reinterpret_cast<zs_fastg_lds*>(zs_fastg_smem);
+#endif
   const int s = blockIdx.x;
   const uint32_t lane = threadIdx.x;
   const uint32_t n = in_len[s];
   const uint8_t* src = in + in_off[s];
   uint32_t* sy = syms + pos_base[s] + s;
   zs_block* blk = blocks + blk_base[s];
+#if ZS_PAR_BUILD
+  for (uint32_t i = lane; i < nheadw; i += 64) L.head[i] = 0;
+  for (uint32_t i = lane; i < kp.w_size / 2u; i += 64) reinterpret_cast<uint32_t*>(L.prev)[i] = 0;
+#else
   for (uint32_t i = lane; i < 16384; i += 64) { L.head[i] = 0; reinterpret_cast<uint32_t*>(L.prev)[i] = 0; }
+#endif
   const uint8_t* ringb = reinterpret_cast<const uint8_t*>(L.ring);
   auto rword = [&](uint32_t x) -> uint32_t {  // input bytes [x, x + 4) from the ring
     const uint32_t w = x >> 2;
@@ -370,8 +456,18 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
 
   while (p < n) {
     // fill_window slide (deflate.ts:180-190), same schedule as deflate_slow
-    const uint32_t m = min(n, base + 65536u);
-    if (p - base >= ZS_SLIDE_AT && m - p < ZS_MIN_LOOKAHEAD) {
+    const uint32_t m = min(n, base + ZS_P_2W);
+    if (p - base >= ZS_P_SLIDE_AT && m - p < ZS_MIN_LOOKAHEAD) {
+#if ZS_PAR_BUILD
+      const uint32_t w = kp.w_size;
+      auto slid = [&](uint32_t v) {  // both half-words moved down by w, or NIL
+        const uint32_t v0 = v & 0xffffu, v1 = v >> 16;
+        return (v0 >= w ? v0 - w : 0u) | ((v1 >= w ? v1 - w : 0u) << 16);
+      };
+      for (uint32_t i = lane; i < nheadw; i += 64) L.head[i] = slid(L.head[i]);
+      for (uint32_t i = lane; i < w / 2u; i += 64)
+        reinterpret_cast<uint32_t*>(L.prev)[i] = slid(reinterpret_cast<uint32_t*>(L.prev)[i]);
+#else
       for (uint32_t i = lane; i < 16384; i += 64) {
         const uint32_t a = L.head[i];
         const uint32_t b = reinterpret_cast<uint32_t*>(L.prev)[i];
@@ -380,7 +476,8 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
         reinterpret_cast<uint32_t*>(L.prev)[i] = (b0 >= 32768u ? b0 - 32768u : 0u) |
                                                  ((b1 >= 32768u ? b1 - 32768u : 0u) << 16);
       }
-      base += 32768u;
+#endif
+      base += ZS_P_W;
       continue;  // re-evaluate the group bounds against the new base
     }
     FG_T(0);
@@ -392,7 +489,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
       const uint32_t q = g0 + lane;
       const bool ins = q < p0 && q + 2 < n;
       const uint32_t hw = rword(q);
-      const uint32_t h = (((hw & 0xffu) << 10) ^ (((hw >> 8) & 0xffu) << 5) ^ ((hw >> 16) & 0xffu)) & ZS_HASH_MASK;
+      const uint32_t h = ZS_P_HASHW(hw);
       const uint32_t ha = zs_fg_addr(&L.head[h >> 1]), sh = 16u * (h & 1u);
       uint32_t tp;
       if (ORD) {
@@ -407,12 +504,12 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
       }
-      if (ins) L.prev[q & 0x7fffu] = (uint16_t)tp;
+      if (ins) L.prev[q & ZS_P_WMASK] = (uint16_t)tp;
       p = min(g0 + 64u, p0);
       continue;
     }
     const uint32_t g0 = p, rg0 = g0 - base;
-    uint32_t tslide = base + ZS_SLIDE_AT;
+    uint32_t tslide = base + ZS_P_SLIDE_AT;
     if (m >= ZS_MIN_LOOKAHEAD - 1 && m - (ZS_MIN_LOOKAHEAD - 1) > tslide) tslide = m - (ZS_MIN_LOOKAHEAD - 1);
     const uint32_t g1 = min(min(g0 + 64u - (uint32_t)lazy, tslide), n);
     fill_to(g0 + 160u);
@@ -421,7 +518,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
     const uint32_t q = g0 + lane;
     const bool ok = q + 2 < n;  // INSERT_STRING needs lookahead >= MIN_MATCH (deflate.ts:1296)
     const uint32_t hw = rword(q);
-    const uint32_t h = (((hw & 0xffu) << 10) ^ (((hw >> 8) & 0xffu) << 5) ^ ((hw >> 16) & 0xffu)) & ZS_HASH_MASK;
+    const uint32_t h = ZS_P_HASHW(hw);
     const uint32_t ha = zs_fg_addr(&L.head[h >> 1]), sh = 16u * (h & 1u);
     const uint32_t hm = ok ? 0xffffu << sh : 0u;
     uint32_t sp;
@@ -443,8 +540,8 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
     const uint32_t srel = q - base;
     const uint32_t maxc = min(look, (uint32_t)ZS_MAX_MATCH), nice = min(look, (uint32_t)nice_cfg);
     const uint32_t capn = min(nice, maxc);
-    const uint32_t limit = srel > ZS_MAX_DIST ? srel - ZS_MAX_DIST : 0u;
-    bool act = ok && q < g1 && sp != 0u && srel - sp <= ZS_MAX_DIST;
+    const uint32_t limit = srel > ZS_P_MAX_DIST ? srel - ZS_P_MAX_DIST : 0u;
+    bool act = ok && q < g1 && sp != 0u && srel - sp <= ZS_P_MAX_DIST;
     uint32_t best = ZS_MIN_MATCH - 1, bms = 0, cur = sp;
     uint64_t vis = 0;
     uint32_t sw[NW];
@@ -474,7 +571,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
       if (__ballot(act) == 0) break;
       // straight-line: the link, the candidate's words and the in-group link issue together
       const bool cin = cur != 0u && cur >= rg0;
-      const uint32_t pl = L.prev[cur & 0x7fffu];
+      const uint32_t pl = L.prev[cur & ZS_P_WMASK];
       const uint32_t lsp = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((cur - rg0) & 63u) * 4u), (int)sp);
       const uint32_t len = min(diff_at(base + cur, sw, NWc{}), capn);
       vis |= act && cin ? 1ull << ((cur - rg0) & 63u) : 0ull;
@@ -527,8 +624,8 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
       if (cnt == 0) return;
       const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(path >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)path, 0u));
       if ((path >> lane) & 1ull) sy[nsym + rk] = sym;
-      if (in_blk + cnt >= ZS_SYM_END) {
-        const uint32_t k = ZS_SYM_END - in_blk;  // symbols up to and including the cut
+      if (in_blk + cnt >= ZS_P_SYM_END) {
+        const uint32_t k = ZS_P_SYM_END - in_blk;  // symbols up to and including the cut
         uint64_t m = path;
         for (uint32_t t = 1; t < k; t++) m &= m - 1;
         const uint32_t c = (uint32_t)__builtin_ctzll(m);
@@ -607,8 +704,8 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
           return c ? rg0 + 63u - (uint32_t)__builtin_clzll(c) : (uint32_t)__builtin_amdgcn_readlane((int)orig, (int)l);
         };
         const uint32_t hh = true_link(i, hi);
-        if (hh != 0u && sr - hh <= ZS_MAX_DIST) {
-          const uint32_t lim = sr > ZS_MAX_DIST ? sr - ZS_MAX_DIST : 0u;
+        if (hh != 0u && sr - hh <= ZS_P_MAX_DIST) {
+          const uint32_t lim = sr > ZS_P_MAX_DIST ? sr - ZS_P_MAX_DIST : 0u;
           uint32_t cl = (uint32_t)chain, b2 = ZS_MIN_MATCH - 1, c = hh;
           do {
             const uint32_t len = exact_len(p, base + c, mx);
@@ -621,7 +718,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
               const uint32_t l = c - rg0;
               c = true_link(l, (uint32_t)__builtin_amdgcn_readlane((int)h, (int)l));
             } else {
-              c = L.prev[c & 0x7fffu];
+              c = L.prev[c & ZS_P_WMASK];
             }
           } while (c > lim && --cl != 0);
           ml = b2 >= ZS_MIN_MATCH ? b2 : 0u;
@@ -637,7 +734,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
         put((uint32_t)__builtin_amdgcn_readlane((int)hw, (int)i) & 0xffu);
         j = i + 1;
       }
-      if (in_blk == ZS_SYM_END) close_block(g0 + j, 0);
+      if (in_blk == ZS_P_SYM_END) close_block(g0 + j, 0);
     }
     p = g0 + j;
 
@@ -657,7 +754,7 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_wave_barrier();
     }
-    if (ins) L.prev[(rg0 + lane) & 0x7fffu] = (uint16_t)tp;
+    if (ins) L.prev[(rg0 + lane) & ZS_P_WMASK] = (uint16_t)tp;
     FG_T(4);
   }
 #ifdef ZS_FG_PROF
@@ -673,18 +770,20 @@ __global__ __launch_bounds__(64) void zs_k_fast(const uint8_t* __restrict__ in, 
 }
 
 #define ZS_FAST_INST(NW, ORD, DICT)                                                                              \
-  template __global__ void zs_k_fast<NW, ORD, DICT>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, \
+  template __global__ void ZS_PN(zs_k_fast)<NW, ORD, DICT>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, \
                                                     const uint32_t*, uint32_t*, zs_block*, zs_stream*, int, int, int, \
-                                                    const uint32_t*);
+                                                    const uint32_t* ZS_PAR_TYPE);
 ZS_FAST_INST(2, true, false)
 ZS_FAST_INST(4, true, false)
 ZS_FAST_INST(8, true, false)
 ZS_FAST_INST(2, false, false)
 ZS_FAST_INST(4, false, false)
 ZS_FAST_INST(8, false, false)
+#if !ZS_PAR_BUILD  // (no dictionaries with non-default windowBits / memLevel)
 ZS_FAST_INST(2, true, true)
 ZS_FAST_INST(4, true, true)
 ZS_FAST_INST(8, true, true)
 ZS_FAST_INST(2, false, true)
 ZS_FAST_INST(4, false, true)
 ZS_FAST_INST(8, false, true)
+#endif

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "zs_common.h"
 #include "zs_kernels.h"
+#include "zs_par.h"  // compiled twice: the plain kernels, and the *_par ones for non-default windowBits / memLevel
 
 // ---------------------------------------------------------------- zs_k_prev
 // One wave per stream walks the positions in order, 64 at a time.  Lane l of
@@ -35,12 +36,17 @@
 // ORD = false (option lane_order = 0, or a device that fails the self-test):
 // each lane's link is the highest lower lane of the group with the same hash
 // (zs_wave_match) or head[h], and the group's last lane of each hash stores it.
+// zs_k_prev_par (non-default windowBits / memLevel): the hash comes from kp's (shift, mask).
+// head[] stays 32,768 entries (128 KiB of LDS), so memLevel 9's 16 hash bits do not fit: chains
+// of different hashes are independent, so the stream is walked TWICE, each pass exchanging only
+// the positions whose hash lies in its half of the hash space (bit 15) through the same table,
+// cleared in between -- exactly the links one 65,536-entry table would give.
 #define ZS_PREV_STAGE 4096u
 template <bool ORD>
-__global__ __launch_bounds__(64) void zs_k_prev(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+__global__ __launch_bounds__(64) void ZS_PN(zs_k_prev)(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                 const uint32_t* __restrict__ in_len,
                                                 const uint64_t* __restrict__ pos_base, uint16_t* __restrict__ prevd,
-                                                uint32_t min_len) {
+                                                uint32_t min_len ZS_PAR_ARG) {
   __shared__ uint32_t head[32768];
   __shared__ uint32_t stg[ZS_PREV_STAGE / 4 + 2];  // input bytes [c0, c0 + 4096 + 8)
   const int s = blockIdx.x;
@@ -49,6 +55,11 @@ __global__ __launch_bounds__(64) void zs_k_prev(const uint8_t* __restrict__ in, 
   const uint8_t* src = in + in_off[s];
   uint16_t* out = prevd + pos_base[s];
   const uint32_t lane = threadIdx.x;
+#if ZS_PAR_BUILD
+  for (uint32_t pass = 0; pass <= (kp.hash_mask >> 15); pass++) {  // one pass per half of a 16-bit hash space
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+#endif
   for (uint32_t i = lane; i < 32768; i += 64) head[i] = 0;
   const bool aligned = ((uintptr_t)src & 3u) == 0;
   for (uint32_t c0 = 0; c0 < n; c0 += ZS_PREV_STAGE) {
@@ -71,13 +82,24 @@ __global__ __launch_bounds__(64) void zs_k_prev(const uint8_t* __restrict__ in, 
     for (uint32_t g0 = c0; g0 < c1; g0 += 256) {
       uint32_t h[4], e[4];
       bool valid[4];
+#if ZS_PAR_BUILD
+      bool mine[4];
+#define ZS_PREV_MINE(j) &&mine[j]
+#else
+#define ZS_PREV_MINE(j)
+#endif
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const uint32_t p = g0 + 64 * j + lane;
         const uint32_t o = p - c0;
         const uint32_t w = __builtin_amdgcn_alignbyte(stg[(o >> 2) + 1], stg[o >> 2], o & 3u);
         valid[j] = p + 2 < n && p < c1;  // positions <= n-3 are inserted (deflate.ts:1367-1370)
-        h[j] = (((w & 0xffu) << 10) ^ (((w >> 8) & 0xffu) << 5) ^ ((w >> 16) & 0xffu)) & ZS_HASH_MASK;
+        h[j] = ZS_P_HASHW(w);
+#if ZS_PAR_BUILD
+        mine[j] = !valid[j] || (h[j] >> 15) == pass;  // this pass writes the position's link
+        valid[j] = valid[j] && (h[j] >> 15) == pass;
+        h[j] &= 0x7fffu;
+#endif
       }
       // in order: group j's exchanges land after group j-1's (LDS executes a wave's ops in order)
       if (ORD) {
@@ -102,19 +124,22 @@ __global__ __launch_bounds__(64) void zs_k_prev(const uint8_t* __restrict__ in, 
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const uint32_t p = g0 + 64 * j + lane;
-        if (p < c1) {
+        if (p < c1 ZS_PREV_MINE(j)) {
           const uint32_t d = e[j] ? p - (e[j] - 1) : 0u;
           out[p] = (uint16_t)(valid[j] && d != 0u && d <= 32767u ? d : 0xffffu);
         }
       }
     }
   }
+#if ZS_PAR_BUILD
+  }
+#endif
 }
 
-template __global__ void zs_k_prev<true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, uint16_t*,
-                                         uint32_t);
-template __global__ void zs_k_prev<false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, uint16_t*,
-                                          uint32_t);
+template __global__ void ZS_PN(zs_k_prev)<true>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, uint16_t*,
+                                         uint32_t ZS_PAR_TYPE);
+template __global__ void ZS_PN(zs_k_prev)<false>(const uint8_t*, const uint64_t*, const uint32_t*, const uint64_t*, uint16_t*,
+                                          uint32_t ZS_PAR_TYPE);
 
 // --------------------------------------------------------------- zs_k_match
 #define ZS_TILE 8192u
@@ -132,11 +157,14 @@ static __device__ __forceinline__ uint32_t win_word(const uint32_t* wb, uint32_t
   return __builtin_amdgcn_alignbyte(wb[i + 1], wb[i], off & 3u);
 }
 
-__global__ __launch_bounds__(1024) void zs_k_match(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+// zs_k_match_par (non-default windowBits / memLevel): the distance limit is kp's MAX_DIST =
+// w_size - 262; the 32 KiB look-back staged here is a superset of every window.  The hash only
+// orders the work (folded to 15 bits for the histogram).
+__global__ __launch_bounds__(1024) void ZS_PN(zs_k_match)(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                    const uint32_t* __restrict__ in_len,
                                                    const uint64_t* __restrict__ pos_base,
                                                    const uint16_t* __restrict__ prevd, uint2* __restrict__ mres,
-                                                   int chain, int nice_cfg, uint32_t min_len) {
+                                                   int chain, int nice_cfg, uint32_t min_len ZS_PAR_ARG) {
   // One LDS array, carved by hand so the window sits at address 0 and the
   // links at a constant below 64 KiB: the walk's LDS reads then need no base
   // add (the link base rides in the instruction's offset field).
@@ -233,7 +261,7 @@ __global__ __launch_bounds__(1024) void zs_k_match(const uint8_t* __restrict__ i
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) {
       const uint32_t w = __builtin_amdgcn_alignbyte(hi, lo, k);
-      const uint32_t h = (((w & 0xffu) << 10) ^ (((w >> 8) & 0xffu) << 5) ^ ((w >> 16) & 0xffu)) & ZS_HASH_MASK;
+      const uint32_t h = ZS_P_HASHW(w) & 0x7fffu;
       if (4 * i + k < hend - w0) atomicAdd(&pvw[h >> 1], 1u << (16 * (h & 1u)));
     }
   }
@@ -246,7 +274,7 @@ __global__ __launch_bounds__(1024) void zs_k_match(const uint8_t* __restrict__ i
     uint32_t c = 0;
     if (p < hend) {
       const uint32_t w = win_word(wb, p - w0);
-      const uint32_t h = (((w & 0xffu) << 10) ^ (((w >> 8) & 0xffu) << 5) ^ ((w >> 16) & 0xffu)) & ZS_HASH_MASK;
+      const uint32_t h = ZS_P_HASHW(w) & 0x7fffu;
       c = (pvw[h >> 1] >> (16 * (h & 1u))) & 0xffffu;
     }
     key[i] = p < t1 ? 255u - min(c, cap) : 0u;
@@ -301,12 +329,12 @@ __global__ __launch_bounds__(1024) void zs_k_match(const uint8_t* __restrict__ i
     const uint32_t d0 = p + 2 < n ? pv[p - w0] : 0xffffu;
     const uint32_t q0 = p - d0;
     // head candidate: non-NIL, distance <= MAX_DIST (deflate.ts:1376)
-    if (q0 != 0 && d0 <= ZS_MAX_DIST) {
+    if (q0 != 0 && d0 <= ZS_P_MAX_DIST) {
       const uint32_t look = n - p;
       const uint32_t maxc = look < ZS_MAX_MATCH ? look : ZS_MAX_MATCH;       // deflate.ts:1068
       const uint32_t nice = look < (uint32_t)nice_cfg ? look : (uint32_t)nice_cfg;  // deflate.ts:1078-1080
       // the walk runs in window coordinates (cr = cur - w0)
-      const int limit = (p > ZS_MAX_DIST ? (int)(p - ZS_MAX_DIST) : 0) - (int)w0;  // deflate.ts:1060
+      const int limit = (p > ZS_P_MAX_DIST ? (int)(p - ZS_P_MAX_DIST) : 0) - (int)w0;  // deflate.ts:1060
       const uint32_t sp = p - w0;
       const uint32_t s0 = win_word(wb, sp), s1 = win_word(wb, sp + 4);
       // best = (len << 16) | cr: its maximum is the first candidate among the
@@ -366,7 +394,7 @@ __global__ __launch_bounds__(1024) void zs_k_match(const uint8_t* __restrict__ i
       const uint32_t best_s = best;  // lanes still walking: after chain >> 2 candidates; others: final
       asm volatile("" : "+v"(cr));  // recompute the chain-end test below instead of keeping a mask live
       if (budget_small < budget && (int)cr > limit) walk(budget - budget_small);
-      const uint32_t flag = d0 == ZS_MAX_DIST ? 0x8000u : 0u;  // SURVEY A3 slide-NIL corner, resolved in parse
+      const uint32_t flag = d0 == ZS_P_MAX_DIST ? 0x8000u : 0u;  // SURVEY A3 slide-NIL corner, resolved in parse
       const uint32_t bl = best >> 16, bsl = best_s >> 16;
       r.x = (bl << 16) | (bl > 2 ? sp - (best & 0xffffu) : 0u) | flag;
       r.y = (bsl << 16) | (bsl > 2 ? sp - (best_s & 0xffffu) : 0u);

@@ -136,6 +136,10 @@ extern "C" int zs_parse_stats(unsigned long long* out) {
 // the parse starts at p0 = dstart[s] in the no-pending-match state deflateSetDictionary leaves
 // (deflate.ts:413-418), the segments, the symbols and the blocks cover [p0, n).
 // FILT: Z_FILTERED's step (zs_parse.h); the sync argument above holds for it unchanged.
+// The *_par build (non-default windowBits / memLevel, zs_par.h): the slide schedule follows kp's
+// w_size (slides at p = w j + 2 w - 262, by w), the blocks close after kp.sym_end symbols, and a
+// block has slid out of the window when it starts below w x slides -- at a 512-byte window nearly
+// every one, so stored blocks mostly disappear, as in the reference (deflate.ts:1120-1124).
 template <uint32_t WIN, uint32_t SEG, uint32_t NWV, bool DICT, bool FILT>
 static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_seg_tab& T, zs_round_state& RS,
                                                      const uint8_t* __restrict__ in,
@@ -146,7 +150,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
                                                      const uint2* __restrict__ mres, uint32_t* __restrict__ syms,
                                                      zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,
                                                      uint32_t* __restrict__ scratch, int good, int lazy,
-                                                     const uint32_t* __restrict__ dstart) {
+                                                     const uint32_t* __restrict__ dstart ZS_PAR_ARG) {
   using CF = zs_seg_cfg<SEG>;
   const int s = blockIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -201,7 +205,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
           yacc.w = m == 3 ? y : yacc.w;
           if (++nsync % 4 == 0) *reinterpret_cast<uint4*>(sync + nsync - 4) = yacc;
         }
-        const uint32_t v = zs_parse_step<FILT>(st, e, lit, n, good, lazy);
+        const uint32_t v = zs_parse_step<FILT>(st, e, lit, n, good, lazy ZS_PAR_PASS);
         if (v != ZS_NONE) {
           const uint32_t m = cnt & 3u;
           sacc.x = m == 0 ? v : sacc.x;
@@ -314,7 +318,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
           if ((sv >> 16) == key) { from = sv & 0xffffu; break; }
         }
         const uint32_t p = c.p;
-        const uint32_t v = zs_parse_step<FILT>(c, M[p], p > 0 ? src[p - 1] : 0u, n, good, lazy);
+        const uint32_t v = zs_parse_step<FILT>(c, M[p], p > 0 ? src[p - 1] : 0u, n, good, lazy ZS_PAR_PASS);
         if (v != ZS_NONE) {  // gathered four at a time (see pass A)
           const uint32_t m = nf & 3u;
           facc.x = m == 0 ? v : facc.x;
@@ -405,7 +409,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     // 1120-1124) -- but not after the final deferred literal, which is tallied
     // after the loop (deflate.ts:1429-1432)
     const uint32_t unchecked = final_lit_r ? tot0 + R - 1 : ZS_NONE;
-    for (uint32_t gi = (tot0 / ZS_SYM_END + 1) * ZS_SYM_END - 1; gi < tot0 + R; gi += ZS_SYM_END) {
+    for (uint32_t gi = (tot0 / ZS_P_SYM_END + 1) * ZS_P_SYM_END - 1; gi < tot0 + R; gi += ZS_P_SYM_END) {
       if (gi == unchecked) continue;
       const uint32_t g = gi - tot0;
       uint32_t j = 0;
@@ -425,9 +429,9 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
       }
       const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)start, (int)j) + acc;
       if (lane == 0) {  // the block's input end; its window base for the stored-block check
-        const uint32_t bi = (gi + 1) / ZS_SYM_END - 1;
+        const uint32_t bi = (gi + 1) / ZS_P_SYM_END - 1;
         blk[bi].in_end = end;
-        blk[bi].pad = zs_slides(end - li + 1, n);
+        blk[bi].pad = zs_slides(end - li + 1, n ZS_PAR_PASS);
       }
     }
     PP_ACC(3, tD);
@@ -447,11 +451,11 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
   // ---- block records (deflate.ts:1434-1440: the final block takes the rest, possibly empty)
   const bool final_lit = nseg > 0 && t.ma != 0;
   const uint32_t checked = final_lit ? total - 1 : total;
-  const uint32_t nflush = checked / ZS_SYM_END;
+  const uint32_t nflush = checked / ZS_P_SYM_END;
   // window base when the final block is flushed: slides up to the last visited
   // position (the symbols tile [0, n), so the last one starts at n - its length)
   const uint32_t v_last = total == 0 ? 0u : final_lit ? n - 1 : n - zs_sym_len(last_sym) + 1;
-  const uint32_t final_slides = zs_slides(v_last, n);
+  const uint32_t final_slides = zs_slides(v_last, n ZS_PAR_PASS);
   ZS_WAVE_SYNC();
   for (uint32_t b0 = 0; b0 <= nflush; b0 += 64) {
     const uint32_t b = b0 + lane;
@@ -460,13 +464,13 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
       const uint32_t in_start = b == 0 ? p0 : blk[b - 1].in_end;
       const uint32_t in_end = b < nflush ? blk[b].in_end : n;
       const uint32_t slides = b < nflush ? blk[b].pad : final_slides;
-      k.sym_start = b * ZS_SYM_END;
-      k.sym_count = b < nflush ? ZS_SYM_END : total - nflush * ZS_SYM_END;
+      k.sym_start = b * ZS_P_SYM_END;
+      k.sym_count = b < nflush ? ZS_P_SYM_END : total - nflush * ZS_P_SYM_END;
       k.in_start = in_start;
       k.in_end = in_end;
       k.type = 0; k.hdr_bits = 0; k.data_bits = 0; k.pad = 0; k.bit_off = 0; k.bit_end = 0;
       // bit 1: the block began before the slid window (matters for stored blocks)
-      k.last = (b == nflush ? 1u : 0u) | ((uint64_t)in_start < 32768ull * slides ? 2u : 0u);
+      k.last = (b == nflush ? 1u : 0u) | ((uint64_t)in_start < ZS_P_W_ULL * slides ? 2u : 0u);
     }
     ZS_WAVE_SYNC();  // every read of in_end / pad in this chunk precedes the writes
     if (b <= nflush) blk[b] = k;
@@ -482,6 +486,21 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
 #endif
 }
 
+#if ZS_PAR_BUILD
+// the *_par instances: the plain parse alone (no _dict or _filt forms with these parameters)
+#define ZS_PARSE_KERNEL(name, WIN, SEG, NWV)                                                                        \
+  __global__ __launch_bounds__(64 * NWV) void name##_par(                                                            \
+      const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,     \
+      const uint64_t* __restrict__ pos_base, const uint32_t* __restrict__ blk_base, const uint2* __restrict__ mres,  \
+      uint32_t* __restrict__ syms, zs_block* __restrict__ blocks, zs_stream* __restrict__ streams,                  \
+      uint32_t* __restrict__ scratch, int good, int lazy, zs_kpar kp) {                                             \
+    __shared__ zs_parse_lds<WIN> U[NWV];                                                                            \
+    __shared__ zs_round_state RS;                                                                                   \
+    const uint32_t w_ = threadIdx.x >> 6;                                                                           \
+    zs_parse_body<WIN, SEG, NWV, false, false>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres,  \
+                                               syms, blocks, streams, scratch, good, lazy, nullptr, kp);            \
+  }
+#else
 #define ZS_PARSE_KERNEL(name, WIN, SEG, NWV)                                                                        \
   __global__ __launch_bounds__(64 * NWV) void name(                                                                  \
       const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len,     \
@@ -516,6 +535,7 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
     zs_parse_body<WIN, SEG, NWV, false, true>(U[w_].W, U[w_].T, RS, in, in_off, in_len, pos_base, blk_base, mres,  \
                                               syms, blocks, streams, scratch, good, lazy, nullptr);                 \
   }
+#endif
 ZS_PARSE_KERNEL(zs_k_parse, ZS_PARSE_WIN, ZS_PARSE_SEG, 1)
 // two waves per stream, 512-position segments: half the speculative pass per lane (small batches)
 ZS_PARSE_KERNEL(zs_k_parse_2w, ZS_PARSE_WIN, ZS_PARSE2W_SEG, 2)

@@ -32,6 +32,7 @@
 
 #include "../../include/zs_gpu.h"
 #include "zs_inflate.h"
+#include "zs_plan.h"  // zs_wbits_split
 
 void zs_set_last_error(const std::string& msg);  // capi.cpp: what zs_last_error() returns on this thread
 
@@ -329,6 +330,28 @@ extern "C" int zs_pool_deflate_batch_strategy(zs_pool* p, int level, int strateg
     return zs_deflate_batch_strategy(p->ctx[k], level, strategy, wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, out,
                                      out_off + s.a, out_cap + s.a, status + s.a, out_len + s.a,
                                      check ? check + s.a : nullptr);
+  });
+}
+
+// with deflateInit2_'s windowBits and memLevel (deflate.ts:253-343; validation :281-294)
+extern "C" int zs_pool_deflate_batch_params(zs_pool* p, int level, int wbits, int mem_level, uint32_t n,
+                                            const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                            uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                            int32_t* status, uint32_t* out_len, uint32_t* check) {
+  int wrap;
+  if (!zs_wbits_split(wbits, &wrap)) {
+    zs_set_last_error("invalid window bits");
+    return ZS_STREAM_ERROR;
+  }
+  if (mem_level < 1 || mem_level > 9) {
+    zs_set_last_error("invalid memLevel");
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_deflate_batch_params(p->ctx[k], level, wbits, mem_level, s.b - s.a, in, in_off + s.a, in_len + s.a, out,
+                                   out_off + s.a, out_cap + s.a, status + s.a, out_len + s.a,
+                                   check ? check + s.a : nullptr);
   });
 }
 

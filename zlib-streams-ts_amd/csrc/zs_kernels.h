@@ -46,6 +46,40 @@ __global__ void zs_k_bucket(const uint8_t* in, const uint64_t* in_off, const uin
 template <bool U8>
 __global__ void zs_k_sweep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* pos_base,
                            const zs_sweep_seg* segs, const uint16_t* members, uint2* mres, int chain, int nice);
+// ---- the *_par instances for non-default windowBits / memLevel (zs_par.h: the same sources
+// compiled a second time with kp, deflate.ts:295-336, in place of the constants); the kernels
+// above and below keep 15 / memLevel 8 compiled in
+template <bool ORD>
+__global__ void zs_k_prev_par(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                              const uint64_t* pos_base, uint16_t* prevd, uint32_t min_len, zs_kpar kp);
+__global__ void zs_k_match_par(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                               const uint64_t* pos_base, const uint16_t* prevd, uint2* mres, int chain, int nice,
+                               uint32_t min_len, zs_kpar kp);
+#define ZS_PARSE_PAR_DECL(name)                                                                                    \
+  __global__ void name##_par(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,                    \
+                             const uint64_t* pos_base, const uint32_t* blk_base, const uint2* mres, uint32_t* syms, \
+                             zs_block* blocks, zs_stream* streams, uint32_t* scratch, int good, int lazy, zs_kpar kp);
+ZS_PARSE_PAR_DECL(zs_k_parse)
+ZS_PARSE_PAR_DECL(zs_k_parse_2w)
+ZS_PARSE_PAR_DECL(zs_k_parse_4w)
+// (DICT = false alone is built; dstart is null)
+template <int NW, bool ORD, bool DICT>
+__global__ void zs_k_fast_par(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                              const uint64_t* pos_base, const uint32_t* blk_base, uint32_t* syms, zs_block* blocks,
+                              zs_stream* streams, int chain, int lazy, int nice, const uint32_t* dstart, zs_kpar kp);
+// GH: head[] in the global workspace ghead, 1 << hash_bits u16 per stream (zs_plan_fast_params)
+template <bool DICT, bool GH>
+__global__ void zs_k_fast_serial_par(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                     const uint64_t* pos_base, const uint32_t* blk_base, uint32_t* syms,
+                                     zs_block* blocks, zs_stream* streams, int chain, int lazy, int nice,
+                                     const uint32_t* dstart, zs_kpar kp, uint16_t* ghead);
+// a block that began before the slid window is never stored (deflate.ts:1120-1124)
+__global__ void zs_k_trees_par(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base,
+                               const uint32_t* blk_base, const uint32_t* syms, zs_block* blocks,
+                               const zs_stream* streams, uint32_t* codes, uint32_t* hdr, int nstreams, int fixed);
+// the zlib header's CINFO = w_bits - 8 (deflate.ts:754)
+__global__ void zs_k_wrap_par(const zs_stream* streams, uint8_t* out, const uint64_t* out_off, const uint32_t* in_len,
+                              int wrap, int level, int nstreams, int strategy, uint32_t w_bits);
 // the lazy parse (deflate_parse.hip): pass A stages 32 match-table entries per lane in LDS; the
 // _dict instances parse joined streams (dictionary tail + data) from dstart[s] on; the _filt
 // instances are Z_FILTERED's (a new match of at most 5 bytes is dropped, deflate.ts:1381-1387)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zs_common.h"
+#include "zs_par.h"
 
 #define ZS_NONE 0xffffffffu
 
@@ -20,12 +21,13 @@ struct zs_pstate {
 // different points of their parses, and a branchy step costs every lane all
 // paths plus the exec-mask bookkeeping.
 // FILT: Z_FILTERED -- a new match of at most 5 bytes is dropped like a too-far one.
+// (the *_par build, zs_par.h: the slide positions follow kp's w_size)
 template <bool FILT = false>
 static __device__ __forceinline__ uint32_t zs_parse_step(zs_pstate& st, uint2 e, uint32_t lit, uint32_t n, int good,
-                                                         int lazy) {
+                                                         int lazy ZS_PAR_ARG) {
   const uint32_t p = st.p, pl = st.ml, pm = st.ms;
   // head slot emptied by a slide at exactly this position
-  const bool nil = ((e.x & 0x8000u) != 0) & (p >= ZS_SLIDE_AT) & (((p - ZS_SLIDE_AT) & 32767u) == 0) &
+  const bool nil = ((e.x & 0x8000u) != 0) & (p >= ZS_P_SLIDE_AT) & (((p - ZS_P_SLIDE_AT) & ZS_P_WMASK) == 0) &
                    (n - p < (uint32_t)ZS_MIN_LOOKAHEAD);
   // (lengths are bits 16..24: the parse may carry a byte in the bits above, deflate_parse.hip)
   const bool search = (((e.x >> 16) & 0x1ffu) != 0) & (pl < (uint32_t)lazy) & !nil;  // deflate.ts:1376
@@ -48,8 +50,9 @@ static __device__ __forceinline__ uint32_t zs_parse_step(zs_pstate& st, uint2 e,
 // Number of fill_window slides performed by the time the parse visits v
 // (slide j happens at the first visited position >= T_j with
 // T_j = max(32768 j + 65274, min(n, 32768 j + 65536) - 261), deflate.ts:180-190).
-static __device__ __forceinline__ uint32_t zs_slides(uint32_t v, uint32_t n) {
-  if (n <= v + 261u) return v >= ZS_SLIDE_AT ? (v - ZS_SLIDE_AT) / 32768u + 1u : 0u;
-  return v >= ZS_SLIDE_AT + 1u ? (v - ZS_SLIDE_AT - 1u) / 32768u + 1u : 0u;
+// (the *_par build: T_j = max(w j + 2 w - 262, min(n, w j + 2 w) - 261) for kp's w = w_size)
+static __device__ __forceinline__ uint32_t zs_slides(uint32_t v, uint32_t n ZS_PAR_ARG) {
+  if (n <= v + 261u) return v >= ZS_P_SLIDE_AT ? (v - ZS_P_SLIDE_AT) / ZS_P_W + 1u : 0u;
+  return v >= ZS_P_SLIDE_AT + 1u ? (v - ZS_P_SLIDE_AT - 1u) / ZS_P_W + 1u : 0u;
 }
 

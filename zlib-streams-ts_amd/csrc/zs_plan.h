@@ -374,6 +374,73 @@ static inline void zs_plan_huff_chunks(uint32_t n, const uint32_t* in_len, std::
     for (uint32_t b = 0; b <= in_len[i] / ZS_SYM_END; b++) chunks.push_back({i, b});
 }
 
+// ---- deflateInit2_'s windowBits and memLevel (deflate.ts:253-343)
+// w_bits 9..15 (8 runs as 9, deflate.ts:295-297); hash_bits = memLevel + 7 and hash_shift =
+// (hash_bits + 2) / 3 in whole numbers (deflate.ts:312-315; the `<<` of :110 truncates the
+// reference's fraction); a block closes after sym_end = lit_bufsize - 1 symbols, lit_bufsize =
+// 1 << (memLevel + 6) (deflate.ts:323,336).  The default -- 15 / memLevel 8 -- is what every
+// kernel had compiled in before the parameters existed.
+struct zs_deflate_params {
+  uint32_t w_bits = 15, hash_bits = 15, hash_shift = 5, sym_end = ZS_SYM_END;
+  bool is_default() const { return w_bits == 15 && hash_bits == 15 && hash_shift == 5 && sym_end == ZS_SYM_END; }
+  uint32_t w_size() const { return 1u << w_bits; }
+  zs_kpar kpar() const { return {1u << w_bits, hash_shift, (1u << hash_bits) - 1u, sym_end}; }
+};
+// window_bits 8..15, mem_level 1..9 (validated by the caller)
+static inline zs_deflate_params zs_make_params(int window_bits, int mem_level) {
+  zs_deflate_params q;
+  q.w_bits = (uint32_t)(window_bits == 8 ? 9 : window_bits);
+  q.hash_bits = (uint32_t)mem_level + 7u;
+  q.hash_shift = (q.hash_bits + 2u) / 3u;
+  q.sym_end = (1u << (mem_level + 6)) - 1u;
+  return q;
+}
+// deflateInit2_'s windowBits argument (deflate.ts:272-294): -9..-15 raw, 8..15 zlib, 25..31
+// gzip; -8 and everything else is refused.  Returns the window bits 8..15, or 0.
+static inline int zs_wbits_split(int wbits, int* wrap) {
+  int w = wbits;
+  *wrap = 1;
+  if (w < 0) {
+    *wrap = 0;
+    w = -w;
+  } else if (w > 15) {
+    *wrap = 2;
+    w -= 16;
+  }
+  if (w == 8 && *wrap != 1) return 0;  // (only a zlib stream takes 8, and runs it as 9: deflate.ts:281-297)
+  return w >= 8 && w <= 15 ? w : 0;
+}
+// Levels 1..3 with non-default parameters (deflate_fast.hip): the kernel instance and its LDS.
+// The tables of the reference are head[1 << hash_bits] and prev[w_size], u16 each; beside them
+// sits the input ring -- 32 KiB in the group-speculative kernel, w_size bytes in the step-by-step
+// one.  memLevel 9 (65,536 heads, 128 KiB) leaves the group kernel no room, and the step-by-step
+// one only up to w_bits 13 (128 + 16 + 8 KiB); at w_bits 14 and 15 its head[] lives in a
+// per-stream global workspace (128 KiB per stream, resident in L2).
+#define ZS_FAST_LDS_MAX (160u << 10)
+enum zs_fast_route { ZS_FAST_GROUP = 0, ZS_FAST_SERIAL = 1, ZS_FAST_SERIAL_GHEAD = 2 };
+struct zs_fast_plan {
+  zs_fast_route route = ZS_FAST_GROUP;
+  uint32_t lds_bytes = 0;    // dynamic LDS of the launch
+  uint64_t ghead_bytes = 0;  // the global head[] workspace of the whole batch (route ZS_FAST_SERIAL_GHEAD)
+};
+static inline zs_fast_plan zs_plan_fast_params(const zs_deflate_params& q, bool fast_group, uint32_t n) {
+  zs_fast_plan f;
+  const uint32_t head = 2u << q.hash_bits, prev = 2u << q.w_bits;
+  const uint32_t group = head + prev + 32768u, serial = head + prev + q.w_size();
+  if (fast_group && group <= ZS_FAST_LDS_MAX) {
+    f.route = ZS_FAST_GROUP;
+    f.lds_bytes = group;
+  } else if (serial <= ZS_FAST_LDS_MAX) {
+    f.route = ZS_FAST_SERIAL;
+    f.lds_bytes = serial;
+  } else {
+    f.route = ZS_FAST_SERIAL_GHEAD;
+    f.lds_bytes = prev + q.w_size();
+    f.ghead_bytes = (uint64_t)head * n;
+  }
+  return f;
+}
+
 // The workspace layout of a deflate batch (levels 1..9).  With the sweep (levels
 // 4..9, option match_sweep), every stream is cut into WINDOWS of at most 65,535
 // inserted positions: a stream of up to 65,537 bytes is one; a longer one has a
@@ -389,6 +456,7 @@ struct zs_deflate_plan {
   uint64_t P = 0, members = 0;
   uint32_t B = 0, max_len = 0, max_blk = 0;
   int pw = 1;  // waves per stream of the parse (zs_k_parse / _2w / _4w)
+  bool sweep = false;  // levels 4..9: zs_k_bucket + zs_k_sweep (else the chain-walk kernels zs_k_prev + zs_k_match)
   // A batch with preset dictionaries (else empty / 0): each stream's parse start L' in its
   // joined stream, the joined streams' offsets in the join buffer, and that buffer's bytes
   std::vector<uint32_t> start;
@@ -405,9 +473,15 @@ ZS_PLAN_FN uint32_t zs_dict_tail(uint32_t dict_len) { return dict_len < ZS_W_SIZ
 // dictionary's tail of L' = zs_dict_tail bytes, then the data: the
 // per-position tables, the windows and max_len follow nv = L' + n, the windows'
 // own positions start at L' (p.start), the block records follow n.
+// q: deflateInit2_'s windowBits / memLevel.  Non-default ones take the chain-walk kernels at
+// levels 4..9 (zs_k_prev + zs_k_match follow prev[] links whatever the hash; the sweep's
+// signatures rest on the 15-bit hash, deflate_sweep.hip:24-27), and the block records follow
+// sym_end: a stream of n bytes closes at most n / sym_end + 1 blocks.
 static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n, const uint32_t* in_len,
-                                   zs_deflate_plan& p, const uint32_t* dict_len = nullptr) {
-  const bool sweep = level >= 4 && o.match_sweep;
+                                   zs_deflate_plan& p, const uint32_t* dict_len = nullptr,
+                                   const zs_deflate_params& q = zs_deflate_params()) {
+  const bool sweep = level >= 4 && o.match_sweep && q.is_default();
+  p.sweep = sweep;
   p.pos.resize(n);
   p.blk.resize(n);
   p.P = 0;
@@ -430,7 +504,7 @@ static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n
     p.pos[i] = p.P;
     p.P += (nv + 7) & ~7ull;  // per-position tables start 8-aligned (16-B link loads in zs_k_match)
     p.blk[i] = p.B;
-    const uint32_t nb = in_len[i] / ZS_SYM_END + 2;
+    const uint32_t nb = in_len[i] / q.sym_end + 2;
     p.B += nb;
     p.max_len = std::max(p.max_len, (uint32_t)std::min<uint64_t>(nv, 0xffffffffull));
     p.max_blk = std::max(p.max_blk, nb);

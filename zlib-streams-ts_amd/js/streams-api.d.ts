@@ -22,6 +22,14 @@ export interface CompressBatchOptions extends BatchOptions {
    * 4 Z_FIXED.  A number out of range fails with "init failed: -2" (code "-2" from the detailed entry);
    * together with `dictionary` it is a TypeError. */
   strategy?: number;
+  /** deflateInit2_'s windowBits (deflate.ts:253-343): 8..15, the window is 1 << windowBits bytes (8 runs as 9;
+   * "deflate" outputs carry it in CINFO); any non-number means 15.  A number out of range, and 8 with
+   * "deflate-raw" or "gzip", fails with "init failed: -2" (code "-2").  Other than 15 it is a TypeError together
+   * with `dictionary` or a `strategy` other than 0, and level 0 fails with "init failed: -2". */
+  windowBits?: number;
+  /** deflateInit2_'s memLevel: 1..9, the hash has memLevel + 7 bits and a block closes after
+   * (1 << (memLevel + 6)) - 1 symbols; any non-number means 8.  The rules of `windowBits` hold for it. */
+  memLevel?: number;
 }
 export const Z_DEFAULT_STRATEGY: 0;
 export const Z_FILTERED: 1;

@@ -84,18 +84,38 @@ function strategyOf(options) {
   return s;
 }
 
+// options.windowBits (8..15) and options.memLevel (1..9): deflateInit2_'s windowBits and memLevel
+// (deflate.ts:253-343).  A value that is not a number means the default, 15 and 8 (the rule of
+// `level`, streams.ts:221); a number out of range -- and 8 for "deflate-raw" or "gzip" -- fails with
+// "init failed: -2" (deflate.ts:281-294); values other than 15 / 8 together with a dictionary or a
+// strategy are a TypeError (not built: zs_gpu.h).  Returns [deflateInit2_'s windowBits argument, memLevel].
+function paramsOf(options, format) {
+  const wb = typeof options.windowBits == "number" ? options.windowBits : 15;
+  const ml = typeof options.memLevel == "number" ? options.memLevel : 8;
+  if (!Number.isInteger(wb) || wb < 8 || wb > 15 || !Number.isInteger(ml) || ml < 1 || ml > 9 ||
+      (wb === 8 && (format === "deflate-raw" || format === "gzip")))
+    throw Object.assign(streamError(Z_STREAM_ERROR, PHASE_INIT), { code: String(Z_STREAM_ERROR) });
+  if (wb !== 15 || ml !== 8) {
+    if (options.dictionary !== undefined && options.dictionary !== null)
+      throw new TypeError("windowBits / memLevel and dictionary cannot be combined");
+    if (typeof options.strategy == "number" && options.strategy !== 0)
+      throw new TypeError("windowBits / memLevel and strategy cannot be combined");
+  }
+  return [format === "deflate-raw" ? -wb : format === "gzip" ? wb + 16 : wb, ml];
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
   options = options || {};
-  const wbits = compressWbits(format);
+  const [wbits, memLevel] = paramsOf(options, format);
   // streams.ts:221: a level that is not a number means Z_DEFAULT_COMPRESSION (-1 -> 6, deflate.ts:268-270)
   const level = typeof options.level == "number" ? options.level : -1;
   let res;
   try {
     const ins = checkInputs(inputs);
     res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                                    strategyOf(options));
+                                    strategyOf(options), memLevel);
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -155,8 +175,9 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
   options = options || {};
   const level = typeof options.level == "number" ? options.level : -1;
   const ins = checkInputs(inputs);
-  return addon.compressBatch(ins, compressWbits(format), level, devicesOf(options), dictionariesOf(options, ins.length),
-                             strategyOf(options));
+  const [wbits, memLevel] = paramsOf(options, format);
+  return addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
+                             strategyOf(options), memLevel);
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

@@ -199,6 +199,8 @@ typedef struct {
   int unbounded; /* decompress without a caller capacity: zs_pool_inflate_batch_auto */
   int wbits, level;
   int strategy;  /* compress: deflateInit2_'s strategy (zs_pool_deflate_batch_strategy when not 0) */
+  int params;    /* compress: windowBits / memLevel other than 15 / 8 (zs_pool_deflate_batch_params): wbits is */
+  int mem_level; /* deflateInit2_'s windowBits argument then (-9..-15, 8..15, 25..31) */
   uint32_t n;
   zs_pool *pool;
   uint64_t *in_off, *out_off;
@@ -273,6 +275,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_deflate_batch_dict(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                        j->out_off, j->cap, j->status, j->olen, j->check, j->dict, j->dict_off,
                                        j->dict_len);
+  else if (j->params)
+    j->rc = zs_pool_deflate_batch_params(j->pool, j->level, j->wbits, j->mem_level, j->n, j->base, j->in_off, j->in_len,
+                                         j->out, j->out_off, j->cap, j->status, j->olen, j->check);
   else if (j->strategy)
     j->rc = zs_pool_deflate_batch_strategy(j->pool, j->level, j->strategy, j->wbits, j->n, j->base, j->in_off, j->in_len,
                                            j->out, j->out_off, j->cap, j->status, j->olen, j->check);
@@ -447,22 +452,37 @@ static int copy_dicts(napi_env env, job *j, napi_value arr) {
 }
 
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
- *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined) ->
+ *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined,
+ *               memLevel: number | undefined) ->
+ * wbits: deflateInit2_'s windowBits argument, -9..-15 / 8..15 / 25..31; memLevel 1..9 (a non-number means 8);
+ * anything else throws code "-2" (deflate.ts:281-294), and so does a window other than 15 or a memLevel other
+ * than 8 together with dictionaries or a strategy (not built, zs_gpu.h), before any device is touched.
  * strategy: 0..4 (a non-number means 0); out of range, or not 0 together with dictionaries, throws code "-2"
  * (deflate.ts:289-290; no dictionaries with a strategy, zs_gpu.h) before any device is touched ->
  *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
 static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 3)
-    return throw_code(env, ZS_STREAM_ERROR, "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy]]])");
+    return throw_code(env, ZS_STREAM_ERROR,
+                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel]]]])");
   const int32_t strategy = argc > 5 ? arg_i32(env, argv[5], 0) : 0;
   if (strategy < 0 || strategy > ZS_FIXED) return throw_code(env, ZS_STREAM_ERROR, "invalid strategy");
   napi_valuetype dt = napi_undefined;
   if (argc > 4) napi_typeof(env, argv[4], &dt);
   if (strategy && dt != napi_undefined && dt != napi_null)
     return throw_code(env, ZS_STREAM_ERROR, "a strategy with preset dictionaries is not built");
+  const int32_t wbits = arg_i32(env, argv[1], -15), mem_level = argc > 6 ? arg_i32(env, argv[6], 8) : 8;
+  {
+    const int32_t w = wbits < 0 ? -wbits : wbits > 15 ? wbits - 16 : wbits;  /* deflate.ts:272-294 */
+    if (w < 8 || w > 15 || (w == 8 && (wbits < 0 || wbits > 15)))
+      return throw_code(env, ZS_STREAM_ERROR, "invalid window bits");
+    if (mem_level < 1 || mem_level > 9) return throw_code(env, ZS_STREAM_ERROR, "invalid memLevel");
+  }
+  const int params = mem_level != 8 || (wbits != -15 && wbits != 15 && wbits != 31);
+  if (params && (strategy || (dt != napi_undefined && dt != napi_null)))
+    return throw_code(env, ZS_STREAM_ERROR, "windowBits / memLevel with preset dictionaries or a strategy is not built");
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -476,9 +496,11 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
     return pool ? throw_code(env, ZS_MEM_ERROR, "out of host memory") : NULL;
   }
   j->pool = pool;
-  j->wbits = arg_i32(env, argv[1], -15);
+  j->wbits = wbits;
   j->level = arg_i32(env, argv[2], -1);
   j->strategy = strategy;
+  j->params = params;
+  j->mem_level = mem_level;
   if (dt != napi_undefined && dt != napi_null) {
     bool is_arr = false;
     napi_is_array(env, argv[4], &is_arr);
@@ -493,7 +515,9 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   uint64_t tout = 0;
   for (uint32_t i = 0; i < n; i++) {
     j->out_off[i] = tout;
-    j->cap[i] = (uint32_t)((zs_deflate_bound_dict(v[i].n, j->wbits, j->dict_len ? j->dict_len[i] : 0) + 3) & ~3ull);
+    const uint64_t bound = params ? zs_deflate_bound_params(v[i].n, wbits, mem_level, j->level == -1 ? 6 : j->level)
+                                  : zs_deflate_bound_dict(v[i].n, j->wbits, j->dict_len ? j->dict_len[i] : 0);
+    j->cap[i] = (uint32_t)((bound + 3) & ~3ull);
     tout += j->cap[i];
   }
   j->out = (uint8_t *)malloc(tout ? tout : 1);  /* (uninitialised: only the outputs are written) */

@@ -76,6 +76,31 @@ def compress_strategy(strategy, zdict=None) -> int:
     return strategy
 
 
+def compress_params(fmt: str, window_bits=None, mem_level=8, zdict=None, strategy=0) -> int:
+    """The `window_bits` (8..15; None = 15) and `mem_level` (1..9) keywords of the compress entries:
+    deflateInit2_'s windowBits and memLevel (deflate.ts:253-343).  Returns the windowBits code of
+    the zs_deflate_batch_params entries: -window_bits for "deflate-raw", window_bits + 16 for
+    "gzip", window_bits for "deflate".  Values deflateInit2_ refuses (deflate.ts:281-294: not an
+    int, out of range, 8 for deflate-raw or gzip) raise ZsError("init failed: -2"), as the stream
+    layer reports them (streams.ts:53).  Parameters other than 15 / 8 together with a preset
+    dictionary or a strategy are not built (zs_gpu.h): ValueError, before any call."""
+    wb = 15 if window_bits is None else window_bits
+    if isinstance(wb, bool) or not isinstance(wb, int) or not 8 <= wb <= 15 or (wb == 8 and fmt in ("deflate-raw", "gzip")):
+        raise ZsError("init failed: %d" % Z_STREAM_ERROR, Z_STREAM_ERROR, PHASE_INIT, "invalid window bits")
+    if isinstance(mem_level, bool) or not isinstance(mem_level, int) or not 1 <= mem_level <= 9:
+        raise ZsError("init failed: %d" % Z_STREAM_ERROR, Z_STREAM_ERROR, PHASE_INIT, "invalid memLevel")
+    if wb != 15 or mem_level != 8:
+        if zdict is not None:
+            raise ValueError("window_bits %d / mem_level %d with a preset dictionary is not built" % (wb, mem_level))
+        if strategy:
+            raise ValueError("window_bits %d / mem_level %d with strategy %d is not built" % (wb, mem_level, strategy))
+    return -wb if fmt == "deflate-raw" else wb + 16 if fmt == "gzip" else wb
+
+
+def _params_default(window_bits, mem_level) -> bool:
+    return window_bits in (None, 15) and mem_level == 8
+
+
 def stream_error_text(status: int, phase: int) -> str:
     if phase == PHASE_INIT:
         return "init failed: %d" % status
@@ -132,6 +157,13 @@ def lib():
         L.zs_deflate_batch_strategy.argtypes = _with(L.zs_deflate_batch_ex.argtypes)
         L.zs_deflate_batch_strategy_device.argtypes = _with(L.zs_deflate_batch_device_ex.argtypes)
         L.zs_pool_deflate_batch_strategy.argtypes = _with(L.zs_deflate_batch_ex.argtypes)
+    if hasattr(L, "zs_deflate_batch_params"):  # `mem_level` behind `wbits`
+        _withm = lambda a: a[:3] + [ctypes.c_int] + a[3:]
+        L.zs_deflate_batch_params.argtypes = _withm(L.zs_deflate_batch_ex.argtypes)
+        L.zs_deflate_batch_params_device.argtypes = _withm(L.zs_deflate_batch_device_ex.argtypes)
+        L.zs_pool_deflate_batch_params.argtypes = _withm(L.zs_deflate_batch_ex.argtypes)
+        L.zs_deflate_bound_params.restype = ctypes.c_uint64
+        L.zs_deflate_bound_params.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -281,18 +313,26 @@ class Engine:
 
     # ---------------------------------------------------------- host buffers
     def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                           strategy: int = 0) -> List[Tuple[int, bytes]]:
+                           strategy: int = 0, window_bits=None, mem_level=8) -> List[Tuple[int, bytes]]:
         """Returns [(status, bytes)] -- status Z_STREAM_END on success.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
         (zs_deflate_batch_dict: deflateSetDictionary, deflate.ts:367-424).
-        strategy: Z_DEFAULT_STRATEGY .. Z_FIXED (zs_deflate_batch_strategy; not with zdict)."""
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy)]
+        strategy: Z_DEFAULT_STRATEGY .. Z_FIXED (zs_deflate_batch_strategy; not with zdict).
+        window_bits (8..15, None = 15), mem_level (1..9): deflateInit2_'s windowBits and memLevel
+        (zs_deflate_batch_params; other than 15 / 8 not with zdict or a strategy, levels 1..9)."""
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
+                                                                     mem_level)]
 
     def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                                strategy: int = 0) -> List[Tuple[int, bytes, int]]:
+                                strategy: int = 0, window_bits=None, mem_level=8) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
+        compress_strategy(strategy, zdict)
+        code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
+        if not _params_default(window_bits, mem_level):
+            return _deflate_host(self._L, self._L.zs_deflate_batch_params, self._ctx, inputs, fmt, level, self._check,
+                                 params=(code, mem_level))
         if compress_strategy(strategy, zdict):
             return _deflate_host(self._L, self._L.zs_deflate_batch_strategy, self._ctx, inputs, fmt, level,
                                  self._check, strategy=strategy)
@@ -302,8 +342,8 @@ class Engine:
         return _deflate_host(self._L, self._L.zs_deflate_batch_ex, self._ctx, inputs, fmt, level, self._check)
 
     def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                       strategy: int = 0) -> List[bytes]:
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy))
+                       strategy: int = 0, window_bits=None, mem_level=8) -> List[bytes]:
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None):
@@ -333,11 +373,21 @@ class Engine:
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                         d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
-                        dict_off=None, dict_len=None, strategy: int = 0):
+                        dict_off=None, dict_len=None, strategy: int = 0, window_bits=None, mem_level=8):
         """Device pointers (ints) + host layout arrays (ctypes arrays).
         d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
-        strategy: zs_deflate_batch_strategy_device (not with dictionaries)."""
+        strategy: zs_deflate_batch_strategy_device (not with dictionaries).
+        window_bits / mem_level: zs_deflate_batch_params_device (other than 15 / 8 not with either)."""
+        compress_strategy(strategy, dict_off)
+        code = compress_params(fmt, window_bits, mem_level, dict_off, strategy)
+        if not _params_default(window_bits, mem_level):
+            r = self._L.zs_deflate_batch_params_device(self._ctx, compress_level(level), code, mem_level, n, _P(d_in),
+                                                       in_off, in_len, _P(d_out), out_off, out_cap, _P(d_status),
+                                                       _P(d_out_len), _P(d_check) if d_check else None,
+                                                       _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_deflate_batch_params_device")
+            return
         if compress_strategy(strategy, dict_off):
             r = self._L.zs_deflate_batch_strategy_device(self._ctx, compress_level(level), strategy,
                                                          compress_wbits(fmt), n, _P(d_in), in_off, in_len, _P(d_out),
@@ -380,10 +430,18 @@ class Engine:
         self._check(r, "zs_inflate_batch_device")
 
     def compress_host(self, level: int, fmt: str, n: int, h_in: int, in_off, in_len, h_out: int, out_off, out_cap,
-                      status, out_len, strategy: int = 0):
+                      status, out_len, strategy: int = 0, window_bits=None, mem_level=8):
         """zs_deflate_batch on caller-owned host memory (pointers as ints,
         layout/result arrays as ctypes arrays): the end-to-end host->host path
-        (strategy: zs_deflate_batch_strategy)."""
+        (strategy: zs_deflate_batch_strategy; window_bits / mem_level: zs_deflate_batch_params)."""
+        compress_strategy(strategy)
+        code = compress_params(fmt, window_bits, mem_level, None, strategy)
+        if not _params_default(window_bits, mem_level):
+            r = self._L.zs_deflate_batch_params(self._ctx, level, code, mem_level, n,
+                                                ctypes.cast(h_in, ctypes.c_char_p), in_off, in_len, _P(h_out), out_off,
+                                                out_cap, status, out_len, None)
+            self._check(r, "zs_deflate_batch_params")
+            return
         if compress_strategy(strategy):
             r = self._L.zs_deflate_batch_strategy(self._ctx, level, strategy, compress_wbits(fmt), n,
                                                   ctypes.cast(h_in, ctypes.c_char_p), in_off, in_len, _P(h_out),
@@ -443,13 +501,18 @@ def _layout(inputs):
     return b"".join(inputs), offs, lens
 
 
-def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None):
+def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None, params=None):
+    """params: (the windowBits code, mem_level) for a _params entry (fn), which takes mem_level behind wbits."""
     n = len(inputs)
     if n == 0:
         return []
-    wbits = compress_wbits(fmt)
+    wbits = compress_wbits(fmt) if params is None else params[0]
     blob, offs, lens = _layout(inputs)
-    if zdict:
+    if params is not None:
+        lv = compress_level(level)
+        caps = [(int(L.zs_deflate_bound_params(len(b), wbits, params[1], 6 if lv == -1 else lv)) + 3) & ~3
+                for b in inputs]
+    elif zdict:
         caps = [(int(L.zs_deflate_bound_dict(len(b), wbits, zdict[2][i])) + 3) & ~3 for i, b in enumerate(inputs)]
     else:
         caps = [(int(L.zs_deflate_bound(len(b), wbits)) + 3) & ~3 for b in inputs]
@@ -460,7 +523,8 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=N
     out = ctypes.create_string_buffer(max(1, oo))
     status, olen, chk = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
     lead = (compress_level(level),) if strategy is None else (compress_level(level), strategy)  # (fn: a _strategy entry)
-    r = fn(handle, *lead, wbits, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
+    mid = (wbits,) if params is None else (wbits, params[1])
+    r = fn(handle, *lead, *mid, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
            out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk, *zdict)
     check(r, "deflate batch")
     raw = out.raw
@@ -593,7 +657,13 @@ class Pool:
     def _check(self, r: int, what: str):
         Engine._check(self, r, what)
 
-    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
+    def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
+                                mem_level=8):
+        compress_strategy(strategy, zdict)
+        code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
+        if not _params_default(window_bits, mem_level):
+            return _deflate_host(self._L, self._L.zs_pool_deflate_batch_params, self._pool, inputs, fmt, level,
+                                 self._check, params=(code, mem_level))
         if compress_strategy(strategy, zdict):
             return _deflate_host(self._L, self._L.zs_pool_deflate_batch_strategy, self._pool, inputs, fmt, level,
                                  self._check, strategy=strategy)
@@ -602,11 +672,14 @@ class Pool:
                                  self._check, _dict_layout(zdict, len(inputs)))
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
-    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
-        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy)]
+    def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
+                           mem_level=8):
+        return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
+                                                                     mem_level)]
 
-    def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0):
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy))
+    def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
+                       mem_level=8):
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
         L = self._L
