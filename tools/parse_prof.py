@@ -18,9 +18,6 @@ L = zsamd.lib()
 out = (ctypes.c_ulonglong * 16)()
 L.zs_parse_stats(out)
 waves = max(1, out[5])
-for i, nm in enumerate(["pass A", "phase 1 (pass B)", "splice", "block cuts (dw: walk phases)", "block records (dw: count)"]):
+for i, nm in enumerate(["pass A", "phase 1 (pass B)", "splice", "block cuts", "block records"]):
     print("%-18s %8.1f us per stream-wave" % (nm, out[i] / waves / 100.0))
-print("dw: stages %.1f per stream, drain steps %.1f per stream, staging time %.1f us per stream-wave" % (
-    out[8] / n, out[9] / n, out[10] / n / 100.0))
-print("waves %d, demand walks %d (%.1f per stream), members walked %.1f per walk" % (
-    out[5], out[6], out[6] / n, out[7] / max(1, out[6])))
+print("waves %d" % out[5])

@@ -32,6 +32,7 @@
 // the slide falls on p itself, i.e. p = 32768 j + 65274 with the input ending
 // within the window (n - p < 262) -- a pure function of p, so no state is needed.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "zs_common.h"
 #include "zs_kernels.h"
 #include "zs_parse.h"
@@ -68,12 +69,18 @@ struct zs_round_state {
 // LDS, then parses from LDS until every lane has left its window.  One memory
 // round trip per stage instead of one per parse step: a step's position depends
 // on the previous step's entry, so direct loads put the full memory latency on
-// every step.  Entry k of lane l is at m[k / 2][l] (a lane's reads are 16 B
-// apart from its neighbours': conflict-free), bytes in[w + 4 j, +4) at s[j][l].
-// WIN = 32 (19 KiB of LDS: 8 workgroups per CU) halves the stages of WIN = 16
-// (10 KiB) and measured faster in round 2: 1.54 vs 1.77 ms at 4096 streams,
-// 2.99 ms with direct loads (WIN = 0); 0.40 / 0.42 / 0.54 ms at 512.  Only
-// WIN = 32 is built.
+// every step.  The stage is cooperative (round 13): the WIN / 2 lanes of a group
+// load the WIN / 2 consecutive uint4 of ONE lane's window, target after target, so
+// a load instruction asks for a few 128-byte lines instead of 64 (parse 1.47 ->
+// 1.24 ms at 4,096 streams).  Entries 2 c and 2 c + 1 of lane l are at
+// m[c][l ^ (c & 7)]: the eight lanes of a ds_write_b128 group, which hold eight
+// pieces of one target, then write eight different 16-byte columns.  The parse's
+// ds_read_b64 of lanes at different c can now meet in a bank (LDS conflict cycles
+// 8.9 % -> 14.3 % of the LDS-array cycles, profiles/r13/parse_loads.txt).
+// WIN = 32 (16 KiB of LDS: ten workgroups per CU) halves the stages of WIN = 16
+// (8 KiB, sixteen per CU: 4,096 streams in one round) and stays faster with the
+// cooperative loads: 1.24 vs 1.28 ms at 4,096 streams, 0.29 vs 0.41 ms at 512.
+// Only WIN = 32 is built.
 // The input byte each step needs, in[p - 1], rides in the staged entry of p
 // (round 6; before, 2 KiB of staged input words per wave: 19 KiB per workgroup,
 // eight per CU, parse 1.55 ms at 4,096 streams; now 16 KiB, ten per CU, 1.47 ms).
@@ -221,56 +228,82 @@ static __device__ __forceinline__ void zs_parse_body(zs_parse_win<WIN>& W, zs_se
           step(M[p], p > 0 ? src[p - 1] : 0u);
         }
       } else {
-        while (__ballot(st.p < b) != 0) {
-          // stage: this lane's window [w, w + WIN) (entries past n are never read)
+        // Staging is cooperative: in round r the NP = WIN / 2 lanes of group g load the NP
+        // consecutive uint4 of the window of target lane T = r + NP g, piece c each, so one load
+        // instruction covers 64 / NP whole windows (a few 128-byte lines) instead of 64 lines.
+        constexpr uint32_t NP = WIN / 2;
+        const uint32_t c = lane & (NP - 1u), tg = lane & ~(NP - 1u);
+        const uint4* g = reinterpret_cast<const uint4*>(M);
+        const uint32_t glast = ((n + 7u) >> 1) & ~3u;  // the stream's uint4s (two entries each)
+        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
+        const uint32_t slast = (n - 1u) >> 2;
+        // the word this lane fetches for its piece is w_T / 4 + cw - 1: pieces 2 k - 1 and 2 k both fetch word k - 1
+        const uint32_t cw = (c + 1u) >> 1;
+        for (uint64_t staging; (staging = __ballot(st.p < b)) != 0;) {
+          // stage: every staging lane's window [w, w + WIN) (entries past n are never read)
           const uint32_t w = st.p & ~3u;
-          if (st.p < b) {
-            // every load is issued before the first is waited for: indices are
-            // clamped into the stream instead of branched around (entries past
-            // n are never read; the table's rows are 8-entry aligned, pos_base)
-            const uint4* g = reinterpret_cast<const uint4*>(M);
-            const uint32_t glast = ((n + 7u) >> 1) & ~3u;  // the stream's uint4s (two entries each)
-            uint4 mv[WIN / 2];
-            auto load_m = [&]() __attribute__((always_inline)) {
+          // every load is issued before the first is waited for: indices are
+          // clamped into the stream instead of branched around (entries past
+          // n are never read; the table's rows are 8-entry aligned, pos_base)
+          auto stage = [&](auto al) __attribute__((always_inline)) {
+            constexpr bool AL = decltype(al)::value;
+            uint4 mv[NP];
+            uint32_t sv[NP];  // the round's w_T, then the input bytes loaded for the piece
+            // bit r: the round's target stages (nothing is loaded for a lane that does not)
+            const uint32_t act = (uint32_t)(staging >> tg) & ((1u << NP) - 1u);
+            // (formed per stage behind an empty asm: sixteen shuffle and sixteen LDS addresses would
+            // otherwise be kept in registers across the whole parse loop)
+            uint32_t tb = tg << 2, c7 = c & 7u;
+            asm volatile("" : "+v"(tb), "+v"(c7));
 #pragma unroll
-              for (uint32_t j = 0; j < WIN / 2; j++) mv[j] = g[min(w / 2 + j, glast - 1u)];
-            };
-            auto store_m = [&]() __attribute__((always_inline)) {
+            for (uint32_t r = 0; r < NP; r++) sv[r] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(tb + 4u * r), (int)w);
 #pragma unroll
-              for (uint32_t j = 0; j < WIN / 2; j++) W.m[j][lane] = mv[j];
-            };
+            for (uint32_t r = 0; r < NP; r++) {
+              if ((act >> r) & 1u) {
+                const uint32_t wt = sv[r];
+                mv[r] = g[min(wt / 2 + c, glast - 1u)];
+                // the two input bytes of the piece, in[q - 1] and in[q] with q = w_T + 2 c (at q = 0 the first
+                // is never read: a parse enters position 0 with no literal pending)
+                if constexpr (AL) {
+                  // aligned words holding at least one byte of the stream never leave its pages.  Pieces
+                  // 2 k - 1 and 2 k both fetch word w_T / 4 + k - 1: an odd piece finds both bytes in it, an
+                  // even one in[q - 1] at its top and in[q] in the next lane's word
+                  sv[r] = s4[min(max(wt / 4 + cw, 1u) - 1u, slast)];
+                } else {
+                  // one load of the bytes [q' - 1, q'], q' = min(max(q, 1), n - 1); bit 16 marks q = 0
+                  uint16_t h = 0;
+                  if (n > 1) __builtin_memcpy(&h, src + min(max(wt + 2u * c, 1u), n - 1u) - 1u, 2);
+                  sv[r] = n > 1 ? (uint32_t)h | ((wt | c) == 0 ? 0x10000u : 0u) : src[0] | 0x10000u;
+                }
+              }
+            }
             // in[p - 1] rides in the entry of p: bits 25..31 of x (L <= 258 uses bits 16..24) and bit 31 of
             // y; the parse masks them (zs_parse_step), so the window holds no input bytes
-            uint32_t sv[WIN / 4], bw;
-            if (aligned) {  // aligned words holding at least one byte of the stream never leave its pages
-              load_m();
-              const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
-              const uint32_t slast = (n - 1u) >> 2;
 #pragma unroll
-              for (uint32_t j = 0; j < WIN / 4; j++) sv[j] = s4[min(w / 4 + j, slast)];
-              bw = w ? s4[w / 4 - 1] >> 24 : 0u;
-            } else {
-              load_m();
-#pragma unroll
-              for (uint32_t j = 0; j < WIN / 4; j++) sv[j] = zs_load_word(src, n, w + 4 * j);
-              bw = w ? (uint32_t)src[w - 1] : 0u;
+            for (uint32_t r = 0; r < NP; r++) {
+              uint32_t l0, l1;
+              if constexpr (AL) {
+                // the next lane's word (row_shl:1; the last piece is odd and needs none)
+                const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sv[r], 0x101, 0xf, 0xf, false);
+                l0 = (c & 1u) ? (sv[r] >> 8) & 0xffu : sv[r] >> 24;
+                l1 = (c & 1u) ? (sv[r] >> 16) & 0xffu : nx & 0xffu;
+              } else {
+                l0 = sv[r] & 0xffu;
+                l1 = (sv[r] >> 16) ? l0 : (sv[r] >> 8) & 0xffu;  // q = 0: in[0] is the first byte loaded
+              }
+              mv[r].x |= l0 << 25;
+              mv[r].y |= (l0 >> 7) << 31;
+              mv[r].z |= l1 << 25;
+              mv[r].w |= (l1 >> 7) << 31;
+              // column T ^ (c & 7): the eight lanes of one ds_write_b128 group hold eight pieces of ONE target
+              // (tg + r) ^ c7 = tg + (r ^ c7): tg is a multiple of NP >= 8
+              if ((act >> r) & 1u) W.m[c][tg + (r ^ c7)] = mv[r];
             }
-            auto byte_at = [&](uint32_t k) __attribute__((always_inline)) {  // in[w + k]
-              return (sv[k >> 2] >> (8u * (k & 3u))) & 0xffu;
-            };
-#pragma unroll
-            for (uint32_t j = 0; j < WIN / 2; j++) {
-              const uint32_t l0 = j == 0 ? bw : byte_at(2 * j - 1), l1 = byte_at(2 * j);
-              mv[j].x |= l0 << 25;
-              mv[j].y |= (l0 >> 7) << 31;
-              mv[j].z |= l1 << 25;
-              mv[j].w |= (l1 >> 7) << 31;
-            }
-            store_m();
-          }
+          };
+          if (aligned) stage(std::true_type{}); else stage(std::false_type{});
           while (st.p < b && st.p < w + WIN) {
             const uint32_t o = st.p - w;
-            const uint2 e = reinterpret_cast<const uint2*>(&W.m[o >> 1][lane])[o & 1];
+            const uint2 e = reinterpret_cast<const uint2*>(&W.m[o >> 1][lane ^ ((o >> 1) & 7u)])[o & 1];
             step(e, (e.x >> 25) | ((e.y >> 31) << 7));
           }
         }
