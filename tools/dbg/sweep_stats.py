@@ -11,6 +11,8 @@ ins = [buf[i * 65536:(i + 1) * 65536] for i in range(4096)]
 e.compress_batch_raw(ins, "deflate-raw", 6)
 out = (ctypes.c_ulonglong * 8)()
 print("rc", zsamd.lib().zs_sw_stats(out))
-names = ["chunks", "fast groups", "masked groups", "long branches", "wave steps"]
+names = ["chunks", "fast groups", "ends groups", "long branches", "wave steps behind the opening group",
+         "ends and opening groups reading winners' keys",
+         "ends groups failing validation", "opening groups failing validation"]
 for i, nm in enumerate(names):
     print(nm, out[i], "per chunk %.2f" % (out[i] / max(1, out[0])))

@@ -4,7 +4,11 @@ ratios that bound an integer/LDS kernel:
   lds_bank_conflict_frac = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE
                            (extra cycles / all LDS-array cycles, MI355X_MICROARCH.md LDS section)
   valu_busy              = 4 * SQ_INSTS_VALU / (1024 SIMDs * GRBM_GUI_ACTIVE / 8)
-                           (a wave64 VALU instruction holds its SIMD 4 cycles; GRBM_GUI_ACTIVE
+                           (a wave64 VALU instruction holds its SIMD 4 cycles: measured for
+                           v_ffbl_b32, v_min3_u32 and v_and_or_b32, 4.2-4.3 with loop overhead;
+                           v_xor_b32 holds it 2.35, so the figure is an upper bound for a kernel
+                           rich in plain VOP2 integer instructions -- tools/valu_issue.hip,
+                           profiles/r14/valu_issue.txt.  The formula is unchanged.  GRBM_GUI_ACTIVE
                            is summed over the 8 XCDs; the two come from different passes)
   active / wait / wait_inst = SQ_ACTIVE_INST_ANY, SQ_WAIT_ANY, SQ_WAIT_INST_ANY over SQ_WAVE_CYCLES
                            (disjoint; they sum to ~1)

@@ -48,6 +48,7 @@
 #include "zs_kernels.h"
 #include "zs_sweep_ring.h"
 #include "zs_sweep_long.h"
+#include "zs_sweep_ends.h"
 #include <type_traits>
 #include <utility>
 
@@ -393,34 +394,40 @@ struct SwSig<true> {
   // forwarding hazard), so a plain instruction that consumes a block's result straight behind it gets
   // an s_nop 0 in front.  With the min3 and the and_or inside, a step's result is first read by the
   // group's max tree, after the other steps.
-  // (in place in the registers of the record's words: a block that wrote a register of the block
-  // before it would meet the same rule)
+  // (the first word in place in its register, the second through a scratch register t that is an
+  // output only -- its first write is the second instruction, behind the last read of a and x and
+  // with the read of y and b, so t may share any input's register, and it takes y's where y dies
+  // here.  With y tied in and out, the compiler copied the word of two records of every group into
+  // a free register first: two v_mov per group.  A block that wrote a register of the block before
+  // it would meet the hazard rule above.)
   template <uint32_t U>
   __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t) const {
-    asm("v_xor_b32_e32 %0, %0, %2\n\t"
-        "v_xor_b32_e32 %1, %1, %3\n\t"
+    uint32_t t;
+    asm("v_xor_b32_e32 %0, %0, %3\n\t"
+        "v_xor_b32_e32 %1, %2, %4\n\t"
         "v_ffbl_b32 %0, %0\n\t"
         "v_ffbl_b32 %1, %1\n\t"
         "v_add_u32_e64 %1, %1, 32 clamp\n\t"
         "v_min3_u32 %0, %0, %1, 64\n\t"
-        "v_and_or_b32 %0, %0, -8, %4"
-        : "+v"(x), "+v"(y)
-        : "v"(a), "v"(b), "n"(7u - U));
+        "v_and_or_b32 %0, %0, -8, %5"
+        : "+v"(x), "=v"(t)
+        : "v"(y), "v"(a), "v"(b), "n"(7u - U));
     return x;
   }
   // ... and 0 for a lane outside lm (the masked groups' select)
   template <uint32_t U>
   __device__ __forceinline__ uint32_t step(uint32_t x, uint32_t y, uint32_t, uint64_t lm) const {
-    asm("v_xor_b32_e32 %0, %0, %2\n\t"
-        "v_xor_b32_e32 %1, %1, %3\n\t"
+    uint32_t t;
+    asm("v_xor_b32_e32 %0, %0, %3\n\t"
+        "v_xor_b32_e32 %1, %2, %4\n\t"
         "v_ffbl_b32 %0, %0\n\t"
         "v_ffbl_b32 %1, %1\n\t"
         "v_add_u32_e64 %1, %1, 32 clamp\n\t"
         "v_min3_u32 %0, %0, %1, 64\n\t"
-        "v_and_or_b32 %0, %0, -8, %4\n\t"
-        "v_cndmask_b32_e64 %0, 0, %0, %5"
-        : "+v"(x), "+v"(y)
-        : "v"(a), "v"(b), "n"(7u - U), "s"(lm));
+        "v_and_or_b32 %0, %0, -8, %5\n\t"
+        "v_cndmask_b32_e64 %0, 0, %0, %6"
+        : "+v"(x), "=v"(t)
+        : "v"(y), "v"(a), "v"(b), "n"(7u - U), "s"(lm));
     return x;
   }
   static __device__ __forceinline__ uint32_t len(uint32_t sigma) { return sigma ? sigma + 2u : 2u; }
@@ -513,7 +520,9 @@ struct SwRingP {
 #define ZS_SW_PROF 0  // instrumentation: counts of chunks, groups, long branches and wave steps (0 in the product)
 #endif
 #if ZS_SW_PROF
-__device__ unsigned long long zs_sw_stat[8];  // chunks, fast groups, masked groups, long branches, wave steps
+// chunks, fast groups, groups in which a chain ends, long branches, wave steps; of the ends groups those that read
+// the winners' keys and those that fail validation (zs_sweep_ends.h); opening groups that fail it
+__device__ unsigned long long zs_sw_stat[8];
 #define SW_STAT(i, v) do { if ((threadIdx.x & 63u) == __builtin_ctzll(__builtin_amdgcn_read_exec())) atomicAdd(&zs_sw_stat[i], (unsigned long long)(v)); } while (0)
 extern "C" int zs_sw_stats(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(zs_sw_stat), sizeof(zs_sw_stat));
@@ -796,6 +805,78 @@ struct SwWave {
     fold(L, sw_gmax<N>(sc), t0, sc, N, c_of(g), g.K);
   }
 
+  // A group of eight in which some lane's chain ends, behind its max tree: gm
+  // is the maximum of the UNMASKED scores sc (0 for a lane outside a0, the
+  // lanes live when the group began), last the lanes live at its last step, K
+  // the group's part of the ring's keys.  Returns the lanes that are not settled.
+  // zs_sweep_ends.h has the rule: a lane with dead steps keeps gm when it
+  // neither raises its best nor is long -- no key is read -- or when it is not
+  // long and its winner's step is live: that key alone is read, and only when
+  // some such lane would raise its best.  Otherwise the wave loads the eight
+  // keys, zeroes the dead steps' scores (they are still in registers) and takes
+  // the maximum again.
+  // HEAD: the opening group, whose step 0 is live for every lane of a0.
+  template <bool HEAD>
+  __device__ __forceinline__ uint64_t ends(const Lane& L, const uint32_t* K, uint64_t a0, uint64_t last,
+                                           uint32_t gm) const {
+    const uint64_t part = a0 & ~last;  // the lanes with dead steps
+    const uint64_t raise = __builtin_amdgcn_ballot_w64(zs_swe_raises(gm, L.thr)) & part;
+    uint64_t bad = __builtin_amdgcn_ballot_w64(zs_swe_long(gm, L.long_m)) & part;
+    if (raise) {
+      SW_STAT(5, 1);
+      const uint32_t wk = ((const zs_sw_lds_u32*)K)[zs_swe_winner_slot(gm)];
+      bad |= raise & ~__builtin_amdgcn_ballot_w64(zs_swe_winner_live(gm, wk, L.klim, HEAD));
+    }
+    return bad;
+  }
+  // ... and the piece for a group that fails: the maximum of the masked scores
+  template <bool HEAD>
+  __device__ __forceinline__ uint32_t remask(const Lane& L, const uint32_t* K, uint64_t a0, uint32_t* sc) const {
+    SW_STAT(HEAD ? 7 : 6, 1);
+    uint32_t key[8];
+#pragma unroll
+    for (uint32_t u = HEAD ? 1u : 0u; u < 8; u++) key[u] = K[7u - u];
+    sw_each<8>([&](auto uc) __attribute__((always_inline)) {
+      constexpr uint32_t u = decltype(uc)::value;
+      if (!HEAD || u) {
+        // (asm results go through locals: an asm operand cannot name a captured variable)
+        uint64_t gt;
+        const uint32_t ku = key[u], klim = L.klim;
+        asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(gt) : "v"(ku), "v"(klim));
+        uint32_t v;
+        const uint32_t su = sc[u];
+        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(v) : "v"(su), "s"(gt));
+        sc[u] = v;
+      }
+    });
+    return __builtin_amdgcn_inverse_ballot_w64(a0) ? sw_gmax<8>(sc) : 0u;
+  }
+
+  // U8: steps 1..8, the group that opens the walk, in the same way.  The head
+  // candidate (step 1, deflate.ts:1376) has its own liveness rule,
+  // key >= khead, and starts alive_m; the chain steps after it are live while
+  // their keys are, so the lanes alive after the group are the head's with a
+  // live step 8.
+  __device__ __forceinline__ void open8(Lane& L, const Grp& g) const {
+    const uint32_t k1 = g.K[7], k8 = g.K[0];
+    uint32_t sc[8];
+    sw_each<8>([&](auto uc) __attribute__((always_inline)) {
+      constexpr uint32_t u = decltype(uc)::value;
+      const uint2 ab = g.A[7u - u];
+      sc[u] = L.S.template step<u>(ab.x, ab.y, A7 ? 0u : g.C[7u - u]);
+    });
+    const bool a1 = L.own && k1 >= L.khead;
+    L.head = a1 ? 1u | ((L.p - (k1 & 0xffffu)) == ZS_MAX_DIST ? 0x8000u : 0u) : 0u;
+    const uint64_t a0 = __builtin_amdgcn_ballot_w64(a1);
+    const uint64_t last = __builtin_amdgcn_ballot_w64(k8 > L.klim) & a0;
+    uint32_t gm = a1 ? sw_gmax<8>(sc) : 0u;
+    uint64_t bad = 0;
+    if (last != a0) bad = ends<true>(L, g.K, a0, last, gm);
+    if (__builtin_expect(bad != 0, 0)) gm = remask<true>(L, g.K, a0, sc);
+    L.alive_m = last;
+    fold(L, gm, 1u, sc, 8u, c_of(g), g.K);
+  }
+
   // Steps [ta, tb] of a block (ta = 1 mod 4, tb = 0 mod 4, wave-uniform) in
   // groups of 8 (4 where the range or the snapshot cuts them).  A group in
   // which every live lane is still live at its last step runs unmasked with
@@ -851,39 +932,33 @@ struct SwWave {
       g.K = (const uint32_t*)(k8 + 8);
       SW_STAT(last_live == L.alive_m ? 1 : 2, 1);
       SW_STAT(4, 8u);
-      // The steps run unmasked.  A group in which a chain ends loads the steps' keys with the
-      // records and, behind the steps, zeroes step by step the scores of the lanes whose key is no
-      // longer live: group_masked's liveness rule.  (Two conditional pieces around one copy of the
-      // steps, the max tree and the fold -- not group_fast and group_masked joined: the join of the
-      // two forms cost register moves and flag tests in both, and the long branch stood twice.)
+      // The steps run unmasked, and a group in which a chain ends validates its maximum behind the
+      // max tree (ends: zs_sweep_ends.h); only a group that fails loads the steps' keys and zeroes the
+      // dead steps' scores, group_masked's liveness rule.  (One copy of the steps, the max tree and
+      // the fold with a conditional piece between them -- not group_fast and group_masked joined:
+      // the join of the two forms cost register moves and flag tests in both, and the long branch
+      // stood twice.)
       const uint64_t a0 = L.alive_m;  // the lanes live when the group begins
-      const bool ends = last_live != a0;
-      uint32_t sc[8], key[8];
-      if (ends) {  // (the keys' loads go out with the records')
-#pragma unroll
-        for (uint32_t u = 0; u < 8; u++) key[u] = g.K[7u - u];
-      }
+      uint32_t sc[8];
       sw_each<8>([&](auto uc) __attribute__((always_inline)) {
         constexpr uint32_t u = decltype(uc)::value;
         const uint2 ab = g.A[7u - u];
         sc[u] = L.S.template step<u>(ab.x, ab.y, A7 ? 0u : g.C[7u - u]);
+        // (the steps stay in the order of their records' loads, two to a load, and each pair waits for its own
+        // load alone: left to itself the scheduler began with a record of the last load but one.  LDS reads
+        // may cross the barrier (0x180), so the loads still go out ahead.)
+        if (u & 1u) __builtin_amdgcn_sched_barrier(0x180);
       });
-      if (ends) {
-        uint64_t lm = a0;
-        sw_each<8>([&](auto uc) __attribute__((always_inline)) {
-          constexpr uint32_t u = decltype(uc)::value;
-          uint64_t gt;
-          const uint32_t ku = key[u], klim = L.klim;
-          asm("v_cmp_gt_u32_e64 %0, %1, %2" : "=s"(gt) : "v"(ku), "v"(klim));
-          lm = gt & a0;
-          const uint64_t lmu = lm;
-          uint32_t v = sc[u];
-          asm("v_cndmask_b32_e64 %0, 0, %0, %1" : "+v"(v) : "s"(lmu));
-          sc[u] = v;
-        });
-        L.alive_m = lm;  // the lanes live at the group's last step
+      uint32_t gm = __builtin_amdgcn_inverse_ballot_w64(a0) ? sw_gmax<8>(sc) : 0u;
+      uint64_t bad = 0;
+      if (last_live != a0) {
+        bad = ends<false>(L, g.K, a0, last_live, gm);
+        L.alive_m = last_live;  // the lanes live at the group's last step
       }
-      const uint32_t gm = __builtin_amdgcn_inverse_ballot_w64(a0) ? sw_gmax<8>(sc) : 0u;
+      // (empty asm: the compiler does not learn that a group without an end has nothing to remask -- it would
+      // thread that path past the test, and the paths' join then costs nine register moves in each)
+      asm("" : "+s"(bad));
+      if (__builtin_expect(bad != 0, 0)) gm = remask<false>(L, g.K, a0, sc);
       fold(L, gm, t0, sc, 8u, c_of(g), g.K);
       t0 += 8u;
       g.A -= 8;
@@ -904,7 +979,8 @@ struct SwWave {
     const uint32_t base0 = Ring::base(cc, 0u, lane);
     const bool open8 = U8 || (budget_s >= 8u && budget >= 8u);  // wave-uniform
     if (open8) {
-      group_masked<8, true>(L, at<8>(base0, 1u), 1u);
+      if constexpr (U8) this->open8(L, at<8>(base0, 1u));
+      else group_masked<8, true>(L, at<8>(base0, 1u), 1u);
       if (budget_s == 8u) L.snap();
     } else if constexpr (!U8) {
       group_masked<1, true>(L, at<1>(base0, 1u), 1u);
