@@ -55,7 +55,9 @@ static void inflate_case(const char* name, const zs_route_opts& o, int wbits, co
 
 static void deflate_case(const char* name, const zs_route_opts& o, int level, const std::vector<uint32_t>& in_len) {
   zs_deflate_plan p;
-  zs_plan_deflate(o, level, (uint32_t)in_len.size(), in_len.data(), p);
+  zs_deflate_req r;
+  r.level = level;
+  zs_plan_deflate(r, o, true, true, (uint32_t)in_len.size(), in_len.data(), nullptr, 0, p);
   printf("case=%s n=%zu P=%llu B=%u members=%llu max_len=%u max_blk=%u pw=%d nwin=%zu pos=", name, in_len.size(),
          (unsigned long long)p.P, p.B, (unsigned long long)p.members, p.max_len, p.max_blk, p.pw, p.segs.size());
   for (size_t i = 0; i < p.pos.size() && i < 4; i++) printf("%s%llu", i ? "," : "", (unsigned long long)p.pos[i]);

@@ -37,10 +37,13 @@ static void run_case(const char* name, const zs_route_opts& o, int level, const 
   }
   const uint32_t k = (uint32_t)st.size();
   zs_deflate_plan p, plain, zeros, joined;
-  zs_plan_deflate(o, level, k, n.data(), p, L.data());
-  zs_plan_deflate(o, level, k, n.data(), plain);            // today's plan of the data alone
-  zs_plan_deflate(o, level, k, n.data(), zeros, zero.data());  // ... and with every dict_len 0
-  zs_plan_deflate(o, level, k, nv.data(), joined);          // a plain batch of nv-byte streams: the table sizes
+  zs_deflate_req r, rd;
+  r.level = rd.level = level;
+  rd.dict = true;
+  zs_plan_deflate(rd, o, true, true, k, n.data(), L.data(), 1, p);
+  zs_plan_deflate(r, o, true, true, k, n.data(), nullptr, 0, plain);        // today's plan of the data alone
+  zs_plan_deflate(rd, o, true, true, k, n.data(), zero.data(), 1, zeros);   // ... and with every dict_len 0
+  zs_plan_deflate(r, o, true, true, k, nv.data(), nullptr, 0, joined);      // a plain batch of nv-byte streams: the table sizes
   printf("case=%s n=%u zero_same=%d zero_J=%llu P=%llu P_joined=%llu B=%u B_plain=%u B_joined=%u members=%llu members_joined=%llu "
          "max_len=%u max_blk=%u max_blk_plain=%u J=%llu nwin=%zu nwin_joined=%zu tables_joined=%d",
          name, k, (int)same_plan(plain, zeros), (unsigned long long)zeros.J, (unsigned long long)p.P,

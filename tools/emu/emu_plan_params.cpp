@@ -13,6 +13,14 @@
 static const uint32_t kLens[] = {0, 1, 100, 16383, 65537, 65538, 200000};
 static const uint32_t kN = 7;
 
+// the plan of a batch without dictionaries at `level`, parameters q (both levels 1..3 options on)
+static void plan(const zs_route_opts& o, int level, const zs_deflate_params& q, zs_deflate_plan& p) {
+  zs_deflate_req r;
+  r.level = level;
+  r.q = q;
+  zs_plan_deflate(r, o, true, true, kN, kLens, nullptr, 0, p);
+}
+
 static void print_plan(const char* name, const zs_deflate_plan& p, uint32_t n) {
   uint64_t pos = 0, blk = 0, seg = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -34,12 +42,12 @@ int main() {
       zs_route_opts o;
       o.match_sweep = sweep != 0;
       zs_deflate_plan p;
-      zs_plan_deflate(o, level, kN, kLens, p);  // as every plain entry calls it
+      plan(o, level, zs_deflate_params(), p);  // as every plain entry calls it
       snprintf(name, sizeof name, "default/s%d/l%d", sweep, level);
       print_plan(name, p, kN);
 #ifndef EMU_PLAN_BEFORE
       zs_deflate_plan e;
-      zs_plan_deflate(o, level, kN, kLens, e, nullptr, zs_make_params(15, 8));  // ... and the params entries at 15 / 8
+      plan(o, level, zs_make_params(15, 8), e);  // ... and the params entries at 15 / 8
       snprintf(name, sizeof name, "explicit/s%d/l%d", sweep, level);
       print_plan(name, e, kN);
       printf("case=route/default/s%d/l%d sweep=%d\n", sweep, level, p.sweep);
@@ -51,7 +59,7 @@ int main() {
       const zs_deflate_params q = zs_make_params(wb, ml);
       zs_route_opts o;
       zs_deflate_plan p;
-      zs_plan_deflate(o, 6, kN, kLens, p, nullptr, q);
+      plan(o, 6, q, p);
       const zs_fast_plan fg = zs_plan_fast_params(q, true, kN), fs = zs_plan_fast_params(q, false, kN);
       int fits = 1;  // every stream's blocks fit the records the plan gives it
       for (uint32_t i = 0; i < kN; i++) fits &= kLens[i] / q.sym_end + 1 <= (i + 1 < kN ? p.blk[i + 1] : p.B) - p.blk[i];

@@ -17,7 +17,10 @@ int main() {
         // the workspace plan of three streams at the level the route asks for
         const uint32_t len[3] = {100, 70000, 0};
         zs_deflate_plan p;
-        zs_plan_deflate(o, sp.plan_level, 3, len, p);
+        zs_deflate_req r;
+        r.level = level;
+        r.strategy = strategy;
+        zs_plan_deflate(r, o, true, true, 3, len, nullptr, 0, p);
         printf("case=r%d/l%d/s%d stored=%d tally=%d filtered=%d fixed=%d wrap_strategy=%d plan_level=%d nwin=%zu pscr=%zu\n",
                rle_ref, level, strategy, sp.stored, sp.tally, sp.filtered, sp.fixed, sp.wrap_strategy, sp.plan_level,
                p.segs.size(), p.pscr_bytes);
@@ -31,7 +34,9 @@ int main() {
   // every stream's blocks fit the records the workspace plan gives it
   zs_route_opts o;
   zs_deflate_plan p;
-  zs_plan_deflate(o, 1, 7, lens, p);
+  zs_deflate_req r;
+  r.level = 1;
+  zs_plan_deflate(r, o, true, true, 7, lens, nullptr, 0, p);
   int fits = 1;
   for (uint32_t i = 0; i < 7; i++) fits &= lens[i] / ZS_SYM_END + 1 <= (i + 1 < 7 ? p.blk[i + 1] : p.B) - p.blk[i];
   printf("case=records fits=%d\n", fits);

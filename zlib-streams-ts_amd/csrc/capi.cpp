@@ -11,7 +11,6 @@
 #include <algorithm>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/zs_gpu.h"
@@ -72,10 +71,6 @@ struct BufT {
 using Buf = BufT<false>;
 using HostBuf = BufT<true>;
 
-const zs_level_cfg kLevels[10] = {{0, 0, 0, 0},     {4, 4, 8, 4},     {4, 5, 16, 8},     {4, 6, 32, 32},
-                                  {4, 4, 16, 16},   {8, 16, 32, 32},  {8, 16, 128, 128}, {8, 32, 128, 256},
-                                  {32, 128, 258, 1024}, {32, 258, 258, 4096}};  // deflate.ts:86-103
-
 }  // namespace
 
 void zs_set_last_error(const std::string& msg) { g_err = msg; }
@@ -90,7 +85,6 @@ struct zs_ctx {
   zs_deflate_plan dp;
   zs_inflate_plan ip;
   zs_seg_plan gp;
-  std::vector<zs_huff_chunk> hchunks;  // zs_k_huff_tally's (stream, block) list
   // workspace
   Buf meta, prevd, mres, syms, blocks, streams, codes, hdr, check, istate, pscr, ltabs, lres, llen, lstat;
   bool fast_group = true;    // L1..3: zs_k_fast (group-speculative) instead of zs_k_fast_serial
@@ -397,23 +391,6 @@ uint64_t zs_deflate_bound_dict(uint64_t n, int wbits, uint64_t dict_len) {  // d
 
 }  // extern "C"
 
-// Device metadata block: in_off | in_len | out_off | out_cap | pos_base | blk_base
-struct MetaLayout {
-  size_t in_off, in_len, out_off, out_cap, pos_base, blk_base, segs, bytes;
-  explicit MetaLayout(uint32_t n, uint32_t nwin = 0) {
-    size_t o = 0;
-    auto take = [&](size_t b) { size_t r = o; o = (o + b + 255) & ~size_t(255); return r; };
-    in_off = take(8ull * n);
-    in_len = take(4ull * n);
-    out_off = take(8ull * n);
-    out_cap = take(4ull * n);
-    pos_base = take(8ull * n);
-    blk_base = take(4ull * n);
-    segs = take(sizeof(zs_sweep_seg) * nwin);  // the sweep's windows (levels 4..9)
-    bytes = o;
-  }
-};
-
 // A batch's arrays: the data pointers (device memory) and the per-stream offsets,
 // lengths and capacities -- host arrays as an entry point receives them, device
 // arrays (in c->meta) as upload_batch returns them.
@@ -427,8 +404,8 @@ struct Batch {
   const uint32_t* out_cap;
 };
 
-// The preset dictionaries of a batch: the bytes in device memory, host arrays of
-// the members' offsets and lengths (length 0: none)
+// The preset dictionaries of a batch: the bytes (device memory; the caller's host memory on the
+// way into deflate_host), host arrays of the members' offsets and lengths (length 0: none)
 struct DictIn {
   const uint8_t* d_dict;
   const uint64_t* off;
@@ -439,7 +416,7 @@ struct DictIn {
 // (the output arrays may be null) and with fill(block) for whatever else it holds,
 // grows c->meta, uploads the block on st and returns the batch with device arrays.
 template <class Fill>
-static int upload_batch(zs_ctx* c, hipStream_t st, const MetaLayout& ml, size_t bytes, const Batch& h, Batch* d,
+static int upload_batch(zs_ctx* c, hipStream_t st, const zs_meta_layout& ml, size_t bytes, const Batch& h, Batch* d,
                         Fill fill) {
   c->hmeta.resize(bytes);
   c->last_n = h.n;
@@ -469,177 +446,192 @@ __global__ void zs_k_copy_check(const uint32_t* check, zs_stream* streams, int n
   if (s < n) streams[s].check = check[s];
 }
 
-// level 0: stored blocks (zs_k_stored), trailer checksums from zs_k_checksum
-static int deflate_stored_batch(zs_ctx* c, int wrap, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                                hipStream_t st) {
-  const uint32_t n = h.n;
-  uint64_t max_total = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const uint64_t t = (wrap == 0 ? 0 : wrap == 1 ? 6 : 18) + 5ull * (h.in_len[i] / ZS_STORED_CHUNK + 1) + h.in_len[i];
-    max_total = std::max(max_total, t);
-  }
-  const MetaLayout ml(n);
-  HIPCHK(c->check.ensure(4ull * n));
-  Batch b;
-  if (int r = upload_batch(c, st, ml, ml.bytes, h, &b, [](uint8_t*) {})) return r;
-  MARK("start");
-  if (wrap) {
-    zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, c->check.as<uint32_t>(), wrap == 1 ? 1 : 2);
-    MARK("checksum");
-  }
-  const dim3 g((unsigned)((max_total + 4095) / 4096), n);  // 256 threads x 16 bytes per workgroup
-  zs_k_stored<<<g, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, c->check.as<uint32_t>(), wrap,
-                                 d_status, d_out_len);
-  MARK("stored");
-  HIPCHK(hipGetLastError());
-  return ZS_OK;  // timing marks are collected when queried (no wait here)
+// zs_deflate_validate's findings, as the entries report them
+static int deflate_fail(zs_deflate_err e) {
+  static const char* const kMsg[ZS_DE_COUNT] = {
+      "",
+      "unsupported windowBits (use -15, 15 or 31)",
+      "invalid level",
+      "invalid strategy",
+      "invalid window bits",
+      "invalid memLevel",
+      "null dictionary arrays",
+      "null dictionary buffer",
+      "dictionaries are for deflate-raw (-15) and zlib (15) only",
+      "level 0 with a preset dictionary is not built",
+      "stream too long for a preset dictionary",
+      "level 0 with non-default windowBits / memLevel is not built",
+      "stream too long for Z_RLE",
+      "output offsets/capacities must be multiples of 4",
+      "a preset dictionary with a strategy or windowBits / memLevel is not built",
+  };
+  return fail(ZS_STREAM_ERROR, "%s", kMsg[e]);
 }
 
-// The deflate launch sequence of a batch b (levels 1..9, planned in c->dp) on
-// stream st: the match finding (levels 4..9) and the parse, or deflate_fast
-// (1..3); then trees, layout, emit, wrapper, statuses.  (A pipeline of chunks of
-// streams -- chunk j's parse .. emit on a side stream beside chunk j + 1's sweep
-// -- measured slower twice: DESIGN 5, tools/variants/r05_paths.patch.)
-// A batch with preset dictionaries (dd): b holds the JOINED streams (dictionary tail + data,
-// DESIGN 4.6), dd->data the caller's data (the check values are over the data alone); the
-// parse starts at dd->start[s], the zlib wrapper carries FDICT / DICTID.
-struct DeflDict {
-  const Batch* data;
-  const uint32_t *start, *did, *dadler;
-};
-// sp: the strategy's routes (zs_plan_strategy); d_chunks: zs_k_huff_tally's list (c->hchunks, uploaded).
-static int deflate_launch(zs_ctx* c, hipStream_t st, int level, int wrap, const zs_level_cfg& cfg, const Batch& b,
-                          const MetaLayout& ml, int32_t* d_status, uint32_t* d_out_len, const DeflDict* dd = nullptr,
-                          const zs_strategy_plan& sp = zs_strategy_plan(), const zs_huff_chunk* d_chunks = nullptr,
-                          const zs_deflate_params& q = zs_deflate_params()) {
-  const zs_deflate_plan& p = c->dp;
-  // non-default windowBits / memLevel (never with dd or a strategy): the *_par instances
-  const bool par = !q.is_default();
-  const zs_kpar kp = q.kpar();
-  const uint32_t n = b.n;
+// ---- the kernel instances of a deflate batch, by the plan's coordinates (zs_plan.h)
+typedef decltype(&zs_k_parse) parse_fn;
+typedef decltype(&zs_k_parse_dict) parse_dict_fn;
+typedef decltype(&zs_k_parse_par) parse_par_fn;
+typedef decltype(&zs_k_fast<2, true, false>) fast_fn;
+typedef decltype(&zs_k_fast_par<2, true, false>) fast_par_fn;
+static int pw_index(int pw) { return pw == 4 ? 2 : pw == 2 ? 1 : 0; }
+static int nice_index(int bucket) { return bucket == 8 ? 2 : bucket == 4 ? 1 : 0; }
+// the lazy parse (deflate_parse.hip): one, two or four waves per stream
+static parse_fn parse_kernel(zs_variant v, int pw) {
+  static const parse_fn k[2][3] = {{zs_k_parse, zs_k_parse_2w, zs_k_parse_4w},
+                                   {zs_k_parse_filt, zs_k_parse_2w_filt, zs_k_parse_4w_filt}};
+  return k[v == ZS_VAR_FILT][pw_index(pw)];
+}
+static parse_dict_fn parse_dict_kernel(int pw) {
+  static const parse_dict_fn k[3] = {zs_k_parse_dict, zs_k_parse_2w_dict, zs_k_parse_4w_dict};
+  return k[pw_index(pw)];
+}
+static parse_par_fn parse_par_kernel(int pw) {
+  static const parse_par_fn k[3] = {zs_k_parse_par, zs_k_parse_2w_par, zs_k_parse_4w_par};
+  return k[pw_index(pw)];
+}
+// levels 1..3: the group-speculative replay or the step-by-step one; [nice bucket][lane_order]
+#define ZS_FAST_INSTANCES(K, D) {{K<2, false, D>, K<2, true, D>}, {K<4, false, D>, K<4, true, D>}, {K<8, false, D>, K<8, true, D>}}
+static fast_fn fast_kernel(zs_sym_route route, bool dict, int nice_bucket, bool lane_order) {
+  static const fast_fn group[2][3][2] = {ZS_FAST_INSTANCES(zs_k_fast, false), ZS_FAST_INSTANCES(zs_k_fast, true)};
+  static const fast_fn serial[2] = {zs_k_fast_serial<false>, zs_k_fast_serial<true>};
+  return route == ZS_SYM_FAST_GROUP ? group[dict][nice_index(nice_bucket)][lane_order] : serial[dict];
+}
+static fast_par_fn fast_par_kernel(int nice_bucket, bool lane_order) {
+  static const fast_par_fn k[3][2] = ZS_FAST_INSTANCES(zs_k_fast_par, false);
+  return k[nice_index(nice_bucket)][lane_order];
+}
+#undef ZS_FAST_INSTANCES
+
+// The deflate launch sequence of a batch b (planned in p, its metadata uploaded) on
+// stream st: the stored blocks (level 0); else the match finding (levels 4..9) and
+// the parse, or deflate_fast (1..3), or a strategy's tally; then trees, layout, emit,
+// wrapper, statuses.  (A pipeline of chunks of streams -- chunk j's parse .. emit on a
+// side stream beside chunk j + 1's sweep -- measured slower twice: DESIGN 5,
+// tools/variants/r05_paths.patch.)
+// A batch with preset dictionaries (p.dict): b holds the JOINED streams (dictionary tail + data,
+// DESIGN 4.6), `data` the caller's data (the check values are over the data alone; else data is b);
+// the parse starts at the streams' parse starts, the zlib wrapper carries FDICT / DICTID.
+static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, const Batch& b, const Batch& data,
+                          int32_t* d_status, uint32_t* d_out_len) {
+  const zs_level_cfg& cfg = zs_level_cfgs[p.cfg];
+  const zs_meta_layout& ml = p.ml;
+  const int wrap = p.req.wrap, level = p.req.level;
+  const bool par = p.variant == ZS_VAR_PAR;  // non-default windowBits / memLevel: the *_par instances
+  const zs_kpar kp = p.req.q.kpar();
+  const uint32_t n = p.n;
   const uint8_t* dm = c->meta.as<uint8_t>();
   const uint64_t* d_pos = (const uint64_t*)(dm + ml.pos_base);
   const uint32_t* d_blk = (const uint32_t*)(dm + ml.blk_base);
   const zs_sweep_seg* d_segs = (const zs_sweep_seg*)(dm + ml.segs);
+  const uint32_t* d_start = p.dict ? (const uint32_t*)(dm + ml.start) : nullptr;
   zs_stream* d_st = c->streams.as<zs_stream>();
   zs_block* d_bk = c->blocks.as<zs_block>();
   uint32_t* syms = c->syms.as<uint32_t>();
   uint32_t* check = c->check.as<uint32_t>();
-  const int nthreads_s = 256, nblocks_s = (int)((n + 255) / 256);
+  const int nthreads_s = 256, nblocks_s = (int)p.g_streams;
   MARK("start");
+  if (p.stored) {
+    if (wrap) {
+      zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
+      MARK("checksum");
+    }
+    zs_k_stored<<<dim3(p.g_stored_x, n), 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, check, wrap,
+                                                       d_status, d_out_len);
+    MARK("stored");
+    return ZS_OK;
+  }
   if (wrap) {
-    const Batch& d = dd ? *dd->data : b;
-    zs_k_checksum<<<n, 64, 0, st>>>(d.in, d.in_off, d.in_len, check, wrap == 1 ? 1 : 2);
+    zs_k_checksum<<<n, 64, 0, st>>>(data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
     zs_k_copy_check<<<nblocks_s, nthreads_s, 0, st>>>(check, d_st, (int)n);
     MARK("checksum");
   }
-  if (sp.tally == ZS_TALLY_HUFF) {
-    zs_k_huff_tally<<<(uint32_t)c->hchunks.size(), 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, d_chunks, syms,
-                                                                 d_bk, d_st);
-    MARK("huff_tally");
-  } else if (sp.tally == ZS_TALLY_RLE) {
-    zs_k_rle_tally<<<n, 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st);
-    MARK("rle_tally");
-  } else if (level >= 4 && p.sweep) {
+  if (p.match == ZS_MATCH_SWEEP) {
     const uint32_t nw = (uint32_t)p.segs.size();
     // a window: counting sort by hash + lock-step sweep (deflate_sweep.hip)
-    (c->lane_order ? zs_k_bucket<true> : zs_k_bucket<false>)<<<nw, ZS_BK_THREADS, 0, st>>>(
+    (p.lane_order ? zs_k_bucket<true> : zs_k_bucket<false>)<<<nw, ZS_BK_THREADS, 0, st>>>(
         b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(), c->mres.as<uint2>());
     MARK("bucket");
     // (a chain budget that is not all groups of eight falls back to the general walk)
-    (zs_sweep_uniform8(cfg.chain) ? zs_k_sweep<true> : zs_k_sweep<false>)<<<nw, 1024, 0, st>>>(
+    (p.sweep_u8 ? zs_k_sweep<true> : zs_k_sweep<false>)<<<nw, 1024, 0, st>>>(
         b.in, b.in_off, b.in_len, d_pos, d_segs, c->prevd.as<uint16_t>(), c->mres.as<uint2>(), cfg.chain, cfg.nice);
     MARK("sweep");
-  } else if (level >= 4 && par) {
-    // the chain-walk kernels with the runtime window and hash (they follow prev[] links whatever the hash)
-    const dim3 g((p.max_len + 8191) / 8192, n);
-    (c->lane_order ? zs_k_prev_par<true> : zs_k_prev_par<false>)<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_pos,
-                                                                                   c->prevd.as<uint16_t>(), 0u, kp);
+  } else if (p.match == ZS_MATCH_CHAIN) {
+    // the chain-walk kernels: a cross-check of the sweep (option match_sweep = 0), or with the runtime
+    // window and hash (they follow prev[] links whatever the hash)
+    const dim3 g(p.g_match_x, n);
+    if (par) (p.lane_order ? zs_k_prev_par<true> : zs_k_prev_par<false>)<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_pos,
+                                                                                             c->prevd.as<uint16_t>(), 0u, kp);
+    else (p.lane_order ? zs_k_prev<true> : zs_k_prev<false>)<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_pos,
+                                                                                c->prevd.as<uint16_t>(), 0u);
     MARK("prev");
-    if (p.max_len) zs_k_match_par<<<g, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, c->prevd.as<uint16_t>(),
-                                                       c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u, kp);
-    MARK("match");
-  } else if (level >= 4) {
-    // cross-check (option match_sweep = 0): the chain-walk kernels for every stream
-    const dim3 g((p.max_len + 8191) / 8192, n);
-    (c->lane_order ? zs_k_prev<true> : zs_k_prev<false>)<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_pos,
-                                                                           c->prevd.as<uint16_t>(), 0u);
-    MARK("prev");
-    if (p.max_len) zs_k_match<<<g, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, c->prevd.as<uint16_t>(),
-                                                   c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u);
+    if (p.max_len && par) zs_k_match_par<<<g, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, c->prevd.as<uint16_t>(),
+                                                              c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u, kp);
+    else if (p.max_len) zs_k_match<<<g, 1024, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, c->prevd.as<uint16_t>(),
+                                                        c->mres.as<uint2>(), cfg.chain, cfg.nice, 0u);
     MARK("match");
   }
-  if (sp.tally != ZS_TALLY_LEVEL) {
-    // (the tally kernels wrote the symbols and the block records)
-  } else if (level >= 4) {
-    const int pw = p.pw;  // waves per stream of the lazy parse (deflate_parse.hip)
-    if (par) {
-      auto parse = pw == 4 ? zs_k_parse_4w_par : pw == 2 ? zs_k_parse_2w_par : zs_k_parse_par;
-      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
-                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, kp);
-    } else if (dd) {
-      auto parse = pw == 4 ? zs_k_parse_4w_dict : pw == 2 ? zs_k_parse_2w_dict : zs_k_parse_dict;
-      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
-                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, dd->start);
-    } else {
-      auto parse = sp.filtered ? (pw == 4 ? zs_k_parse_4w_filt : pw == 2 ? zs_k_parse_2w_filt : zs_k_parse_filt)
-                               : (pw == 4 ? zs_k_parse_4w : pw == 2 ? zs_k_parse_2w : zs_k_parse);
-      parse<<<n, 64 * pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms, d_bk, d_st,
-                                   c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
-    }
-    MARK("parse");
-  } else if (par) {
-    // levels 1..3: the instance and its LDS by the tables' sizes (zs_plan_fast_params)
-    const zs_fast_plan f = zs_plan_fast_params(q, c->fast_group, n);
-    uint16_t* gh = f.route == ZS_FAST_SERIAL_GHEAD ? c->ghead.as<uint16_t>() : nullptr;
-    if (f.route == ZS_FAST_GROUP) {
-      auto fast = c->lane_order ? (cfg.nice <= 8 ? zs_k_fast_par<2, true, false> : cfg.nice <= 16 ? zs_k_fast_par<4, true, false> : zs_k_fast_par<8, true, false>)
-                                : (cfg.nice <= 8 ? zs_k_fast_par<2, false, false> : cfg.nice <= 16 ? zs_k_fast_par<4, false, false> : zs_k_fast_par<8, false, false>);
-      HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
-      fast<<<n, 64, f.lds_bytes, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
-                                       cfg.nice, nullptr, kp);
-    } else {
-      auto fast = gh ? zs_k_fast_serial_par<false, true> : zs_k_fast_serial_par<false, false>;
-      HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
-      fast<<<n, 64, f.lds_bytes, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
-                                       cfg.nice, nullptr, kp, gh);
-    }
-    MARK("fast");
-  } else {
-    const int fast_smem = 2 * 32768 * 2 + 32768;  // head[] + prev[] (u16 x 32 K each) + the 32 KiB input ring
-    // levels 1..3: the group-speculative replay (default) or the step-by-step one (fast_group = 0);
-    // the DICT instances for a batch with dictionaries
-    auto pick = [&](auto D) {
-      constexpr bool DICT = decltype(D)::value;
-      return !c->fast_group ? zs_k_fast_serial<DICT>
-             : c->lane_order ? (cfg.nice <= 8 ? zs_k_fast<2, true, DICT> : cfg.nice <= 16 ? zs_k_fast<4, true, DICT> : zs_k_fast<8, true, DICT>)
-                             : (cfg.nice <= 8 ? zs_k_fast<2, false, DICT> : cfg.nice <= 16 ? zs_k_fast<4, false, DICT> : zs_k_fast<8, false, DICT>);
-    };
-    auto fast = dd ? pick(std::true_type{}) : pick(std::false_type{});
-    HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, fast_smem));
-    fast<<<n, 64, fast_smem, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
-                                   cfg.nice, dd ? dd->start : nullptr);
-    MARK("fast");
+  switch (p.sym) {
+    case ZS_SYM_HUFF:
+      zs_k_huff_tally<<<(uint32_t)p.chunks.size(), 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk,
+                                                                 (const zs_huff_chunk*)(dm + ml.chunks), syms, d_bk, d_st);
+      MARK("huff_tally");
+      break;
+    case ZS_SYM_RLE:
+      zs_k_rle_tally<<<n, 256, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st);
+      MARK("rle_tally");
+      break;
+    case ZS_SYM_PARSE:  // the lazy parse (deflate_parse.hip), p.pw waves per stream
+      if (par)
+        parse_par_kernel(p.pw)<<<n, 64 * p.pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms,
+                                                        d_bk, d_st, c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, kp);
+      else if (p.dict)
+        parse_dict_kernel(p.pw)<<<n, 64 * p.pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(), syms,
+                                                         d_bk, d_st, c->pscr.as<uint32_t>(), cfg.good, cfg.lazy, d_start);
+      else
+        parse_kernel(p.variant, p.pw)<<<n, 64 * p.pw, 0, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, c->mres.as<uint2>(),
+                                                               syms, d_bk, d_st, c->pscr.as<uint32_t>(), cfg.good, cfg.lazy);
+      MARK("parse");
+      break;
+    default:  // levels 1..3 (deflate_fast.hip): the instance and its LDS by the tables' sizes (zs_plan_fast_params)
+      if (!par) {
+        const fast_fn fast = fast_kernel(p.sym, p.dict, p.nice_bucket, p.lane_order);
+        HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fast_lds));
+        fast<<<n, 64, p.fast_lds, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                        cfg.nice, d_start);
+      } else if (p.sym == ZS_SYM_FAST_GROUP) {
+        const fast_par_fn fast = fast_par_kernel(p.nice_bucket, p.lane_order);
+        HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fast_lds));
+        fast<<<n, 64, p.fast_lds, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                        cfg.nice, nullptr, kp);
+      } else {
+        uint16_t* gh = p.sym == ZS_SYM_FAST_SERIAL_GHEAD ? c->ghead.as<uint16_t>() : nullptr;
+        const auto fast = gh ? zs_k_fast_serial_par<false, true> : zs_k_fast_serial_par<false, false>;
+        HIPCHK(hipFuncSetAttribute((const void*)fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fast_lds));
+        fast<<<n, 64, p.fast_lds, st>>>(b.in, b.in_off, b.in_len, d_pos, d_blk, syms, d_bk, d_st, cfg.chain, cfg.lazy,
+                                        cfg.nice, nullptr, kp, gh);
+      }
+      MARK("fast");
   }
   (par ? zs_k_trees_par : zs_k_trees)<<<dim3(p.max_blk, n), 64, 0, st>>>(
       b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st, c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n,
-      sp.fixed ? 1 : 0);
+      p.fixed ? 1 : 0);
   MARK("trees");
-  if (dd) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
-                                                             dd->start);
+  if (p.dict) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
+                                                                 d_start);
   else zs_k_layout<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n);
   MARK("layout");
   zs_k_emit<<<dim3(p.max_blk, n), 256, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
                                                 c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), b.out, b.out_off, wrap);
   MARK("emit");
-  if (wrap && dd)
-    zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, dd->start,
-                                                     dd->did, dd->dadler);
+  if (wrap && p.dict)
+    zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, d_start,
+                                                     (const uint32_t*)(dm + ml.did), c->dadler.as<uint32_t>());
   else if (wrap && par)
     zs_k_wrap_par<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n,
-                                                    sp.wrap_strategy, q.w_bits);
+                                                    p.wrap_strategy, p.req.q.w_bits);
   else if (wrap)
-    zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, sp.wrap_strategy);
+    zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, p.wrap_strategy);
   zs_k_finish<<<nblocks_s, nthreads_s, 0, st>>>(d_st, d_status, d_out_len, (int)n);
   MARK("finish");
   return ZS_OK;
@@ -655,136 +647,101 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
   out[s] = status[s] != ZS_Z_STREAM_END ? 0u : wrap ? check[s] : 1u;
 }
 
-// The device compress.  out_cap[i] is the stream's capacity as the caller set
+// The device compress: validate, plan, ensure, upload, launch, check values.
+// out_cap[i] is the stream's capacity as the caller set
 // it (Z_BUF_ERROR past it, exactly); the kernels store whole dwords, so the
 // stream's region must reach out_off[i] + out_cap[i] rounded up to 4.
 // `caller_regions` (the public device entries): the regions are the caller's
 // buffers, so capacities must be multiples of 4; the host entries stage in
 // regions of the capacities rounded up and pass the exact capacities.
-// `dict` (the _dict entries): the streams' preset dictionaries; a batch with none
+// `dict` (requests with req.dict, else null): the streams' preset dictionaries; a batch with none
 // of them set is the plain batch.
-static int deflate_device(zs_ctx* c, int level, int wbits, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict = nullptr,
-                          int strategy = ZS_DEFAULT_STRATEGY, const zs_deflate_params& q = zs_deflate_params()) {
+static int deflate_device(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
+                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION, deflate.ts:268-270
-  int wrap;
-  if (wbits == -15) wrap = 0;
-  else if (wbits == 15) wrap = 1;
-  else if (wbits == 31) wrap = 2;
-  else return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15 or 31)");
-  if (level < 0 || level > 9) return fail(ZS_STREAM_ERROR, "invalid level");  // deflate.ts:281-294
-  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
-  const zs_strategy_plan sp = zs_plan_strategy(c->o, level, strategy);
-  // The streams' dictionaries (dict: the _dict entries), the distinct ones found once.
-  // deflateSetDictionary refuses gzip (wrap == 2, deflate.ts:373); level 0 is not built.
-  zs_dict_set& ds = c->dset;
-  ds.any = false;
-  if (dict && h.n) {
-    if (!dict->off || !dict->len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
-    zs_dict_distinct(h.n, dict->off, dict->len, ds);
-    if (ds.any && !dict->d_dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
-    if (ds.any && wrap == 2) return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
-    if (ds.any && level == 0) return fail(ZS_STREAM_ERROR, "level 0 with a preset dictionary is not built");
-    for (uint32_t i = 0; ds.any && i < h.n; i++)
-      if (dict->len[i] && h.in_len[i] > 0xffffffffu - ZS_W_SIZE)
-        return fail(ZS_STREAM_ERROR, "stream too long for a preset dictionary");
-  }
-  const bool hasdict = ds.any;
+  zs_deflate_call a;
+  a.n = h.n;
+  a.in_len = h.in_len;
+  a.out_off = h.out_off;
+  a.out_cap = h.out_cap;
+  a.caller_regions = caller_regions;
+  a.dict_arrays = dict && dict->off && dict->len;
+  a.dict_buf = dict && dict->d_dict;
+  a.dict_len = a.dict_arrays ? dict->len : nullptr;
+  if (const zs_deflate_err e = zs_deflate_validate(req, c->o, a)) return deflate_fail(e);
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
   HIPCHK(hipSetDevice(c->device));
   const uint32_t n = h.n;
   if (n == 0) return ZS_OK;
-  for (uint32_t i = 0; i < n; i++)
-    if ((h.out_off[i] & 3) || (caller_regions && (h.out_cap[i] & 3)))
-      return fail(ZS_STREAM_ERROR, "output offsets/capacities must be multiples of 4");
-  if (level == 0 && !q.is_default())
-    return fail(ZS_STREAM_ERROR, "level 0 with non-default windowBits / memLevel is not built");
-  if (level == 0) {
-    const int r = deflate_stored_batch(c, wrap, h, d_status, d_out_len, st);
-    if (r == ZS_OK && d_check) {
-      zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), wrap, d_check, (int)n);
-      HIPCHK(hipGetLastError());
-    }
-    return r;
-  }
-  // host-side layout: workspace bases (and the sweep's windows, levels 4..9)
+  // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
+  // metadata block; the streams' dictionaries, the distinct ones found once
+  zs_dict_set& ds = c->dset;
+  ds.any = false;
+  if (req.dict) zs_dict_distinct(n, dict->off, dict->len, ds);
   zs_deflate_plan& p = c->dp;
-  zs_plan_deflate(c->o, sp.plan_level, n, h.in_len, p, hasdict ? dict->len : nullptr, q);
-  if (!q.is_default() && level <= 3) HIPCHK(c->ghead.ensure(zs_plan_fast_params(q, c->fast_group, n).ghead_bytes));
-  const MetaLayout ml(n, (uint32_t)p.segs.size());
-  if (sp.tally == ZS_TALLY_HUFF) zs_plan_huff_chunks(n, h.in_len, c->hchunks);
-  else c->hchunks.clear();
-  if (sp.tally == ZS_TALLY_RLE)  // (zs_k_rle_tally's 32-bit positions run 4,416 past a stream's end)
-    for (uint32_t i = 0; i < n; i++)
-      if (h.in_len[i] > 0xffff0000u) return fail(ZS_STREAM_ERROR, "stream too long for Z_RLE");
-  // behind the batch's metadata: the streams' dictionary offsets, lengths, ids and parse starts, the
-  // joined streams' offsets and lengths, the distinct dictionaries' offsets and lengths
-  const size_t nu = hasdict ? ds.uoff.size() : 0;
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
-               m_start = m_did + up256(4ull * n), m_joff = m_start + up256(4ull * n),
-               m_jlen = m_joff + up256(8ull * n), m_uoff = m_jlen + up256(4ull * n),
-               m_ulen = m_uoff + up256(8ull * nu), m_chunks = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes,
-               m_end = m_chunks + up256(sizeof(zs_huff_chunk) * c->hchunks.size());  // zs_k_huff_tally's list last
-  if (hasdict) {
-    HIPCHK(c->djoin.ensure(p.J + 16));
-    HIPCHK(c->dadler.ensure(4ull * nu));
-  }
-  if (sp.tally == ZS_TALLY_LEVEL) {  // (the tallies search no matches)
-    HIPCHK(c->prevd.ensure(p.prevd_bytes));
-    HIPCHK(c->mres.ensure(p.mres_bytes));
-  }
-  HIPCHK(c->syms.ensure(p.syms_bytes));
-  HIPCHK(c->pscr.ensure(p.pscr_bytes));
-  HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
-  HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)n));
-  HIPCHK(c->codes.ensure(p.codes_bytes));
-  HIPCHK(c->hdr.ensure(p.hdr_bytes));
+  zs_plan_deflate(req, c->o, c->fast_group, c->lane_order, n, h.in_len, ds.any ? dict->len : nullptr,
+                  (uint32_t)ds.uoff.size(), p);
+  const zs_meta_layout& ml = p.ml;
   HIPCHK(c->check.ensure(4ull * n));
+  if (!p.stored) {
+    HIPCHK(c->ghead.ensure(p.ghead_bytes));
+    if (p.dict) {
+      HIPCHK(c->djoin.ensure(p.J + 16));
+      HIPCHK(c->dadler.ensure(4ull * p.ndict));
+    }
+    if (p.sym != ZS_SYM_HUFF && p.sym != ZS_SYM_RLE) {  // (the tallies search no matches)
+      HIPCHK(c->prevd.ensure(p.prevd_bytes));
+      HIPCHK(c->mres.ensure(p.mres_bytes));
+    }
+    HIPCHK(c->syms.ensure(p.syms_bytes));
+    HIPCHK(c->pscr.ensure(p.pscr_bytes));
+    HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
+    HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)n));
+    HIPCHK(c->codes.ensure(p.codes_bytes));
+    HIPCHK(c->hdr.ensure(p.hdr_bytes));
+  }
   Batch b;
-  int r = upload_batch(c, st, ml, m_end, h, &b, [&](uint8_t* hm) {
+  int r = upload_batch(c, st, ml, ml.bytes, h, &b, [&](uint8_t* hm) {
+    if (p.stored) return;
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * n);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * n);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
-    if (!c->hchunks.empty()) memcpy(hm + m_chunks, c->hchunks.data(), sizeof(zs_huff_chunk) * c->hchunks.size());
-    if (!hasdict) return;
-    memcpy(hm + m_doff, dict->off, 8ull * n);
-    memcpy(hm + m_dlen, dict->len, 4ull * n);
-    memcpy(hm + m_did, ds.id.data(), 4ull * n);
-    memcpy(hm + m_start, p.start.data(), 4ull * n);
-    memcpy(hm + m_joff, p.joff.data(), 8ull * n);
-    uint32_t* jl = (uint32_t*)(hm + m_jlen);
+    if (!p.chunks.empty()) memcpy(hm + ml.chunks, p.chunks.data(), sizeof(zs_huff_chunk) * p.chunks.size());
+    if (!p.dict) return;
+    memcpy(hm + ml.doff, dict->off, 8ull * n);
+    memcpy(hm + ml.dlen, dict->len, 4ull * n);
+    memcpy(hm + ml.did, ds.id.data(), 4ull * n);
+    memcpy(hm + ml.start, p.start.data(), 4ull * n);
+    memcpy(hm + ml.joff, p.joff.data(), 8ull * n);
+    uint32_t* jl = (uint32_t*)(hm + ml.jlen);
     for (uint32_t i = 0; i < n; i++) jl[i] = p.start[i] + h.in_len[i];
-    memcpy(hm + m_uoff, ds.uoff.data(), 8ull * nu);
-    memcpy(hm + m_ulen, ds.ulen.data(), 4ull * nu);
+    memcpy(hm + ml.uoff, ds.uoff.data(), 8ull * p.ndict);
+    memcpy(hm + ml.ulen, ds.ulen.data(), 4ull * p.ndict);
   });
-  if (r == ZS_OK && hasdict) {
+  if (r != ZS_OK) return r;
+  if (p.dict) {
+    // the joined streams take the data's place (and the DICTID of the zlib wrapper is worked out)
     const uint8_t* dm = c->meta.as<uint8_t>();
-    const uint32_t* d_start = (const uint32_t*)(dm + m_start);
-    const uint64_t* d_joff = (const uint64_t*)(dm + m_joff);
+    const uint64_t* d_joff = (const uint64_t*)(dm + ml.joff);
     MARK("start");
     // DICTID (zlib): the adler32 of each distinct dictionary, once
-    if (wrap == 1)
-      zs_k_checksum<<<(uint32_t)nu, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + m_uoff),
-                                                 (const uint32_t*)(dm + m_ulen), c->dadler.as<uint32_t>(), 1);
-    // the joined streams: 4 KiB per workgroup
-    zs_k_dict_join<<<dim3(std::max(1u, (uint32_t)(((uint64_t)p.max_len + 4095) / 4096)), n), 256, 0, st>>>(
-        b.in, b.in_off, b.in_len, dict->d_dict, (const uint64_t*)(dm + m_doff), (const uint32_t*)(dm + m_dlen),
-        d_start, c->djoin.as<uint8_t>(), d_joff);
+    if (req.wrap == 1)
+      zs_k_checksum<<<p.ndict, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + ml.uoff),
+                                            (const uint32_t*)(dm + ml.ulen), c->dadler.as<uint32_t>(), 1);
+    zs_k_dict_join<<<dim3(p.g_join_x, n), 256, 0, st>>>(
+        b.in, b.in_off, b.in_len, dict->d_dict, (const uint64_t*)(dm + ml.doff), (const uint32_t*)(dm + ml.dlen),
+        (const uint32_t*)(dm + ml.start), c->djoin.as<uint8_t>(), d_joff);
     MARK("dict_join");
     HIPCHK(hipGetLastError());
-    const Batch bj = {n, c->djoin.as<uint8_t>(), d_joff, (const uint32_t*)(dm + m_jlen), b.out, b.out_off, b.out_cap};
-    const DeflDict dd = {&b, d_start, (const uint32_t*)(dm + m_did), c->dadler.as<uint32_t>()};
-    r = deflate_launch(c, st, level, wrap, kLevels[level], bj, ml, d_status, d_out_len, &dd);
-  } else if (r == ZS_OK) {
-    r = deflate_launch(c, st, level, wrap, kLevels[level], b, ml, d_status, d_out_len, nullptr, sp,
-                       (const zs_huff_chunk*)(c->meta.as<uint8_t>() + m_chunks), q);
+    const Batch bj = {n, c->djoin.as<uint8_t>(), d_joff, (const uint32_t*)(dm + ml.jlen), b.out, b.out_off, b.out_cap};
+    r = deflate_launch(c, st, p, bj, b, d_status, d_out_len);
+  } else {
+    r = deflate_launch(c, st, p, b, b, d_status, d_out_len);
   }
   if (r != ZS_OK) return r;
   if (d_check)
-    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), wrap, d_check, (int)n);
-  MARK("end");
+    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), req.wrap, d_check, (int)n);
+  if (!p.stored) MARK("end");  // (a stored batch ends at its "stored" mark)
   HIPCHK(hipGetLastError());
   return ZS_OK;  // timing marks are collected when queried (no wait here)
 }
@@ -793,8 +750,10 @@ extern "C" int zs_deflate_batch_device_ex(zs_ctx* c, int level, int wbits, uint3
                                           const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
                                           const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
                                           uint32_t* d_out_len, uint32_t* d_check, void* hip_stream) {
-  return deflate_device(c, level, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len,
-                        d_check, hip_stream, true);
+  zs_deflate_req req;
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, &req);
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, nullptr);
 }
 
 extern "C" int zs_deflate_batch_device(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
@@ -993,20 +952,34 @@ static int host_batch(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64_t* 
   return rc;
 }
 
-extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                                const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                int32_t* status, uint32_t* out_len) {
-  return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, nullptr);
-}
-
-// The host compress: zs_deflate_batch_ex (strategy 0) and zs_deflate_batch_strategy
-static int deflate_host(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
-                        const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
-                        const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check,
-                        const zs_deflate_params& q = zs_deflate_params()) {
+// The host compress of every zs_deflate_batch* entry.  dict (requests with req.dict, else null):
+// the caller's dictionary bytes, offsets and lengths, all host memory.
+static int deflate_host(zs_ctx* c, const zs_deflate_req& req, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                        int32_t* status, uint32_t* out_len, uint32_t* check, const DictIn* dict) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  zs_deflate_call call;
+  call.n = n;
+  call.dict_arrays = dict && dict->off && dict->len;
+  call.dict_buf = dict && dict->d_dict;
+  call.dict_len = call.dict_arrays ? dict->len : nullptr;
+  if (const zs_deflate_err e = zs_deflate_validate_host(req, call)) return deflate_fail(e);
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
+  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them);
+  // a batch without any is the plain batch
+  zs_deflate_req rq = req;
+  rq.dict = zs_deflate_any_dict(req, call);
+  std::vector<uint64_t> upos, poff;
+  if (rq.dict) {
+    zs_dict_set ds;
+    zs_dict_distinct(n, dict->off, dict->len, ds);
+    const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict->len, upos, poff);
+    HIPCHK(c->d_dict.ensure(dbytes + 16));
+    std::vector<uint8_t> pack(dbytes);
+    zs_dict_pack(ds, upos, dict->d_dict, pack.data());
+    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
+  }
   // device regions: the caller's capacity rounded up to whole words (the kernels store dwords);
   // the caller's exact capacities are the Z_BUF_ERROR limits
   std::vector<uint32_t> ocap(n);
@@ -1015,11 +988,12 @@ static int deflate_host(zs_ctx* c, int level, int strategy, int wbits, uint32_t 
   return host_batch(c, n, in, in_off, in_len, ocap, 3, res, 1, out, out_off,
                     [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
                         uint32_t** dr) {
-                      return deflate_device(c, level, wbits,
+                      const DictIn di = rq.dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
+                      return deflate_device(c, rq,
                                             {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
                                              ooff, out_cap + a},
-                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false, nullptr,
-                                            strategy, q);
+                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false,
+                                            rq.dict ? &di : nullptr);
                     });  // out_len is 0 for failed streams
 }
 
@@ -1027,8 +1001,15 @@ extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, 
                                    const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                    const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
                                    uint32_t* out_len, uint32_t* check) {
-  return deflate_host(c, level, ZS_DEFAULT_STRATEGY, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len,
-                      check);
+  zs_deflate_req req;
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, &req);
+  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
+}
+
+extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                int32_t* status, uint32_t* out_len) {
+  return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, nullptr);
 }
 
 // ---- compression strategies (deflateInit2_'s strategy: validation deflate.ts:289-290, dispatch :923-931)
@@ -1037,51 +1018,41 @@ extern "C" int zs_deflate_batch_strategy_device(zs_ctx* c, int level, int strate
                                                 uint8_t* d_out, const uint64_t* out_off, const uint32_t* out_cap,
                                                 int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check,
                                                 void* hip_stream) {
-  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
-  return deflate_device(c, level, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len,
-                        d_check, hip_stream, true, nullptr, strategy);
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req(level, wbits, strategy, false, &req)) return deflate_fail(e);
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, nullptr);
 }
 
 extern "C" int zs_deflate_batch_strategy(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                          const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
                                          uint32_t* out_len, uint32_t* check) {
-  if (strategy < 0 || strategy > ZS_FIXED) return fail(ZS_STREAM_ERROR, "invalid strategy");  // deflate.ts:289-290
-  return deflate_host(c, level, strategy, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check);
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req(level, wbits, strategy, false, &req)) return deflate_fail(e);
+  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
 }
 
-// ---- windowBits and memLevel (deflateInit2_, deflate.ts:253-343; validation :281-294)
-// wbits -> the plain entries' code (-15 / 15 / 31) and the parameters; an error before the context is looked at
-static int params_split(int wbits, int mem_level, int* plain_wbits, zs_deflate_params* q) {
-  int wrap;
-  const int wb = zs_wbits_split(wbits, &wrap);
-  if (!wb) return fail(ZS_STREAM_ERROR, "invalid window bits");
-  if (mem_level < 1 || mem_level > 9) return fail(ZS_STREAM_ERROR, "invalid memLevel");
-  *q = zs_make_params(wb, mem_level);
-  *plain_wbits = wrap == 0 ? -15 : wrap == 1 ? 15 : 31;
-  return ZS_OK;
-}
+// ---- windowBits and memLevel (deflateInit2_, deflate.ts:253-343; validation :281-294): a fault of
+// theirs is reported before the context is looked at
 extern "C" int zs_deflate_batch_params_device(zs_ctx* c, int level, int wbits, int mem_level, uint32_t n,
                                               const uint8_t* d_in, const uint64_t* in_off, const uint32_t* in_len,
                                               uint8_t* d_out, const uint64_t* out_off, const uint32_t* out_cap,
                                               int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check,
                                               void* hip_stream) {
-  int pw;
-  zs_deflate_params q;
-  if (int r = params_split(wbits, mem_level, &pw, &q)) return r;
-  return deflate_device(c, level, pw, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, nullptr, ZS_DEFAULT_STRATEGY, q);
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req_params(level, wbits, mem_level, &req)) return deflate_fail(e);
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, nullptr);
 }
 
 extern "C" int zs_deflate_batch_params(zs_ctx* c, int level, int wbits, int mem_level, uint32_t n, const uint8_t* in,
                                        const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                        const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
                                        uint32_t* out_len, uint32_t* check) {
-  int pw;
-  zs_deflate_params q;
-  if (int r = params_split(wbits, mem_level, &pw, &q)) return r;
-  return deflate_host(c, level, ZS_DEFAULT_STRATEGY, pw, n, in, in_off, in_len, out, out_off, out_cap, status, out_len,
-                      check, q);
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req_params(level, wbits, mem_level, &req)) return deflate_fail(e);
+  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
 }
 
 // ---- preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778)
@@ -1091,9 +1062,11 @@ extern "C" int zs_deflate_batch_dict_device(zs_ctx* c, int level, int wbits, uin
                                             uint32_t* d_out_len, uint32_t* d_check, void* hip_stream,
                                             const uint8_t* d_dict, const uint64_t* dict_off,
                                             const uint32_t* dict_len) {
+  zs_deflate_req req;
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, true, &req);
   const DictIn di = {d_dict, dict_off, dict_len};
-  return deflate_device(c, level, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len,
-                        d_check, hip_stream, true, &di);
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, &di);
 }
 
 extern "C" int zs_deflate_batch_dict(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
@@ -1101,38 +1074,10 @@ extern "C" int zs_deflate_batch_dict(zs_ctx* c, int level, int wbits, uint32_t n
                                      const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
                                      uint32_t* out_len, uint32_t* check, const uint8_t* dict,
                                      const uint64_t* dict_off, const uint32_t* dict_len) {
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  if (!dict_off || !dict_len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them)
-  zs_dict_set ds;
-  zs_dict_distinct(n, dict_off, dict_len, ds);
-  if (!ds.any)
-    return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check);
-  if (!dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
-  if (wbits == 31) return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
-  if (level == 0) return fail(ZS_STREAM_ERROR, "level 0 with a preset dictionary is not built");
-  std::vector<uint64_t> upos, poff;
-  const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict_len, upos, poff);
-  HIPCHK(c->d_dict.ensure(dbytes + 16));
-  {
-    std::vector<uint8_t> pack(dbytes);
-    zs_dict_pack(ds, upos, dict, pack.data());
-    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
-  }
-  std::vector<uint32_t> ocap(n);
-  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
-  uint32_t* res[3] = {(uint32_t*)status, out_len, check};
-  return host_batch(c, n, in, in_off, in_len, ocap, 3, res, 1, out, out_off,
-                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
-                        uint32_t** dr) {
-                      const DictIn di = {c->d_dict.as<uint8_t>(), poff.data() + a, dict_len + a};
-                      return deflate_device(c, level, wbits,
-                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
-                                             ooff, out_cap + a},
-                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false, &di);
-                    });
+  zs_deflate_req req;
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, true, &req);
+  const DictIn di = {dict, dict_off, dict_len};  // (host memory here)
+  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, &di);
 }
 
 static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
@@ -1141,7 +1086,7 @@ static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, 
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  const MetaLayout ml(n);  // (the seeds behind it)
+  const zs_meta_layout ml(n);  // (the seeds behind it)
   Batch b;
   const int r = upload_batch(c, st, ml, ml.bytes + (seeds ? 4ull * n : 0), {n, d_in, in_off, in_len, nullptr, nullptr, nullptr},
                              &b, [&](uint8_t* hm) { if (seeds) memcpy(hm + ml.bytes, seeds, 4ull * n); });
@@ -1288,7 +1233,7 @@ extern "C" uint64_t zs_debug_fetch(zs_ctx* c, int what, uint32_t s, void* dst, u
   uint32_t blk_base = 0, n = 0;
   // meta layout of the last call: recompute offsets from the host copy
   const size_t nstreams = c->last_n;
-  MetaLayout m2((uint32_t)nstreams);
+  zs_meta_layout m2((uint32_t)nstreams);
   const uint8_t* hm = c->hmeta.data();
   pos_base = ((const uint64_t*)(hm + m2.pos_base))[s];
   blk_base = ((const uint32_t*)(hm + m2.blk_base))[s];
@@ -1568,7 +1513,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   const bool fastp = c->o.inflate_fast;
   zs_inflate_plan& p = c->ip;
   if (fastp) zs_plan_inflate(c->o, wbits, n, h.in_len, h.out_cap, p, hasdict ? dict->len : nullptr);
-  const MetaLayout ml(n);
+  const zs_meta_layout ml(n);
   // behind the batch's metadata: the members' dictionary offsets, lengths and ids, the distinct ones' too
   const size_t nu = hasdict ? ds.uoff.size() : 0;
   auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "zs_common.h"
+#include "zs_sweep_ring.h"  // zs_sweep_uniform8
 
 #if defined(__HIPCC__)
 #define ZS_PLAN_FN static __host__ __device__ inline
@@ -441,7 +442,168 @@ static inline zs_fast_plan zs_plan_fast_params(const zs_deflate_params& q, bool 
   return f;
 }
 
-// The workspace layout of a deflate batch (levels 1..9).  With the sweep (levels
+// ---- a deflate request: what an entry point asks for, whichever of the eight it is
+struct zs_deflate_req {
+  int level = 6;  // 0..9 (-1 has become 6, deflate.ts:268-270); anything else is refused
+  int wrap = 0;   // 0 deflate-raw, 1 zlib, 2 gzip; -1: a windowBits the entry does not take
+  int strategy = ZS_STRAT_DEFAULT;
+  zs_deflate_params q;
+  bool dict = false;  // the call carries preset dictionaries (a batch with every length 0 is the plain batch)
+};
+enum zs_deflate_err {
+  ZS_DE_OK = 0,
+  ZS_DE_WBITS,         // "unsupported windowBits (use -15, 15 or 31)"
+  ZS_DE_LEVEL,         // "invalid level"
+  ZS_DE_STRATEGY,      // "invalid strategy"
+  ZS_DE_WINDOW_BITS,   // "invalid window bits"
+  ZS_DE_MEM_LEVEL,     // "invalid memLevel"
+  ZS_DE_DICT_ARRAYS,   // "null dictionary arrays"
+  ZS_DE_DICT_BUFFER,   // "null dictionary buffer"
+  ZS_DE_DICT_GZIP,     // "dictionaries are for deflate-raw (-15) and zlib (15) only"
+  ZS_DE_DICT_LEVEL0,   // "level 0 with a preset dictionary is not built"
+  ZS_DE_DICT_LONG,     // "stream too long for a preset dictionary"
+  ZS_DE_PARAMS_LEVEL0, // "level 0 with non-default windowBits / memLevel is not built"
+  ZS_DE_RLE_LONG,      // "stream too long for Z_RLE"
+  ZS_DE_ALIGN,         // "output offsets/capacities must be multiples of 4"
+  ZS_DE_DICT_COMBINED, // internal (no public entry makes it): dictionaries with a strategy or parameters
+  ZS_DE_COUNT
+};
+// The request of the plain, _strategy and _dict entries: wbits -15 / 15 / 31.  Only a strategy out of
+// range fails here, before the context is looked at (deflate.ts:289-290).
+static inline zs_deflate_err zs_deflate_make_req(int level, int wbits, int strategy, bool dict, zs_deflate_req* r) {
+  r->level = level == -1 ? 6 : level;
+  r->wrap = wbits == -15 ? 0 : wbits == 15 ? 1 : wbits == 31 ? 2 : -1;
+  r->strategy = strategy;
+  r->q = zs_deflate_params();
+  r->dict = dict;
+  return strategy < 0 || strategy > ZS_STRAT_FIXED ? ZS_DE_STRATEGY : ZS_DE_OK;
+}
+// ... and of the _params entries: deflateInit2_'s windowBits and memLevel (validation deflate.ts:281-294)
+static inline zs_deflate_err zs_deflate_make_req_params(int level, int wbits, int mem_level, zs_deflate_req* r) {
+  int wrap;
+  const int wb = zs_wbits_split(wbits, &wrap);
+  if (!wb) return ZS_DE_WINDOW_BITS;
+  if (mem_level < 1 || mem_level > 9) return ZS_DE_MEM_LEVEL;
+  r->level = level == -1 ? 6 : level;
+  r->wrap = wrap;
+  r->strategy = ZS_STRAT_DEFAULT;
+  r->q = zs_make_params(wb, mem_level);
+  r->dict = false;
+  return ZS_DE_OK;
+}
+// The arrays of a call, as far as validation reads them
+struct zs_deflate_call {
+  uint32_t n = 0;
+  const uint32_t* in_len = nullptr;
+  const uint64_t* out_off = nullptr;
+  const uint32_t* out_cap = nullptr;
+  bool caller_regions = false;  // the device entries: the capacities must be multiples of 4 too
+  bool dict_arrays = false, dict_buf = false;  // the dictionary offsets and lengths / bytes are given
+  const uint32_t* dict_len = nullptr;          // (with dict_arrays)
+};
+static inline bool zs_deflate_any_dict(const zs_deflate_req& r, const zs_deflate_call& a) {
+  for (uint32_t i = 0; r.dict && a.dict_len && i < a.n; i++)
+    if (a.dict_len[i]) return true;
+  return false;
+}
+// What a host entry checks of the whole batch before it stages anything; an empty batch is done
+// after it, whatever its level.  The chunks then pass zs_deflate_validate one by one.
+static inline zs_deflate_err zs_deflate_validate_host(const zs_deflate_req& r, const zs_deflate_call& a) {
+  if (r.dict && !a.dict_arrays) return ZS_DE_DICT_ARRAYS;
+  if (a.n == 0 || !zs_deflate_any_dict(r, a)) return ZS_DE_OK;
+  if (!a.dict_buf) return ZS_DE_DICT_BUFFER;
+  if (r.wrap == 2) return ZS_DE_DICT_GZIP;  // deflateSetDictionary refuses gzip (deflate.ts:373)
+  if (r.level == 0) return ZS_DE_DICT_LEVEL0;
+  return ZS_DE_OK;
+}
+// The first fault of a device batch, in the order the entries have always reported them.
+static inline zs_deflate_err zs_deflate_validate(const zs_deflate_req& r, const zs_route_opts& o,
+                                                 const zs_deflate_call& a) {
+  if (r.wrap < 0) return ZS_DE_WBITS;
+  if (r.level < 0 || r.level > 9) return ZS_DE_LEVEL;  // deflate.ts:281-294
+  if (r.strategy < 0 || r.strategy > ZS_STRAT_FIXED) return ZS_DE_STRATEGY;
+  if (r.dict && a.n) {
+    if (!a.dict_arrays) return ZS_DE_DICT_ARRAYS;
+    if (zs_deflate_any_dict(r, a)) {
+      if (!a.dict_buf) return ZS_DE_DICT_BUFFER;
+      if (r.wrap == 2) return ZS_DE_DICT_GZIP;
+      if (r.level == 0) return ZS_DE_DICT_LEVEL0;
+      if (r.strategy != ZS_STRAT_DEFAULT || !r.q.is_default()) return ZS_DE_DICT_COMBINED;
+      for (uint32_t i = 0; i < a.n; i++)
+        if (a.dict_len[i] && a.in_len[i] > 0xffffffffu - ZS_W_SIZE) return ZS_DE_DICT_LONG;
+    }
+  }
+  if (a.n == 0) return ZS_DE_OK;
+  for (uint32_t i = 0; i < a.n; i++)
+    if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_DE_ALIGN;
+  if (r.level == 0) return r.q.is_default() ? ZS_DE_OK : ZS_DE_PARAMS_LEVEL0;
+  if (zs_plan_strategy(o, r.level, r.strategy).tally == ZS_TALLY_RLE)  // (zs_k_rle_tally's 32-bit positions run 4,416 past a stream's end)
+    for (uint32_t i = 0; i < a.n; i++)
+      if (a.in_len[i] > 0xffff0000u) return ZS_DE_RLE_LONG;
+  return ZS_DE_OK;
+}
+
+// Device metadata block: in_off | in_len | out_off | out_cap | pos_base | blk_base | the sweep's
+// windows; for a deflate batch with preset dictionaries the streams' dictionary offsets, lengths,
+// ids and parse starts, the joined streams' offsets and lengths and the distinct dictionaries'
+// offsets and lengths (no room without); zs_k_huff_tally's list last.  Every section starts on
+// a multiple of 256 bytes.
+struct zs_meta_layout {
+  size_t in_off, in_len, out_off, out_cap, pos_base, blk_base, segs;
+  size_t doff, dlen, did, start, joff, jlen, uoff, ulen;
+  size_t chunks, bytes;
+  explicit zs_meta_layout(uint32_t n = 0, uint32_t nwin = 0, bool dict = false, uint32_t ndict = 0, size_t nchunks = 0) {
+    size_t o = 0;
+    auto take = [&](size_t b) { size_t r = o; o = (o + b + 255) & ~size_t(255); return r; };
+    const size_t nd = dict ? n : 0, nu = dict ? ndict : 0;
+    in_off = take(8ull * n);
+    in_len = take(4ull * n);
+    out_off = take(8ull * n);
+    out_cap = take(4ull * n);
+    pos_base = take(8ull * n);
+    blk_base = take(4ull * n);
+    segs = take(sizeof(zs_sweep_seg) * nwin);  // the sweep's windows (levels 4..9)
+    doff = take(8ull * nd);
+    dlen = take(4ull * nd);
+    did = take(4ull * nd);
+    start = take(4ull * nd);
+    joff = take(8ull * nd);
+    jlen = take(4ull * nd);
+    uoff = take(8ull * nu);
+    ulen = take(4ull * nu);
+    chunks = take(sizeof(zs_huff_chunk) * nchunks);
+    bytes = o;
+  }
+};
+
+// deflate.ts:86-103: good_length, max_lazy, nice_length, max_chain of levels 0..9
+static const zs_level_cfg zs_level_cfgs[10] = {{0, 0, 0, 0},     {4, 4, 8, 4},     {4, 5, 16, 8},     {4, 6, 32, 32},
+                                               {4, 4, 16, 16},   {8, 16, 32, 32},  {8, 16, 128, 128}, {8, 32, 128, 256},
+                                               {32, 128, 258, 1024}, {32, 258, 258, 4096}};
+
+// Who finds the matches of a batch, who tallies its symbols, and which build of those kernels
+enum zs_match_route {
+  ZS_MATCH_NONE = 0,  // nobody: the tallies, and levels 1..3 (deflate_fast finds its own)
+  ZS_MATCH_SWEEP,     // zs_k_bucket + zs_k_sweep over the windows
+  ZS_MATCH_CHAIN      // the chain-walk kernels zs_k_prev + zs_k_match
+};
+enum zs_sym_route {
+  ZS_SYM_HUFF = 0,          // zs_k_huff_tally
+  ZS_SYM_RLE,               // zs_k_rle_tally
+  ZS_SYM_PARSE,             // the lazy parse, levels 4..9
+  ZS_SYM_FAST_GROUP,        // levels 1..3: zs_k_fast, the group-speculative replay
+  ZS_SYM_FAST_SERIAL,       // ... the step-by-step one
+  ZS_SYM_FAST_SERIAL_GHEAD  // ... with head[] in the global workspace
+};
+enum zs_variant {
+  ZS_VAR_PLAIN = 0,
+  ZS_VAR_PAR,   // the *_par instances: non-default windowBits / memLevel
+  ZS_VAR_DICT,  // the _dict / DICT instances: joined streams
+  ZS_VAR_FILT   // the lazy parse's _filt instances (Z_FILTERED at levels 4..9)
+};
+
+// Everything the host layer decides about a deflate batch: the workspace layout, the routes, the
+// kernel instances' coordinates, the grids and the metadata block.  With the sweep (levels
 // 4..9, option match_sweep), every stream is cut into WINDOWS of at most 65,535
 // inserted positions: a stream of up to 65,537 bytes is one; a longer one has a
 // first window owning positions [0, 65520) and then windows owning 32,752
@@ -463,32 +625,85 @@ struct zs_deflate_plan {
   std::vector<uint64_t> joff;
   uint64_t J = 0;
   size_t prevd_bytes = 0, mres_bytes = 0, syms_bytes = 0, pscr_bytes = 0, codes_bytes = 0, hdr_bytes = 0;
+  // ---- the launch
+  zs_deflate_req req;   // what was asked (level and wrap go to the wrapper kernels, q to the *_par ones)
+  uint32_t n = 0;
+  bool stored = false;  // level 0: zs_k_stored alone, whatever the strategy; nothing below is set
+  zs_match_route match = ZS_MATCH_NONE;
+  zs_sym_route sym = ZS_SYM_PARSE;
+  zs_variant variant = ZS_VAR_PLAIN;
+  int cfg = 0;          // index into zs_level_cfgs
+  int nice_bucket = 2;  // zs_k_fast<NW, ..>: 2, 4 or 8 by the level's nice_length
+  bool lane_order = true;  // the ORD instances of zs_k_bucket, zs_k_prev and zs_k_fast
+  bool sweep_u8 = false;   // zs_k_sweep<true> (zs_sweep_uniform8 of the level's chain)
+  bool fixed = false;      // zs_k_trees takes the static trees' length (Z_FIXED)
+  int wrap_strategy = 0;   // zs_k_wrap's strategy argument
+  bool dict = false;       // the streams are joined streams; the dictionary sections of ml are laid out
+  uint32_t ndict = 0;      // ... and this many distinct dictionaries
+  // grids: per stream in workgroups of 256 lanes; zs_k_match's, zs_k_dict_join's and zs_k_stored's x
+  // (y: the streams); the others are n, segs.size(), chunks.size() and (max_blk, n)
+  uint32_t g_streams = 0, g_match_x = 0, g_join_x = 0, g_stored_x = 0;
+  uint32_t fast_lds = 0;     // dynamic LDS of the levels 1..3 kernel
+  uint64_t ghead_bytes = 0;  // its global head[] workspace (ZS_SYM_FAST_SERIAL_GHEAD)
+  std::vector<zs_huff_chunk> chunks;  // zs_k_huff_tally's (stream, block) list
+  zs_meta_layout ml;
 };
 
 // The part of a preset dictionary that enters the window (deflate.ts:383-392: its last w_size bytes)
 ZS_PLAN_FN uint32_t zs_dict_tail(uint32_t dict_len) { return dict_len < ZS_W_SIZE ? dict_len : ZS_W_SIZE; }
 
-// dict_len: the streams' preset-dictionary lengths, or null for a batch without
-// dictionaries.  A stream with one is planned as its JOINED stream -- the
+// r: a request that passed zs_deflate_validate.  fast_group, lane_order: the context's options of
+// those names.  dict_len: the streams' preset-dictionary lengths (r.dict), or null for a batch
+// without dictionaries, and ndict the number of distinct ones (zs_dict_distinct).  A stream with a
+// dictionary is planned as its JOINED stream -- the
 // dictionary's tail of L' = zs_dict_tail bytes, then the data: the
 // per-position tables, the windows and max_len follow nv = L' + n, the windows'
 // own positions start at L' (p.start), the block records follow n.
-// q: deflateInit2_'s windowBits / memLevel.  Non-default ones take the chain-walk kernels at
+// r.q: deflateInit2_'s windowBits / memLevel.  Non-default ones take the chain-walk kernels at
 // levels 4..9 (zs_k_prev + zs_k_match follow prev[] links whatever the hash; the sweep's
 // signatures rest on the 15-bit hash, deflate_sweep.hip:24-27), and the block records follow
 // sym_end: a stream of n bytes closes at most n / sym_end + 1 blocks.
-static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n, const uint32_t* in_len,
-                                   zs_deflate_plan& p, const uint32_t* dict_len = nullptr,
-                                   const zs_deflate_params& q = zs_deflate_params()) {
-  const bool sweep = level >= 4 && o.match_sweep && q.is_default();
+static inline void zs_plan_deflate(const zs_deflate_req& r, const zs_route_opts& o, bool fast_group, bool lane_order,
+                                   uint32_t n, const uint32_t* in_len, const uint32_t* dict_len, uint32_t ndict,
+                                   zs_deflate_plan& p) {
+  const zs_strategy_plan sp = zs_plan_strategy(o, r.level, r.strategy);
+  const zs_deflate_params& q = r.q;
+  if (!r.dict) dict_len = nullptr;
+  p.req = r;
+  p.n = n;
+  p.stored = sp.stored;
+  p.dict = dict_len != nullptr;
+  p.ndict = p.dict ? ndict : 0;
+  p.g_streams = (n + 255) / 256;
+  p.segs.clear();
+  p.win0.clear();
+  p.chunks.clear();
+  p.start.clear();
+  p.joff.clear();
+  p.members = p.J = 0;
+  p.sweep = false;
+  p.pscr_bytes = 0;
+  p.fast_lds = 0;
+  p.ghead_bytes = 0;
+  if (sp.stored) {
+    // level 0: 256 threads x 16 bytes per workgroup over the longest stream's stored blocks and wrapper
+    uint64_t max_total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint64_t t = (r.wrap == 0 ? 0 : r.wrap == 1 ? 6 : 18) + 5ull * (in_len[i] / ZS_STORED_CHUNK + 1) + in_len[i];
+      max_total = std::max(max_total, t);
+    }
+    p.g_stored_x = (uint32_t)((max_total + 4095) / 4096);
+    p.ml = zs_meta_layout(n);
+    return;
+  }
+  const int level = sp.plan_level;  // (1 for the tallies: no windows, no parse scratch)
+  const bool par = !q.is_default();
+  const bool sweep = level >= 4 && o.match_sweep && !par;
   p.sweep = sweep;
   p.pos.resize(n);
   p.blk.resize(n);
   p.P = 0;
   p.B = p.max_len = p.max_blk = 0;
-  p.start.clear();
-  p.joff.clear();
-  p.J = 0;
   if (dict_len) {
     p.start.resize(n);
     p.joff.resize(n);
@@ -509,9 +724,6 @@ static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n
     p.max_len = std::max(p.max_len, (uint32_t)std::min<uint64_t>(nv, 0xffffffffull));
     p.max_blk = std::max(p.max_blk, nb);
   }
-  p.segs.clear();
-  p.win0.clear();
-  p.members = 0;
   if (sweep) {
     uint64_t mb = (p.P + 7) & ~7ull;
     p.win0.resize(n + 1);
@@ -539,6 +751,33 @@ static inline void zs_plan_deflate(const zs_route_opts& o, int level, uint32_t n
   p.pscr_bytes = level >= 4 ? 4ull * zs_parse_seg_words(p.pw) * (p.P / zs_parse_seg(p.pw) + n + 1) : 0;
   p.codes_bytes = 4ull * (ZS_L_CODES + ZS_D_CODES) * p.B;
   p.hdr_bytes = 4ull * ZS_HDR_WORDS * p.B;
+  // the routes and the instances
+  const zs_level_cfg& cfg = zs_level_cfgs[r.level];
+  p.cfg = r.level;
+  p.variant = par ? ZS_VAR_PAR : p.dict ? ZS_VAR_DICT : sp.filtered ? ZS_VAR_FILT : ZS_VAR_PLAIN;
+  p.fixed = sp.fixed;
+  p.wrap_strategy = sp.wrap_strategy;
+  p.lane_order = lane_order;
+  p.nice_bucket = cfg.nice <= 8 ? 2 : cfg.nice <= 16 ? 4 : 8;
+  p.sweep_u8 = zs_sweep_uniform8(cfg.chain) != 0;
+  p.g_match_x = (p.max_len + 8191) / 8192;
+  p.g_join_x = std::max(1u, (uint32_t)(((uint64_t)p.max_len + 4095) / 4096));  // the joined streams: 4 KiB per workgroup
+  if (sp.tally != ZS_TALLY_LEVEL) {
+    p.match = ZS_MATCH_NONE;
+    p.sym = sp.tally == ZS_TALLY_HUFF ? ZS_SYM_HUFF : ZS_SYM_RLE;
+    if (sp.tally == ZS_TALLY_HUFF) zs_plan_huff_chunks(n, in_len, p.chunks);
+  } else if (level >= 4) {
+    p.match = sweep ? ZS_MATCH_SWEEP : ZS_MATCH_CHAIN;
+    p.sym = ZS_SYM_PARSE;
+  } else {
+    // levels 1..3: the instance and its LDS by the tables' sizes; the default parameters fit both kernels
+    const zs_fast_plan f = zs_plan_fast_params(q, fast_group, n);
+    p.match = ZS_MATCH_NONE;
+    p.sym = f.route == ZS_FAST_GROUP ? ZS_SYM_FAST_GROUP : f.route == ZS_FAST_SERIAL ? ZS_SYM_FAST_SERIAL : ZS_SYM_FAST_SERIAL_GHEAD;
+    p.fast_lds = f.lds_bytes;
+    p.ghead_bytes = f.ghead_bytes;
+  }
+  p.ml = zs_meta_layout(n, (uint32_t)p.segs.size(), p.dict, p.ndict, p.chunks.size());
 }
 
 #endif
