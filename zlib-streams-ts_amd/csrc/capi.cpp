@@ -1209,7 +1209,9 @@ extern "C" void zs_corpus(int kind, uint32_t first, uint32_t n_streams, uint32_t
 // Copies an intermediate array of stream `s` of the last deflate batch to host
 // memory: what = 0 prevd (u16/position, 0xffff = no link), 1 match table (u32x2/position),
 // 2 symbols (u32 each; count = streams[s].nsym), 3 blocks (zs_block each),
-// 4 stream record (zs_stream).  Returns the number of bytes copied.
+// 4 stream record (zs_stream), 7 the sweep route's members of the stream's first window
+// (u16 each, window-relative: the inserted positions sorted by (hash, position)).
+// Returns the number of bytes copied.
 extern "C" uint64_t zs_debug_fetch(zs_ctx* c, int what, uint32_t s, void* dst, uint64_t cap) {
   if (c && what >= 16 && what <= 21) {
     // the segmented decode's records of the last inflate batch: 16 counters (-, members
@@ -1251,6 +1253,16 @@ extern "C" uint64_t zs_debug_fetch(zs_ctx* c, int what, uint32_t s, void* dst, u
     case 4: src = c->streams.as<zs_stream>() + s; bytes = sizeof(zs_stream); break;
     case 5: src = c->codes.as<uint32_t>() + (size_t)blk_base * (ZS_L_CODES + ZS_D_CODES); bytes = 4ull * (ZS_L_CODES + ZS_D_CODES) * st.nblk; break;
     case 6: src = c->hdr.as<uint32_t>() + (size_t)blk_base * ZS_HDR_WORDS; bytes = 4ull * ZS_HDR_WORDS * st.nblk; break;
+    case 7: {
+      const zs_deflate_plan& p = c->dp;
+      if (p.match != ZS_MATCH_SWEEP || (size_t)s + 1 >= p.win0.size()) return 0;
+      const zs_sweep_seg& g = p.segs[p.win0[s]];
+      const uint32_t m = n > 2 ? std::min(n - 2, g.ohi) : 0u;  // zs_k_bucket's member count
+      if (2ull * (g.mb + m) > c->prevd.cap) return 0;
+      src = c->prevd.as<uint16_t>() + g.mb;
+      bytes = 2ull * m;
+      break;
+    }
     default: return 0;
   }
   bytes = std::min(bytes, cap);

@@ -79,7 +79,9 @@ static __device__ __forceinline__ uint32_t sw_hash(uint32_t w) {  // SURVEY A1, 
 // 64 per instruction, claiming slots with ONE ds_add_rtn_u32 per lane: gfx950
 // applies same-address LDS atomics of one wave instruction in increasing lane
 // order (zs_selftest checks it, including the 16-bit half form used here), so
-// equal hashes get slots in position order.  Pass 1 hashes input words held
+// equal hashes get slots in position order; the other waves store the
+// positions to their slots, a chunk's stores grouped by slot so that an
+// instruction writes few lines.  Pass 1 hashes input words held
 // in registers, pass 2 a 4 KiB LDS stage of the input.  Results of the
 // positions that are not inserted (the last two) are zeroed.
 #define ZS_BK_WPT (16384u / ZS_BK_THREADS)  // scan: count words per thread
@@ -98,6 +100,15 @@ extern "C" int zs_bucket_stats(unsigned long long* out) {
 #endif
 #define ZS_BK_INFLIGHT 8  // pass 2: wave instructions (x 64 positions) per wait
 #define ZS_BK_CHUNK 2048u  // pass 2: positions per chunk (input bytes staged in LDS, slots queued)
+#define ZS_BK_KEYS 256u    // pass 2: a chunk's member stores are grouped by slot >> 8 (four 128-byte lines)
+#define ZS_BK_HELPERS (ZS_BK_THREADS - 64u)                                    // pass 2: the threads of waves 1..7
+#define ZS_BK_EPT ((ZS_BK_CHUNK + ZS_BK_HELPERS - 1u) / ZS_BK_HELPERS)  // ... and a chunk's queue entries per thread
+
+// Workgroup barrier that waits for this wave's LDS operations only: the claim
+// wave's loads of the next chunk and the helpers' member stores stay in flight.
+static __device__ __forceinline__ void bk_lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
 
 template <bool ORD>  // false: claims ranked by zs_wave_match instead of the LDS atomics' lane order
 __global__ __launch_bounds__(ZS_BK_THREADS) void zs_k_bucket(const uint8_t* __restrict__ in,
@@ -107,7 +118,9 @@ __global__ __launch_bounds__(ZS_BK_THREADS) void zs_k_bucket(const uint8_t* __re
                                                             const zs_sweep_seg* __restrict__ segs,
                                                             uint16_t* __restrict__ members, uint2* __restrict__ mres) {
   __shared__ uint32_t cnt[16384];
-  __shared__ uint32_t part[ZS_BK_THREADS];
+  // the scan's partial sums; in pass 2 its words are the key counters [0, KEYS) and the chunk's sorted order
+  __shared__ uint32_t part[ZS_BK_KEYS + ZS_BK_CHUNK / 2];
+  static_assert(ZS_BK_KEYS + ZS_BK_CHUNK / 2 >= ZS_BK_THREADS, "part[] holds the scan's partial sums");
   __shared__ uint32_t stg[ZS_BK_CHUNK / 4 + 2];
   __shared__ uint16_t q[2][ZS_BK_CHUNK];
   const zs_sweep_seg G = segs[blockIdx.x];
@@ -191,13 +204,26 @@ __global__ __launch_bounds__(ZS_BK_THREADS) void zs_k_bucket(const uint8_t* __re
   BK_MARK(1);
   // pass 2: wave 0 claims the slots in position order, ZS_BK_CHUNK positions
   // at a time, into an LDS queue (slot of chunk position o at q[c & 1][o]);
-  // waves 1..3 scatter the previous chunk's positions to their slots while it
-  // claims the next one (stores from one wave alone take longer than the
-  // claims: 64 scattered 2-byte stores per instruction).  The input goes
-  // through LDS a chunk at a time (stg), the next chunk's loads in flight in
-  // registers while this chunk's positions are claimed, ZS_BK_INFLIGHT
-  // instructions per wait.
+  // waves 1..7 store the previous chunk's positions to their slots while it
+  // claims the next one.  The member stores bound this pass by their number,
+  // one write request per 128-byte line an instruction touches (a request per
+  // member when stored in position order), so the helpers first group the
+  // chunk's entries by slot >> 8 -- a counting sort of the queue indices over
+  // ZS_BK_KEYS keys, in any order within a key -- and store them in that
+  // order: neighbouring lanes then write neighbouring slots.  A chunk is PH
+  // steps with a barrier each: the claim wave claims 64 ZS_BK_INFLIGHT
+  // positions per step, the helpers count the keys, scan them (wave 1), place
+  // the indices, store.  The input goes through LDS a chunk at a time (stg),
+  // the next chunk's loads in flight in registers while this chunk's positions
+  // are claimed, ZS_BK_INFLIGHT instructions per wait.
   const uint32_t wave = tid >> 6, lane = tid & 63u;
+  constexpr uint32_t PH = ZS_BK_CHUNK / (64 * ZS_BK_INFLIGHT);
+  static_assert(PH == 4, "a chunk is four steps: count, scan, place, store");
+  uint32_t* const kc = part;                                          // key counters, then the keys' next places
+  uint16_t* const srt = reinterpret_cast<uint16_t*>(part + ZS_BK_KEYS);  // the chunk's queue indices grouped by key
+  if (tid < ZS_BK_KEYS) kc[tid] = 0;
+  uint32_t sl[ZS_BK_EPT];  // a helper's entries of the chunk: queue index ht + HELPERS k, its slot
+  const uint32_t ht = tid - 64u;
   constexpr uint32_t CW = ZS_BK_CHUNK / 4 / 64;  // words per lane per chunk
   uint32_t nxt[CW + 1];
   auto fetch = [&](uint32_t c0) {
@@ -219,18 +245,25 @@ __global__ __launch_bounds__(ZS_BK_THREADS) void zs_k_bucket(const uint8_t* __re
   const uint32_t nch = (m + ZS_BK_CHUNK - 1) / ZS_BK_CHUNK;
   for (uint32_t c = 0; c <= nch; c++) {
     const uint32_t c0 = c * ZS_BK_CHUNK;
-    if (wave == 0 && c < nch) {
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
+    const uint32_t c1 = min(m, c0 + ZS_BK_CHUNK);
+    const uint32_t b0 = c0 - ZS_BK_CHUNK, cnt1 = min(m, c0) - b0;  // (helpers, c > 0: the previous chunk)
+    const uint16_t* const qp = q[(c - 1) & 1u];
 #pragma unroll
-      for (uint32_t i = 0; i <= CW; i++)
-        if (64 * i + lane < ZS_BK_CHUNK / 4 + 2) stg[64 * i + lane] = nxt[i];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      if (c0 + ZS_BK_CHUNK < m) fetch(c0 + ZS_BK_CHUNK);
-      const uint32_t c1 = min(m, c0 + ZS_BK_CHUNK);
+    for (uint32_t ph = 0; ph < PH; ph++) {
+    const uint32_t g0 = c0 + 64 * ZS_BK_INFLIGHT * ph;
+    if (wave == 0 && c < nch) {
+      if (ph == 0) {
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (uint32_t i = 0; i <= CW; i++)
+          if (64 * i + lane < ZS_BK_CHUNK / 4 + 2) stg[64 * i + lane] = nxt[i];
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+        if (c0 + ZS_BK_CHUNK < m) fetch(c0 + ZS_BK_CHUNK);
+      }
       uint16_t* const qc = q[c & 1u];
-      for (uint32_t g0 = c0; g0 < c1; g0 += 64 * ZS_BK_INFLIGHT) {
+      if (g0 < c1) {
         uint32_t a[ZS_BK_INFLIGHT], v[ZS_BK_INFLIGHT], sh[ZS_BK_INFLIGHT], e[ZS_BK_INFLIGHT], hh[ZS_BK_INFLIGHT];
 #pragma unroll
         for (int j = 0; j < ZS_BK_INFLIGHT; j++) {
@@ -281,11 +314,45 @@ __global__ __launch_bounds__(ZS_BK_THREADS) void zs_k_bucket(const uint8_t* __re
         }
       }
     } else if (wave != 0 && c > 0) {
-      const uint32_t b0 = c0 - ZS_BK_CHUNK, cnt1 = min(m, c0) - b0;
-      const uint16_t* const qp = q[(c - 1) & 1u];
-      for (uint32_t o = tid - 64u; o < cnt1; o += ZS_BK_THREADS - 64u) mem[qp[o]] = (uint16_t)(b0 + o);
+      if (ph == 0) {  // the keys' counts
+#pragma unroll
+        for (uint32_t k = 0; k < ZS_BK_EPT; k++) {
+          const uint32_t o = ht + ZS_BK_HELPERS * k;
+          sl[k] = o < cnt1 ? (uint32_t)qp[o] : 0u;
+          if (o < cnt1) atomicAdd(&kc[sl[k] >> 8], 1u);
+        }
+      } else if (ph == 1) {  // exclusive scan of the counts: the keys' first places (one wave)
+        if (wave == 1) {
+          constexpr uint32_t KPL = ZS_BK_KEYS / 64u;
+          uint32_t v[KPL], t = 0;
+#pragma unroll
+          for (uint32_t j = 0; j < KPL; j++) { v[j] = kc[KPL * lane + j]; t += v[j]; }
+          uint32_t x = t;
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d, 64);
+            if (lane >= (uint32_t)d) x += y;
+          }
+          uint32_t run = x - t;
+#pragma unroll
+          for (uint32_t j = 0; j < KPL; j++) { kc[KPL * lane + j] = run; run += v[j]; }
+        }
+      } else if (ph == 2) {  // places: any order within a key
+#pragma unroll
+        for (uint32_t k = 0; k < ZS_BK_EPT; k++) {
+          const uint32_t o = ht + ZS_BK_HELPERS * k;
+          if (o < cnt1) srt[atomicAdd(&kc[sl[k] >> 8], 1u)] = (uint16_t)o;
+        }
+      } else {  // the stores, and the counters cleared for the next chunk
+        for (uint32_t i = ht; i < cnt1; i += ZS_BK_HELPERS) {
+          const uint32_t o = srt[i];
+          mem[qp[o]] = (uint16_t)(b0 + o);
+        }
+        if (ht < ZS_BK_KEYS) kc[ht] = 0;
+      }
     }
-    __syncthreads();
+    bk_lds_barrier();
+    }
   }
   BK_MARK(2);
 }

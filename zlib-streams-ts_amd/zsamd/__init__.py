@@ -288,6 +288,10 @@ class Engine:
         k = self._L.zs_debug_fetch(self._ctx, what, stream, buf, nbytes)
         return buf.raw[:k]
 
+    def bucket_members(self, stream: int) -> bytes:
+        """the sweep route's members (u16 each) of `stream`'s first window in the last deflate batch"""
+        return self.debug_fetch(7, stream, 2 * 65535)
+
     def set_timing(self, on: bool):
         self._L.zs_set_timing(self._ctx, 1 if on else 0)
 
