@@ -39,9 +39,10 @@
  *   - Output offsets and capacities of the device entry points must be
  *     multiples of 4 bytes (the engine writes 32-bit words; ZS_STREAM_ERROR
  *     otherwise): no store leaves [out_off[i], out_off[i] + out_cap[i]).  The
- *     host-buffer entries take any inflate capacity (they round it up inside
- *     their own staging and copy back only the bytes produced).  Inputs may be
- *     packed at any byte offset.
+ *     host-buffer entries, deflate and inflate, take any capacity exactly as
+ *     given and any output offset (they round the capacity up inside their
+ *     own staging, report Z_BUF_ERROR past the caller's value and copy back
+ *     only the bytes produced).  Inputs may be packed at any byte offset.
  */
 #ifndef ZS_GPU_H
 #define ZS_GPU_H
@@ -358,6 +359,65 @@ int zs_pool_deflate_batch_params(zs_pool *pool, int level, int wbits, int mem_le
                                  const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
                                  const uint64_t *out_off, const uint32_t *out_cap, int32_t *status,
                                  uint32_t *out_len, uint32_t *check);
+
+/* Z_FULL_FLUSH points: one stream's pieces compressed in parallel.  Stream i has the flush
+ * positions 0 <= p_1 < p_2 < ... < p_k <= in_len[i], all given with the call, and its output is
+ * what the z_stream functions produce for deflateInit2_(level, Z_DEFLATED, wbits, 8,
+ * Z_DEFAULT_STRATEGY); then for each piece in[p_(j-1) .. p_j) the stream layer's 32 KiB
+ * sub-chunks with Z_NO_FLUSH and deflate(Z_FULL_FLUSH) until it has drained; then the rest and
+ * Z_FINISH (deflate.ts:716-989).  At a full flush the reference closes the pending block if it
+ * holds symbols (deflate.ts:1343,1441), writes an empty stored block -- 00 00 FF FF behind three
+ * header bits and the padding to a byte -- clears the hash and, all input consumed, sets strstart
+ * = block_start = insert = 0 (deflate.ts:923-961, the branch at 942-955): the bytes behind a
+ * point are those of a fresh stream over the next piece, they start on a byte boundary, and a
+ * decoder can restart there (pigz -i, seekable .gz).  The pieces are independent, so one long
+ * stream with flush points uses the whole device as a batch of as many streams does.
+ * This stays a one-shot batch: the whole input and every position are given in one call.
+ * The entries take the arguments of zs_deflate_batch_device_ex / zs_deflate_batch_ex /
+ * zs_pool_deflate_batch, then `flush` and the positions: flush_first is a host array of
+ * n_streams + 1 entries and stream i's positions are flush_pos[flush_first[i] ..
+ * flush_first[i + 1]) (host array, increasing).
+ *  - flush must be ZS_FULL_FLUSH.  Z_PARTIAL_FLUSH (1), Z_SYNC_FLUSH (2) and Z_BLOCK (5):
+ *    ZS_STREAM_ERROR, "flush mode not built"; anything else: ZS_STREAM_ERROR, "invalid flush"
+ *    (deflate.ts:720).  Checked before the context is looked at;
+ *  - a null flush_first, or a null flush_pos with any position: ZS_STREAM_ERROR, "null flush arrays";
+ *  - equal or decreasing positions, or one past in_len[i]: ZS_STREAM_ERROR, "invalid flush
+ *    positions" (a second flush with no input between is Z_BUF_ERROR in the reference,
+ *    deflate.ts:742-743; no caller wants that, so the call is refused);
+ *  - level 0 with any flush point: ZS_STREAM_ERROR (not built: deflate_stored's cuts depend on
+ *    the stream layer's output buffers, as for dictionaries);
+ *  - streams + flush points above 65,535 in one call: ZS_STREAM_ERROR (split the batch);
+ *  - a flush at 0 writes the five marker bytes alone behind the wrapper's header; a flush at
+ *    in_len[i] writes the marker and Z_FINISH then the empty final block 03 00; only the block
+ *    Z_FINISH closes carries BFINAL;
+ *  - the wrapper and check[i] cover the whole stream: adler32 / crc32 of all its bytes, the whole
+ *    length in gzip's ISIZE;
+ *  - a call whose streams have no flush point is the counterpart's call: the same plan, kernels
+ *    and bytes;
+ *  - preset dictionaries, strategies and windowBits / memLevel are not built with flush points:
+ *    there are no _dict, _strategy or _params forms of these entries;
+ *  - statuses, Z_BUF_ERROR (against the stream's out_cap[i]) and the 4-byte alignment rule of the
+ *    device form as the plain entries.  Size outputs with zs_deflate_bound_flush. */
+#define ZS_FULL_FLUSH 3 /* Z_FULL_FLUSH, common/constants.ts */
+/* zs_deflate_bound + 12 n_flush: every extra piece costs at most the raw bound's constant 7 and
+ * the marker's 5 bytes; the bound's shifted terms are sub-additive. */
+uint64_t zs_deflate_bound_flush(uint64_t source_len, int wbits, uint64_t n_flush);
+/* deflate.ts:923-961 -- device buffers (as zs_deflate_batch_device_ex) */
+int zs_deflate_batch_flush_device(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                  const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                  const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                  uint32_t *d_out_len, uint32_t *d_check, void *hip_stream, int flush,
+                                  const uint64_t *flush_first, const uint32_t *flush_pos);
+/* deflate.ts:923-961 -- host buffers (as zs_deflate_batch_ex) */
+int zs_deflate_batch_flush(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                           const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                           const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check, int flush,
+                           const uint64_t *flush_first, const uint32_t *flush_pos);
+/* deflate.ts:923-961 -- the pool (as zs_pool_deflate_batch; sharded by stream) */
+int zs_pool_deflate_batch_flush(zs_pool *pool, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                                const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                                const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
+                                int flush, const uint64_t *flush_first, const uint32_t *flush_pos);
 
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);

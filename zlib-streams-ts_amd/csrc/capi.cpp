@@ -100,6 +100,8 @@ struct zs_ctx {
   Buf dadler, d_dict;  // preset dictionaries: the distinct ones' adler32; the host entries' staging of their bytes
   Buf djoin;           // deflate with dictionaries: the joined streams (zs_k_dict_join)
   Buf ghead;           // levels 1..3 at memLevel 9 and a large window: head[] per stream (zs_plan_fast_params)
+  Buf fstreams, fscan;  // a batch with flush points: the streams' records (`streams` holds the segments'); the layout scan
+  zs_flush_plan fp;
   zs_dict_set dset;
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
@@ -464,6 +466,12 @@ static int deflate_fail(zs_deflate_err e) {
       "stream too long for Z_RLE",
       "output offsets/capacities must be multiples of 4",
       "a preset dictionary with a strategy or windowBits / memLevel is not built",
+      "flush mode not built",
+      "invalid flush",
+      "null flush arrays",
+      "invalid flush positions",
+      "level 0 with a flush point is not built",
+      "too many flush points (streams + flush points above 65,535 in one call)",
   };
   return fail(ZS_STREAM_ERROR, "%s", kMsg[e]);
 }
@@ -512,8 +520,14 @@ static fast_par_fn fast_par_kernel(int nice_bucket, bool lane_order) {
 // A batch with preset dictionaries (p.dict): b holds the JOINED streams (dictionary tail + data,
 // DESIGN 4.6), `data` the caller's data (the check values are over the data alone; else data is b);
 // the parse starts at the streams' parse starts, the zlib wrapper carries FDICT / DICTID.
+// A batch with flush points (fl): b holds the SEGMENTS (b.out_off the segment's stream's),
+// `data` the streams, whose check values, layout scan, wrapper and results are per stream.
+struct FlushDev {
+  const uint32_t* sfirst;   // device: each stream's first segment
+  const uint32_t* sstream;  // ... each segment's stream
+};
 static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, const Batch& b, const Batch& data,
-                          int32_t* d_status, uint32_t* d_out_len) {
+                          int32_t* d_status, uint32_t* d_out_len, const FlushDev* fl = nullptr) {
   const zs_level_cfg& cfg = zs_level_cfgs[p.cfg];
   const zs_meta_layout& ml = p.ml;
   const int wrap = p.req.wrap, level = p.req.level;
@@ -526,11 +540,16 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   const zs_sweep_seg* d_segs = (const zs_sweep_seg*)(dm + ml.segs);
   const uint32_t* d_start = p.dict ? (const uint32_t*)(dm + ml.start) : nullptr;
   zs_stream* d_st = c->streams.as<zs_stream>();
+  // the records the check values, the wrapper and the results go by: the streams', n_res of them
+  zs_stream* d_res = fl ? c->fstreams.as<zs_stream>() : d_st;
+  const uint32_t n_res = data.n;
   zs_block* d_bk = c->blocks.as<zs_block>();
   uint32_t* syms = c->syms.as<uint32_t>();
   uint32_t* check = c->check.as<uint32_t>();
   const int nthreads_s = 256, nblocks_s = (int)p.g_streams;
+  const int nblocks_r = (int)((n_res + 255) / 256);
   MARK("start");
+  if (fl) HIPCHK(hipMemsetAsync(d_res, 0, sizeof(zs_stream) * (size_t)n_res, st));
   if (p.stored) {
     if (wrap) {
       zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
@@ -542,8 +561,8 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
     return ZS_OK;
   }
   if (wrap) {
-    zs_k_checksum<<<n, 64, 0, st>>>(data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
-    zs_k_copy_check<<<nblocks_s, nthreads_s, 0, st>>>(check, d_st, (int)n);
+    zs_k_checksum<<<n_res, 64, 0, st>>>(data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
+    zs_k_copy_check<<<nblocks_r, nthreads_s, 0, st>>>(check, d_res, (int)n_res);
     MARK("checksum");
   }
   if (p.match == ZS_MATCH_SWEEP) {
@@ -619,7 +638,16 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   MARK("trees");
   if (p.dict) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
                                                                  d_start);
-  else zs_k_layout<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n);
+  else if (fl) {
+    // per segment, joined by a scan of the segments' bytes (deflate_flush.hip)
+    const zs_flush_layout fo(ml.bytes, n_res, n);
+    uint64_t* segx = c->fscan.as<uint64_t>();
+    uint64_t* tile = segx + n + 1;
+    zs_k_flush_local<<<fo.tiles, ZS_FLUSH_TILE, 0, st>>>(d_blk, d_bk, d_st, fl->sfirst, fl->sstream, d_res, segx, tile, n);
+    zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tile, fo.tiles);
+    zs_k_flush_place<<<fo.tiles, ZS_FLUSH_TILE, 0, st>>>(d_blk, d_bk, d_st, fl->sfirst, fl->sstream, d_res, segx, tile,
+                                                         data.out_cap, data.out, data.out_off, wrap, n);
+  } else zs_k_layout<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n);
   MARK("layout");
   zs_k_emit<<<dim3(p.max_blk, n), 256, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
                                                 c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), b.out, b.out_off, wrap);
@@ -631,8 +659,9 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
     zs_k_wrap_par<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n,
                                                     p.wrap_strategy, p.req.q.w_bits);
   else if (wrap)
-    zs_k_wrap<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, p.wrap_strategy);
-  zs_k_finish<<<nblocks_s, nthreads_s, 0, st>>>(d_st, d_status, d_out_len, (int)n);
+    zs_k_wrap<<<nblocks_r, nthreads_s, 0, st>>>(d_res, data.out, data.out_off, data.in_len, wrap, level, (int)n_res,
+                                                p.wrap_strategy);
+  zs_k_finish<<<nblocks_r, nthreads_s, 0, st>>>(d_res, d_status, d_out_len, (int)n_res);
   MARK("finish");
   return ZS_OK;
 }
@@ -656,10 +685,22 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
 // regions of the capacities rounded up and pass the exact capacities.
 // `dict` (requests with req.dict, else null): the streams' preset dictionaries; a batch with none
 // of them set is the plain batch.
-static int deflate_device(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict) {
+// `flush` (requests with req.flush, else null): the streams' flush positions; a batch without any is
+// the plain batch.
+struct FlushIn {
+  const uint64_t* first;  // host, n + 1 entries: stream i's positions are pos[first[i] .. first[i + 1])
+  const uint32_t* pos;    // host
+};
+static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush);
+static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
+                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict,
+                          const FlushIn* flush = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  zs_deflate_req req = req_in;
   zs_deflate_call a;
+  a.flush_first = flush ? flush->first : nullptr;
+  a.flush_pos = flush ? flush->pos : nullptr;
   a.n = h.n;
   a.in_len = h.in_len;
   a.out_off = h.out_off;
@@ -673,6 +714,8 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req, const Batch& h, 
   HIPCHK(hipSetDevice(c->device));
   const uint32_t n = h.n;
   if (n == 0) return ZS_OK;
+  if (zs_deflate_any_flush(req, a)) return deflate_device_flush(c, req, h, d_status, d_out_len, d_check, st, *flush);
+  req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
   // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
   // metadata block; the streams' dictionaries, the distinct ones found once
   zs_dict_set& ds = c->dset;
@@ -744,6 +787,64 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req, const Batch& h, 
   if (!p.stored) MARK("end");  // (a stored batch ends at its "stored" mark)
   HIPCHK(hipGetLastError());
   return ZS_OK;  // timing marks are collected when queried (no wait here)
+}
+
+// A batch with Z_FULL_FLUSH points (validated; levels 1..9): the plan runs over the SEGMENTS -- the
+// pieces between the flush points, each a stream of its own to the match, parse, trees and emit
+// kernels -- and the flushed layout joins them per stream (deflate_flush.hip).
+static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush) {
+  const uint32_t n = h.n;
+  zs_flush_plan& f = c->fp;
+  zs_plan_flush(n, h.in_len, flush.first, flush.pos, f);
+  const uint32_t M = f.M;
+  zs_deflate_plan& p = c->dp;
+  zs_plan_deflate(req, c->o, c->fast_group, c->lane_order, M, f.slen.data(), nullptr, 0, p);
+  const zs_meta_layout& ml = p.ml;
+  const zs_flush_layout fo(ml.bytes, n, M);
+  HIPCHK(c->check.ensure(4ull * n));
+  HIPCHK(c->ghead.ensure(p.ghead_bytes));
+  HIPCHK(c->prevd.ensure(p.prevd_bytes));
+  HIPCHK(c->mres.ensure(p.mres_bytes));
+  HIPCHK(c->syms.ensure(p.syms_bytes));
+  HIPCHK(c->pscr.ensure(p.pscr_bytes));
+  HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
+  HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)M));
+  HIPCHK(c->fstreams.ensure(sizeof(zs_stream) * (size_t)n));
+  HIPCHK(c->fscan.ensure(fo.scan_bytes));
+  HIPCHK(c->codes.ensure(p.codes_bytes));
+  HIPCHK(c->hdr.ensure(p.hdr_bytes));
+  // the segments as a batch: their bytes where they lie in their streams, every one with its stream's output
+  std::vector<uint64_t> sin(M), sout(M);
+  for (uint32_t g = 0; g < M; g++) {
+    sin[g] = h.in_off[f.sstream[g]] + f.soff[g];
+    sout[g] = h.out_off[f.sstream[g]];
+  }
+  const Batch hs = {M, h.in, sin.data(), f.slen.data(), h.out, sout.data(), nullptr};
+  Batch b;
+  const int r = upload_batch(c, st, ml, fo.bytes, hs, &b, [&](uint8_t* hm) {
+    memcpy(hm + ml.pos_base, p.pos.data(), 8ull * M);
+    memcpy(hm + ml.blk_base, p.blk.data(), 4ull * M);
+    if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
+    memcpy(hm + fo.in_off, h.in_off, 8ull * n);
+    memcpy(hm + fo.in_len, h.in_len, 4ull * n);
+    memcpy(hm + fo.out_off, h.out_off, 8ull * n);
+    memcpy(hm + fo.out_cap, h.out_cap, 4ull * n);
+    memcpy(hm + fo.sfirst, f.sfirst.data(), 4ull * (n + 1));
+    memcpy(hm + fo.sstream, f.sstream.data(), 4ull * (M + 1));
+  });
+  if (r != ZS_OK) return r;
+  const uint8_t* dm = c->meta.as<uint8_t>();
+  const Batch real = {n, h.in, (const uint64_t*)(dm + fo.in_off), (const uint32_t*)(dm + fo.in_len), h.out,
+                      (const uint64_t*)(dm + fo.out_off), (const uint32_t*)(dm + fo.out_cap)};
+  const FlushDev fd = {(const uint32_t*)(dm + fo.sfirst), (const uint32_t*)(dm + fo.sstream)};
+  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, &fd);
+  if (rl != ZS_OK) return rl;
+  if (d_check)
+    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), req.wrap, d_check, (int)n);
+  MARK("end");
+  HIPCHK(hipGetLastError());
+  return ZS_OK;
 }
 
 extern "C" int zs_deflate_batch_device_ex(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
@@ -956,10 +1057,14 @@ static int host_batch(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64_t* 
 // the caller's dictionary bytes, offsets and lengths, all host memory.
 static int deflate_host(zs_ctx* c, const zs_deflate_req& req, uint32_t n, const uint8_t* in, const uint64_t* in_off,
                         const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                        int32_t* status, uint32_t* out_len, uint32_t* check, const DictIn* dict) {
+                        int32_t* status, uint32_t* out_len, uint32_t* check, const DictIn* dict,
+                        const FlushIn* flush = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
   zs_deflate_call call;
   call.n = n;
+  call.in_len = in_len;
+  call.flush_first = flush ? flush->first : nullptr;
+  call.flush_pos = flush ? flush->pos : nullptr;
   call.dict_arrays = dict && dict->off && dict->len;
   call.dict_buf = dict && dict->d_dict;
   call.dict_len = call.dict_arrays ? dict->len : nullptr;
@@ -989,11 +1094,13 @@ static int deflate_host(zs_ctx* c, const zs_deflate_req& req, uint32_t n, const 
                     [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
                         uint32_t** dr) {
                       const DictIn di = rq.dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
+                      // (a chunk's positions: the same position array, the chunk's part of the index)
+                      const FlushIn fi = flush ? FlushIn{flush->first + a, flush->pos} : FlushIn{};
                       return deflate_device(c, rq,
                                             {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
                                              ooff, out_cap + a},
                                             (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false,
-                                            rq.dict ? &di : nullptr);
+                                            rq.dict ? &di : nullptr, flush ? &fi : nullptr);
                     });  // out_len is 0 for failed streams
 }
 
@@ -1010,6 +1117,36 @@ extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, con
                                 const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
                                 int32_t* status, uint32_t* out_len) {
   return zs_deflate_batch_ex(c, level, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, nullptr);
+}
+
+// ---- Z_FULL_FLUSH points (deflate()'s flush argument, deflate.ts:716-989; the flush branch :942-961): a
+// fault of `flush` is reported before the context is looked at
+extern "C" uint64_t zs_deflate_bound_flush(uint64_t source_len, int wbits, uint64_t n_flush) {
+  // every extra piece costs at most the raw bound's constant 7 and the marker's 5 bytes
+  return zs_deflate_bound(source_len, wbits) + 12 * n_flush;
+}
+
+extern "C" int zs_deflate_batch_flush_device(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
+                                             const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                             const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                             uint32_t* d_out_len, uint32_t* d_check, void* hip_stream, int flush,
+                                             const uint64_t* flush_first, const uint32_t* flush_pos) {
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
+  const FlushIn fi = {flush_first, flush_pos};
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, true, nullptr, &fi);
+}
+
+extern "C" int zs_deflate_batch_flush(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
+                                      const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                      const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                      uint32_t* out_len, uint32_t* check, int flush, const uint64_t* flush_first,
+                                      const uint32_t* flush_pos) {
+  zs_deflate_req req;
+  if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
+  const FlushIn fi = {flush_first, flush_pos};
+  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr, &fi);
 }
 
 // ---- compression strategies (deflateInit2_'s strategy: validation deflate.ts:289-290, dispatch :923-931)

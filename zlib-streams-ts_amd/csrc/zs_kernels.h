@@ -131,6 +131,14 @@ __global__ void zs_k_layout_dict(const uint32_t* blk_base, zs_block* blocks, zs_
 __global__ void zs_k_wrap_dict(const zs_stream* streams, uint8_t* out, const uint64_t* out_off, const uint32_t* in_len,
                                int wrap, int level, int nstreams, const uint32_t* dstart, const uint32_t* did,
                                const uint32_t* dadler);
+// a batch with Z_FULL_FLUSH points (deflate_flush.hip): the layout per segment, a scan of the
+// segments' bytes over workgroups of ZS_FLUSH_TILE, the blocks rebased to their streams' outputs
+__global__ void zs_k_flush_local(const uint32_t* blk_base, zs_block* blocks, zs_stream* segs, const uint32_t* sfirst,
+                                 const uint32_t* sstream, zs_stream* streams, uint64_t* segx, uint64_t* tile, uint32_t M);
+__global__ void zs_k_flush_tiles(uint64_t* tile, uint32_t T);
+__global__ void zs_k_flush_place(const uint32_t* blk_base, zs_block* blocks, zs_stream* segs, const uint32_t* sfirst,
+                                 const uint32_t* sstream, zs_stream* streams, const uint64_t* segx, const uint64_t* tile,
+                                 const uint32_t* out_cap, uint8_t* out, const uint64_t* out_off, int wrap, uint32_t M);
 __global__ void zs_k_emit(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base, const uint32_t* blk_base,
                           const uint32_t* syms, const zs_block* blocks, const zs_stream* streams, const uint32_t* codes,
                           const uint32_t* hdr, uint8_t* out, const uint64_t* out_off, int wrap);

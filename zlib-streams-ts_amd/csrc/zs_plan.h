@@ -449,7 +449,13 @@ struct zs_deflate_req {
   int strategy = ZS_STRAT_DEFAULT;
   zs_deflate_params q;
   bool dict = false;  // the call carries preset dictionaries (a batch with every length 0 is the plain batch)
+  // 0, or ZS_FLUSH_FULL: the call carries Z_FULL_FLUSH positions (a batch without any is the plain batch)
+  int flush = 0;
 };
+#define ZS_FLUSH_FULL 3  // Z_FULL_FLUSH, common/constants.ts
+// streams + flush points of one device call at most: the segments are the y dimension of the
+// trees' and emit's grids
+#define ZS_FLUSH_SEG_MAX 65535u
 enum zs_deflate_err {
   ZS_DE_OK = 0,
   ZS_DE_WBITS,         // "unsupported windowBits (use -15, 15 or 31)"
@@ -466,6 +472,12 @@ enum zs_deflate_err {
   ZS_DE_RLE_LONG,      // "stream too long for Z_RLE"
   ZS_DE_ALIGN,         // "output offsets/capacities must be multiples of 4"
   ZS_DE_DICT_COMBINED, // internal (no public entry makes it): dictionaries with a strategy or parameters
+  ZS_DE_FLUSH_MODE,    // "flush mode not built"
+  ZS_DE_FLUSH_INVALID, // "invalid flush"
+  ZS_DE_FLUSH_ARRAYS,  // "null flush arrays"
+  ZS_DE_FLUSH_POS,     // "invalid flush positions"
+  ZS_DE_FLUSH_LEVEL0,  // "level 0 with a flush point is not built"
+  ZS_DE_FLUSH_MANY,    // "too many flush points (streams + flush points above 65,535 in one call)"
   ZS_DE_COUNT
 };
 // The request of the plain, _strategy and _dict entries: wbits -15 / 15 / 31.  Only a strategy out of
@@ -491,6 +503,16 @@ static inline zs_deflate_err zs_deflate_make_req_params(int level, int wbits, in
   r->dict = false;
   return ZS_DE_OK;
 }
+// ... and of the _flush entries: deflate()'s flush argument (deflate.ts:720: anything outside
+// Z_NO_FLUSH .. Z_BLOCK is Z_STREAM_ERROR).  Z_FULL_FLUSH alone is built; a fault is reported before
+// the context is looked at.
+static inline zs_deflate_err zs_deflate_make_req_flush(int level, int wbits, int flush, zs_deflate_req* r) {
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, r);
+  if (flush == 1 || flush == 2 || flush == 5) return ZS_DE_FLUSH_MODE;  // Z_PARTIAL_FLUSH, Z_SYNC_FLUSH, Z_BLOCK
+  if (flush != ZS_FLUSH_FULL) return ZS_DE_FLUSH_INVALID;
+  r->flush = flush;
+  return ZS_DE_OK;
+}
 // The arrays of a call, as far as validation reads them
 struct zs_deflate_call {
   uint32_t n = 0;
@@ -500,7 +522,31 @@ struct zs_deflate_call {
   bool caller_regions = false;  // the device entries: the capacities must be multiples of 4 too
   bool dict_arrays = false, dict_buf = false;  // the dictionary offsets and lengths / bytes are given
   const uint32_t* dict_len = nullptr;          // (with dict_arrays)
+  // requests with flush set: stream i's flush positions are flush_pos[flush_first[i] .. flush_first[i + 1])
+  const uint64_t* flush_first = nullptr;
+  const uint32_t* flush_pos = nullptr;
 };
+static inline bool zs_deflate_any_flush(const zs_deflate_req& r, const zs_deflate_call& a) {
+  return r.flush && a.n && a.flush_first && a.flush_first[a.n] > a.flush_first[0];
+}
+// The flush positions of a call: 0 <= p_1 < p_2 < ... <= in_len[i] for every stream (a second flush
+// with no input between is Z_BUF_ERROR in the reference, deflate.ts:742-743: refused up front), no
+// level 0 (deflate_stored's cuts depend on the output buffers), and at most ZS_FLUSH_SEG_MAX segments.
+static inline zs_deflate_err zs_deflate_validate_flush(const zs_deflate_req& r, const zs_deflate_call& a) {
+  if (!r.flush || a.n == 0) return ZS_DE_OK;
+  if (!a.flush_first) return ZS_DE_FLUSH_ARRAYS;
+  const uint64_t* ff = a.flush_first;
+  for (uint32_t i = 0; i < a.n; i++)
+    if (ff[i + 1] < ff[i]) return ZS_DE_FLUSH_POS;
+  if (ff[a.n] == ff[0]) return ZS_DE_OK;
+  if (!a.flush_pos) return ZS_DE_FLUSH_ARRAYS;
+  for (uint32_t i = 0; i < a.n; i++)
+    for (uint64_t k = ff[i]; k < ff[i + 1]; k++)
+      if (a.flush_pos[k] > a.in_len[i] || (k > ff[i] && a.flush_pos[k] <= a.flush_pos[k - 1])) return ZS_DE_FLUSH_POS;
+  if (r.level == 0) return ZS_DE_FLUSH_LEVEL0;
+  if (ff[a.n] - ff[0] + a.n > ZS_FLUSH_SEG_MAX) return ZS_DE_FLUSH_MANY;
+  return ZS_DE_OK;
+}
 static inline bool zs_deflate_any_dict(const zs_deflate_req& r, const zs_deflate_call& a) {
   for (uint32_t i = 0; r.dict && a.dict_len && i < a.n; i++)
     if (a.dict_len[i]) return true;
@@ -510,6 +556,12 @@ static inline bool zs_deflate_any_dict(const zs_deflate_req& r, const zs_deflate
 // after it, whatever its level.  The chunks then pass zs_deflate_validate one by one.
 static inline zs_deflate_err zs_deflate_validate_host(const zs_deflate_req& r, const zs_deflate_call& a) {
   if (r.dict && !a.dict_arrays) return ZS_DE_DICT_ARRAYS;
+  if (r.flush) {  // (no entry takes flush positions and dictionaries): the device batches' order
+    if (a.n == 0) return ZS_DE_OK;
+    if (r.wrap < 0) return ZS_DE_WBITS;
+    if (r.level < 0 || r.level > 9) return ZS_DE_LEVEL;
+    return zs_deflate_validate_flush(r, a);
+  }
   if (a.n == 0 || !zs_deflate_any_dict(r, a)) return ZS_DE_OK;
   if (!a.dict_buf) return ZS_DE_DICT_BUFFER;
   if (r.wrap == 2) return ZS_DE_DICT_GZIP;  // deflateSetDictionary refuses gzip (deflate.ts:373)
@@ -536,6 +588,7 @@ static inline zs_deflate_err zs_deflate_validate(const zs_deflate_req& r, const 
   if (a.n == 0) return ZS_DE_OK;
   for (uint32_t i = 0; i < a.n; i++)
     if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_DE_ALIGN;
+  if (const zs_deflate_err e = zs_deflate_validate_flush(r, a)) return e;
   if (r.level == 0) return r.q.is_default() ? ZS_DE_OK : ZS_DE_PARAMS_LEVEL0;
   if (zs_plan_strategy(o, r.level, r.strategy).tally == ZS_TALLY_RLE)  // (zs_k_rle_tally's 32-bit positions run 4,416 past a stream's end)
     for (uint32_t i = 0; i < a.n; i++)
@@ -573,6 +626,66 @@ struct zs_meta_layout {
     ulen = take(4ull * nu);
     chunks = take(sizeof(zs_huff_chunk) * nchunks);
     bytes = o;
+  }
+};
+
+// ---- Z_FULL_FLUSH points.  At a full flush with all input consumed the reference
+// closes the pending block, writes an empty stored block, clears the hash and sets strstart =
+// block_start = insert = 0 (deflate.ts:942-955): the piece behind the point is compressed as a fresh
+// stream that starts on a byte boundary.  A stream with k flush points is therefore planned as k + 1
+// SEGMENTS, each a stream of its own to every per-position kernel (zs_plan_deflate over the
+// segments' lengths); the flushed layout kernels (deflate_flush.hip) put them back together.
+struct zs_flush_plan {
+  uint32_t n = 0, M = 0;          // streams, segments
+  std::vector<uint32_t> sfirst;   // each stream's first segment (sfirst[n] = M)
+  std::vector<uint32_t> sstream;  // each segment's stream (sstream[M] = n)
+  std::vector<uint32_t> soff;     // each segment's start in its stream ...
+  std::vector<uint32_t> slen;     // ... and its length
+};
+// flush_first / flush_pos: positions that passed zs_deflate_validate_flush (flush_first may be null: none)
+static inline void zs_plan_flush(uint32_t n, const uint32_t* in_len, const uint64_t* flush_first,
+                                 const uint32_t* flush_pos, zs_flush_plan& f) {
+  f.n = n;
+  f.sfirst.assign(n + 1, 0);
+  f.sstream.clear();
+  f.soff.clear();
+  f.slen.clear();
+  for (uint32_t i = 0; i < n; i++) {
+    f.sfirst[i] = (uint32_t)f.sstream.size();
+    uint32_t at = 0;
+    for (uint64_t k = flush_first ? flush_first[i] : 0; flush_first && k < flush_first[i + 1]; k++) {
+      f.sstream.push_back(i);
+      f.soff.push_back(at);
+      f.slen.push_back(flush_pos[k] - at);
+      at = flush_pos[k];
+    }
+    f.sstream.push_back(i);  // the piece Z_FINISH closes (empty after a flush at the stream's end)
+    f.soff.push_back(at);
+    f.slen.push_back(in_len[i] - at);
+  }
+  f.M = (uint32_t)f.sstream.size();
+  f.sfirst[n] = f.M;
+  f.sstream.push_back(n);
+}
+// The flushed batch's section of the metadata block, behind the segments' own (zs_meta_layout of
+// M): the streams' arrays and the two maps; and the scan workspace of the layout kernels.
+#define ZS_FLUSH_TILE 256u  // segments per workgroup of the layout scan
+struct zs_flush_layout {
+  size_t in_off, in_len, out_off, out_cap, sfirst, sstream, bytes;
+  size_t scan_bytes;  // u64 per segment (+ 1), then u64 per tile
+  uint32_t tiles;
+  zs_flush_layout(size_t base, uint32_t n, uint32_t M) {
+    size_t o = base;
+    auto take = [&](size_t b) { size_t r = o; o = (o + b + 255) & ~size_t(255); return r; };
+    in_off = take(8ull * n);
+    in_len = take(4ull * n);
+    out_off = take(8ull * n);
+    out_cap = take(4ull * n);
+    sfirst = take(4ull * (n + 1));
+    sstream = take(4ull * (M + 1));
+    bytes = o;
+    tiles = M / ZS_FLUSH_TILE + 1;  // (M + 1 entries)
+    scan_bytes = 8ull * (M + 1) + 8ull * tiles;
   }
 };
 
@@ -719,7 +832,7 @@ static inline void zs_plan_deflate(const zs_deflate_req& r, const zs_route_opts&
     p.pos[i] = p.P;
     p.P += (nv + 7) & ~7ull;  // per-position tables start 8-aligned (16-B link loads in zs_k_match)
     p.blk[i] = p.B;
-    const uint32_t nb = in_len[i] / q.sym_end + 2;
+    const uint32_t nb = in_len[i] / q.sym_end + 2 + (r.flush ? 1u : 0u);  // (a flushed segment's marker block)
     p.B += nb;
     p.max_len = std::max(p.max_len, (uint32_t)std::min<uint64_t>(nv, 0xffffffffull));
     p.max_blk = std::max(p.max_blk, nb);

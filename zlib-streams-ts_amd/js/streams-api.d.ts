@@ -30,6 +30,15 @@ export interface CompressBatchOptions extends BatchOptions {
   /** deflateInit2_'s memLevel: 1..9, the hash has memLevel + 7 bits and a block closes after
    * (1 << (memLevel + 6)) - 1 symbols; any non-number means 8.  The rules of `windowBits` hold for it. */
   memLevel?: number;
+  /** Z_FULL_FLUSH points (deflate.ts:942-961), levels 1..9: positions 0 <= p1 < p2 < ... <= the input's length, one
+   * array for every input or one array per input (null = none).  At each one the pending block is closed, an empty
+   * stored block (00 00 FF FF) is written and the history is dropped, so a decoder can restart behind it and the
+   * pieces are compressed in parallel.  Positions out of order or past the length, and level 0, fail with "init
+   * failed: -2" (code "-2"); together with `dictionary`, a `strategy` other than 0 or `windowBits` / `memLevel`
+   * other than 15 / 8 it is a TypeError. */
+  flushAt?: number[] | (number[] | null)[];
+  /** flushAt at N, 2N, ... below each input's length. */
+  flushEvery?: number;
 }
 export const Z_DEFAULT_STRATEGY: 0;
 export const Z_FILTERED: 1;
@@ -71,6 +80,6 @@ export function compressBatchDetailed(inputs: ArrayBufferView[] | ArrayBuffer[],
                                       options?: CompressBatchOptions): Promise<CompressDetail>;
 export function decompressBatchDetailed(inputs: ArrayBufferView[] | ArrayBuffer[], format?: string,
                                         options?: DecompressBatchOptions): Promise<DecompressDetail>;
-export function deflateBound(length: number, format?: string): number;
+export function deflateBound(length: number, format?: string, nFlush?: number): number;
 export function engineVersion(): string;
 export function selfTest(device?: number): number;

@@ -104,6 +104,45 @@ function paramsOf(options, format) {
   return [format === "deflate-raw" ? -wb : format === "gzip" ? wb + 16 : wb, ml];
 }
 
+// options.flushAt / options.flushEvery: Z_FULL_FLUSH points (deflate.ts:942-961; zs_deflate_batch_flush in
+// zs_gpu.h).  flushAt: one array of positions for every input, or one array per input (null = none);
+// flushEvery: N, the positions N, 2N, ... below each input's length.  Returns one array per input, or
+// undefined without either.  Together with a dictionary, a strategy or windowBits / memLevel other than
+// 15 / 8 they are a TypeError (not built); positions that do not increase or pass the input's length fail
+// with "init failed: -2".
+function flushOf(options, ins) {
+  const at = options.flushAt, every = options.flushEvery;
+  const has = (x) => x !== undefined && x !== null;
+  if (!has(at) && !has(every)) return undefined;
+  if (has(at) && has(every)) throw new TypeError("flushAt and flushEvery are alternatives");
+  if (has(options.dictionary)) throw new TypeError("flush points and dictionary cannot be combined");
+  if (typeof options.strategy == "number" && options.strategy !== 0)
+    throw new TypeError("flush points and strategy cannot be combined");
+  if ((typeof options.windowBits == "number" && options.windowBits !== 15) ||
+      (typeof options.memLevel == "number" && options.memLevel !== 8))
+    throw new TypeError("flush points and windowBits / memLevel cannot be combined");
+  const pos = (x) => {
+    if (!Number.isInteger(x) || x < 0 || x > 0xffffffff) throw new TypeError("flush positions are integers in 0 .. 2^32 - 1");
+    return x;
+  };
+  if (has(every)) {
+    if (!Number.isInteger(every) || every <= 0) throw new TypeError("flushEvery must be a positive integer");
+    return ins.map((x) => {
+      const out = [];
+      for (let p = every; p < x.byteLength; p += every) out.push(p);
+      return out;
+    });
+  }
+  if (!Array.isArray(at)) throw new TypeError("flushAt must be an array of positions, or an array of such arrays, one per input");
+  if (at.every((x) => typeof x == "number")) return ins.map(() => at.map(pos));
+  if (at.length !== ins.length) throw new TypeError("flushAt must be an array of positions, or one array per input");
+  return at.map((a) => {
+    if (a === null || a === undefined) return [];
+    if (!Array.isArray(a)) throw new TypeError("flushAt must be an array of positions, or one array per input");
+    return a.map(pos);
+  });
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
@@ -115,7 +154,7 @@ async function runCompress(inputs, format, options) {
   try {
     const ins = checkInputs(inputs);
     res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                                    strategyOf(options), memLevel);
+                                    strategyOf(options), memLevel, flushOf(options, ins));
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -167,7 +206,9 @@ export async function decompressBatchSettled(inputs, format = "deflate", options
   return settle(await runDecompress(inputs, format, options));
 }
 
-export const deflateBound = (length, format = "deflate") => addon.deflateBound(length, compressWbits(format));
+// (nFlush: the stream's Z_FULL_FLUSH points, 12 bytes each: zs_deflate_bound_flush)
+export const deflateBound = (length, format = "deflate", nFlush = 0) =>
+  addon.deflateBound(length, compressWbits(format)) + 12 * nFlush;
 
 /** Per-stream results with the check value (the reference's strm.adler after the
  * stream: adler32 / crc32 of the uncompressed bytes for "deflate" / "gzip"). */
@@ -177,7 +218,7 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
   const ins = checkInputs(inputs);
   const [wbits, memLevel] = paramsOf(options, format);
   return addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                             strategyOf(options), memLevel);
+                             strategyOf(options), memLevel, flushOf(options, ins));
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

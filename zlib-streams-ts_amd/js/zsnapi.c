@@ -212,6 +212,10 @@ typedef struct {
   uint8_t *dict;
   uint64_t *dict_off;
   uint32_t *dict_len;
+  /* Z_FULL_FLUSH points (zs_pool_deflate_batch_flush): input i's positions are flush_pos[flush_first[i] ..
+   * flush_first[i + 1]); NULL: none given */
+  uint64_t *flush_first;
+  uint32_t *flush_pos;
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -223,6 +227,7 @@ static void job_free(job *j) {
   free(j->in_off); free(j->out_off); free(j->in_len); free(j->cap); free(j->olen); free(j->cons); free(j->check);
   free(j->status); free(j->phase); free(j->msg); free(j->base);
   free(j->dict); free(j->dict_off); free(j->dict_len);
+  free(j->flush_first); free(j->flush_pos);
   if (!j->out_given) {
     if (j->unbounded) zs_free(j->out);
     else free(j->out);
@@ -275,6 +280,10 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_deflate_batch_dict(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                        j->out_off, j->cap, j->status, j->olen, j->check, j->dict, j->dict_off,
                                        j->dict_len);
+  else if (j->flush_first)
+    j->rc = zs_pool_deflate_batch_flush(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
+                                        j->out_off, j->cap, j->status, j->olen, j->check, ZS_FULL_FLUSH, j->flush_first,
+                                        j->flush_pos);
   else if (j->params)
     j->rc = zs_pool_deflate_batch_params(j->pool, j->level, j->wbits, j->mem_level, j->n, j->base, j->in_off, j->in_len,
                                          j->out, j->out_off, j->cap, j->status, j->olen, j->check);
@@ -451,9 +460,57 @@ static int copy_dicts(napi_env env, job *j, napi_value arr) {
   return rc;
 }
 
+/* The flush positions of a job: arr[i] an array of numbers (input i's Z_FULL_FLUSH positions) or null /
+ * undefined (none).  0, -1 out of memory, -2 not such an array.  (The positions' order and range are the
+ * entry's to check: "invalid flush positions".) */
+static int copy_flush(napi_env env, job *j, napi_value arr) {
+  uint32_t len = 0;
+  bool is_arr = false;
+  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, arr, &len) != napi_ok ||
+      len != j->n)
+    return -2;
+  j->flush_first = (uint64_t *)calloc((size_t)j->n + 1, 8);
+  if (!j->flush_first) return -1;
+  uint64_t tot = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    /* pass 0: the counts; pass 1: the positions */
+    if (pass == 1) {
+      j->flush_pos = (uint32_t *)calloc((size_t)tot + 1, 4);
+      if (!j->flush_pos) return -1;
+    }
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < j->n; i++) {
+      napi_value e;
+      napi_valuetype t;
+      uint32_t k = 0;
+      if (napi_get_element(env, arr, i, &e) != napi_ok || napi_typeof(env, e, &t) != napi_ok) return -2;
+      if (t != napi_undefined && t != napi_null) {
+        if (napi_is_array(env, e, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, e, &k) != napi_ok)
+          return -2;
+      }
+      if (pass == 0) j->flush_first[i] = at;
+      for (uint32_t q = 0; pass == 1 && q < k; q++) {
+        napi_value x;
+        double d = -1;
+        if (napi_get_element(env, e, q, &x) != napi_ok || napi_get_value_double(env, x, &d) != napi_ok ||
+            !(d >= 0 && d <= 4294967295.0) || d != (double)(uint32_t)d)
+          return -2;
+        j->flush_pos[at + q] = (uint32_t)d;
+      }
+      at += k;
+    }
+    tot = at;
+    j->flush_first[j->n] = tot;
+  }
+  return 0;
+}
+
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
  *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined,
- *               memLevel: number | undefined) ->
+ *               memLevel: number | undefined, flushAt: (number[] | null)[] | undefined) ->
+ * flushAt: Z_FULL_FLUSH positions, one array per input (zs_gpu.h: increasing, at most the input's length;
+ * levels 1..9); together with dictionaries, a strategy or windowBits / memLevel other than 15 / 8 it throws
+ * code "-2" (not built), before any device is touched.
  * wbits: deflateInit2_'s windowBits argument, -9..-15 / 8..15 / 25..31; memLevel 1..9 (a non-number means 8);
  * anything else throws code "-2" (deflate.ts:281-294), and so does a window other than 15 or a memLevel other
  * than 8 together with dictionaries or a strategy (not built, zs_gpu.h), before any device is touched.
@@ -461,12 +518,12 @@ static int copy_dicts(napi_env env, job *j, napi_value arr) {
  * (deflate.ts:289-290; no dictionaries with a strategy, zs_gpu.h) before any device is touched ->
  *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
 static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 7;
-  napi_value argv[7];
+  size_t argc = 8;
+  napi_value argv[8];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 3)
     return throw_code(env, ZS_STREAM_ERROR,
-                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel]]]])");
+                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel[, flushAt]]]]])");
   const int32_t strategy = argc > 5 ? arg_i32(env, argv[5], 0) : 0;
   if (strategy < 0 || strategy > ZS_FIXED) return throw_code(env, ZS_STREAM_ERROR, "invalid strategy");
   napi_valuetype dt = napi_undefined;
@@ -483,6 +540,12 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   const int params = mem_level != 8 || (wbits != -15 && wbits != 15 && wbits != 31);
   if (params && (strategy || (dt != napi_undefined && dt != napi_null)))
     return throw_code(env, ZS_STREAM_ERROR, "windowBits / memLevel with preset dictionaries or a strategy is not built");
+  napi_valuetype ft = napi_undefined;
+  if (argc > 7) napi_typeof(env, argv[7], &ft);
+  const int flush = ft != napi_undefined && ft != napi_null;
+  if (flush && (params || strategy || (dt != napi_undefined && dt != napi_null)))
+    return throw_code(env, ZS_STREAM_ERROR,
+                      "flush points with preset dictionaries, a strategy or windowBits / memLevel are not built");
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -512,10 +575,20 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
                       : throw_code(env, ZS_STREAM_ERROR, "dictionaries must be (Uint8Array | null)[], one per input");
     }
   }
+  if (flush) {
+    const int rc = copy_flush(env, j, argv[7]);
+    if (rc != 0) {
+      free(v);
+      job_free(j);
+      return rc == -1 ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
+                      : throw_code(env, ZS_STREAM_ERROR, "flushAt must be (number[] | null)[], one per input");
+    }
+  }
   uint64_t tout = 0;
   for (uint32_t i = 0; i < n; i++) {
     j->out_off[i] = tout;
     const uint64_t bound = params ? zs_deflate_bound_params(v[i].n, wbits, mem_level, j->level == -1 ? 6 : j->level)
+                           : j->flush_first ? zs_deflate_bound_flush(v[i].n, j->wbits, j->flush_first[i + 1] - j->flush_first[i])
                                   : zs_deflate_bound_dict(v[i].n, j->wbits, j->dict_len ? j->dict_len[i] : 0);
     j->cap[i] = (uint32_t)((bound + 3) & ~3ull);
     tout += j->cap[i];

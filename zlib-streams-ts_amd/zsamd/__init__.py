@@ -97,6 +97,55 @@ def compress_params(fmt: str, window_bits=None, mem_level=8, zdict=None, strateg
     return -wb if fmt == "deflate-raw" else wb + 16 if fmt == "gzip" else wb
 
 
+Z_FULL_FLUSH = 3  # deflate()'s flush argument (ZS_FULL_FLUSH in zs_gpu.h)
+
+
+def compress_flush(lens, flush_at=None, flush_every=None, zdict=None, strategy=0, window_bits=None, mem_level=8):
+    """The `flush_at` / `flush_every` keywords of the compress entries: Z_FULL_FLUSH points
+    (zs_deflate_batch_flush; deflate.ts:942-961).  flush_at: one list of positions for every
+    stream, or one list per stream (None / empty = none); flush_every=N: the positions N, 2N, ...
+    below each stream's length.  Returns None without either, else a list of position lists, one
+    per stream.  Together with zdict, a strategy or parameters other than 15 / 8 they are not
+    built (zs_gpu.h): ValueError, before any call.  Positions the entry refuses (not increasing,
+    past the length) are its ZS_STREAM_ERROR."""
+    if flush_at is None and flush_every is None:
+        return None
+    if flush_at is not None and flush_every is not None:
+        raise ValueError("flush_at and flush_every are alternatives")
+    if zdict is not None:
+        raise ValueError("flush points with a preset dictionary are not built")
+    if strategy:
+        raise ValueError("flush points with strategy %d are not built" % strategy)
+    if not _params_default(window_bits, mem_level):
+        raise ValueError("flush points with window_bits / mem_level are not built")
+    n = len(lens)
+    if flush_every is not None:
+        if isinstance(flush_every, bool) or not isinstance(flush_every, int) or flush_every <= 0:
+            raise ValueError("flush_every must be a positive int")
+        return [list(range(flush_every, ln, flush_every)) for ln in lens]
+    fa = list(flush_at)
+    if all(isinstance(x, int) and not isinstance(x, bool) for x in fa):  # (an empty list: no points)
+        per = [fa] * n
+    else:
+        per = [[] if x is None else list(x) for x in fa]
+        if len(per) != n:
+            raise ValueError("flush_at: %d position lists for %d inputs" % (len(per), n))
+    for ps in per:
+        for x in ps:
+            if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x <= 0xffffffff:
+                raise ValueError("flush_at: positions are ints in 0 .. 2^32 - 1")
+    return per
+
+
+def _flush_arrays(per):
+    """(flush_first, flush_pos) ctypes arrays of compress_flush's position lists"""
+    first, pos = [0], []
+    for ps in per:
+        pos.extend(ps)
+        first.append(len(pos))
+    return _arr(ctypes.c_uint64, first), _arr(ctypes.c_uint32, pos)
+
+
 def _params_default(window_bits, mem_level) -> bool:
     return window_bits in (None, 15) and mem_level == 8
 
@@ -164,6 +213,13 @@ def lib():
         L.zs_pool_deflate_batch_params.argtypes = _withm(L.zs_deflate_batch_ex.argtypes)
         L.zs_deflate_bound_params.restype = ctypes.c_uint64
         L.zs_deflate_bound_params.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    if hasattr(L, "zs_deflate_batch_flush"):  # `flush`, flush_first, flush_pos behind the counterpart's arguments
+        _fl = [ctypes.c_int, _U64P, _U32P]
+        L.zs_deflate_batch_flush.argtypes = L.zs_deflate_batch_ex.argtypes + _fl
+        L.zs_deflate_batch_flush_device.argtypes = L.zs_deflate_batch_device_ex.argtypes + _fl
+        L.zs_pool_deflate_batch_flush.argtypes = L.zs_deflate_batch_ex.argtypes + _fl
+        L.zs_deflate_bound_flush.restype = ctypes.c_uint64
+        L.zs_deflate_bound_flush.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -229,9 +285,14 @@ def _arr(ctype, values):
     return a
 
 
-def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0) -> int:
+def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0, n_flush: int = 0) -> int:
     """deflateBound (deflate.ts:615-674) for a fresh stream, memLevel 8; dict_len: the
-    length of its preset dictionary (zs_deflate_bound_dict: DICTID, deflate.ts:633)."""
+    length of its preset dictionary (zs_deflate_bound_dict: DICTID, deflate.ts:633);
+    n_flush: its Z_FULL_FLUSH points (zs_deflate_bound_flush: 12 bytes each)."""
+    if n_flush:
+        if dict_len:
+            raise ValueError("flush points with a preset dictionary are not built")
+        return int(lib().zs_deflate_bound_flush(n, compress_wbits(fmt), n_flush))
     if dict_len:
         return int(lib().zs_deflate_bound_dict(n, compress_wbits(fmt), dict_len))
     return int(lib().zs_deflate_bound(n, compress_wbits(fmt)))
@@ -317,23 +378,31 @@ class Engine:
 
     # ---------------------------------------------------------- host buffers
     def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                           strategy: int = 0, window_bits=None, mem_level=8) -> List[Tuple[int, bytes]]:
+                           strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
+                           flush_every=None) -> List[Tuple[int, bytes]]:
         """Returns [(status, bytes)] -- status Z_STREAM_END on success.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
         (zs_deflate_batch_dict: deflateSetDictionary, deflate.ts:367-424).
         strategy: Z_DEFAULT_STRATEGY .. Z_FIXED (zs_deflate_batch_strategy; not with zdict).
         window_bits (8..15, None = 15), mem_level (1..9): deflateInit2_'s windowBits and memLevel
-        (zs_deflate_batch_params; other than 15 / 8 not with zdict or a strategy, levels 1..9)."""
+        (zs_deflate_batch_params; other than 15 / 8 not with zdict or a strategy, levels 1..9).
+        flush_at (positions for every stream, or a list per stream), flush_every=N: Z_FULL_FLUSH
+        points (zs_deflate_batch_flush; levels 1..9, not with any of the above)."""
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level)]
+                                                                     mem_level, flush_at, flush_every)]
 
     def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                                strategy: int = 0, window_bits=None, mem_level=8) -> List[Tuple[int, bytes, int]]:
+                                strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
+                                flush_every=None) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
         compress_strategy(strategy, zdict)
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
+        per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
+        if per is not None:
+            return _deflate_host(self._L, self._L.zs_deflate_batch_flush, self._ctx, inputs, fmt, level, self._check,
+                                 flush=per)
         if not _params_default(window_bits, mem_level):
             return _deflate_host(self._L, self._L.zs_deflate_batch_params, self._ctx, inputs, fmt, level, self._check,
                                  params=(code, mem_level))
@@ -346,8 +415,9 @@ class Engine:
         return _deflate_host(self._L, self._L.zs_deflate_batch_ex, self._ctx, inputs, fmt, level, self._check)
 
     def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                       strategy: int = 0, window_bits=None, mem_level=8) -> List[bytes]:
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level))
+                       strategy: int = 0, window_bits=None, mem_level=8, flush_at=None, flush_every=None) -> List[bytes]:
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
+                                                      flush_at, flush_every))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None):
@@ -377,14 +447,26 @@ class Engine:
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                         d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
-                        dict_off=None, dict_len=None, strategy: int = 0, window_bits=None, mem_level=8):
+                        dict_off=None, dict_len=None, strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
+                        flush_every=None):
         """Device pointers (ints) + host layout arrays (ctypes arrays).
+        flush_at / flush_every: Z_FULL_FLUSH points (zs_deflate_batch_flush_device; not with the others).
         d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
         strategy: zs_deflate_batch_strategy_device (not with dictionaries).
         window_bits / mem_level: zs_deflate_batch_params_device (other than 15 / 8 not with either)."""
         compress_strategy(strategy, dict_off)
         code = compress_params(fmt, window_bits, mem_level, dict_off, strategy)
+        per = compress_flush([in_len[i] for i in range(n)], flush_at, flush_every, dict_off, strategy, window_bits,
+                             mem_level)
+        if per is not None:
+            first, pos = _flush_arrays(per)
+            r = self._L.zs_deflate_batch_flush_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
+                                                      _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
+                                                      _P(d_status), _P(d_out_len), _P(d_check) if d_check else None,
+                                                      _P(hip_stream) if hip_stream else None, Z_FULL_FLUSH, first, pos)
+            self._check(r, "zs_deflate_batch_flush_device")
+            return
         if not _params_default(window_bits, mem_level):
             r = self._L.zs_deflate_batch_params_device(self._ctx, compress_level(level), code, mem_level, n, _P(d_in),
                                                        in_off, in_len, _P(d_out), out_off, out_cap, _P(d_status),
@@ -505,8 +587,9 @@ def _layout(inputs):
     return b"".join(inputs), offs, lens
 
 
-def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None, params=None):
-    """params: (the windowBits code, mem_level) for a _params entry (fn), which takes mem_level behind wbits."""
+def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None, params=None, flush=None):
+    """params: (the windowBits code, mem_level) for a _params entry (fn), which takes mem_level behind wbits.
+    flush: compress_flush's position lists for a _flush entry, which takes them behind `check`."""
     n = len(inputs)
     if n == 0:
         return []
@@ -516,6 +599,9 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=N
         lv = compress_level(level)
         caps = [(int(L.zs_deflate_bound_params(len(b), wbits, params[1], 6 if lv == -1 else lv)) + 3) & ~3
                 for b in inputs]
+    elif flush is not None:
+        caps = [(int(L.zs_deflate_bound_flush(len(b), wbits, len(flush[i]))) + 3) & ~3 for i, b in enumerate(inputs)]
+        zdict = (Z_FULL_FLUSH,) + _flush_arrays(flush)  # (the trailing arguments)
     elif zdict:
         caps = [(int(L.zs_deflate_bound_dict(len(b), wbits, zdict[2][i])) + 3) & ~3 for i, b in enumerate(inputs)]
     else:
@@ -662,9 +748,13 @@ class Pool:
         Engine._check(self, r, what)
 
     def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                                mem_level=8):
+                                mem_level=8, flush_at=None, flush_every=None):
         compress_strategy(strategy, zdict)
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
+        per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
+        if per is not None:
+            return _deflate_host(self._L, self._L.zs_pool_deflate_batch_flush, self._pool, inputs, fmt, level,
+                                 self._check, flush=per)
         if not _params_default(window_bits, mem_level):
             return _deflate_host(self._L, self._L.zs_pool_deflate_batch_params, self._pool, inputs, fmt, level,
                                  self._check, params=(code, mem_level))
@@ -677,13 +767,14 @@ class Pool:
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
     def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                           mem_level=8):
+                           mem_level=8, flush_at=None, flush_every=None):
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level)]
+                                                                     mem_level, flush_at, flush_every)]
 
     def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                       mem_level=8):
-        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level))
+                       mem_level=8, flush_at=None, flush_every=None):
+        return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
+                                                      flush_at, flush_every))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
         L = self._L
