@@ -437,6 +437,15 @@ int zs_crc32_batch(zs_ctx *ctx, uint32_t n_streams, const uint8_t *in, const uin
                    const uint32_t *in_len, const uint32_t *seeds, uint32_t *check);
 int zs_adler32_batch(zs_ctx *ctx, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
                      const uint32_t *in_len, const uint32_t *seeds, uint32_t *check);
+/* Joins the checksums of two pieces: the crc32 / adler32 of A followed by B from
+ * crc32(A), crc32(B) and B's length len2 (adler32: from reduced values, as every
+ * entry here returns them for a non-empty piece).  len2 == 0 returns the first
+ * value.  For pieces checksummed in several calls, contexts or devices (the
+ * seeds above continue one piece after the other; these need no order).  Host
+ * arithmetic, no context.  No reference counterpart: zlib's crc32_combine /
+ * adler32_combine. */
+uint32_t zs_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
+uint32_t zs_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2);
 
 /* Kernel timing of the batch calls made on this context since the last query
  * (HIP events on the streams the kernels ran on; the calls themselves never
@@ -453,6 +462,12 @@ uint32_t zs_last_inflate_lane_count(zs_ctx *ctx);
  * (inflate_seg.hip; the others of its members went on to the wave kernel).
  * Synchronizes.  For tests and tuning. */
 uint32_t zs_last_inflate_seg_count(zs_ctx *ctx);
+/* Parts of the last batch call's data checksum (the deflate wrappers' check
+ * values, the checksum entries, the inflate trailer check): 0 when every
+ * stream took one wave, else the parts of option "checksum_part" bytes that
+ * the batch was cut into (a host entry's chunks added up).  Known when the
+ * call returns; does not synchronize.  For tests and tuning. */
+uint32_t zs_last_checksum_parts(zs_ctx *ctx);
 double zs_last_phase_ms(zs_ctx *ctx, const char *phase);
 void zs_set_timing(zs_ctx *ctx, int on);
 /* Engine options: "timing" (0/1, as zs_set_timing); "inflate_fast" (default 1):
@@ -500,8 +515,13 @@ void zs_set_timing(zs_ctx *ctx, int on);
  * "seg_big_bits" (>= 65536, default 2^21): members with more input bits also
  * walk from the block starts a finder kernel proposes (more walks per member);
  * "seg_scratch_mb" (default 16384): the segmented decode's u16 scratch per
- * batch (2 bytes per byte of capacity); members past it take the other paths.
- * These options never change output bytes.  "inflate_ref_wrap" (default 1)
+ * batch (2 bytes per byte of capacity); members past it take the other paths;
+ * "checksum_split" (bytes, default 262144; 0 = never): a batch with a stream
+ * longer than this computes its data checksums (gzip / zlib check values, the
+ * checksum entries, the inflate trailer check) in parts of "checksum_part"
+ * bytes (a power of two 1024 .. 1048576, default 65536), a wave per part, and
+ * joins them per stream; other batches take one wave per stream.
+ * These options never change output bytes or check values.  "inflate_ref_wrap" (default 1)
  * does: 1 reproduces the reference's inflate_fast window-wrap copy
  * (inffast.ts:133-147), which changes the output of members whose match
  * crosses the reference's window wrap between inflate() calls; 0 decodes with

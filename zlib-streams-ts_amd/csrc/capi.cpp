@@ -103,6 +103,9 @@ struct zs_ctx {
   Buf fstreams, fscan;  // a batch with flush points: the streams' records (`streams` holds the segments'); the layout scan
   zs_flush_plan fp;
   zs_dict_set dset;
+  zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
+  Buf ckvals;              // ... its parts' values
+  uint32_t ck_parts = 0;   // the last batch call's parts (zs_last_checksum_parts)
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
   bool seg_used = false;            // the last inflate batch ran the segmented decode (inflate_seg.hip)
@@ -235,6 +238,9 @@ static const Option kOptions[] = {
             "lane_block must be 0 or a power of two <= 64"),
     OPT_INT("lane_large_min", o.lane_large_min, v >= 0, "lane_large_min must be >= 0"),
     OPT_INT("inflate_wave_min", o.inflate_wave_min, v >= 0, "inflate_wave_min must be >= 0"),
+    OPT_INT("checksum_split", o.checksum_split, zs_checksum_split_ok(v), "checksum_split must be >= 0"),
+    OPT_INT("checksum_part", o.checksum_part, zs_checksum_part_ok(v),
+            "checksum_part must be a power of two, 1024 .. 1048576"),
 };
 
 extern "C" {
@@ -358,12 +364,46 @@ uint32_t zs_last_inflate_seg_count(zs_ctx* c) {
     return 0;
   return v;
 }
+uint32_t zs_last_checksum_parts(zs_ctx* c) { return c ? c->ck_parts : 0u; }
 double zs_last_phase_ms(zs_ctx* c, const char* phase) {
   collect_marks(c);
   double t = -1;
   for (auto& p : c->phase_ms)
     if (p.first == phase) t = (t < 0 ? 0 : t) + p.second;
   return t;
+}
+
+// zlib's crc32_combine: crc32(A) x^(8 |B|) + crc32(B) modulo the reflected polynomial, the power
+// from x^(2^j) by squaring (x^(2^32) = x: the exponent's bits above 31 wrap round)
+static uint32_t multmodp(uint32_t a, uint32_t b) {
+  uint32_t m = 1u << 31, p = 0;
+  for (;;) {
+    if (a & m) {
+      p ^= b;
+      if ((a & (m - 1)) == 0) break;
+    }
+    m >>= 1;
+    b = (b & 1) ? (b >> 1) ^ 0xedb88320u : b >> 1;
+  }
+  return p;
+}
+uint32_t zs_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
+  if (!len2) return crc1;
+  uint32_t x2 = 1u << 30, p = 1u << 31;  // x^(2^j), j = 0; x^0
+  for (int j = 0; j < 3; j++) x2 = multmodp(x2, x2);  // bytes: x^8
+  for (uint64_t e = len2; e; e >>= 1, x2 = multmodp(x2, x2))
+    if (e & 1) p = multmodp(x2, p);
+  return multmodp(p, crc1) ^ crc2;
+}
+// zlib's adler32_combine: with A1, B1 and A2, B2 the halves, A = A1 + A2 - 1 and
+// B = B1 + B2 + |B| (A1 - 1) (mod 65521)
+uint32_t zs_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2) {
+  if (!len2) return adler1;
+  const uint64_t base = 65521, rem = len2 % base;
+  const uint64_t a1 = adler1 & 0xffffu, b1 = adler1 >> 16, a2 = adler2 & 0xffffu, b2 = adler2 >> 16;
+  const uint64_t a = (a1 + a2 + base - 1) % base;
+  const uint64_t b = (rem * a1 + b1 + b2 + base - rem) % base;
+  return (uint32_t)(b << 16 | a);
 }
 
 uint64_t zs_deflate_bound(uint64_t n, int wbits) {  // deflate.ts:615-674, memLevel 8 / windowBits 15
@@ -434,6 +474,37 @@ static int upload_batch(zs_ctx* c, hipStream_t st, const zs_meta_layout& ml, siz
   *d = {h.n, h.in, (const uint64_t*)(dm + ml.in_off), (const uint32_t*)(dm + ml.in_len), h.out,
         (const uint64_t*)(dm + ml.out_off), (const uint32_t*)(dm + ml.out_cap)};
   return ZS_OK;
+}
+
+// The data checksum of a batch (the deflate wrappers' check values, the checksum entries, the
+// inflate trailer check), in three steps around upload_batch: ck_prepare plans it from the
+// lengths' bounds and returns the bytes its part map takes behind the metadata block; ck_fill
+// writes the map there; ck_launch runs it -- one wave per stream as ever, or the parts and the fold.
+static int ck_prepare(zs_ctx* c, uint32_t n, const uint32_t* len_bound, size_t* map_bytes) {
+  zs_plan_checksum(c->o, n, len_bound, c->cp);
+  c->ck_parts = (c->keep_counts ? c->ck_parts : 0u) + c->cp.P;
+  *map_bytes = c->cp.map_bytes();
+  HIPCHK(c->ckvals.ensure(c->cp.ws_bytes));
+  return ZS_OK;
+}
+static void ck_fill(const zs_checksum_plan& cp, uint8_t* map) {
+  if (!cp.split) return;
+  memcpy(map, cp.pfirst.data(), 4ull * cp.pfirst.size());
+  memcpy(map + cp.map_pstream(), cp.pstream.data(), 4ull * cp.P);
+}
+// map: the part map's place in c->meta (a split plan); in_off, in_len, seeds: device arrays
+static void ck_launch(zs_ctx* c, hipStream_t st, size_t map, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                      const uint32_t* in_len, uint32_t* check, int kind, const uint32_t* seeds = nullptr) {
+  const zs_checksum_plan& cp = c->cp;
+  if (!cp.split) {
+    zs_k_checksum<<<n, 64, 0, st>>>(in, in_off, in_len, check, kind, seeds);
+    return;
+  }
+  const uint32_t* pfirst = (const uint32_t*)(c->meta.as<uint8_t>() + map);
+  const uint32_t* pstream = (const uint32_t*)(c->meta.as<uint8_t>() + map + cp.map_pstream());
+  uint32_t* vals = c->ckvals.as<uint32_t>();
+  zs_k_checksum_parts<<<cp.P, 64, 0, st>>>(in, in_off, in_len, pfirst, pstream, cp.part_lg, vals, kind);
+  zs_k_checksum_fold<<<n, 64, 0, st>>>(in_len, pfirst, cp.part_lg, vals, check, kind, seeds);
 }
 
 __global__ void zs_k_finish(const zs_stream* streams, int32_t* status, uint32_t* out_len, int n) {
@@ -527,7 +598,7 @@ struct FlushDev {
   const uint32_t* sstream;  // ... each segment's stream
 };
 static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, const Batch& b, const Batch& data,
-                          int32_t* d_status, uint32_t* d_out_len, const FlushDev* fl = nullptr) {
+                          int32_t* d_status, uint32_t* d_out_len, size_t ck_map, const FlushDev* fl = nullptr) {
   const zs_level_cfg& cfg = zs_level_cfgs[p.cfg];
   const zs_meta_layout& ml = p.ml;
   const int wrap = p.req.wrap, level = p.req.level;
@@ -552,7 +623,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   if (fl) HIPCHK(hipMemsetAsync(d_res, 0, sizeof(zs_stream) * (size_t)n_res, st));
   if (p.stored) {
     if (wrap) {
-      zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
+      ck_launch(c, st, ck_map, n, b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
       MARK("checksum");
     }
     zs_k_stored<<<dim3(p.g_stored_x, n), 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, check, wrap,
@@ -561,7 +632,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
     return ZS_OK;
   }
   if (wrap) {
-    zs_k_checksum<<<n_res, 64, 0, st>>>(data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
+    ck_launch(c, st, ck_map, n_res, data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
     zs_k_copy_check<<<nblocks_r, nthreads_s, 0, st>>>(check, d_res, (int)n_res);
     MARK("checksum");
   }
@@ -726,6 +797,14 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
                   (uint32_t)ds.uoff.size(), p);
   const zs_meta_layout& ml = p.ml;
   HIPCHK(c->check.ensure(4ull * n));
+  // the check values' part map behind the block (a raw batch has none)
+  size_t ck_bytes = 0;
+  c->cp.split = false;
+  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
+  if (req.wrap) {
+    const int rc = ck_prepare(c, n, h.in_len, &ck_bytes);
+    if (rc != ZS_OK) return rc;
+  }
   if (!p.stored) {
     HIPCHK(c->ghead.ensure(p.ghead_bytes));
     if (p.dict) {
@@ -744,7 +823,8 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
     HIPCHK(c->hdr.ensure(p.hdr_bytes));
   }
   Batch b;
-  int r = upload_batch(c, st, ml, ml.bytes, h, &b, [&](uint8_t* hm) {
+  int r = upload_batch(c, st, ml, ml.bytes + ck_bytes, h, &b, [&](uint8_t* hm) {
+    ck_fill(c->cp, hm + ml.bytes);
     if (p.stored) return;
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * n);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * n);
@@ -777,9 +857,9 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
     MARK("dict_join");
     HIPCHK(hipGetLastError());
     const Batch bj = {n, c->djoin.as<uint8_t>(), d_joff, (const uint32_t*)(dm + ml.jlen), b.out, b.out_off, b.out_cap};
-    r = deflate_launch(c, st, p, bj, b, d_status, d_out_len);
+    r = deflate_launch(c, st, p, bj, b, d_status, d_out_len, ml.bytes);
   } else {
-    r = deflate_launch(c, st, p, b, b, d_status, d_out_len);
+    r = deflate_launch(c, st, p, b, b, d_status, d_out_len, ml.bytes);
   }
   if (r != ZS_OK) return r;
   if (d_check)
@@ -803,6 +883,14 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   const zs_meta_layout& ml = p.ml;
   const zs_flush_layout fo(ml.bytes, n, M);
   HIPCHK(c->check.ensure(4ull * n));
+  // the streams' check values' part map behind the flushed section (a raw batch has none)
+  size_t ck_bytes = 0;
+  c->cp.split = false;
+  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
+  if (req.wrap) {
+    const int rc = ck_prepare(c, n, h.in_len, &ck_bytes);
+    if (rc != ZS_OK) return rc;
+  }
   HIPCHK(c->ghead.ensure(p.ghead_bytes));
   HIPCHK(c->prevd.ensure(p.prevd_bytes));
   HIPCHK(c->mres.ensure(p.mres_bytes));
@@ -822,7 +910,8 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   }
   const Batch hs = {M, h.in, sin.data(), f.slen.data(), h.out, sout.data(), nullptr};
   Batch b;
-  const int r = upload_batch(c, st, ml, fo.bytes, hs, &b, [&](uint8_t* hm) {
+  const int r = upload_batch(c, st, ml, fo.bytes + ck_bytes, hs, &b, [&](uint8_t* hm) {
+    ck_fill(c->cp, hm + fo.bytes);
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * M);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * M);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
@@ -838,7 +927,7 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   const Batch real = {n, h.in, (const uint64_t*)(dm + fo.in_off), (const uint32_t*)(dm + fo.in_len), h.out,
                       (const uint64_t*)(dm + fo.out_off), (const uint32_t*)(dm + fo.out_cap)};
   const FlushDev fd = {(const uint32_t*)(dm + fo.sfirst), (const uint32_t*)(dm + fo.sstream)};
-  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, &fd);
+  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, fo.bytes, &fd);
   if (rl != ZS_OK) return rl;
   if (d_check)
     zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), req.wrap, d_check, (int)n);
@@ -1223,14 +1312,20 @@ static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, 
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  const zs_meta_layout ml(n);  // (the seeds behind it)
+  const zs_meta_layout ml(n);  // (the seeds behind it, then the part map)
+  const size_t ck_map = ml.bytes + (seeds ? (4ull * n + 255) & ~size_t(255) : 0);
+  size_t ck_bytes = 0;
+  if (const int rc = ck_prepare(c, n, in_len, &ck_bytes)) return rc;
   Batch b;
-  const int r = upload_batch(c, st, ml, ml.bytes + (seeds ? 4ull * n : 0), {n, d_in, in_off, in_len, nullptr, nullptr, nullptr},
-                             &b, [&](uint8_t* hm) { if (seeds) memcpy(hm + ml.bytes, seeds, 4ull * n); });
+  const int r = upload_batch(c, st, ml, ck_bytes ? ck_map + ck_bytes : ml.bytes + (seeds ? 4ull * n : 0),
+                             {n, d_in, in_off, in_len, nullptr, nullptr, nullptr}, &b, [&](uint8_t* hm) {
+                               if (seeds) memcpy(hm + ml.bytes, seeds, 4ull * n);
+                               ck_fill(c->cp, hm + ck_map);
+                             });
   if (r != ZS_OK) return r;
   MARK("start");
-  zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, d_check, kind,
-                                  seeds ? (const uint32_t*)(c->meta.as<uint8_t>() + ml.bytes) : nullptr);
+  ck_launch(c, st, ck_map, n, b.in, b.in_off, b.in_len, d_check, kind,
+            seeds ? (const uint32_t*)(c->meta.as<uint8_t>() + ml.bytes) : nullptr);
   MARK("checksum");
   HIPCHK(hipGetLastError());
   return ZS_OK;  // timing marks are collected when queried (no wait here)
@@ -1669,6 +1764,12 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
                m_uoff = m_did + up256(4ull * n), m_ulen = m_uoff + up256(8ull * nu),
                m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
+  // ... and the trailer check's part map (its lengths are the decoders': the capacities bound them)
+  size_t ck_bytes = 0;
+  c->cp.split = false;
+  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
+  if (fastp && wbits > 0)
+    if (const int rc = ck_prepare(c, n, h.out_cap, &ck_bytes)) return rc;
   HIPCHK(c->istate.ensure(sizeof(zs_inflate_result) * (size_t)n));
   if (fastp) {
     HIPCHK(c->ltabs.ensure(zs_inflate_lane_scratch_bytes() * (size_t)n));
@@ -1676,7 +1777,8 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     HIPCHK(c->llen.ensure(8ull * n));
   }
   Batch b;
-  if (int r = upload_batch(c, st, ml, m_end, h, &b, [&](uint8_t* hm) {
+  if (int r = upload_batch(c, st, ml, m_end + ck_bytes, h, &b, [&](uint8_t* hm) {
+        ck_fill(c->cp, hm + m_end);
         if (!hasdict) return;
         memcpy(hm + m_doff, dict->off, 8ull * n);
         memcpy(hm + m_dlen, dict->len, 4ull * n);
@@ -1772,7 +1874,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     }
     if (wbits > 0) {  // trailer checks over the decoded bytes: adler32 (zlib) / crc32 (gzip)
       uint32_t* chk = llen + n;
-      zs_k_checksum<<<n, 64, 0, st>>>(b.out, b.out_off, llen, chk, wbits == 31 ? 2 : 1);
+      ck_launch(c, st, m_end, n, b.out, b.out_off, llen, chk, wbits == 31 ? 2 : 1);
       zs_k_inflate_lane_verify<<<(n + 255) / 256, 256, 0, st>>>(lres, chk, n);
       MARK("inflate_check");
     }

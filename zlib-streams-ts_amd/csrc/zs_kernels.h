@@ -149,4 +149,10 @@ __global__ void zs_k_wrap(const zs_stream* streams, uint8_t* out, const uint64_t
                           int wrap, int level, int nstreams, int strategy);
 __global__ void zs_k_checksum(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* check,
                               int kind, const uint32_t* seeds = nullptr);
+// ... of long streams in parts of 1 << part_lg bytes (zs_plan_checksum): a wave per part, then a wave per stream
+__global__ void zs_k_checksum_parts(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                    const uint32_t* pfirst, const uint32_t* pstream, uint32_t part_lg, uint32_t* vals,
+                                    int kind);
+__global__ void zs_k_checksum_fold(const uint32_t* in_len, const uint32_t* pfirst, uint32_t part_lg,
+                                   const uint32_t* vals, uint32_t* check, int kind, const uint32_t* seeds);
 __global__ void zs_k_selftest(uint32_t* bad, int rounds);

@@ -90,7 +90,64 @@ struct zs_route_opts {
   // Z_RLE: 1 reproduces the reference's deflate_rle, whose scan compares the previous byte's value
   // with the scan index (deflate.ts:1469-1481) and so finds no run: deflate_huff's tally; 0: zlib's
   bool rle_ref = true;
+  // the data checksums (zs_plan_checksum): a batch with a stream longer than checksum_split bytes
+  // runs in parts of checksum_part bytes (0: never; measured)
+  uint32_t checksum_split = 1u << 18;
+  uint32_t checksum_part = 65536;  // a power of two, ZS_CK_PART_MIN .. ZS_CK_PART_MAX
 };
+
+// ---- checksums of long streams
+#define ZS_CK_PART_MIN 1024u
+#define ZS_CK_PART_MAX (1u << 20)
+#define ZS_CK_PARTS_MAX (1u << 24)  // parts of one call at most (a wave each: the grid); past it, one wave per stream
+// zs_set_option's values of "checksum_split" and "checksum_part"
+static inline bool zs_checksum_split_ok(int v) { return v >= 0; }
+static inline bool zs_checksum_part_ok(int v) {
+  return v >= (int)ZS_CK_PART_MIN && v <= (int)ZS_CK_PART_MAX && !(v & (v - 1));
+}
+// A data checksum of n streams: one wave per stream (zs_k_checksum, as ever), or -- with any
+// stream's length bound above checksum_split -- a wave per part of checksum_part bytes and a wave
+// per stream that joins them (zs_k_checksum_parts, zs_k_checksum_fold).  Stream i then has
+// max(1, ceil(len_bound[i] / part)) parts, pfirst[i] .. pfirst[i + 1] of the pstream map.
+struct zs_checksum_plan {
+  bool split = false;
+  uint32_t part_lg = 16;
+  uint32_t P = 0;                        // parts in all (0 unsplit)
+  std::vector<uint32_t> pfirst, pstream;  // n + 1 and P entries (empty unsplit)
+  size_t ws_bytes = 0;                   // the parts' values: 4 bytes each
+  // the map behind a metadata block (at a multiple of 256): pfirst, then pstream
+  size_t map_pstream() const { return (4ull * pfirst.size() + 255) & ~size_t(255); }
+  size_t map_bytes() const { return split ? map_pstream() + ((4ull * P + 255) & ~size_t(255)) : 0; }
+};
+// len_bound: the lengths where the host knows them (deflate, the checksum entries), the output
+// capacities for the inflate check, whose lengths exist only on the device
+static inline void zs_plan_checksum(const zs_route_opts& o, uint32_t n, const uint32_t* len_bound,
+                                    zs_checksum_plan& p) {
+  p.split = false;
+  p.P = 0;
+  p.ws_bytes = 0;
+  p.pfirst.clear();
+  p.pstream.clear();
+  for (p.part_lg = 0; (1u << p.part_lg) < o.checksum_part;) p.part_lg++;
+  uint64_t total = 0;
+  bool any = false;
+  for (uint32_t i = 0; i < n; i++) {
+    any |= o.checksum_split && len_bound[i] > o.checksum_split;
+    total += std::max<uint64_t>(1, ((uint64_t)len_bound[i] + o.checksum_part - 1) >> p.part_lg);
+  }
+  if (!any || total > ZS_CK_PARTS_MAX) return;
+  p.split = true;
+  p.P = (uint32_t)total;
+  p.ws_bytes = 4ull * p.P;
+  p.pfirst.resize(n + 1);
+  p.pstream.reserve(p.P);
+  for (uint32_t i = 0; i < n; i++) {
+    p.pfirst[i] = (uint32_t)p.pstream.size();
+    const uint64_t k = std::max<uint64_t>(1, ((uint64_t)len_bound[i] + o.checksum_part - 1) >> p.part_lg);
+    p.pstream.insert(p.pstream.end(), (size_t)k, i);
+  }
+  p.pfirst[n] = p.P;
+}
 
 // ---- inflate
 // A member's span slots in the segmented decode: one per ZS_SEG_BLOCK_BITS input

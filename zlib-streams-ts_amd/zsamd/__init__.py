@@ -245,6 +245,12 @@ def lib():
     L.zs_adler32_batch_device.argtypes = [_P, ctypes.c_uint32, _P, _U64P, _U32P, _U32P, _P, _P]
     L.zs_crc32_batch.argtypes = [_P, ctypes.c_uint32, ctypes.c_char_p, _U64P, _U32P, _U32P, _U32P]
     L.zs_adler32_batch.argtypes = [_P, ctypes.c_uint32, ctypes.c_char_p, _U64P, _U32P, _U32P, _U32P]
+    if hasattr(L, "zs_crc32_combine"):
+        for fn in (L.zs_crc32_combine, L.zs_adler32_combine):
+            fn.restype = ctypes.c_uint32
+            fn.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+        L.zs_last_checksum_parts.restype = ctypes.c_uint32
+        L.zs_last_checksum_parts.argtypes = [_P]
     L.zs_last_batch_ms.restype = ctypes.c_double
     L.zs_last_batch_ms.argtypes = [_P]
     L.zs_last_inflate_lane_count.restype = ctypes.c_uint32
@@ -303,6 +309,18 @@ def deflate_capacity(n: int, fmt: str = "deflate-raw", dict_len: int = 0) -> int
     return (deflate_bound(n, fmt, dict_len) + 3) & ~3
 
 
+def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
+    """zs_crc32_combine: the crc32 of A + B from crc32(A), crc32(B) and len(B) (zlib's
+    crc32_combine; host arithmetic, no GPU)."""
+    return int(lib().zs_crc32_combine(crc1 & 0xffffffff, crc2 & 0xffffffff, len2))
+
+
+def adler32_combine(adler1: int, adler2: int, len2: int) -> int:
+    """zs_adler32_combine: the adler32 of A + B from adler32(A), adler32(B) and len(B)
+    (zlib's adler32_combine, for reduced values; host arithmetic, no GPU)."""
+    return int(lib().zs_adler32_combine(adler1 & 0xffffffff, adler2 & 0xffffffff, len2))
+
+
 class Engine:
     """One device context (one per GPU / process)."""
 
@@ -338,7 +356,9 @@ class Engine:
         return self._ctx
 
     def set_option(self, name: str, value: int):
-        """zs_set_option: "timing", "inflate_fast", "check_phases", "match_sweep" (see zs_gpu.h)."""
+        """zs_set_option: "timing", "inflate_fast", "check_phases", "match_sweep", ...; "checksum_split"
+        (bytes, 0 = never) and "checksum_part" (a power of two 1024 .. 1048576): a batch with a
+        longer stream computes its data checksums in parts (see zs_gpu.h)."""
         if self._L.zs_set_option(self._ctx, name.encode(), int(value)) != 0:
             raise ZsError(self._L.zs_last_error().decode())
 
@@ -363,6 +383,10 @@ class Engine:
     def last_seg_count(self) -> int:
         """members of the last inflate batch the segmented decode finished (inflate_seg.hip)"""
         return self._L.zs_last_inflate_seg_count(self._ctx)
+
+    def last_checksum_parts(self) -> int:
+        """parts of the last batch call's data checksum (0: one wave per stream; zs_last_checksum_parts)"""
+        return self._L.zs_last_checksum_parts(self._ctx)
 
     def last_ms(self, phase: Optional[str] = None) -> float:
         if phase is None:
