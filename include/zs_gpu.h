@@ -419,6 +419,87 @@ int zs_pool_deflate_batch_flush(zs_pool *pool, int level, int wbits, uint32_t n_
                                 const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
                                 int flush, const uint64_t *flush_first, const uint32_t *flush_pos);
 
+/* Restart points: one stream's segments decoded in parallel.  Behind a Z_FULL_FLUSH marker (00 00 FF FF)
+ * the bit stream is byte-aligned and the window empty; inflateSync (inflate.ts:1285-1337; syncsearch
+ * :1267-1283) looks for those bytes and resets the stream there, the window with it.  These entries are
+ * the decoder that zs_deflate_batch_flush* promises: stream i is given with its k_i >= 1 POINTS
+ * (in_pos, out_pos), increasing in both coordinates; its k_i segments decode as independent members of
+ * one batch -- so one long flushed stream uses the whole device -- and are joined, checked and reported
+ * as one stream.
+ *  - The first point is the start of the deflate data: in_pos the length of the wrapper's header
+ *    (zs_wrapper_header_len: 0 raw, 2 zlib, gzip 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC), out_pos 0.
+ *    Every further point is a restart point: in_pos the offset in the stream's input of the first byte
+ *    behind a marker, out_pos the uncompressed bytes before it.  Segment j is the input from point j to
+ *    point j + 1, the last one to in_len[i], the trailer included.
+ *  - The entries take the arguments of zs_inflate_batch_device_ex / zs_inflate_batch_ex /
+ *    zs_pool_inflate_batch, then the points: restart_first is a host array of n_streams + 1 entries and
+ *    stream i's points are (restart_in[k], restart_out[k]) for k in restart_first[i] ..
+ *    restart_first[i + 1] (host arrays, the layout of flush_first / flush_pos).
+ *  - ZS_STREAM_END when every segment decodes cleanly; every segment but the last has 00 00 FF FF in
+ *    its last four bytes, consumes exactly its bytes and produces exactly the bytes up to the next
+ *    point; the last ends at its own final block; the first point lies behind a well-formed header (zlib:
+ *    method 8, CINFO <= 7, the check mod 31, no FDICT; gzip: magic, method 8, no reserved flag -- FHCRC
+ *    is skipped, not verified); and the trailer agrees with the whole output (zlib: adler32, big-endian;
+ *    gzip: crc32 and ISIZE, little-endian).  Then the output is what zlib's inflate produces for the whole
+ *    stream, out_len[i] its length, consumed[i] reaches the end of the trailer (bytes behind it are
+ *    ignored) and check[i] is as in zs_inflate_batch_ex.
+ *  - zlib semantics, always: the segments decode with the instances that option inflate_ref_wrap = 0
+ *    selects, whatever the context's option says (it is neither read nor changed).  The reference's
+ *    window-wrap copy (inffast.ts:133-147) depends on its stream layer's inflate() call boundaries over
+ *    the whole stream, and that layer never calls inflateSync: behind a reset there is no reference
+ *    behaviour to reproduce.
+ *  - Anything else: ZS_DATA_ERROR, ZS_PHASE_PROCESS, the message "restart points do not decode the
+ *    stream", out_len = consumed = check = 0 -- except a stream whose output does not fit out_cap[i] (the
+ *    last segment runs past it, or the last out_pos lies past it), which reports the plain entry's
+ *    capacity outcome (ZS_BUF_ERROR, "output capacity exceeded").  The library does not fall back to a
+ *    sequential decode: a caller who wants the reference's exact status for a broken stream runs the plain
+ *    entry on it.  One failed stream does not touch the others; the bytes in its region are unspecified,
+ *    but no store leaves [out_off[i], out_off[i] + out_cap[i]) rounded up to 4.
+ *  - A raw stream has no trailer: a false point is caught by the marker bytes, the exact consumption and
+ *    the exact length only.
+ *  - A stream with only its first point is the plain decode of that stream with inflate_ref_wrap = 0.
+ *  - Refused with ZS_STREAM_ERROR and a zs_last_error text, before the context is looked at: wbits -16
+ *    (deflate64 has no flush on this side) or one the plain entry refuses; null point arrays; a stream
+ *    without its first point; more than 67,108,863 segments in one call (every decoder runs a 64-thread
+ *    workgroup per member, and a launch takes fewer than 2^32 threads); a first out_pos other than 0;
+ *    an in_pos less than 5 bytes (a marker alone) behind the point before; a decreasing out_pos; an
+ *    in_pos past in_len[i]; for the device entry, out_off / out_cap that are no multiples of 4.
+ *  - Preset dictionaries and the unbounded (_auto) output are not built with restart points: there are
+ *    no _dict or _auto forms.  Finding the points (a batched syncsearch) is not built either.
+ *  - Timing phases: "restart_gather", "restart_place", "restart_stitch", around the decoders' own. */
+/* inflate.ts:1267-1337 -- device buffers (as zs_inflate_batch_device_ex) */
+int zs_inflate_batch_restart_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                    const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                    const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                    int32_t *d_phase, int32_t *d_msg, uint32_t *d_out_len, uint32_t *d_consumed,
+                                    uint32_t *d_check, void *hip_stream, const uint64_t *restart_first,
+                                    const uint32_t *restart_in, const uint32_t *restart_out);
+/* inflate.ts:1267-1337 -- host buffers (as zs_inflate_batch_ex) */
+int zs_inflate_batch_restart(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                             const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                             int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
+                             uint32_t *check, const uint64_t *restart_first, const uint32_t *restart_in,
+                             const uint32_t *restart_out);
+/* inflate.ts:1267-1337 -- the pool (as zs_pool_inflate_batch; sharded by stream) */
+int zs_pool_inflate_batch_restart(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                                  const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                                  const uint64_t *out_off, const uint32_t *out_cap, int32_t *status, int32_t *phase,
+                                  int32_t *msg, uint32_t *out_len, uint32_t *consumed, uint32_t *check,
+                                  const uint64_t *restart_first, const uint32_t *restart_in,
+                                  const uint32_t *restart_out);
+/* The length of the wrapper's header in front of the deflate data (inflate.ts:560-728): 0 for raw, 2 for
+ * zlib; for gzip the parsed length -- 10, plus FEXTRA, FNAME, FCOMMENT and FHCRC where the flags name
+ * them -- or 0 when the header is malformed (magic, method, a reserved flag) or does not end inside
+ * in_len.  The first point of a stream.  Host arithmetic, no context. */
+uint32_t zs_wrapper_header_len(int wbits, const uint8_t *in, uint32_t in_len);
+/* The producer of an index: for the last zs_deflate_batch_flush_device / zs_deflate_batch_flush call on
+ * the context, in the order of flush_pos, the offset within each stream's output (the wrapper's header
+ * included) of the byte behind each marker -- the in_pos of a restart point whose out_pos is the flush
+ * position.  Writes at most cap values, returns the count of flush points and synchronises the device.
+ * 0 when the last compress call had no flush point.  Not offered on the pool (its shards' contexts are
+ * its own). */
+uint64_t zs_last_flush_index(zs_ctx *ctx, uint32_t *in_pos, uint64_t cap);
+
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);
 

@@ -102,6 +102,21 @@ struct zs_ctx {
   Buf ghead;           // levels 1..3 at memLevel 9 and a large window: head[] per stream (zs_plan_fast_params)
   Buf fstreams, fscan;  // a batch with flush points: the streams' records (`streams` holds the segments'); the layout scan
   zs_flush_plan fp;
+  // the flushed device calls of the last compress call (a host entry's chunks, one after the other in
+  // fscan): where their scans lie and which segments start their streams (zs_last_flush_index)
+  struct FlushIdx {
+    size_t at;  // u64 index of the call's scan in fscan
+    uint32_t n, M, hl;
+    std::vector<uint32_t> sfirst;
+  };
+  std::vector<FlushIdx> fidx;
+  size_t fscan_at = 0, fscan_used = 0;  // the current call's scan in fscan; u64 values in use
+  // a batch with restart points: the plan, the closed copies of the segments, the staging
+  // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
+  // and trailer values (2 arrays of n)
+  zs_restart_plan rp;
+  Buf rgather, rstage, rres, rmark, rsum;
+  std::vector<uint8_t> rhmeta;
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
@@ -712,7 +727,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   else if (fl) {
     // per segment, joined by a scan of the segments' bytes (deflate_flush.hip)
     const zs_flush_layout fo(ml.bytes, n_res, n);
-    uint64_t* segx = c->fscan.as<uint64_t>();
+    uint64_t* segx = c->fscan.as<uint64_t>() + c->fscan_at;
     uint64_t* tile = segx + n + 1;
     zs_k_flush_local<<<fo.tiles, ZS_FLUSH_TILE, 0, st>>>(d_blk, d_bk, d_st, fl->sfirst, fl->sstream, d_res, segx, tile, n);
     zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tile, fo.tiles);
@@ -787,6 +802,7 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
   if (n == 0) return ZS_OK;
   if (zs_deflate_any_flush(req, a)) return deflate_device_flush(c, req, h, d_status, d_out_len, d_check, st, *flush);
   req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
+  if (!c->keep_counts) c->fidx.clear();  // (zs_last_flush_index: the last compress call had no flush point)
   // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
   // metadata block; the streams' dictionaries, the distinct ones found once
   zs_dict_set& ds = c->dset;
@@ -899,7 +915,15 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
   HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)M));
   HIPCHK(c->fstreams.ensure(sizeof(zs_stream) * (size_t)n));
-  HIPCHK(c->fscan.ensure(fo.scan_bytes));
+  // (a later chunk of one host batch keeps the chunks' scans before it: deflate_host sized fscan for all)
+  if (!c->keep_counts) {
+    c->fidx.clear();
+    c->fscan_used = 0;
+  }
+  c->fscan_at = c->fscan_used;
+  HIPCHK(c->fscan.ensure(8ull * c->fscan_at + fo.scan_bytes));
+  c->fscan_used += fo.scan_bytes / 8;
+  c->fidx.push_back({c->fscan_at, n, M, req.wrap == 1 ? 2u : req.wrap == 2 ? 10u : 0u, f.sfirst});
   HIPCHK(c->codes.ensure(p.codes_bytes));
   HIPCHK(c->hdr.ensure(p.hdr_bytes));
   // the segments as a batch: their bytes where they lie in their streams, every one with its stream's output
@@ -1178,6 +1202,12 @@ static int deflate_host(zs_ctx* c, const zs_deflate_req& req, uint32_t n, const 
   // the caller's exact capacities are the Z_BUF_ERROR limits
   std::vector<uint32_t> ocap(n);
   for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
+  // a flushed batch: room for the scans of all its chunks, so that none is lost to a regrown buffer
+  // before zs_last_flush_index reads them
+  if (zs_deflate_any_flush(rq, call)) {
+    const uint64_t mt = (uint64_t)n + (flush->first[n] - flush->first[0]);
+    HIPCHK(c->fscan.ensure(8ull * (mt + mt / ZS_FLUSH_TILE + 16)));
+  }
   uint32_t* res[3] = {(uint32_t*)status, out_len, check};
   return host_batch(c, n, in, in_off, in_len, ocap, 3, res, 1, out, out_off,
                     [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
@@ -1525,6 +1555,7 @@ static const char* kInflateMsgs[ZS_MSG_COUNT] = {
     "incorrect data check",
     "incorrect length check",
     "output capacity exceeded",
+    "restart points do not decode the stream",
 };
 
 extern "C" const char* zs_inflate_message(int32_t i) { return (i >= 0 && i < ZS_MSG_COUNT) ? kInflateMsgs[i] : ""; }
@@ -1586,10 +1617,11 @@ static auto lane_kernel_dict(int rt) {
 // reaches this point; then the wave kernel over the same members for any the pieces
 // could not finish (skip_done: the others return at once), the exact kernel after
 // it for whatever fails there.
-static int seg_launch(zs_ctx* c, hipStream_t st, int wbits, const Batch& h, const Batch& b, zs_lane_res* lres) {
+static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbits, const Batch& h, const Batch& b,
+                      zs_lane_res* lres) {
   const std::vector<uint32_t>& list = c->ip.seg;
   zs_seg_plan& p = c->gp;
-  zs_plan_seg(c->o, wbits, list, h.in_len, h.out_cap, p);
+  zs_plan_seg(o, wbits, list, h.in_len, h.out_cap, p);
   const uint32_t ng = (uint32_t)list.size(), nb = p.nb, nbig = (uint32_t)p.big.size();
   HIPCHK(c->glist.ensure(4ull * ng));
   HIPCHK(c->gspb.ensure(4ull * (ng + 1)));
@@ -1726,8 +1758,11 @@ static int split_launch(zs_ctx* c, hipStream_t st, int wbits, const Batch& b, zs
 // capacities with caller_regions = false.
 static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
                           uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
-                          bool caller_regions, const DictIn* dict = nullptr) {
+                          bool caller_regions, const DictIn* dict = nullptr, const zs_route_opts* opts = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  // the options that decide routes and instances: the context's, or the caller's copy of them (the
+  // restart entries decode with zlib semantics whatever the context's inflate_ref_wrap says)
+  const zs_route_opts& o = opts ? *opts : c->o;
   // inflateInit2_ / inflateReset2 validation (inflate.ts:138-192) for the stream-layer formats
   if (!(wbits == -15 || wbits == 15 || wbits == 31 || wbits == -16))
     return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15, 31 or -16)");
@@ -1754,9 +1789,9 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   for (uint32_t i = 0; i < n; i++)
     if ((h.out_off[i] & 3) || (caller_regions && (h.out_cap[i] & 3)))
       return fail(ZS_STREAM_ERROR, "output offsets/capacities must be multiples of 4");
-  const bool fastp = c->o.inflate_fast;
+  const bool fastp = o.inflate_fast;
   zs_inflate_plan& p = c->ip;
-  if (fastp) zs_plan_inflate(c->o, wbits, n, h.in_len, h.out_cap, p, hasdict ? dict->len : nullptr);
+  if (fastp) zs_plan_inflate(o, wbits, n, h.in_len, h.out_cap, p, hasdict ? dict->len : nullptr);
   const zs_meta_layout ml(n);
   // behind the batch's metadata: the members' dictionary offsets, lengths and ids, the distinct ones' too
   const size_t nu = hasdict ? ds.uoff.size() : 0;
@@ -1803,7 +1838,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   const size_t smem = zs_inflate_smem_bytes(wbits);
   HIPCHK(hipFuncSetAttribute((const void*)zs_k_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   zs_lane_res* const lres = fastp ? c->lres.as<zs_lane_res>() : nullptr;
-  const int lflags = c->o.inflate_ref_wrap ? ZS_INF_REF_WRAP : 0;
+  const int lflags = o.inflate_ref_wrap ? ZS_INF_REF_WRAP : 0;
   MARK("start");
   if (fastp) {
     zs_lane_tabs* const lt = (zs_lane_tabs*)c->ltabs.p;
@@ -1817,7 +1852,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     // the 2.19 MB fixture's split decode took 8.0 ms beside it, 2.5 ms alone)
     c->seg_used |= !p.seg.empty();
     if (!p.seg.empty()) {
-      const int r = seg_launch(c, st, wbits, h, b, lres);
+      const int r = seg_launch(c, o, st, wbits, h, b, lres);
       if (r != ZS_OK) return r;
       // (the join below waits for the side stream's last kernel)
       if (p.wave.empty()) HIPCHK(hipEventRecord(c->join, c->side));
@@ -1859,7 +1894,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     // Members the single-call instance bailed on whose cap allows more than one
     // inflate() call of the reference (more than 32 KiB of input, or output past
     // 64 KiB): re-run by the call-tracking instance, here, before the exact kernel
-    if (c->o.inflate_ref_wrap && wbits != -16) {
+    if (o.inflate_ref_wrap && wbits != -16) {
       const size_t lsmr = 64 * zs_inflate_lane_lds_bytes(false);
       auto lkr = p.dict ? zs_k_inflate_lane<0, true, true> : zs_k_inflate_lane<0, true>;
       HIPCHK(hipFuncSetAttribute((const void*)lkr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsmr));
@@ -1944,6 +1979,204 @@ extern "C" int zs_inflate_batch_ex(zs_ctx* c, int wbits, uint32_t n, const uint8
                                             (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
                                             check ? dr[5] : nullptr, c->stream, false);
                     });
+}
+
+// ---- restart points (inflateSync, inflate.ts:1267-1337): a stream's segments decoded as the
+// members of one raw batch and joined per stream.  A fault of the arguments is reported before the
+// context is looked at.
+struct RestartIn {
+  const uint64_t* first;  // host, n + 1 entries: stream i's points are (in[k], out[k]), k in first[i] .. first[i + 1]
+  const uint32_t* in;     // host
+  const uint32_t* out;    // host
+};
+static int restart_refused(int wbits, const Batch& h, bool device_entry, const RestartIn& rs) {
+  zs_restart_call a;
+  a.n = h.n;
+  a.in_len = h.in_len;
+  a.out_off = device_entry ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = device_entry;
+  a.rfirst = rs.first;
+  a.rin = rs.in;
+  a.rout = rs.out;
+  if (const zs_restart_err e = zs_restart_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_restart_err_text(e));
+  return ZS_OK;
+}
+
+// The device decode of a validated call (regions as inflate_device's: the caller's own, or the host
+// entry's staging with the caller's exact capacities).
+static int restart_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
+                          uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
+                          const RestartIn& rs) {
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t n = h.n;
+  if (n == 0) return ZS_OK;
+  zs_restart_plan& p = c->rp;
+  zs_plan_restart(n, h.in_len, h.out_cap, rs.first, rs.in, rs.out, p);
+  const uint32_t M = p.M;
+  // the segment batch's metadata block is inflate_device's own (it uploads it); this call's section
+  // lies behind it, the streams' checksum map behind that
+  const zs_meta_layout ml(M);
+  const zs_restart_layout ro(ml.bytes, n, M);
+  size_t ck_bytes = 0;
+  c->cp.split = false;
+  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
+  if (wbits > 0)
+    if (const int rc = ck_prepare(c, n, h.out_cap, &ck_bytes)) return rc;
+  HIPCHK(c->rgather.ensure(p.gather_bytes));
+  HIPCHK(c->rstage.ensure(p.stage_bytes));
+  HIPCHK(c->rres.ensure(20ull * M + 64));
+  HIPCHK(c->rmark.ensure(4ull * M + 16));
+  HIPCHK(c->rsum.ensure(8ull * n + 16));
+  HIPCHK(c->meta.ensure(ro.bytes + ck_bytes));  // (before inflate_device's own ensure, which then keeps the block)
+  // where each segment lies, decodes and belongs
+  std::vector<uint64_t> src(M), ooff(M), dst(M);
+  for (uint32_t g = 0; g < M; g++) {
+    const uint32_t i = p.rstream[g];
+    src[g] = h.in_off[i] + p.soff[g];
+    dst[g] = h.out_off[i] + p.opos[g];
+    // (a segment without room stores nothing: it stays at its stream's start)
+    ooff[g] = p.in_place ? h.out_off[i] + (p.ocap[g] ? p.opos[g] : 0u) : p.stoff[g];
+  }
+  c->rhmeta.assign(ro.bytes + ck_bytes - ml.bytes, 0);
+  // (the layout's offsets count from the block's start, this host copy from the section's)
+  auto hm = [&](size_t at) { return c->rhmeta.data() + (at - ml.bytes); };
+  memcpy(hm(ro.in_off), h.in_off, 8ull * n);
+  memcpy(hm(ro.in_len), h.in_len, 4ull * n);
+  memcpy(hm(ro.out_off), h.out_off, 8ull * n);
+  memcpy(hm(ro.over), p.over.data(), 4ull * n);
+  memcpy(hm(ro.rfirst), p.rfirst.data(), 4ull * (n + 1));
+  memcpy(hm(ro.src), src.data(), 8ull * M);
+  memcpy(hm(ro.soff), p.soff.data(), 4ull * M);
+  memcpy(hm(ro.slen), p.slen.data(), 4ull * M);
+  memcpy(hm(ro.goff), p.goff.data(), 8ull * M);
+  memcpy(hm(ro.glen), p.glen.data(), 4ull * M);
+  memcpy(hm(ro.ooff), ooff.data(), 8ull * M);
+  memcpy(hm(ro.ocap), p.ocap.data(), 4ull * M);
+  memcpy(hm(ro.olen), p.olen.data(), 4ull * M);
+  memcpy(hm(ro.opos), p.opos.data(), 4ull * M);
+  memcpy(hm(ro.dst), dst.data(), 8ull * M);
+  memcpy(hm(ro.gtile), p.gtile.data(), 4ull * (M + 1));
+  memcpy(hm(ro.ptile), p.ptile.data(), 4ull * (M + 1));
+  ck_fill(c->cp, hm(ro.bytes));
+  HIPCHK(hipMemcpyAsync(c->meta.as<uint8_t>() + ml.bytes, c->rhmeta.data(), c->rhmeta.size(), hipMemcpyHostToDevice, st));
+  const uint8_t* dm = c->meta.as<uint8_t>();
+  auto u32 = [&](size_t at) { return (const uint32_t*)(dm + at); };
+  auto u64 = [&](size_t at) { return (const uint64_t*)(dm + at); };
+  uint8_t* gather = c->rgather.as<uint8_t>();
+  uint32_t* mark_ = c->rmark.as<uint32_t>();
+  const uint32_t gmax = 32u * c->o.ncu;  // workgroups of the gather and the place: grid-stride beyond
+  MARK("start");
+  if (p.gtile[M])
+    zs_k_restart_gather<<<std::min(p.gtile[M], gmax), 256, 0, st>>>(h.in, u64(ro.src), u32(ro.slen), u32(ro.glen),
+                                                                   u64(ro.goff), u32(ro.gtile), M, gather, mark_);
+  MARK("restart_gather");
+  HIPCHK(hipGetLastError());
+  // the segments as M raw members, decoded with zlib semantics: behind a reset there is no call
+  // boundary of the reference's to reproduce, whatever the context's inflate_ref_wrap says
+  int32_t* s_status = c->rres.as<int32_t>();
+  int32_t* s_phase = s_status + M;
+  int32_t* s_msg = s_phase + M;
+  uint32_t* s_len = (uint32_t*)(s_msg + M);
+  uint32_t* s_used = s_len + M;
+  zs_route_opts o2 = c->o;
+  o2.inflate_ref_wrap = false;
+  const Batch hs = {M, gather, p.goff.data(), p.glen.data(), p.in_place ? h.out : c->rstage.as<uint8_t>(), ooff.data(),
+                    p.ocap.data()};
+  // (the raw segment batch plans no checksum and clears the streams' plan flag and part count)
+  const bool ck_split = c->cp.split;
+  const uint32_t ck_parts = c->ck_parts;
+  const int ri = inflate_device(c, -15, hs, s_status, s_phase, s_msg, s_len, s_used, nullptr, st, false, nullptr, &o2);
+  c->cp.split = ck_split;
+  c->ck_parts = ck_parts;
+  if (ri != ZS_OK) return ri;
+  if (!p.in_place) {
+    if (p.ptile[M])
+      zs_k_restart_place<<<std::min(p.ptile[M], gmax), 256, 0, st>>>(c->rstage.as<uint8_t>(), u64(ro.ooff), u32(ro.ocap),
+                                                                    s_len, u64(ro.dst), u32(ro.ptile), M, h.out);
+    MARK("restart_place");
+  }
+  uint32_t* sum = c->rsum.as<uint32_t>();
+  uint32_t* want = sum + n;
+  zs_k_restart_stitch<<<n, 64, 0, st>>>(h.in, u64(ro.in_off), u32(ro.in_len), u32(ro.over), u32(ro.rfirst), u32(ro.soff),
+                                        u32(ro.slen), u32(ro.olen), u32(ro.opos), mark_, s_status, s_msg, s_len, s_used,
+                                        wbits, n, d_status, d_phase, d_msg, d_out_len, d_consumed, want);
+  // the check value over the joined output, the lengths the stitch wrote, against the trailer's
+  if (wbits > 0) ck_launch(c, st, ro.bytes, n, h.out, u64(ro.out_off), d_out_len, sum, wbits == 31 ? 2 : 1);
+  zs_k_restart_check<<<(n + 255) / 256, 256, 0, st>>>(sum, want, wbits, n, d_status, d_phase, d_msg, d_out_len,
+                                                      d_consumed, d_check);
+  MARK("restart_stitch");
+  HIPCHK(hipGetLastError());
+  return ZS_OK;
+}
+
+// inflate.ts:1267-1337 -- device buffers
+extern "C" int zs_inflate_batch_restart_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
+                                               const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                               const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                               int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
+                                               uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
+                                               const uint64_t* restart_first, const uint32_t* restart_in,
+                                               const uint32_t* restart_out) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  const RestartIn rs = {restart_first, restart_in, restart_out};
+  if (const int r = restart_refused(wbits, h, true, rs)) return r;
+  if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  return restart_device(c, wbits, h, d_status, d_phase, d_msg, d_out_len, d_consumed, d_check, hip_stream, rs);
+}
+
+// inflate.ts:1267-1337 -- host buffers
+extern "C" int zs_inflate_batch_restart(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                        const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                        uint32_t* out_len, uint32_t* consumed, uint32_t* check,
+                                        const uint64_t* restart_first, const uint32_t* restart_in,
+                                        const uint32_t* restart_out) {
+  const RestartIn rs = {restart_first, restart_in, restart_out};
+  if (const int r = restart_refused(wbits, {n, in, in_off, in_len, out, out_off, out_cap}, false, rs)) return r;
+  if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  std::vector<uint32_t> ocap(n), creq(out_cap, out_cap + n);
+  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
+  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
+  return host_batch(c, n, in, in_off, in_len, ocap, 6, res, 3, out, out_off,
+                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
+                        uint32_t** dr) {
+                      // (a chunk's points: the same point arrays, the chunk's part of the index)
+                      const RestartIn ri = {restart_first + a, restart_in, restart_out};
+                      return restart_device(c, wbits,
+                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
+                                             ooff, creq.data() + a},
+                                            (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
+                                            check ? dr[5] : nullptr, c->stream, ri);
+                    });
+}
+
+extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t in_len) {
+  return zs_wrapper_header_len_of(wbits, in, in_len);
+}
+
+// The index of the last flushed compress call on the context: for every flush point, in the order of
+// flush_pos, the offset in its stream's output of the byte behind the marker -- the wrapper's header,
+// then the bytes of the segments before it (zs_k_flush_local's scan, which zs_k_flush_place rebases
+// the blocks by).  A host entry's chunks follow each other.
+extern "C" uint64_t zs_last_flush_index(zs_ctx* c, uint32_t* in_pos, uint64_t cap) {
+  if (!c || c->fidx.empty() || !c->fscan.p) return 0;
+  if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
+  std::vector<uint64_t> scan(c->fscan_used);
+  if (hipMemcpy(scan.data(), c->fscan.p, 8ull * scan.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  uint64_t k = 0;
+  for (const zs_ctx::FlushIdx& f : c->fidx) {
+    const uint64_t* segx = scan.data() + f.at;
+    const uint64_t* tile = segx + f.M + 1;
+    auto at = [&](uint32_t x) { return tile[x / ZS_FLUSH_TILE] + segx[x]; };  // the bytes of all segments before x
+    for (uint32_t s = 0; s < f.n; s++)
+      for (uint32_t g = f.sfirst[s] + 1; g < f.sfirst[s + 1]; g++, k++)
+        if (in_pos && k < cap) in_pos[k] = (uint32_t)(f.hl + (at(g) - at(f.sfirst[s])));
+  }
+  return k;
 }
 
 // ---- preset dictionaries (inflateSetDictionary, inflate.ts:1220-1249; Z_NEED_DICT, inflate.ts:594-597)

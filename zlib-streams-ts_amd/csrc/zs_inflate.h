@@ -33,6 +33,7 @@ enum zs_msg_id {
   ZS_MSG_DATA_CHECK,
   ZS_MSG_LENGTH_CHECK,
   ZS_MSG_CAPACITY,
+  ZS_MSG_RESTART,  // the restart entries: "restart points do not decode the stream"
   ZS_MSG_COUNT
 };
 
@@ -83,3 +84,20 @@ size_t zs_inflate_smem_bytes(int wbits);
 size_t zs_inflate_lane_lds_bytes(bool root);
 size_t zs_inflate_lane_scratch_bytes();
 size_t zs_inflate_wave_lds_bytes(bool d64);
+
+// a stream decoded from its restart points (inflate_restart.hip): the segments copied and
+// closed, the staging route's copy back, the results joined per stream, the trailer's check
+__global__ void zs_k_restart_gather(const uint8_t* in, const uint64_t* src, const uint32_t* slen, const uint32_t* glen,
+                                    const uint64_t* goff, const uint32_t* gtile, uint32_t M, uint8_t* gather,
+                                    uint32_t* mark);
+__global__ void zs_k_restart_place(const uint8_t* stage, const uint64_t* stoff, const uint32_t* ocap,
+                                   const uint32_t* seg_len, const uint64_t* dst, const uint32_t* ptile, uint32_t M,
+                                   uint8_t* out);
+__global__ void zs_k_restart_stitch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                    const uint32_t* over, const uint32_t* rfirst, const uint32_t* soff,
+                                    const uint32_t* slen, const uint32_t* olen, const uint32_t* opos, const uint32_t* mark,
+                                    const int32_t* seg_status, const int32_t* seg_msg, const uint32_t* seg_len,
+                                    const uint32_t* seg_used, int wbits, uint32_t n, int32_t* status, int32_t* phase,
+                                    int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* want);
+__global__ void zs_k_restart_check(const uint32_t* sum, const uint32_t* want, int wbits, uint32_t n, int32_t* status,
+                                   int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* check);

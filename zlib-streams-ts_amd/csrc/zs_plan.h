@@ -950,4 +950,209 @@ static inline void zs_plan_deflate(const zs_deflate_req& r, const zs_route_opts&
   p.ml = zs_meta_layout(n, (uint32_t)p.segs.size(), p.dict, p.ndict, p.chunks.size());
 }
 
+// ---- inflate with restart points (inflateSync, inflate.ts:1267-1337).  Behind a full-flush
+// marker the bit stream is byte-aligned and the window empty, so the piece from one restart point to
+// the next is a raw deflate stream of its own but for its end: it closes with the marker's empty stored
+// block, BFINAL clear.  A stream given with k points is therefore planned as k SEGMENTS; each is copied
+// into a gather buffer with the empty final static block 03 00 appended (the last one ends by itself),
+// the copies decode as the members of one raw batch (zs_plan_inflate over their lengths, unchanged),
+// and the stitch kernel joins their results per stream (inflate_restart.hip).
+//
+// Segments of one device call at most: every decoder and the stitch run a 64-thread workgroup per
+// member, and a launch takes fewer than 2^32 threads.
+#define ZS_RESTART_SEG_MAX 67108863u  // (2^32 - 1) / 64
+#define ZS_RESTART_MIN_GAP 5u         // a marker alone: three header bits padded to a byte, 00 00 FF FF
+#define ZS_RESTART_TILE 4096u         // bytes per workgroup step of the gather and place kernels
+enum zs_restart_err {
+  ZS_RE_OK = 0,
+  ZS_RE_WBITS,      // "unsupported windowBits (use -15, 15 or 31)"
+  ZS_RE_D64,        // "deflate64 has no restart points"
+  ZS_RE_ARRAYS,     // "null restart arrays"
+  ZS_RE_NO_FIRST,   // "a stream without its first point"
+  ZS_RE_MANY,       // "too many restart points (more than 67,108,863 segments in one call)"
+  ZS_RE_FIRST_OUT,  // "the first point's out_pos must be 0"
+  ZS_RE_IN_POS,     // "restart in_pos must increase by at least 5"
+  ZS_RE_OUT_POS,    // "restart out_pos must not decrease"
+  ZS_RE_PAST_END,   // "restart in_pos past the stream's input"
+  ZS_RE_ALIGN,      // "output offsets/capacities must be multiples of 4"
+  ZS_RE_COUNT
+};
+static inline const char* zs_restart_err_text(zs_restart_err e) {
+  static const char* const kMsg[ZS_RE_COUNT] = {
+      "",
+      "unsupported windowBits (use -15, 15 or 31)",
+      "deflate64 has no restart points",
+      "null restart arrays",
+      "a stream without its first point",
+      "too many restart points (more than 67,108,863 segments in one call)",
+      "the first point's out_pos must be 0",
+      "restart in_pos must increase by at least 5",
+      "restart out_pos must not decrease",
+      "restart in_pos past the stream's input",
+      "output offsets/capacities must be multiples of 4",
+  };
+  return kMsg[e];
+}
+struct zs_restart_call {
+  uint32_t n = 0;
+  const uint32_t* in_len = nullptr;
+  const uint64_t* out_off = nullptr;  // (may be null: the host entries stage their own regions)
+  const uint32_t* out_cap = nullptr;
+  bool caller_regions = false;  // the device entry: offsets and capacities are multiples of 4
+  // stream i's points are (rin[k], rout[k]), k in rfirst[i] .. rfirst[i + 1]
+  const uint64_t* rfirst = nullptr;
+  const uint32_t* rin = nullptr;
+  const uint32_t* rout = nullptr;
+};
+// The fault that wins, in this order: the format; the arrays; the index (every stream has its first
+// point); the segment count; then the points stream by stream and point by point (out_pos of the
+// first, the step of in_pos, the step of out_pos, in_pos against the input's length); the device
+// entry's alignment rule last.  Nothing here looks at a context.
+static inline zs_restart_err zs_restart_validate(int wbits, const zs_restart_call& a) {
+  if (wbits == -16) return ZS_RE_D64;
+  if (!(wbits == -15 || wbits == 15 || wbits == 31)) return ZS_RE_WBITS;
+  if (a.n == 0) return ZS_RE_OK;
+  if (!a.rfirst || !a.rin || !a.rout) return ZS_RE_ARRAYS;
+  for (uint32_t i = 0; i < a.n; i++)
+    if (a.rfirst[i + 1] <= a.rfirst[i]) return ZS_RE_NO_FIRST;
+  if (a.rfirst[a.n] - a.rfirst[0] > ZS_RESTART_SEG_MAX) return ZS_RE_MANY;
+  for (uint32_t i = 0; i < a.n; i++)
+    for (uint64_t k = a.rfirst[i]; k < a.rfirst[i + 1]; k++) {
+      if (k == a.rfirst[i]) {
+        if (a.rout[k] != 0) return ZS_RE_FIRST_OUT;
+      } else {
+        if ((uint64_t)a.rin[k] < (uint64_t)a.rin[k - 1] + ZS_RESTART_MIN_GAP) return ZS_RE_IN_POS;
+        if (a.rout[k] < a.rout[k - 1]) return ZS_RE_OUT_POS;
+      }
+      if (a.rin[k] > a.in_len[i]) return ZS_RE_PAST_END;
+    }
+  for (uint32_t i = 0; a.out_off && i < a.n; i++)
+    if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_RE_ALIGN;
+  return ZS_RE_OK;
+}
+
+// The length of the wrapper's header in front of the deflate data: 0 raw, 2 zlib; gzip the fixed 10
+// bytes plus FEXTRA / FNAME / FCOMMENT / FHCRC (inflate.ts:600-728), or 0 when the magic, the method
+// or a reserved flag is wrong or the header does not end inside the n bytes.  FHCRC is skipped, not verified.
+ZS_PLAN_FN uint32_t zs_wrapper_header_len_of(int wbits, const uint8_t* p, uint32_t n) {
+  if (wbits < 0) return 0;
+  if (wbits <= 15) return 2;
+  if (!p || n < 10 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || (p[3] & 0xe0)) return 0;
+  const uint32_t flg = p[3];
+  uint64_t at = 10;
+  if (flg & 4) {  // FEXTRA: a 16-bit length, then the field
+    if (at + 2 > n) return 0;
+    at += 2ull + p[at] + ((uint32_t)p[at + 1] << 8);
+    if (at > n) return 0;
+  }
+  for (uint32_t f = 8; f <= 16; f <<= 1)  // FNAME, FCOMMENT: to a zero byte
+    if (flg & f) {
+      while (at < n && p[at]) at++;
+      if (at >= n) return 0;
+      at++;
+    }
+  if (flg & 2) at += 2;  // FHCRC
+  return at <= n ? (uint32_t)at : 0u;
+}
+// ... and whether the header in front of the first point `at` is well formed and ends exactly there
+ZS_PLAN_FN bool zs_wrapper_header_ok(int wbits, const uint8_t* p, uint32_t n, uint32_t at) {
+  if (wbits < 0) return at == 0;
+  if (wbits <= 15) {  // inflate.ts:560-597: method 8, CINFO <= 7, the check mod 31, no FDICT
+    if (at != 2 || n < 2) return false;
+    const uint32_t cmf = p[0], flg = p[1];
+    return (cmf & 15u) == 8u && (cmf >> 4) <= 7u && ((cmf << 8) + flg) % 31u == 0u && !(flg & 0x20u);
+  }
+  return at != 0 && zs_wrapper_header_len_of(wbits, p, n) == at;
+}
+
+struct zs_restart_plan {
+  uint32_t n = 0, M = 0;          // streams, segments
+  bool in_place = true;           // every restart out_pos is a multiple of 4: the segments decode where they belong
+  std::vector<uint32_t> rfirst;   // each stream's first segment (rfirst[n] = M)
+  std::vector<uint32_t> rstream;  // each segment's stream
+  std::vector<uint32_t> soff, slen;  // the segment's bytes in its stream's input
+  std::vector<uint64_t> goff;     // ... its copy's place in the gather buffer (a multiple of 16)
+  std::vector<uint32_t> glen;     // ... and length: slen + 2 (03 00) unless it is its stream's last
+  std::vector<uint32_t> opos;     // the segment's first byte in its stream's output
+  std::vector<uint32_t> olen;     // the bytes it must produce (the last one: its capacity)
+  std::vector<uint32_t> ocap;     // its capacity: olen, cut at the stream's out_cap
+  std::vector<uint64_t> stoff;    // staging route: its 4-aligned region in the staging buffer
+  std::vector<uint32_t> over;     // per stream: the last out_pos lies past out_cap (the capacity outcome)
+  std::vector<uint32_t> gtile, ptile;  // M + 1 each: prefix sums of the gather's / the place's tiles
+  uint64_t gather_bytes = 0, stage_bytes = 0;
+};
+// points that passed zs_restart_validate
+static inline void zs_plan_restart(uint32_t n, const uint32_t* in_len, const uint32_t* out_cap, const uint64_t* rfirst,
+                                   const uint32_t* rin, const uint32_t* rout, zs_restart_plan& p) {
+  p.n = n;
+  p.in_place = true;
+  p.rfirst.assign(n + 1, 0);
+  p.over.assign(n, 0);
+  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.glen, &p.opos, &p.olen, &p.ocap}) v->clear();
+  p.goff.clear();
+  p.stoff.clear();
+  p.gtile.assign(1, 0);
+  p.ptile.assign(1, 0);
+  uint64_t g = 0, st = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    p.rfirst[i] = (uint32_t)p.rstream.size();
+    for (uint64_t k = rfirst[i]; k < rfirst[i + 1]; k++) {
+      const bool last = k + 1 == rfirst[i + 1];
+      const uint32_t len = (last ? in_len[i] : rin[k + 1]) - rin[k];
+      const uint32_t room = out_cap[i] > rout[k] ? out_cap[i] - rout[k] : 0u;
+      const uint32_t want = last ? room : rout[k + 1] - rout[k];
+      const uint32_t cap = std::min(want, room);
+      if (k > rfirst[i] && (rout[k] & 3u)) p.in_place = false;
+      if (last) p.over[i] = rout[k] > out_cap[i];
+      p.rstream.push_back(i);
+      p.soff.push_back(rin[k]);
+      p.slen.push_back(len);
+      p.glen.push_back(last ? len : len + 2);
+      p.goff.push_back(g);
+      g += ((uint64_t)p.glen.back() + 15) & ~15ull;  // (03 00, then zeros: the readers load whole aligned words)
+      p.opos.push_back(rout[k]);
+      p.olen.push_back(want);
+      p.ocap.push_back(cap);
+      p.stoff.push_back(st);
+      st += ((uint64_t)cap + 3) & ~3ull;
+      p.gtile.push_back(p.gtile.back() + (uint32_t)(((uint64_t)p.glen.back() + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
+      // (the place's words: the destination's leading bytes of its first word count too)
+      p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)cap + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
+    }
+  }
+  p.M = (uint32_t)p.rstream.size();
+  p.rfirst[n] = p.M;
+  p.gather_bytes = g + 16;
+  p.stage_bytes = p.in_place ? 0 : st + 16;
+}
+// The restart call's section of the metadata block, behind the segment batch's own (zs_meta_layout of
+// M, which inflate_device uploads): what the restart kernels read of the streams and of the segments; the data
+// checksum's part map follows at `bytes`.
+struct zs_restart_layout {
+  size_t in_off, in_len, out_off, over, rfirst, src, soff, slen, goff, glen, ooff, ocap, olen, opos, dst,
+      gtile, ptile, bytes;
+  zs_restart_layout(size_t base, uint32_t n, uint32_t M) {
+    size_t o = base;
+    auto take = [&](size_t b) { size_t r = o; o = (o + b + 255) & ~size_t(255); return r; };
+    in_off = take(8ull * n);
+    in_len = take(4ull * n);
+    out_off = take(8ull * n);
+    over = take(4ull * n);
+    rfirst = take(4ull * (n + 1));
+    src = take(8ull * M);   // the segment's first byte in the caller's input
+    soff = take(4ull * M);  // ... and in its stream's
+    slen = take(4ull * M);
+    goff = take(8ull * M);
+    glen = take(4ull * M);
+    ooff = take(8ull * M);  // where it decodes: in the caller's output (in place) or the staging buffer
+    ocap = take(4ull * M);
+    olen = take(4ull * M);
+    opos = take(4ull * M);
+    dst = take(8ull * M);   // its place in the caller's output
+    gtile = take(4ull * (M + 1));
+    ptile = take(4ull * (M + 1));
+    bytes = o;
+  }
+};
+
 #endif

@@ -53,7 +53,18 @@ export interface DecompressBatchOptions extends BatchOptions {
    * shared by all inputs, or one per input (null = none).  A "deflate" input with FDICT and the wrong
    * dictionary fails with "process error: -3", without one with "process error: 2". */
   dictionary?: ArrayBufferView | (ArrayBufferView | null)[];
+  /** Restart points (inflateSync, inflate.ts:1267-1337): per input (null = none) the [inPos, outPos] pairs of its
+   * Z_FULL_FLUSH markers, without its start -- inPos the offset in the input of the first byte behind a marker,
+   * outPos the uncompressed bytes before it.  The segments between the points decode in parallel and come back
+   * as one stream, with zlib semantics (the reference's window-wrap copy is not reproduced on this path).  A
+   * stream whose points do not decode it fails with "process error: -3", zmsg "restart points do not decode
+   * the stream"; points out of order, or past the input, fail with "init failed: -2" (code "-2").  Needs
+   * `outCapacity`; without it, with `dictionary` or for "deflate64-raw" it is a TypeError. */
+  restartPoints?: ([number, number][] | null)[];
 }
+/** The length of the wrapper's header in front of the deflate data: 0 for "deflate-raw", 2 for "deflate", for
+ * "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC, or 0 when that header is malformed or does not fit. */
+export function wrapperHeaderLength(input: Uint8Array, format?: string): number;
 export type Settled<T> = { status: "fulfilled"; value: T } | { status: "rejected"; reason: Error & { zmsg?: string } };
 
 export interface CompressDetail {

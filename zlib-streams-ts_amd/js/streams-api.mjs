@@ -163,14 +163,75 @@ async function runCompress(inputs, format, options) {
   return res.outputs.map((out, i) => (res.status[i] === Z_STREAM_END ? out : streamError(res.status[i], PHASE_FINISH)));
 }
 
+// The length of the wrapper's header in front of the deflate data (zs_wrapper_header_len in zs_gpu.h): 0
+// for "deflate-raw", 2 for "deflate", for "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC -- or 0 when the
+// magic, the method or a reserved flag is wrong or the header does not end inside the input.
+export function wrapperHeaderLength(input, format = "gzip") {
+  if (format === "deflate-raw" || format === "deflate64-raw") return 0;
+  if (format !== "gzip") return 2;
+  const p = input, n = input.length;
+  if (n < 10 || p[0] !== 0x1f || p[1] !== 0x8b || p[2] !== 8 || (p[3] & 0xe0)) return 0;
+  let at = 10;
+  if (p[3] & 4) {
+    if (at + 2 > n) return 0;
+    at += 2 + p[at] + (p[at + 1] << 8);
+    if (at > n) return 0;
+  }
+  for (const f of [8, 16])
+    if (p[3] & f) {
+      while (at < n && p[at]) at++;
+      if (at >= n) return 0;
+      at++;
+    }
+  if (p[3] & 2) at += 2;
+  return at <= n ? at : 0;
+}
+
+// options.restartPoints: one array per input (null = none) of [inPos, outPos] pairs, the input's restart
+// points WITHOUT its start -- inPos the offset of the first byte behind a Z_FULL_FLUSH marker, outPos the
+// uncompressed bytes before it (zs_inflate_batch_restart in zs_gpu.h; inflateSync, inflate.ts:1267-1337).
+// The segments decode in parallel, with zlib semantics.  Needs outCapacity; with a dictionary it is a
+// TypeError (not built).  Returns, per input, the flat pairs with the start -- [header length, 0] -- first.
+function restartOf(options, ins, format) {
+  const r = options.restartPoints;
+  if (r === undefined || r === null) return undefined;
+  if (options.dictionary !== undefined && options.dictionary !== null)
+    throw new TypeError("restartPoints and dictionary cannot be combined");
+  if (options.outCapacity === undefined || options.outCapacity === null)
+    throw new TypeError("restartPoints need outCapacity");
+  if (format === "deflate64-raw") throw new TypeError("deflate64-raw has no restart points");
+  if (!Array.isArray(r) || r.length !== ins.length)
+    throw new TypeError("restartPoints must be an array with one entry per input");
+  const u32 = (x) => Number.isInteger(x) && x >= 0 && x <= 0xffffffff;
+  return r.map((ps, i) => {
+    if (ps === null || ps === undefined) ps = [];
+    if (!Array.isArray(ps)) throw new TypeError("restartPoints: an array of [inPos, outPos] pairs, or null, per input");
+    const flat = [wrapperHeaderLength(ins[i], format), 0];
+    for (const pt of ps) {
+      if (!Array.isArray(pt) || pt.length !== 2 || !u32(pt[0]) || !u32(pt[1]))
+        throw new TypeError("restartPoints: [inPos, outPos] pairs of integers in 0 .. 2^32 - 1");
+      flat.push(pt[0], pt[1]);
+    }
+    return flat;
+  });
+}
+
 async function runDecompress(inputs, format, options) {
   options = options || {};
   const wbits = decompressWbits(format);
   const ins = checkInputs(inputs);
   // no outCapacity: unbounded output, as DecompressionStream (streams.ts:46,132-182); a caller cap is a cap
   // (a dictionary for "gzip" / "deflate64-raw" rejects with code "-2": inflateSetDictionary's Z_STREAM_ERROR)
-  const res = await addon.decompressBatch(ins, wbits, options.outCapacity, devicesOf(options),
-                                          dictionariesOf(options, ins.length));
+  let res;
+  try {
+    res = await addon.decompressBatch(ins, wbits, options.outCapacity, devicesOf(options),
+                                      dictionariesOf(options, ins.length), restartOf(options, ins, format));
+  } catch (e) {
+    // points the entry refuses (zs_gpu.h): ZS_STREAM_ERROR, reported as the stream layer reports it
+    if (options.restartPoints && e.code === String(Z_STREAM_ERROR))
+      throw Object.assign(streamError(Z_STREAM_ERROR, PHASE_INIT), { code: e.code, zmsg: e.message });
+    throw e;
+  }
   return res.outputs.map((out, i) => {
     if (res.status[i] === Z_STREAM_END) return out;
     const err = streamError(res.status[i], res.phase[i]);
@@ -225,7 +286,7 @@ export async function decompressBatchDetailed(inputs, format = "deflate", option
   options = options || {};
   const ins = checkInputs(inputs);
   return addon.decompressBatch(ins, decompressWbits(format), options.outCapacity, devicesOf(options),
-                               dictionariesOf(options, ins.length));
+                               dictionariesOf(options, ins.length), restartOf(options, ins, format));
 }
 export const engineVersion = () => addon.version();
 export const selfTest = (device = 0) => addon.selfTest(device);

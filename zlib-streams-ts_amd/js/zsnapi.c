@@ -216,6 +216,10 @@ typedef struct {
    * flush_first[i + 1]); NULL: none given */
   uint64_t *flush_first;
   uint32_t *flush_pos;
+  /* restart points (zs_pool_inflate_batch_restart): input i's points, its start included, are
+   * (restart_in[k], restart_out[k]) for k in restart_first[i] .. restart_first[i + 1]; NULL: none given */
+  uint64_t *restart_first;
+  uint32_t *restart_in, *restart_out;
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -228,6 +232,7 @@ static void job_free(job *j) {
   free(j->status); free(j->phase); free(j->msg); free(j->base);
   free(j->dict); free(j->dict_off); free(j->dict_len);
   free(j->flush_first); free(j->flush_pos);
+  free(j->restart_first); free(j->restart_in); free(j->restart_out);
   if (!j->out_given) {
     if (j->unbounded) zs_free(j->out);
     else free(j->out);
@@ -270,6 +275,10 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
                                        j->dict_off, j->dict_len);
+  else if (j->inflate && j->restart_first)
+    j->rc = zs_pool_inflate_batch_restart(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
+                                          j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check,
+                                          j->restart_first, j->restart_in, j->restart_out);
   else if (j->inflate && j->unbounded)
     j->rc = zs_pool_inflate_batch_auto(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, &j->out, j->out_off,
                                        j->status, j->phase, j->msg, j->olen, j->cons, j->check);
@@ -505,6 +514,38 @@ static int copy_flush(napi_env env, job *j, napi_value arr) {
   return 0;
 }
 
+/* The restart points of a decompress job: arr[i] a flat array of numbers in0, out0, in1, out1, ... (input i's
+ * points, its start first).  0, -1 out of memory, -2 not such an array.  (Their order and range are the
+ * entry's to check.) */
+static int copy_restart(napi_env env, job *j, napi_value arr) {
+  const int rc = copy_flush(env, j, arr);  /* (the same shape: one list of 32-bit values per input) */
+  uint64_t *first = j->flush_first;
+  uint32_t *flat = j->flush_pos;
+  j->flush_first = NULL;
+  j->flush_pos = NULL;
+  int r = rc;
+  if (r == 0) {
+    const uint64_t tot = first[j->n];
+    for (uint32_t i = 0; i <= j->n && r == 0; i++)
+      if (first[i] & 1) r = -2;
+    j->restart_in = (uint32_t *)calloc((size_t)tot / 2 + 1, 4);
+    j->restart_out = (uint32_t *)calloc((size_t)tot / 2 + 1, 4);
+    if (r == 0 && (!j->restart_in || !j->restart_out)) r = -1;
+    for (uint64_t k = 0; r == 0 && k < tot / 2; k++) {
+      j->restart_in[k] = flat[2 * k];
+      j->restart_out[k] = flat[2 * k + 1];
+    }
+    for (uint32_t i = 0; r == 0 && i <= j->n; i++) first[i] /= 2;
+  }
+  if (r == 0) {
+    j->restart_first = first;
+    first = NULL;
+  }
+  free(first);
+  free(flat);
+  return r;
+}
+
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
  *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined,
  *               memLevel: number | undefined, flushAt: (number[] | null)[] | undefined) ->
@@ -604,16 +645,29 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
 }
 
 /* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,
- *                 dictionaries: (Uint8Array | null)[] | undefined) ->
+ *                 dictionaries: (Uint8Array | null)[] | undefined, restart: number[][] | undefined) ->
  *   Promise<{status, phase: Int32Array, message: string[], outputs: Uint8Array[], consumed: Int32Array,
  *            check: Uint32Array}>
- * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto). */
+ * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto).
+ * restart: per input the flat pairs in_pos, out_pos of its points, the start first (zs_pool_inflate_batch_restart,
+ * zs_gpu.h); needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any
+ * device is touched. */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 6;
+  napi_value argv[6];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 2)
-    return throw_code(env, ZS_STREAM_ERROR, "decompressBatch(inputs, wbits[, outCapacity[, devices[, dictionaries]]])");
+    return throw_code(env, ZS_STREAM_ERROR,
+                      "decompressBatch(inputs, wbits[, outCapacity[, devices[, dictionaries[, restart]]]])");
+  {
+    napi_valuetype rt = napi_undefined, dt0 = napi_undefined, ct0 = napi_undefined;
+    if (argc > 5) napi_typeof(env, argv[5], &rt);
+    if (argc > 4) napi_typeof(env, argv[4], &dt0);
+    if (argc > 2) napi_typeof(env, argv[2], &ct0);
+    if (rt != napi_undefined && rt != napi_null &&
+        ((dt0 != napi_undefined && dt0 != napi_null) || ct0 == napi_undefined || ct0 == napi_null))
+      return throw_code(env, ZS_STREAM_ERROR, "restart points need outCapacity and take no preset dictionaries");
+  }
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -664,6 +718,16 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
       job_free(j);
       return rc == -1 ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
                       : throw_code(env, ZS_STREAM_ERROR, "dictionaries must be (Uint8Array | null)[], one per input");
+    }
+  }
+  napi_valuetype rt = napi_undefined;
+  if (argc > 5) napi_typeof(env, argv[5], &rt);
+  if (rt != napi_undefined && rt != napi_null) {
+    const int rc = copy_restart(env, j, argv[5]);
+    if (rc != 0) {
+      job_free(j);
+      return rc == -1 ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
+                      : throw_code(env, ZS_STREAM_ERROR, "restart must be number[][]: in_pos, out_pos pairs, one list per input");
     }
   }
   return queue_job(env, j, "zs.decompressBatch");

@@ -220,6 +220,16 @@ def lib():
         L.zs_pool_deflate_batch_flush.argtypes = L.zs_deflate_batch_ex.argtypes + _fl
         L.zs_deflate_bound_flush.restype = ctypes.c_uint64
         L.zs_deflate_bound_flush.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
+    if hasattr(L, "zs_inflate_batch_restart"):  # restart_first, restart_in, restart_out behind the counterpart's arguments
+        _rs = [_U64P, _U32P, _U32P]
+        L.zs_inflate_batch_restart.argtypes = L.zs_inflate_batch_ex.argtypes + _rs
+        L.zs_pool_inflate_batch_restart.argtypes = L.zs_inflate_batch_ex.argtypes + _rs
+        L.zs_inflate_batch_restart_device.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, _P, _U64P, _U32P, _P, _U64P,
+                                                      _U32P, _P, _P, _P, _P, _P, _P, _P] + _rs
+        L.zs_wrapper_header_len.restype = ctypes.c_uint32
+        L.zs_wrapper_header_len.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32]
+        L.zs_last_flush_index.restype = ctypes.c_uint64
+        L.zs_last_flush_index.argtypes = [_P, _U32P, ctypes.c_uint64]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -307,6 +317,44 @@ def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0, n_flush: 
 def deflate_capacity(n: int, fmt: str = "deflate-raw", dict_len: int = 0) -> int:
     """deflate_bound rounded up to the engine's 4-byte output granularity."""
     return (deflate_bound(n, fmt, dict_len) + 3) & ~3
+
+
+def wrapper_header_len(data: bytes, fmt: str = "gzip") -> int:
+    """zs_wrapper_header_len: the length of the wrapper's header in front of the deflate data -- 0 for
+    "deflate-raw", 2 for "deflate", for "gzip" the parsed length (10 plus FEXTRA / FNAME / FCOMMENT /
+    FHCRC), or 0 when that header is malformed or does not fit.  Host arithmetic, no GPU."""
+    data = bytes(data)
+    return int(lib().zs_wrapper_header_len(decompress_wbits(fmt), data, len(data)))
+
+
+def decompress_restart(inputs, fmt, restart, out_caps, zdict=None):
+    """The `restart` keyword of the decompress entries: one list per stream (None / empty = none) of
+    (in_pos, out_pos) pairs, the stream's restart points WITHOUT its start -- in_pos the offset in the
+    stream's input of the first byte behind a Z_FULL_FLUSH marker, out_pos the uncompressed bytes before
+    it (zs_inflate_batch_restart; inflateSync, inflate.ts:1267-1337).  The start, (the wrapper's header
+    length, 0), is prepended here.  Returns the (restart_first, restart_in, restart_out) ctypes arrays.
+    The capacities must be given, and dictionaries are not built with restart points: ValueError,
+    before any call.  Points the entry refuses are its ZS_STREAM_ERROR."""
+    if out_caps is None:
+        raise ValueError("restart points need out_caps (the unbounded output is not built with them)")
+    if zdict is not None:
+        raise ValueError("restart points with a preset dictionary are not built")
+    per = list(restart)
+    if len(per) != len(inputs):
+        raise ValueError("restart: %d point lists for %d inputs" % (len(per), len(inputs)))
+    first, rin, rout = [0], [], []
+    for data, ps in zip(inputs, per):
+        pts = [(wrapper_header_len(data, fmt), 0)]
+        for pt in ps or []:
+            a, b = pt
+            for x in (a, b):
+                if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x <= 0xffffffff:
+                    raise ValueError("restart: points are pairs of ints in 0 .. 2^32 - 1")
+            pts.append((a, b))
+        rin.extend(a for a, _ in pts)
+        rout.extend(b for _, b in pts)
+        first.append(len(rin))
+    return _arr(ctypes.c_uint64, first), _arr(ctypes.c_uint32, rin), _arr(ctypes.c_uint32, rout)
 
 
 def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
@@ -424,7 +472,9 @@ class Engine:
         compress_strategy(strategy, zdict)
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
         per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
+        self._flush_counts = None
         if per is not None:
+            self._flush_counts = [len(ps) for ps in per]
             return _deflate_host(self._L, self._L.zs_deflate_batch_flush, self._ctx, inputs, fmt, level, self._check,
                                  flush=per)
         if not _params_default(window_bits, mem_level):
@@ -444,17 +494,22 @@ class Engine:
                                                       flush_at, flush_every))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                             out_caps: Optional[Sequence[int]] = None, zdict=None):
+                             out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None):
         """Returns [(status, phase, msg, bytes, consumed)].  out_caps None: unbounded
         output, as DecompressionStream (zs_inflate_batch_auto); else per-stream caps.
         zdict: a preset dictionary for every input (bytes), or one per input (a
-        list; None = none) -- "deflate-raw" and "deflate" only (zs_inflate_batch_dict*)."""
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict)]
+        list; None = none) -- "deflate-raw" and "deflate" only (zs_inflate_batch_dict*).
+        restart: one list per input of (in_pos, out_pos) restart points (decompress_restart;
+        zs_inflate_batch_restart: the segments decode in parallel, zlib semantics; needs out_caps)."""
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                                  out_caps: Optional[Sequence[int]] = None, zdict=None):
+                                  out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
+        if restart is not None:
+            rs = decompress_restart(inputs, fmt, restart, out_caps, zdict)
+            return _inflate_host(L, L.zs_inflate_batch_restart, self._ctx, inputs, fmt, out_caps, self._check, rs)
         if zdict is not None:
             d = _dict_layout(zdict, len(inputs))
             if out_caps is None:
@@ -465,8 +520,27 @@ class Engine:
         return _inflate_host(L, L.zs_inflate_batch_ex, self._ctx, inputs, fmt, out_caps, self._check)
 
     def decompress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                         out_caps: Optional[Sequence[int]] = None, zdict=None) -> List[bytes]:
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict))
+                         out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None) -> List[bytes]:
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart))
+
+    def last_flush_index(self) -> List[List[int]]:
+        """zs_last_flush_index: for the last compress call with flush points on this engine
+        (compress_batch*(..., flush_at / flush_every) or compress_device), one list per stream of the
+        offsets in its output of the byte behind each marker: the in_pos of the restart points whose
+        out_pos are the flush positions.  Synchronises."""
+        per = getattr(self, "_flush_counts", None)
+        if not per:
+            return []
+        total = sum(per)
+        buf = (ctypes.c_uint32 * max(1, total))()
+        k = int(self._L.zs_last_flush_index(self._ctx, buf, total))
+        if k != total:
+            raise ZsError("zs_last_flush_index: %d points, %d expected" % (k, total))
+        out, at = [], 0
+        for c in per:
+            out.append(list(buf[at: at + c]))
+            at += c
+        return out
 
     # ---------------------------------------------------- device-resident
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
@@ -483,7 +557,9 @@ class Engine:
         code = compress_params(fmt, window_bits, mem_level, dict_off, strategy)
         per = compress_flush([in_len[i] for i in range(n)], flush_at, flush_every, dict_off, strategy, window_bits,
                              mem_level)
+        self._flush_counts = None
         if per is not None:
+            self._flush_counts = [len(ps) for ps in per]
             first, pos = _flush_arrays(per)
             r = self._L.zs_deflate_batch_flush_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
                                                       _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
@@ -522,9 +598,29 @@ class Engine:
 
     def decompress_device(self, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                           d_status: int, d_phase: int, d_msg: int, d_out_len: int, d_consumed: int,
-                          hip_stream: int = 0, d_dict: int = 0, dict_off=None, dict_len=None, d_check: int = 0):
+                          hip_stream: int = 0, d_dict: int = 0, dict_off=None, dict_len=None, d_check: int = 0,
+                          restart=None, headers=None):
         """d_dict / dict_off / dict_len: preset dictionaries (zs_inflate_batch_dict_device:
-        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none)."""
+        device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
+        restart: one list per stream of (in_pos, out_pos) restart points without the start
+        (zs_inflate_batch_restart_device); the streams' bytes are on the device, so `headers` gives the
+        first bytes of each stream on the host (enough to hold its wrapper's header; not needed for
+        "deflate-raw" and "deflate") for the first point."""
+        if restart is not None:
+            if dict_off is not None:
+                raise ValueError("restart points with a preset dictionary are not built")
+            if headers is None:
+                if fmt == "gzip":
+                    raise ValueError("restart points of gzip streams on the device need `headers`")
+                headers = [b""] * n
+            rs = decompress_restart(headers, fmt, restart, out_cap)
+            r = self._L.zs_inflate_batch_restart_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
+                                                        _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase),
+                                                        _P(d_msg), _P(d_out_len), _P(d_consumed),
+                                                        _P(d_check) if d_check else None,
+                                                        _P(hip_stream) if hip_stream else None, *rs)
+            self._check(r, "zs_inflate_batch_restart_device")
+            return
         if dict_off is not None:
             r = self._L.zs_inflate_batch_dict_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
                                                      _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase),
@@ -800,8 +896,11 @@ class Pool:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
                                                       flush_at, flush_every))
 
-    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
+    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
         L = self._L
+        if restart is not None:  # (zs_last_flush_index is not offered on the pool: an index comes from an Engine)
+            rs = decompress_restart(inputs, fmt, restart, out_caps, zdict)
+            return _inflate_host(L, L.zs_pool_inflate_batch_restart, self._pool, inputs, fmt, out_caps, self._check, rs)
         if zdict is not None:
             d = _dict_layout(zdict, len(inputs))
             if out_caps is None:
@@ -811,11 +910,11 @@ class Pool:
             return _inflate_host_auto(L, L.zs_pool_inflate_batch_auto, self._pool, inputs, fmt, self._check)
         return _inflate_host(L, L.zs_pool_inflate_batch, self._pool, inputs, fmt, out_caps, self._check)
 
-    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict)]
+    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart)]
 
-    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None):
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict))
+    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart))
 
 
 _default: Optional[Engine] = None
