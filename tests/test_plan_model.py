@@ -130,3 +130,45 @@ def test_parse_waves(plans):
     has(plans["PW_2048"], pscr=4 * 3596 * (32768 // 1024 + 2049))
     has(plans["PW_opt2_2048"], pscr=4 * 2060 * (32768 // 512 + 2049))
     has(plans["PW_opt4_2048"], pscr=4 * 1292 * (32768 // 256 + 2049))
+
+
+# ---- the routes tests/test_gpu_inflate_regions.py forces with options and asserts by count on the GPU: its batches'
+# lengths (14 large members of 11,640 .. 102,571 input bytes at indices 0-13, four small ones behind them)
+def test_region_batches_take_the_segmented_decode_and_its_small_batch_resolve(plans):
+    # more than seg_small_min (4,096) input bytes: segmented; under 64 KiB of input on average: the 1,024-bit window,
+    # 2,048-bit lanes, whole pieces
+    has(plans["R_few"], seg="0-13", split="-", wave="-", wave_min=4096, lane_block=1, lane_rt=2, walk="0/1024/0",
+        bits=2048, seg_split=0, nwalk=14, resolve="512/65536", decode="0/1")
+    has(plans["R_few_split1"], seg="0-13", seg_split=1, resolve="512/65536")
+    has(plans["R_few_bits"], seg="0-13", bits=1024, walk="0/1024/0")
+    # 89,939 and 102,571 input bytes alone: the wide window, 4,096-bit lanes, pieces cut in two
+    has(plans["R_wide"], seg="0-3", walk="0/2048/1", bits=4096, seg_split=1, resolve="512/65536")
+
+
+def test_more_than_two_segmented_members_per_compute_unit_take_the_other_resolve(plans):
+    # 520 > 2 x 256 members of 2,322 .. 24,960 input bytes, seg_small_min = 256
+    for name in ("R520", "R520_gzip"):
+        has(plans[name], seg="0-519", split="-", wave="-", wave_min=256, resolve="256/32768", nwalk=520, seg_split=0,
+            walk="0/1024/0", bits=2048, lane_block=1, lane_rt=2, gfb=256)
+    has(plans["R16"], seg="0-15", resolve="512/65536", nwalk=16, gfb=16)
+
+
+def test_region_batches_without_the_segmented_decode(plans):
+    # zlib / gzip, every member over one input byte large: the wave kernel, with and without the reference's calls
+    has(plans["R_wave"], seg="-", split="-", wave="0-17", wave_min=1, wave_refw=1, wave_lanes=0)
+    has(plans["R_wave_nowrap"], seg="-", split="-", wave="0-17", wave_refw=0, wave_lanes=0)
+    # raw deflate without the window-wrap copy splits: 18 x (2 x 64 + 4) x 262,208 scratch bytes fit 2 GiB
+    assert 18 * (2 * 64 + 4) * 262208 <= 2 << 30
+    has(plans["R_split_raw"], seg="-", split="0-17", wave="-", piece_cap=262208, val_stride=262208)
+    # members over 1,024 input bytes large: a wave each, or with lane_large_min = 1 a lane each
+    has(plans["R_nolanes"], seg="-", split="-", wave="0-13,16-17", wave_min=1024, wave_refw=1, wave_lanes=0)
+    has(plans["R_lanes"], seg="-", split="-", wave="0-13,16-17", wave_min=1024, wave_refw=1, wave_lanes=1, wave_block=1,
+        wave_rt=2)
+
+
+def test_expanding_members_leave_the_segmented_decode(plans):
+    # a capacity past 64 KiB and 8 bytes of it per input byte: deflate64 splits, raw deflate takes the wave kernel
+    # (the window-wrap copy) or splits (without it); the text member beside them is segmented
+    has(plans["R_zeros64"], seg="2", split="0-1", wave="-", piece_cap=100064, val_stride=100064, decode="1/0")
+    has(plans["R_zeros"], seg="2", split="-", wave="0-1", wave_refw=1, wave_lanes=0)
+    has(plans["R_zeros_nowrap"], seg="2", split="0-1", wave="-", piece_cap=262148, val_stride=262148)

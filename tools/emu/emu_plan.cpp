@@ -110,6 +110,59 @@ int main() {
     inflate_case("P7", o, 31, std::vector<Member>(16, {20000, 65536}));
   }
   inflate_case("P8", def, -15, std::vector<Member>(2, {300000, 1048576}));
+  // the batches of tests/test_gpu_inflate_regions.py: 14 large members (7, each with its output rounded up to 4
+  // and with 64 more) and four small ones behind them
+  std::vector<Member> few;
+  for (const Member& x : {Member{11640, 33004}, {35527, 70004}, {49609, 150004}, {89939, 200004}, {102571, 262144},
+                          {25924, 157920}, {70025, 70000}}) {
+    few.push_back(x);
+    few.push_back({x.in_len, x.out_cap + 64});
+  }
+  for (const Member& x : {Member{2, 0}, {20, 64}, {2322, 6004}, {3008, 3004}}) few.push_back(x);
+  inflate_case("R_few", def, -15, few);
+  {
+    zs_route_opts o;
+    o.seg_split = 1;
+    inflate_case("R_few_split1", o, -15, few);
+    o = zs_route_opts();
+    o.seg_bits = 1024;
+    inflate_case("R_few_bits", o, -15, few);
+    o = zs_route_opts();
+    o.inflate_seg = false;
+    o.inflate_wave_min = 1;
+    inflate_case("R_wave", o, 15, few);
+    o.inflate_ref_wrap = false;
+    inflate_case("R_wave_nowrap", o, 31, few);
+    inflate_case("R_split_raw", o, -15, few);
+    o = zs_route_opts();
+    o.inflate_seg = false;
+    o.inflate_wave_min = 1024;
+    inflate_case("R_nolanes", o, -15, few);
+    o.lane_large_min = 1;
+    inflate_case("R_lanes", o, -15, few);
+  }
+  // the three with 64 KiB of input and more on average: the wide window, pieces cut in two
+  inflate_case("R_wide", def, -15, std::vector<Member>(few.begin() + 6, few.begin() + 10));
+  {
+    // 6,001 / 33,002 / 70,003 bytes from about 2 / 12 / 25 KB of input, seg_small_min 256: 520 and 16 of them
+    zs_route_opts o;
+    o.seg_small_min = 256;
+    std::vector<Member> many;
+    const Member kinds[3] = {{2322, 6004}, {11640, 33004}, {24960, 70004}};
+    for (uint32_t k = 0; k < 520; k++) many.push_back({kinds[k % 3].in_len, kinds[k % 3].out_cap + 64 * ((k / 40) % 2)});
+    inflate_case("R520", o, -15, many);
+    inflate_case("R520_gzip", o, 31, many);
+    many.resize(16);
+    inflate_case("R16", o, -15, many);
+  }
+  // members whose capacity shows a high expansion, a text member beside them
+  inflate_case("R_zeros64", def, -16, {{369, 100000}, {369, 100064}, {11640, 33004}});
+  inflate_case("R_zeros", def, -15, {{100, 70004}, {454, 262148}, {11640, 33004}});
+  {
+    zs_route_opts o;
+    o.inflate_ref_wrap = false;
+    inflate_case("R_zeros_nowrap", o, -15, {{100, 70004}, {454, 262148}, {11640, 33004}});
+  }
   deflate_case("D1", def, 6, {100, 65538});
   deflate_case("D_65537", def, 6, {65537});
   deflate_case("D_200000", def, 6, {200000});
