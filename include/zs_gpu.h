@@ -549,6 +549,12 @@ uint32_t zs_last_inflate_seg_count(zs_ctx *ctx);
  * the batch was cut into (a host entry's chunks added up).  Known when the
  * call returns; does not synchronize.  For tests and tuning. */
 uint32_t zs_last_checksum_parts(zs_ctx *ctx);
+/* Chunks of streams that the last host-buffer deflate / inflate call on the
+ * context ran as (options "host_chunk_min", "host_pack_min" below): 1 or 4
+ * after a host call, 0 after a device call (the checksum entries leave it
+ * alone).  Known when the call returns; does not synchronize.  For tests and
+ * tuning. */
+uint32_t zs_last_host_chunks(zs_ctx *ctx);
 double zs_last_phase_ms(zs_ctx *ctx, const char *phase);
 void zs_set_timing(zs_ctx *ctx, int on);
 /* Engine options: "timing" (0/1, as zs_set_timing); "inflate_fast" (default 1):
@@ -601,7 +607,14 @@ void zs_set_timing(zs_ctx *ctx, int on);
  * longer than this computes its data checksums (gzip / zlib check values, the
  * checksum entries, the inflate trailer check) in parts of "checksum_part"
  * bytes (a power of two 1024 .. 1048576, default 65536), a wave per part, and
- * joins them per stream; other batches take one wave per stream.
+ * joins them per stream; other batches take one wave per stream;
+ * "host_chunk_min" (bytes, default 33554432; 0 = never): a host-buffer batch
+ * of at least 64 streams and this many input bytes runs as four chunks of
+ * streams, cut at n/8, 4n/8 and 7n/8, whose staging, kernels and copies back
+ * overlap (other batches: one chunk); "host_pack_min" (bytes, default
+ * 67108864): the floor of the first size of the host entries' packed-output
+ * buffers, min(capacities, max(4 x input, host_pack_min)), which grow when a
+ * chunk's output does not fit.
  * These options never change output bytes or check values.  "inflate_ref_wrap" (default 1)
  * does: 1 reproduces the reference's inflate_fast window-wrap copy
  * (inffast.ts:133-147), which changes the output of members whose match

@@ -130,6 +130,7 @@ struct zs_ctx {
   hipStream_t h2d = nullptr, d2h = nullptr;  // the host entries' copies, beside the kernels (host_batch)
   std::vector<hipEvent_t> hev;               // their events, reused
   bool keep_counts = false;                  // a later chunk of one host batch: the lane / seg counts go on
+  uint32_t host_chunks = 0;                  // the chunks of the last host-buffer call (zs_last_host_chunks)
   std::vector<uint8_t> hmeta;
   size_t last_n = 0;
   // timing
@@ -256,6 +257,8 @@ static const Option kOptions[] = {
     OPT_INT("checksum_split", o.checksum_split, zs_checksum_split_ok(v), "checksum_split must be >= 0"),
     OPT_INT("checksum_part", o.checksum_part, zs_checksum_part_ok(v),
             "checksum_part must be a power of two, 1024 .. 1048576"),
+    OPT_INT("host_chunk_min", o.host_chunk_min, zs_host_chunk_min_ok(v), "host_chunk_min must be >= 0"),
+    OPT_INT("host_pack_min", o.host_pack_min, zs_host_pack_min_ok(v), "host_pack_min must be >= 0"),
 };
 
 extern "C" {
@@ -380,6 +383,7 @@ uint32_t zs_last_inflate_seg_count(zs_ctx* c) {
   return v;
 }
 uint32_t zs_last_checksum_parts(zs_ctx* c) { return c ? c->ck_parts : 0u; }
+uint32_t zs_last_host_chunks(zs_ctx* c) { return c ? c->host_chunks : 0u; }
 double zs_last_phase_ms(zs_ctx* c, const char* phase) {
   collect_marks(c);
   double t = -1;
@@ -783,6 +787,7 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
                           uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict,
                           const FlushIn* flush = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  c->host_chunks = 0;  // (a host entry's call counts its chunks behind this: host_batch_run)
   zs_deflate_req req = req_in;
   zs_deflate_call a;
   a.flush_first = flush ? flush->first : nullptr;
@@ -802,7 +807,12 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
   if (n == 0) return ZS_OK;
   if (zs_deflate_any_flush(req, a)) return deflate_device_flush(c, req, h, d_status, d_out_len, d_check, st, *flush);
   req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
-  if (!c->keep_counts) c->fidx.clear();  // (zs_last_flush_index: the last compress call had no flush point)
+  // (zs_last_flush_index: the last compress call had no flush point; a host batch's later chunks with
+  // points append their scans from 0, inside the room deflate_host reserved for them)
+  if (!c->keep_counts) {
+    c->fidx.clear();
+    c->fscan_used = 0;
+  }
   // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
   // metadata block; the streams' dictionaries, the distinct ones found once
   zs_dict_set& ds = c->dset;
@@ -1021,7 +1031,7 @@ __global__ void zs_k_compact(const uint8_t* __restrict__ src, const uint64_t* __
 }
 
 // The host-buffer entries, pipelined: the batch runs as a few chunks of
-// streams ([1/8, 3/8, 3/8, 1/8] of them for batches of 32 MB or more), so that
+// streams ([1/8, 3/8, 3/8, 1/8] of them for batches of 32 MB or more: zs_plan_host_chunks), so that
 // packing chunk k+1 into the pinned staging and its H2D copy (stream h2d) run
 // while chunk k's kernels do (the context's stream), and chunk k-1's output
 // compaction, D2H copy (stream d2h) and scatter into the caller's buffers run
@@ -1046,17 +1056,15 @@ static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64
   HIPCHK(c->d_out.ensure(tout + 16));
   // the packed outputs (d_pack, h_out) hold produced bytes, not capacities: a
   // first guess, grown in after_kernels once the chunks before are scattered
-  const uint64_t pack0 = std::min<uint64_t>(tout, std::max<uint64_t>(4 * tin, 64ull << 20)) + 16;
+  const uint64_t pack0 = zs_plan_host_pack0(c->o, tin, tout);
   HIPCHK(c->d_pack.ensure(pack0));
   HIPCHK(c->h_out.ensure(pack0));
   HIPCHK(c->d_res.ensure(4ull * nres * n + 16));
   HIPCHK(c->h_res.ensure(4ull * nres * n + 16));
   HIPCHK(c->d_offs.ensure(16ull * n + 16));
   HIPCHK(c->h_offs.ensure(16ull * n + 16));
-  std::vector<uint32_t> bnd{0};
-  if (n >= 64 && tin >= (32ull << 20))
-    for (uint32_t f : {1u, 4u, 7u}) bnd.push_back((uint32_t)((uint64_t)n * f / 8));
-  bnd.push_back(n);
+  std::vector<uint32_t> bnd;
+  zs_plan_host_chunks(c->o, n, tin, bnd);
   const uint32_t K = (uint32_t)bnd.size() - 1;
   while (c->hev.size() < 3 * K) {
     hipEvent_t e;
@@ -1139,6 +1147,7 @@ static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64
     int rc = launch(a, b, doff.data() + a, ooff.data() + a, ocap.data() + a, dr.data());
     c->keep_counts = false;
     if (rc != ZS_OK) return rc;
+    c->host_chunks = K;
     for (uint32_t r = 0; r < nres; r++)
       HIPCHK(hipMemcpyAsync(hres + (size_t)r * n + a, dr[r], 4ull * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipEventRecord(ev_k[k], c->stream));
@@ -1616,9 +1625,10 @@ static auto lane_kernel_dict(int rt) {
 // host arrays, b: its device arrays) on the side stream, after the caller's stream
 // reaches this point; then the wave kernel over the same members for any the pieces
 // could not finish (skip_done: the others return at once), the exact kernel after
-// it for whatever fails there.
+// it for whatever fails there.  first: the call's first segmented launch (a host batch's earlier
+// chunks had no such member, or there is none): the count of members finished starts at 0.
 static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbits, const Batch& h, const Batch& b,
-                      zs_lane_res* lres) {
+                      zs_lane_res* lres, bool first) {
   const std::vector<uint32_t>& list = c->ip.seg;
   zs_seg_plan& p = c->gp;
   zs_plan_seg(o, wbits, list, h.in_len, h.out_cap, p);
@@ -1653,9 +1663,10 @@ static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbi
   HIPCHK(hipMemsetAsync(c->gmem.p, 0, sizeof(zs_seg_mem) * ng, st));
   HIPCHK(hipMemsetAsync(c->gent.p, 0, sizeof(zs_seg_ent) * ZS_SPLIT_MAX * ng, st));
   HIPCHK(hipMemsetAsync(c->gblk.p, 0xff, sizeof(zs_seg_blk) * nb, st));
-  // the counters: spans taken, members left over, and (unless a later chunk of one host batch) the members finished
+  // the counters: spans taken, members left over, and (unless a host batch's earlier chunk counts already) the
+  // members finished
   HIPCHK(hipMemsetAsync(c->gcnt.as<uint32_t>() + 2, 0, 8, st));
-  if (!c->keep_counts) HIPCHK(hipMemsetAsync(c->gcnt.p, 0, 8, st));
+  if (first) HIPCHK(hipMemsetAsync(c->gcnt.p, 0, 8, st));
   HIPCHK(hipEventRecord(c->fork, st));
   HIPCHK(hipStreamWaitEvent(c->side, c->fork, 0));
   hipStream_t sd = c->side;
@@ -1760,6 +1771,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
                           uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
                           bool caller_regions, const DictIn* dict = nullptr, const zs_route_opts* opts = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  c->host_chunks = 0;  // (a host entry's call counts its chunks behind this: host_batch_run)
   // the options that decide routes and instances: the context's, or the caller's copy of them (the
   // restart entries decode with zlib semantics whatever the context's inflate_ref_wrap says)
   const zs_route_opts& o = opts ? *opts : c->o;
@@ -1850,9 +1862,11 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     // the segmented decode after the split kernels are queued: its grids would
     // otherwise fill the chip ahead of the split decode's few long pieces (C5-ii:
     // the 2.19 MB fixture's split decode took 8.0 ms beside it, 2.5 ms alone)
-    c->seg_used |= !p.seg.empty();
     if (!p.seg.empty()) {
-      const int r = seg_launch(c, o, st, wbits, h, b, lres);
+      // (seg_used: cleared with the call, so still false in a later chunk when the chunks before had no such member)
+      const bool first = !c->seg_used;
+      c->seg_used = true;
+      const int r = seg_launch(c, o, st, wbits, h, b, lres, first);
       if (r != ZS_OK) return r;
       // (the join below waits for the side stream's last kernel)
       if (p.wave.empty()) HIPCHK(hipEventRecord(c->join, c->side));

@@ -94,7 +94,32 @@ struct zs_route_opts {
   // runs in parts of checksum_part bytes (0: never; measured)
   uint32_t checksum_split = 1u << 18;
   uint32_t checksum_part = 65536;  // a power of two, ZS_CK_PART_MIN .. ZS_CK_PART_MAX
+  // the host-buffer entries' pipeline (zs_plan_host_chunks, zs_plan_host_pack0)
+  uint64_t host_chunk_min = 32ull << 20;  // input bytes from which a batch of ZS_HOST_CHUNK_STREAMS runs as four chunks; 0: never
+  uint64_t host_pack_min = 64ull << 20;   // the floor of the pack buffers' first guess, in bytes
 };
+
+// ---- the host-buffer entries' pipeline (capi.cpp, host_batch_run)
+#define ZS_HOST_CHUNK_STREAMS 64u  // batches of fewer streams run as one chunk whatever their size
+// zs_set_option's values of "host_chunk_min" and "host_pack_min"
+static inline bool zs_host_chunk_min_ok(int v) { return v >= 0; }
+static inline bool zs_host_pack_min_ok(int v) { return v >= 0; }
+// The chunks of a host batch of n streams and tin input bytes: streams [bnd[k], bnd[k + 1]), K =
+// bnd.size() - 1 of them.  One chunk, or -- from ZS_HOST_CHUNK_STREAMS streams and host_chunk_min bytes
+// on -- four, cut at n/8, 4n/8 and 7n/8: the small first chunk starts the kernels early, the small last
+// one leaves little to copy back after them.  With n >= 64 no chunk is empty.
+static inline void zs_plan_host_chunks(const zs_route_opts& o, uint32_t n, uint64_t tin, std::vector<uint32_t>& bnd) {
+  bnd.assign(1, 0u);
+  if (o.host_chunk_min && n >= ZS_HOST_CHUNK_STREAMS && tin >= o.host_chunk_min)
+    for (uint32_t f : {1u, 4u, 7u}) bnd.push_back((uint32_t)((uint64_t)n * f / 8));
+  bnd.push_back(n);
+}
+// The first size of the packed-output buffers (d_pack, h_out), which hold produced bytes, not
+// capacities: four times the input or host_pack_min, whichever is more, and never more than the
+// capacities' sum; 16 bytes of slack.  A guess: host_batch_run grows them when a chunk does not fit.
+static inline uint64_t zs_plan_host_pack0(const zs_route_opts& o, uint64_t tin, uint64_t tout) {
+  return std::min<uint64_t>(tout, std::max<uint64_t>(4 * tin, o.host_pack_min)) + 16;
+}
 
 // ---- checksums of long streams
 #define ZS_CK_PART_MIN 1024u

@@ -261,6 +261,9 @@ def lib():
             fn.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
         L.zs_last_checksum_parts.restype = ctypes.c_uint32
         L.zs_last_checksum_parts.argtypes = [_P]
+    if hasattr(L, "zs_last_host_chunks"):
+        L.zs_last_host_chunks.restype = ctypes.c_uint32
+        L.zs_last_host_chunks.argtypes = [_P]
     L.zs_last_batch_ms.restype = ctypes.c_double
     L.zs_last_batch_ms.argtypes = [_P]
     L.zs_last_inflate_lane_count.restype = ctypes.c_uint32
@@ -406,7 +409,9 @@ class Engine:
     def set_option(self, name: str, value: int):
         """zs_set_option: "timing", "inflate_fast", "check_phases", "match_sweep", ...; "checksum_split"
         (bytes, 0 = never) and "checksum_part" (a power of two 1024 .. 1048576): a batch with a
-        longer stream computes its data checksums in parts (see zs_gpu.h)."""
+        longer stream computes its data checksums in parts; "host_chunk_min" (input bytes from which a
+        host batch of 64 streams or more runs as four chunks, 0 = never) and "host_pack_min" (the floor
+        of the packed-output buffers' first size) (see zs_gpu.h)."""
         if self._L.zs_set_option(self._ctx, name.encode(), int(value)) != 0:
             raise ZsError(self._L.zs_last_error().decode())
 
@@ -435,6 +440,11 @@ class Engine:
     def last_checksum_parts(self) -> int:
         """parts of the last batch call's data checksum (0: one wave per stream; zs_last_checksum_parts)"""
         return self._L.zs_last_checksum_parts(self._ctx)
+
+    def last_host_chunks(self) -> int:
+        """chunks the last host-buffer compress / decompress call ran as: 1 or 4 (options "host_chunk_min",
+        "host_pack_min"); 0 after a device call (zs_last_host_chunks)"""
+        return self._L.zs_last_host_chunks(self._ctx)
 
     def last_ms(self, phase: Optional[str] = None) -> float:
         if phase is None:
