@@ -102,15 +102,23 @@ struct zs_ctx {
   Buf ghead;           // levels 1..3 at memLevel 9 and a large window: head[] per stream (zs_plan_fast_params)
   Buf fstreams, fscan;  // a batch with flush points: the streams' records (`streams` holds the segments'); the layout scan
   zs_flush_plan fp;
-  // the flushed device calls of the last compress call (a host entry's chunks, one after the other in
-  // fscan): where their scans lie and which segments start their streams (zs_last_flush_index)
+  // The record of the current public call, which the zs_last_* counters read.  call_begin clears it; the
+  // functions that plan and launch a device batch (a host call's chunks, a restart call's segments) only add.
   struct FlushIdx {
-    size_t at;  // u64 index of the call's scan in fscan
+    size_t at;  // u64 index of the device call's scan in fscan
     uint32_t n, M, hl;
     std::vector<uint32_t> sfirst;
   };
-  std::vector<FlushIdx> fidx;
-  size_t fscan_at = 0, fscan_used = 0;  // the current call's scan in fscan; u64 values in use
+  struct Call {
+    uint32_t ck_parts = 0;     // the data checksum's parts (zs_last_checksum_parts)
+    uint32_t host_chunks = 0;  // the chunks of a host-buffer call (zs_last_host_chunks)
+    // the flushed device calls of the compress call (a host entry's chunks, one after the other in fscan):
+    // where their scans lie and which segments start their streams (zs_last_flush_index)
+    std::vector<FlushIdx> fidx;
+    size_t fscan_at = 0, fscan_used = 0;  // the current device call's scan in fscan; u64 values in use
+    bool seg_ran = false;       // a segmented launch has run: its count of members finished goes on
+    bool lanes_zeroed = false;  // the lane counter (lstat) has been zeroed
+  } call;
   // a batch with restart points: the plan, the closed copies of the segments, the staging
   // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
   // and trailer values (2 arrays of n)
@@ -120,17 +128,13 @@ struct zs_ctx {
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
-  uint32_t ck_parts = 0;   // the last batch call's parts (zs_last_checksum_parts)
   Buf slist, sfound, spres, sscr, smem, sval;  // split decode of large members (inflate_split.hip)
   Buf glist, gfound, gbig, gbigs, gspb, gspl, gflist, gent, gblk, glanes, gtab, gmem, gpbase, gplist, gsbase, gscr, gcnt;
-  bool seg_used = false;            // the last inflate batch ran the segmented decode (inflate_seg.hip)
   // host staging for the host-buffer entry points
   Buf d_in, d_out, d_res, d_pack, d_offs;
   HostBuf h_in, h_out, h_res, h_offs;
   hipStream_t h2d = nullptr, d2h = nullptr;  // the host entries' copies, beside the kernels (host_batch)
   std::vector<hipEvent_t> hev;               // their events, reused
-  bool keep_counts = false;                  // a later chunk of one host batch: the lane / seg counts go on
-  uint32_t host_chunks = 0;                  // the chunks of the last host-buffer call (zs_last_host_chunks)
   std::vector<uint8_t> hmeta;
   size_t last_n = 0;
   // timing
@@ -152,6 +156,20 @@ struct zs_ctx {
   hipEvent_t lane_ev = nullptr;
 };
 static constexpr size_t kMaxMarks = 1024;
+
+// A public call starts, once per call: clears the counters that belong to its kind (include/zs_gpu.h) --
+// checksum parts: any; host chunks: deflate and inflate; flush index: deflate; lane and seg counts: inflate.
+enum CallKind { CALL_DEFLATE, CALL_INFLATE, CALL_CHECKSUM };
+static void call_begin(zs_ctx* c, CallKind kind) {
+  zs_ctx::Call& k = c->call;
+  k.ck_parts = 0;
+  if (kind != CALL_CHECKSUM) k.host_chunks = 0;
+  if (kind == CALL_DEFLATE) {
+    k.fidx.clear();
+    k.fscan_at = k.fscan_used = 0;
+  }
+  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = false;
+}
 static void fold_marks(zs_ctx* c);
 
 // Phase boundary: records a timing event and, with check_phases, waits for the
@@ -377,13 +395,13 @@ uint32_t zs_last_inflate_lane_count(zs_ctx* c) {
 }
 uint32_t zs_last_inflate_seg_count(zs_ctx* c) {
   uint32_t v = 0;
-  if (!c || !c->seg_used || !c->gcnt.p || hipStreamSynchronize(c->side) != hipSuccess ||
+  if (!c || !c->call.seg_ran || !c->gcnt.p || hipStreamSynchronize(c->side) != hipSuccess ||
       hipMemcpy(&v, c->gcnt.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
     return 0;
   return v;
 }
-uint32_t zs_last_checksum_parts(zs_ctx* c) { return c ? c->ck_parts : 0u; }
-uint32_t zs_last_host_chunks(zs_ctx* c) { return c ? c->host_chunks : 0u; }
+uint32_t zs_last_checksum_parts(zs_ctx* c) { return c ? c->call.ck_parts : 0u; }
+uint32_t zs_last_host_chunks(zs_ctx* c) { return c ? c->call.host_chunks : 0u; }
 double zs_last_phase_ms(zs_ctx* c, const char* phase) {
   collect_marks(c);
   double t = -1;
@@ -497,24 +515,31 @@ static int upload_batch(zs_ctx* c, hipStream_t st, const zs_meta_layout& ml, siz
 
 // The data checksum of a batch (the deflate wrappers' check values, the checksum entries, the
 // inflate trailer check), in three steps around upload_batch: ck_prepare plans it from the
-// lengths' bounds and returns the bytes its part map takes behind the metadata block; ck_fill
+// lengths' bounds, adds its parts to the call's record and returns the plan and the bytes its part
+// map takes behind the metadata block -- no plan and no bytes for a batch that wants none; ck_fill
 // writes the map there; ck_launch runs it -- one wave per stream as ever, or the parts and the fold.
-static int ck_prepare(zs_ctx* c, uint32_t n, const uint32_t* len_bound, size_t* map_bytes) {
+static int ck_prepare(zs_ctx* c, bool want, uint32_t n, const uint32_t* len_bound, const zs_checksum_plan** plan,
+                      size_t* map_bytes) {
+  *plan = nullptr;
+  *map_bytes = 0;
+  if (!want) return ZS_OK;
   zs_plan_checksum(c->o, n, len_bound, c->cp);
-  c->ck_parts = (c->keep_counts ? c->ck_parts : 0u) + c->cp.P;
+  c->call.ck_parts += c->cp.P;
+  *plan = &c->cp;
   *map_bytes = c->cp.map_bytes();
   HIPCHK(c->ckvals.ensure(c->cp.ws_bytes));
   return ZS_OK;
 }
-static void ck_fill(const zs_checksum_plan& cp, uint8_t* map) {
-  if (!cp.split) return;
-  memcpy(map, cp.pfirst.data(), 4ull * cp.pfirst.size());
-  memcpy(map + cp.map_pstream(), cp.pstream.data(), 4ull * cp.P);
+static void ck_fill(const zs_checksum_plan* cp, uint8_t* map) {
+  if (!cp || !cp->split) return;
+  memcpy(map, cp->pfirst.data(), 4ull * cp->pfirst.size());
+  memcpy(map + cp->map_pstream(), cp->pstream.data(), 4ull * cp->P);
 }
-// map: the part map's place in c->meta (a split plan); in_off, in_len, seeds: device arrays
-static void ck_launch(zs_ctx* c, hipStream_t st, size_t map, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                      const uint32_t* in_len, uint32_t* check, int kind, const uint32_t* seeds = nullptr) {
-  const zs_checksum_plan& cp = c->cp;
+// ck: the batch's plan as ck_prepare returned it; map: the part map's place in c->meta (a split plan);
+// in_off, in_len, seeds: device arrays
+static void ck_launch(zs_ctx* c, hipStream_t st, const zs_checksum_plan& cp, size_t map, uint32_t n, const uint8_t* in,
+                      const uint64_t* in_off, const uint32_t* in_len, uint32_t* check, int kind,
+                      const uint32_t* seeds = nullptr) {
   if (!cp.split) {
     zs_k_checksum<<<n, 64, 0, st>>>(in, in_off, in_len, check, kind, seeds);
     return;
@@ -617,7 +642,8 @@ struct FlushDev {
   const uint32_t* sstream;  // ... each segment's stream
 };
 static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, const Batch& b, const Batch& data,
-                          int32_t* d_status, uint32_t* d_out_len, size_t ck_map, const FlushDev* fl = nullptr) {
+                          int32_t* d_status, uint32_t* d_out_len, const zs_checksum_plan* ck, size_t ck_map,
+                          const FlushDev* fl = nullptr) {
   const zs_level_cfg& cfg = zs_level_cfgs[p.cfg];
   const zs_meta_layout& ml = p.ml;
   const int wrap = p.req.wrap, level = p.req.level;
@@ -642,7 +668,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   if (fl) HIPCHK(hipMemsetAsync(d_res, 0, sizeof(zs_stream) * (size_t)n_res, st));
   if (p.stored) {
     if (wrap) {
-      ck_launch(c, st, ck_map, n, b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
+      ck_launch(c, st, *ck, ck_map, n, b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
       MARK("checksum");
     }
     zs_k_stored<<<dim3(p.g_stored_x, n), 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, check, wrap,
@@ -651,7 +677,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
     return ZS_OK;
   }
   if (wrap) {
-    ck_launch(c, st, ck_map, n_res, data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
+    ck_launch(c, st, *ck, ck_map, n_res, data.in, data.in_off, data.in_len, check, wrap == 1 ? 1 : 2);
     zs_k_copy_check<<<nblocks_r, nthreads_s, 0, st>>>(check, d_res, (int)n_res);
     MARK("checksum");
   }
@@ -731,7 +757,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   else if (fl) {
     // per segment, joined by a scan of the segments' bytes (deflate_flush.hip)
     const zs_flush_layout fo(ml.bytes, n_res, n);
-    uint64_t* segx = c->fscan.as<uint64_t>() + c->fscan_at;
+    uint64_t* segx = c->fscan.as<uint64_t>() + c->call.fscan_at;
     uint64_t* tile = segx + n + 1;
     zs_k_flush_local<<<fo.tiles, ZS_FLUSH_TILE, 0, st>>>(d_blk, d_bk, d_st, fl->sfirst, fl->sstream, d_res, segx, tile, n);
     zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tile, fo.tiles);
@@ -766,29 +792,19 @@ __global__ void zs_k_deflate_check(const int32_t* status, const uint32_t* check,
   out[s] = status[s] != ZS_Z_STREAM_END ? 0u : wrap ? check[s] : 1u;
 }
 
-// The device compress: validate, plan, ensure, upload, launch, check values.
-// out_cap[i] is the stream's capacity as the caller set
-// it (Z_BUF_ERROR past it, exactly); the kernels store whole dwords, so the
-// stream's region must reach out_off[i] + out_cap[i] rounded up to 4.
-// `caller_regions` (the public device entries): the regions are the caller's
-// buffers, so capacities must be multiples of 4; the host entries stage in
-// regions of the capacities rounded up and pass the exact capacities.
-// `dict` (requests with req.dict, else null): the streams' preset dictionaries; a batch with none
-// of them set is the plain batch.
-// `flush` (requests with req.flush, else null): the streams' flush positions; a batch without any is
-// the plain batch.
+// The device compress: validate (zs_deflate_validate), then plan, ensure, upload, launch, check values
+// (deflate_batch).  out_cap[i] is the stream's capacity as the caller set it (Z_BUF_ERROR past it,
+// exactly); the kernels store whole dwords, so the stream's region must reach out_off[i] + out_cap[i]
+// rounded up to 4: `caller_regions` (the public device entries' own buffers) with capacities that are
+// multiples of 4, or the host entries' staging.
+// `dict`, `flush` (requests with req.dict / req.flush, else null): the streams' preset dictionaries /
+// flush positions; a batch with none of them set is the plain batch.
 struct FlushIn {
   const uint64_t* first;  // host, n + 1 entries: stream i's positions are pos[first[i] .. first[i + 1])
   const uint32_t* pos;    // host
 };
-static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
-                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush);
-static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
-                          uint32_t* d_check, void* hip_stream, bool caller_regions, const DictIn* dict,
-                          const FlushIn* flush = nullptr) {
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  c->host_chunks = 0;  // (a host entry's call counts its chunks behind this: host_batch_run)
-  zs_deflate_req req = req_in;
+// The arrays of a call as validation reads them
+static zs_deflate_call deflate_call(const Batch& h, bool caller_regions, const DictIn* dict, const FlushIn* flush) {
   zs_deflate_call a;
   a.flush_first = flush ? flush->first : nullptr;
   a.flush_pos = flush ? flush->pos : nullptr;
@@ -800,19 +816,47 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
   a.dict_arrays = dict && dict->off && dict->len;
   a.dict_buf = dict && dict->d_dict;
   a.dict_len = a.dict_arrays ? dict->len : nullptr;
-  if (const zs_deflate_err e = zs_deflate_validate(req, c->o, a)) return deflate_fail(e);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  HIPCHK(hipSetDevice(c->device));
-  const uint32_t n = h.n;
-  if (n == 0) return ZS_OK;
-  if (zs_deflate_any_flush(req, a)) return deflate_device_flush(c, req, h, d_status, d_out_len, d_check, st, *flush);
-  req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
-  // (zs_last_flush_index: the last compress call had no flush point; a host batch's later chunks with
-  // points append their scans from 0, inside the room deflate_host reserved for them)
-  if (!c->keep_counts) {
-    c->fidx.clear();
-    c->fscan_used = 0;
+  return a;
+}
+// The workspace of a planned batch of p.n streams (a flushed batch's segments)
+static int deflate_ensure(zs_ctx* c, const zs_deflate_plan& p) {
+  if (p.stored) return ZS_OK;
+  HIPCHK(c->ghead.ensure(p.ghead_bytes));
+  if (p.dict) {
+    HIPCHK(c->djoin.ensure(p.J + 16));
+    HIPCHK(c->dadler.ensure(4ull * p.ndict));
   }
+  if (p.sym != ZS_SYM_HUFF && p.sym != ZS_SYM_RLE) {  // (the tallies search no matches)
+    HIPCHK(c->prevd.ensure(p.prevd_bytes));
+    HIPCHK(c->mres.ensure(p.mres_bytes));
+  }
+  HIPCHK(c->syms.ensure(p.syms_bytes));
+  HIPCHK(c->pscr.ensure(p.pscr_bytes));
+  HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
+  HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)p.n));
+  HIPCHK(c->codes.ensure(p.codes_bytes));
+  HIPCHK(c->hdr.ensure(p.hdr_bytes));
+  return ZS_OK;
+}
+// ... and what follows its launch: the n streams' check values and the "end" mark
+static int deflate_finish(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, uint32_t n, const int32_t* d_status,
+                          uint32_t* d_check) {
+  if (d_check)
+    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), p.req.wrap, d_check, (int)n);
+  if (!p.stored) MARK("end");  // (a stored batch ends at its "stored" mark)
+  HIPCHK(hipGetLastError());
+  return ZS_OK;  // timing marks are collected when queried (no wait here)
+}
+static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                               uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush);
+// A validated, non-empty device batch (a public call's, or a chunk of a host call): plan, ensure, upload, launch.
+static int deflate_batch(zs_ctx* c, const zs_deflate_req& req_in, const zs_deflate_call& a, const Batch& h,
+                         int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const DictIn* dict,
+                         const FlushIn* flush) {
+  if (zs_deflate_any_flush(req_in, a)) return deflate_batch_flush(c, req_in, h, d_status, d_out_len, d_check, st, *flush);
+  zs_deflate_req req = req_in;
+  req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
+  const uint32_t n = h.n;
   // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
   // metadata block; the streams' dictionaries, the distinct ones found once
   zs_dict_set& ds = c->dset;
@@ -824,33 +868,13 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
   const zs_meta_layout& ml = p.ml;
   HIPCHK(c->check.ensure(4ull * n));
   // the check values' part map behind the block (a raw batch has none)
-  size_t ck_bytes = 0;
-  c->cp.split = false;
-  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
-  if (req.wrap) {
-    const int rc = ck_prepare(c, n, h.in_len, &ck_bytes);
-    if (rc != ZS_OK) return rc;
-  }
-  if (!p.stored) {
-    HIPCHK(c->ghead.ensure(p.ghead_bytes));
-    if (p.dict) {
-      HIPCHK(c->djoin.ensure(p.J + 16));
-      HIPCHK(c->dadler.ensure(4ull * p.ndict));
-    }
-    if (p.sym != ZS_SYM_HUFF && p.sym != ZS_SYM_RLE) {  // (the tallies search no matches)
-      HIPCHK(c->prevd.ensure(p.prevd_bytes));
-      HIPCHK(c->mres.ensure(p.mres_bytes));
-    }
-    HIPCHK(c->syms.ensure(p.syms_bytes));
-    HIPCHK(c->pscr.ensure(p.pscr_bytes));
-    HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
-    HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)n));
-    HIPCHK(c->codes.ensure(p.codes_bytes));
-    HIPCHK(c->hdr.ensure(p.hdr_bytes));
-  }
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, req.wrap != 0, n, h.in_len, &ck, &ck_bytes)) return rc;
+  if (const int rc = deflate_ensure(c, p)) return rc;
   Batch b;
   int r = upload_batch(c, st, ml, ml.bytes + ck_bytes, h, &b, [&](uint8_t* hm) {
-    ck_fill(c->cp, hm + ml.bytes);
+    ck_fill(ck, hm + ml.bytes);
     if (p.stored) return;
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * n);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * n);
@@ -883,23 +907,19 @@ static int deflate_device(zs_ctx* c, const zs_deflate_req& req_in, const Batch& 
     MARK("dict_join");
     HIPCHK(hipGetLastError());
     const Batch bj = {n, c->djoin.as<uint8_t>(), d_joff, (const uint32_t*)(dm + ml.jlen), b.out, b.out_off, b.out_cap};
-    r = deflate_launch(c, st, p, bj, b, d_status, d_out_len, ml.bytes);
+    r = deflate_launch(c, st, p, bj, b, d_status, d_out_len, ck, ml.bytes);
   } else {
-    r = deflate_launch(c, st, p, b, b, d_status, d_out_len, ml.bytes);
+    r = deflate_launch(c, st, p, b, b, d_status, d_out_len, ck, ml.bytes);
   }
   if (r != ZS_OK) return r;
-  if (d_check)
-    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), req.wrap, d_check, (int)n);
-  if (!p.stored) MARK("end");  // (a stored batch ends at its "stored" mark)
-  HIPCHK(hipGetLastError());
-  return ZS_OK;  // timing marks are collected when queried (no wait here)
+  return deflate_finish(c, st, p, n, d_status, d_check);
 }
 
 // A batch with Z_FULL_FLUSH points (validated; levels 1..9): the plan runs over the SEGMENTS -- the
 // pieces between the flush points, each a stream of its own to the match, parse, trees and emit
 // kernels -- and the flushed layout joins them per stream (deflate_flush.hip).
-static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
-                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush) {
+static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                               uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush) {
   const uint32_t n = h.n;
   zs_flush_plan& f = c->fp;
   zs_plan_flush(n, h.in_len, flush.first, flush.pos, f);
@@ -910,32 +930,17 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   const zs_flush_layout fo(ml.bytes, n, M);
   HIPCHK(c->check.ensure(4ull * n));
   // the streams' check values' part map behind the flushed section (a raw batch has none)
-  size_t ck_bytes = 0;
-  c->cp.split = false;
-  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
-  if (req.wrap) {
-    const int rc = ck_prepare(c, n, h.in_len, &ck_bytes);
-    if (rc != ZS_OK) return rc;
-  }
-  HIPCHK(c->ghead.ensure(p.ghead_bytes));
-  HIPCHK(c->prevd.ensure(p.prevd_bytes));
-  HIPCHK(c->mres.ensure(p.mres_bytes));
-  HIPCHK(c->syms.ensure(p.syms_bytes));
-  HIPCHK(c->pscr.ensure(p.pscr_bytes));
-  HIPCHK(c->blocks.ensure(sizeof(zs_block) * (size_t)p.B));
-  HIPCHK(c->streams.ensure(sizeof(zs_stream) * (size_t)M));
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, req.wrap != 0, n, h.in_len, &ck, &ck_bytes)) return rc;
+  if (const int rc = deflate_ensure(c, p)) return rc;
   HIPCHK(c->fstreams.ensure(sizeof(zs_stream) * (size_t)n));
-  // (a later chunk of one host batch keeps the chunks' scans before it: deflate_host sized fscan for all)
-  if (!c->keep_counts) {
-    c->fidx.clear();
-    c->fscan_used = 0;
-  }
-  c->fscan_at = c->fscan_used;
-  HIPCHK(c->fscan.ensure(8ull * c->fscan_at + fo.scan_bytes));
-  c->fscan_used += fo.scan_bytes / 8;
-  c->fidx.push_back({c->fscan_at, n, M, req.wrap == 1 ? 2u : req.wrap == 2 ? 10u : 0u, f.sfirst});
-  HIPCHK(c->codes.ensure(p.codes_bytes));
-  HIPCHK(c->hdr.ensure(p.hdr_bytes));
+  // this batch's scan behind those of the call's chunks before it (deflate_host sized fscan for all)
+  zs_ctx::Call& k = c->call;
+  k.fscan_at = k.fscan_used;
+  HIPCHK(c->fscan.ensure(8ull * k.fscan_at + fo.scan_bytes));
+  k.fscan_used += fo.scan_bytes / 8;
+  k.fidx.push_back({k.fscan_at, n, M, req.wrap == 1 ? 2u : req.wrap == 2 ? 10u : 0u, f.sfirst});
   // the segments as a batch: their bytes where they lie in their streams, every one with its stream's output
   std::vector<uint64_t> sin(M), sout(M);
   for (uint32_t g = 0; g < M; g++) {
@@ -945,7 +950,7 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   const Batch hs = {M, h.in, sin.data(), f.slen.data(), h.out, sout.data(), nullptr};
   Batch b;
   const int r = upload_batch(c, st, ml, fo.bytes + ck_bytes, hs, &b, [&](uint8_t* hm) {
-    ck_fill(c->cp, hm + fo.bytes);
+    ck_fill(ck, hm + fo.bytes);
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * M);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * M);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
@@ -961,13 +966,22 @@ static int deflate_device_flush(zs_ctx* c, const zs_deflate_req& req, const Batc
   const Batch real = {n, h.in, (const uint64_t*)(dm + fo.in_off), (const uint32_t*)(dm + fo.in_len), h.out,
                       (const uint64_t*)(dm + fo.out_off), (const uint32_t*)(dm + fo.out_cap)};
   const FlushDev fd = {(const uint32_t*)(dm + fo.sfirst), (const uint32_t*)(dm + fo.sstream)};
-  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, fo.bytes, &fd);
+  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, ck, fo.bytes, &fd);
   if (rl != ZS_OK) return rl;
-  if (d_check)
-    zs_k_deflate_check<<<(n + 255) / 256, 256, 0, st>>>(d_status, c->check.as<uint32_t>(), req.wrap, d_check, (int)n);
-  MARK("end");
-  HIPCHK(hipGetLastError());
-  return ZS_OK;
+  return deflate_finish(c, st, p, n, d_status, d_check);
+}
+
+// The shared body of the public device entries: the call begins once it is neither refused nor empty.
+static int deflate_device(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status, uint32_t* d_out_len,
+                          uint32_t* d_check, void* hip_stream, const DictIn* dict, const FlushIn* flush = nullptr) {
+  if (!c) return fail(ZS_STREAM_ERROR, "null context");
+  const zs_deflate_call a = deflate_call(h, true, dict, flush);
+  if (const zs_deflate_err e = zs_deflate_validate(req, c->o, a)) return deflate_fail(e);
+  HIPCHK(hipSetDevice(c->device));
+  if (h.n == 0) return ZS_OK;
+  call_begin(c, CALL_DEFLATE);
+  return deflate_batch(c, req, a, h, d_status, d_out_len, d_check, hip_stream ? (hipStream_t)hip_stream : c->stream, dict,
+                       flush);
 }
 
 extern "C" int zs_deflate_batch_device_ex(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
@@ -977,7 +991,7 @@ extern "C" int zs_deflate_batch_device_ex(zs_ctx* c, int level, int wbits, uint3
   zs_deflate_req req;
   zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, &req);
   return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, nullptr);
+                        hip_stream, nullptr);
 }
 
 extern "C" int zs_deflate_batch_device(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
@@ -1035,19 +1049,23 @@ __global__ void zs_k_compact(const uint8_t* __restrict__ src, const uint64_t* __
 // packing chunk k+1 into the pinned staging and its H2D copy (stream h2d) run
 // while chunk k's kernels do (the context's stream), and chunk k-1's output
 // compaction, D2H copy (stream d2h) and scatter into the caller's buffers run
-// while chunk k+1's do.  `launch(a, b, doff, ooff, ocap, d_res)` enqueues the
+// while chunk k+1's do.  h: the caller's batch, host memory; its regions on the device are the
+// capacities rounded up to whole words (zs_host_region_cap: the kernels store dwords), the exact
+// capacities stay the Z_BUF_ERROR limits.  `launch(a, b, doff, ooff, d_res)` enqueues the
 // device batch of streams [a, b) on c->stream; d_res holds nres u32 arrays of n
 // entries (array r at d_res + r n), res_host the caller's nres arrays, of which
-// res_host[len_idx] is the output length.  Outputs land at out + out_off[i].
+// res_host[len_idx] is the output length.  Outputs land at h.out + h.out_off[i].
 template <class Launch>
-static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                          const std::vector<uint32_t>& ocap, uint32_t nres, uint32_t* const* res_host,
-                          uint32_t len_idx, uint8_t* out, const uint64_t* out_off, Launch launch) {
+static int host_batch_run(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* const* res_host, uint32_t len_idx,
+                          Launch launch) {
+  const uint32_t n = h.n;
   std::vector<uint64_t> doff(n), ooff(n);
+  std::vector<uint32_t> ocap(n);
   uint64_t tin = 0, tout = 0;
   for (uint32_t i = 0; i < n; i++) {
+    ocap[i] = zs_host_region_cap(h.out_cap[i]);
     doff[i] = tin;
-    tin += in_len[i];
+    tin += h.in_len[i];
     ooff[i] = tout;
     tout += ocap[i];
   }
@@ -1088,7 +1106,7 @@ static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64
     HIPCHK(hipEventSynchronize(ev_out[k]));
     uint64_t bytes = 0;
     for (uint32_t i = a; i < b; i++) bytes += res_host[len_idx][i];
-    par_copy(b - a, out, out_off + a, c->h_out.as<uint8_t>(), poff.data() + a, res_host[len_idx] + a, bytes);
+    par_copy(b - a, h.out, h.out_off + a, c->h_out.as<uint8_t>(), poff.data() + a, res_host[len_idx] + a, bytes);
     scattered[k] = 1;
     return ZS_OK;
   };
@@ -1137,17 +1155,15 @@ static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64
   for (uint32_t k = 0; k < K; k++) {
     const uint32_t a = bnd[k], b = bnd[k + 1], m = b - a;
     const uint64_t bytes = (b < n ? doff[b] : tin) - doff[a];
-    par_copy(m, hin, doff.data() + a, in, in_off + a, in_len + a, bytes);
+    par_copy(m, hin, doff.data() + a, h.in, h.in_off + a, h.in_len + a, bytes);
     if (bytes) HIPCHK(hipMemcpyAsync(c->d_in.as<uint8_t>() + doff[a], hin + doff[a], bytes, hipMemcpyHostToDevice, c->h2d));
     HIPCHK(hipEventRecord(ev_in[k], c->h2d));
     HIPCHK(hipStreamWaitEvent(c->stream, ev_in[k], 0));
     std::vector<uint32_t*> dr(nres);
     for (uint32_t r = 0; r < nres; r++) dr[r] = dres + (size_t)r * n + a;
-    c->keep_counts = k > 0;
-    int rc = launch(a, b, doff.data() + a, ooff.data() + a, ocap.data() + a, dr.data());
-    c->keep_counts = false;
+    int rc = launch(a, b, doff.data() + a, ooff.data() + a, dr.data());
     if (rc != ZS_OK) return rc;
-    c->host_chunks = K;
+    c->call.host_chunks = K;
     for (uint32_t r = 0; r < nres; r++)
       HIPCHK(hipMemcpyAsync(hres + (size_t)r * n + a, dr[r], 4ull * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipEventRecord(ev_k[k], c->stream));
@@ -1163,10 +1179,9 @@ static int host_batch_run(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64
 // host_batch_run, and on any error the copies and kernels it left in flight
 // are waited for before returning (the next call reuses the staging buffers)
 template <class Launch>
-static int host_batch(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                      const std::vector<uint32_t>& ocap, uint32_t nres, uint32_t* const* res_host, uint32_t len_idx,
-                      uint8_t* out, const uint64_t* out_off, Launch launch) {
-  const int rc = host_batch_run(c, n, in, in_off, in_len, ocap, nres, res_host, len_idx, out, out_off, launch);
+static int host_batch(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* const* res_host, uint32_t len_idx,
+                      Launch launch) {
+  const int rc = host_batch_run(c, h, nres, res_host, len_idx, launch);
   if (rc != ZS_OK) {
     (void)hipStreamSynchronize(c->h2d);
     (void)hipStreamSynchronize(c->stream);
@@ -1175,60 +1190,62 @@ static int host_batch(zs_ctx* c, uint32_t n, const uint8_t* in, const uint64_t* 
   return rc;
 }
 
+// The distinct dictionaries of a host call, packed, to the device once (the chunks share them); poff: the
+// members' dictionaries' offsets in c->d_dict
+static int host_dict_upload(zs_ctx* c, uint32_t n, const DictIn& dict, std::vector<uint64_t>& poff) {
+  zs_dict_set ds;
+  std::vector<uint64_t> upos;
+  zs_dict_distinct(n, dict.off, dict.len, ds);
+  const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict.len, upos, poff);
+  HIPCHK(c->d_dict.ensure(dbytes + 16));
+  if (!dbytes) return ZS_OK;
+  std::vector<uint8_t> pack(dbytes);
+  zs_dict_pack(ds, upos, dict.d_dict, pack.data());
+  HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
+  return ZS_OK;
+}
+
 // The host compress of every zs_deflate_batch* entry.  dict (requests with req.dict, else null):
 // the caller's dictionary bytes, offsets and lengths, all host memory.
-static int deflate_host(zs_ctx* c, const zs_deflate_req& req, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                        int32_t* status, uint32_t* out_len, uint32_t* check, const DictIn* dict,
-                        const FlushIn* flush = nullptr) {
+// h: the caller's batch, host memory too.
+static int deflate_host(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* status, uint32_t* out_len,
+                        uint32_t* check, const DictIn* dict, const FlushIn* flush = nullptr) {
   if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  zs_deflate_call call;
-  call.n = n;
-  call.in_len = in_len;
-  call.flush_first = flush ? flush->first : nullptr;
-  call.flush_pos = flush ? flush->pos : nullptr;
-  call.dict_arrays = dict && dict->off && dict->len;
-  call.dict_buf = dict && dict->d_dict;
-  call.dict_len = call.dict_arrays ? dict->len : nullptr;
+  const uint32_t n = h.n;
+  const zs_deflate_call call = deflate_call(h, false, dict, flush);
   if (const zs_deflate_err e = zs_deflate_validate_host(req, call)) return deflate_fail(e);
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return ZS_OK;
-  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them);
-  // a batch without any is the plain batch
+  // the request's own faults (windowBits, level, strategy), which the first chunk would name next: here, so
+  // that a call refused for them has not begun
+  if (const zs_deflate_err e = zs_deflate_validate(req, c->o, zs_deflate_call())) return deflate_fail(e);
+  // a batch without any dictionary is the plain batch
   zs_deflate_req rq = req;
   rq.dict = zs_deflate_any_dict(req, call);
-  std::vector<uint64_t> upos, poff;
-  if (rq.dict) {
-    zs_dict_set ds;
-    zs_dict_distinct(n, dict->off, dict->len, ds);
-    const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict->len, upos, poff);
-    HIPCHK(c->d_dict.ensure(dbytes + 16));
-    std::vector<uint8_t> pack(dbytes);
-    zs_dict_pack(ds, upos, dict->d_dict, pack.data());
-    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
-  }
-  // device regions: the caller's capacity rounded up to whole words (the kernels store dwords);
-  // the caller's exact capacities are the Z_BUF_ERROR limits
-  std::vector<uint32_t> ocap(n);
-  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
+  std::vector<uint64_t> poff;
+  if (rq.dict)
+    if (const int r = host_dict_upload(c, n, *dict, poff)) return r;
   // a flushed batch: room for the scans of all its chunks, so that none is lost to a regrown buffer
   // before zs_last_flush_index reads them
   if (zs_deflate_any_flush(rq, call)) {
     const uint64_t mt = (uint64_t)n + (flush->first[n] - flush->first[0]);
     HIPCHK(c->fscan.ensure(8ull * (mt + mt / ZS_FLUSH_TILE + 16)));
   }
+  call_begin(c, CALL_DEFLATE);
   uint32_t* res[3] = {(uint32_t*)status, out_len, check};
-  return host_batch(c, n, in, in_off, in_len, ocap, 3, res, 1, out, out_off,
-                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
-                        uint32_t** dr) {
+  return host_batch(c, h, 3, res, 1,
+                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, uint32_t** dr) {
                       const DictIn di = rq.dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
                       // (a chunk's positions: the same position array, the chunk's part of the index)
                       const FlushIn fi = flush ? FlushIn{flush->first + a, flush->pos} : FlushIn{};
-                      return deflate_device(c, rq,
-                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
-                                             ooff, out_cap + a},
-                                            (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, false,
-                                            rq.dict ? &di : nullptr, flush ? &fi : nullptr);
+                      const Batch hb = {b - a, c->d_in.as<uint8_t>(), doff, h.in_len + a, c->d_out.as<uint8_t>(), ooff,
+                                        h.out_cap + a};
+                      const DictIn* cd = rq.dict ? &di : nullptr;
+                      const FlushIn* cf = flush ? &fi : nullptr;
+                      const zs_deflate_call ca = deflate_call(hb, false, cd, cf);
+                      if (const zs_deflate_err e = zs_deflate_validate(rq, c->o, ca)) return deflate_fail(e);
+                      return deflate_batch(c, rq, ca, hb, (int32_t*)dr[0], dr[1], check ? dr[2] : nullptr, c->stream, cd,
+                                           cf);
                     });  // out_len is 0 for failed streams
 }
 
@@ -1238,7 +1255,7 @@ extern "C" int zs_deflate_batch_ex(zs_ctx* c, int level, int wbits, uint32_t n, 
                                    uint32_t* out_len, uint32_t* check) {
   zs_deflate_req req;
   zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, &req);
-  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr);
 }
 
 extern "C" int zs_deflate_batch(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
@@ -1263,7 +1280,7 @@ extern "C" int zs_deflate_batch_flush_device(zs_ctx* c, int level, int wbits, ui
   if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
   const FlushIn fi = {flush_first, flush_pos};
   return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, nullptr, &fi);
+                        hip_stream, nullptr, &fi);
 }
 
 extern "C" int zs_deflate_batch_flush(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
@@ -1274,7 +1291,7 @@ extern "C" int zs_deflate_batch_flush(zs_ctx* c, int level, int wbits, uint32_t 
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
   const FlushIn fi = {flush_first, flush_pos};
-  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr, &fi);
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr, &fi);
 }
 
 // ---- compression strategies (deflateInit2_'s strategy: validation deflate.ts:289-290, dispatch :923-931)
@@ -1286,7 +1303,7 @@ extern "C" int zs_deflate_batch_strategy_device(zs_ctx* c, int level, int strate
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req(level, wbits, strategy, false, &req)) return deflate_fail(e);
   return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, nullptr);
+                        hip_stream, nullptr);
 }
 
 extern "C" int zs_deflate_batch_strategy(zs_ctx* c, int level, int strategy, int wbits, uint32_t n, const uint8_t* in,
@@ -1295,7 +1312,7 @@ extern "C" int zs_deflate_batch_strategy(zs_ctx* c, int level, int strategy, int
                                          uint32_t* out_len, uint32_t* check) {
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req(level, wbits, strategy, false, &req)) return deflate_fail(e);
-  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr);
 }
 
 // ---- windowBits and memLevel (deflateInit2_, deflate.ts:253-343; validation :281-294): a fault of
@@ -1308,7 +1325,7 @@ extern "C" int zs_deflate_batch_params_device(zs_ctx* c, int level, int wbits, i
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req_params(level, wbits, mem_level, &req)) return deflate_fail(e);
   return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, nullptr);
+                        hip_stream, nullptr);
 }
 
 extern "C" int zs_deflate_batch_params(zs_ctx* c, int level, int wbits, int mem_level, uint32_t n, const uint8_t* in,
@@ -1317,7 +1334,7 @@ extern "C" int zs_deflate_batch_params(zs_ctx* c, int level, int wbits, int mem_
                                        uint32_t* out_len, uint32_t* check) {
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req_params(level, wbits, mem_level, &req)) return deflate_fail(e);
-  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, nullptr);
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr);
 }
 
 // ---- preset dictionaries (deflateSetDictionary, deflate.ts:367-424; FDICT / DICTID, deflate.ts:767-778)
@@ -1331,7 +1348,7 @@ extern "C" int zs_deflate_batch_dict_device(zs_ctx* c, int level, int wbits, uin
   zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, true, &req);
   const DictIn di = {d_dict, dict_off, dict_len};
   return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
-                        hip_stream, true, &di);
+                        hip_stream, &di);
 }
 
 extern "C" int zs_deflate_batch_dict(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
@@ -1342,7 +1359,7 @@ extern "C" int zs_deflate_batch_dict(zs_ctx* c, int level, int wbits, uint32_t n
   zs_deflate_req req;
   zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, true, &req);
   const DictIn di = {dict, dict_off, dict_len};  // (host memory here)
-  return deflate_host(c, req, n, in, in_off, in_len, out, out_off, out_cap, status, out_len, check, &di);
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, &di);
 }
 
 static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
@@ -1353,17 +1370,19 @@ static int checksum_batch(zs_ctx* c, int kind, uint32_t n, const uint8_t* d_in, 
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
   const zs_meta_layout ml(n);  // (the seeds behind it, then the part map)
   const size_t ck_map = ml.bytes + (seeds ? (4ull * n + 255) & ~size_t(255) : 0);
-  size_t ck_bytes = 0;
-  if (const int rc = ck_prepare(c, n, in_len, &ck_bytes)) return rc;
+  call_begin(c, CALL_CHECKSUM);
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, true, n, in_len, &ck, &ck_bytes)) return rc;
   Batch b;
   const int r = upload_batch(c, st, ml, ck_bytes ? ck_map + ck_bytes : ml.bytes + (seeds ? 4ull * n : 0),
                              {n, d_in, in_off, in_len, nullptr, nullptr, nullptr}, &b, [&](uint8_t* hm) {
                                if (seeds) memcpy(hm + ml.bytes, seeds, 4ull * n);
-                               ck_fill(c->cp, hm + ck_map);
+                               ck_fill(ck, hm + ck_map);
                              });
   if (r != ZS_OK) return r;
   MARK("start");
-  ck_launch(c, st, ck_map, n, b.in, b.in_off, b.in_len, d_check, kind,
+  ck_launch(c, st, *ck, ck_map, n, b.in, b.in_off, b.in_len, d_check, kind,
             seeds ? (const uint32_t*)(c->meta.as<uint8_t>() + ml.bytes) : nullptr);
   MARK("checksum");
   HIPCHK(hipGetLastError());
@@ -1625,10 +1644,9 @@ static auto lane_kernel_dict(int rt) {
 // host arrays, b: its device arrays) on the side stream, after the caller's stream
 // reaches this point; then the wave kernel over the same members for any the pieces
 // could not finish (skip_done: the others return at once), the exact kernel after
-// it for whatever fails there.  first: the call's first segmented launch (a host batch's earlier
-// chunks had no such member, or there is none): the count of members finished starts at 0.
+// it for whatever fails there.
 static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbits, const Batch& h, const Batch& b,
-                      zs_lane_res* lres, bool first) {
+                      zs_lane_res* lres) {
   const std::vector<uint32_t>& list = c->ip.seg;
   zs_seg_plan& p = c->gp;
   zs_plan_seg(o, wbits, list, h.in_len, h.out_cap, p);
@@ -1663,10 +1681,11 @@ static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbi
   HIPCHK(hipMemsetAsync(c->gmem.p, 0, sizeof(zs_seg_mem) * ng, st));
   HIPCHK(hipMemsetAsync(c->gent.p, 0, sizeof(zs_seg_ent) * ZS_SPLIT_MAX * ng, st));
   HIPCHK(hipMemsetAsync(c->gblk.p, 0xff, sizeof(zs_seg_blk) * nb, st));
-  // the counters: spans taken, members left over, and (unless a host batch's earlier chunk counts already) the
-  // members finished
+  // the counters: spans taken, members left over, and with the call's first segmented launch (a host
+  // call's earlier chunks may have had no such member) the members finished
   HIPCHK(hipMemsetAsync(c->gcnt.as<uint32_t>() + 2, 0, 8, st));
-  if (first) HIPCHK(hipMemsetAsync(c->gcnt.p, 0, 8, st));
+  if (!c->call.seg_ran) HIPCHK(hipMemsetAsync(c->gcnt.p, 0, 8, st));
+  c->call.seg_ran = true;
   HIPCHK(hipEventRecord(c->fork, st));
   HIPCHK(hipStreamWaitEvent(c->side, c->fork, 0));
   hipStream_t sd = c->side;
@@ -1759,94 +1778,52 @@ static int split_launch(zs_ctx* c, hipStream_t st, int wbits, const Batch& b, zs
   return ZS_OK;
 }
 
-// The device decode.  out_cap[i] is the member's capacity as the caller set it
-// (Z_BUF_ERROR past it, exactly); the decoders store whole dwords, so the
-// member's region must reach out_off[i] + out_cap[i] rounded up to 4.
-// `caller_regions`: the regions are the caller's own buffers (the public
-// device entries), so capacities must be multiples of 4 -- no store may pass
-// the last member's end.  The host entries decode into their own staging,
-// whose regions are the capacities rounded up, and pass their callers' exact
-// capacities with caller_regions = false.
-static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
-                          uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
-                          bool caller_regions, const DictIn* dict = nullptr, const zs_route_opts* opts = nullptr) {
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  c->host_chunks = 0;  // (a host entry's call counts its chunks behind this: host_batch_run)
-  // the options that decide routes and instances: the context's, or the caller's copy of them (the
-  // restart entries decode with zlib semantics whatever the context's inflate_ref_wrap says)
-  const zs_route_opts& o = opts ? *opts : c->o;
-  // inflateInit2_ / inflateReset2 validation (inflate.ts:138-192) for the stream-layer formats
-  if (!(wbits == -15 || wbits == 15 || wbits == 31 || wbits == -16))
-    return fail(ZS_STREAM_ERROR, "unsupported windowBits (use -15, 15, 31 or -16)");
-  // The members' dictionaries (dict: the _dict entries), the distinct ones found once.
-  // gzip is never in DICT mode (inflateSetDictionary returns Z_STREAM_ERROR, inflate.ts:1229);
-  // the 64 KiB window of deflate64 is not covered.
-  zs_dict_set& ds = c->dset;
-  ds.any = false;
-  if (dict && h.n) {
-    if (!dict->off || !dict->len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
-    zs_dict_distinct(h.n, dict->off, dict->len, ds);
-    if (ds.any && !dict->d_dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
-    if (ds.any && (wbits == 31 || wbits == -16))
-      return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
+// The wave-per-member kernel over the members in c->ip.wave -- or, for large ones, the lane kernel's
+// call-tracking instance -- on the side stream, beside the lane kernel.
+static int wave_launch(zs_ctx* c, hipStream_t st, int wbits, const Batch& b, zs_lane_res* lres) {
+  const zs_inflate_plan& p = c->ip;
+  const uint32_t nw = (uint32_t)p.wave.size();
+  uint32_t* const llen = c->llen.as<uint32_t>();
+  HIPCHK(c->wlist.ensure(4ull * nw));
+  HIPCHK(hipMemcpyAsync(c->wlist.p, p.wave.data(), 4ull * nw, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(c->fork, st));
+  HIPCHK(hipStreamWaitEvent(c->side, c->fork, 0));
+  const size_t wsm = zs_inflate_wave_lds_bytes(wbits == -16);
+  auto wave = p.wave_refw ? zs_k_inflate_wave<true> : zs_k_inflate_wave<false>;
+  HIPCHK(hipFuncSetAttribute((const void*)wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsm));
+  if (int r = mark(c, c->side, "start")) return r;
+  if (p.wave_lanes) {
+    const uint32_t B2 = p.wave_lane.block;
+    const size_t lsm2 = B2 * zs_inflate_lane_lds_bytes(p.wave_lane.rt != 0);
+    auto lk2 = lane_kernel(p.wave_lane.rt, true);
+    HIPCHK(hipFuncSetAttribute((const void*)lk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsm2));
+    lk2<<<(nw + B2 - 1) / B2, B2, lsm2, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, nw,
+                                                   (zs_lane_tabs*)c->ltabs.p, lres, llen, ZS_INF_REF_WRAP, 0u,
+                                                   c->wlist.as<uint32_t>(), zs_dict_args{});
+  } else {
+    wave<<<nw, 64, wsm, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, c->wlist.as<uint32_t>(),
+                                   nw, lres, llen, nullptr);
   }
-  const bool hasdict = ds.any;
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  HIPCHK(hipSetDevice(c->device));
-  const uint32_t n = h.n;
-  if (n == 0) return ZS_OK;
-  if (!c->keep_counts) c->seg_used = false;
-  // the decoders store whole dwords (up to 3 bytes past a member's end): offsets are
-  // multiples of 4, and so are the capacities of regions the caller owns
-  for (uint32_t i = 0; i < n; i++)
-    if ((h.out_off[i] & 3) || (caller_regions && (h.out_cap[i] & 3)))
-      return fail(ZS_STREAM_ERROR, "output offsets/capacities must be multiples of 4");
+  HIPCHK(hipGetLastError());
+  if (int r = mark(c, c->side, p.wave_lanes ? "inflate_large" : "inflate_wave")) return r;
+  HIPCHK(hipEventRecord(c->join, c->side));
+  return ZS_OK;
+}
+
+// The results of an inflate batch, an array of n entries each: device memory (the device entries, a
+// host call's chunks) or the caller's host arrays (the host entries).  check may be null.
+struct InflateOut {
+  int32_t *status, *phase, *msg;
+  uint32_t *out_len, *consumed, *check;
+};
+
+// The launch sequence of a planned inflate batch (c->ip by the options o; h: its host arrays, b: its device
+// arrays; dd: its dictionaries; ck, ck_map: the trailer check's plan and its part map's place).
+static int inflate_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbits, const Batch& h, const Batch& b,
+                          const zs_dict_args& dd, const zs_checksum_plan* ck, size_t ck_map, const InflateOut& out) {
+  const zs_inflate_plan& p = c->ip;
+  const uint32_t n = b.n;
   const bool fastp = o.inflate_fast;
-  zs_inflate_plan& p = c->ip;
-  if (fastp) zs_plan_inflate(o, wbits, n, h.in_len, h.out_cap, p, hasdict ? dict->len : nullptr);
-  const zs_meta_layout ml(n);
-  // behind the batch's metadata: the members' dictionary offsets, lengths and ids, the distinct ones' too
-  const size_t nu = hasdict ? ds.uoff.size() : 0;
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
-               m_uoff = m_did + up256(4ull * n), m_ulen = m_uoff + up256(8ull * nu),
-               m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
-  // ... and the trailer check's part map (its lengths are the decoders': the capacities bound them)
-  size_t ck_bytes = 0;
-  c->cp.split = false;
-  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
-  if (fastp && wbits > 0)
-    if (const int rc = ck_prepare(c, n, h.out_cap, &ck_bytes)) return rc;
-  HIPCHK(c->istate.ensure(sizeof(zs_inflate_result) * (size_t)n));
-  if (fastp) {
-    HIPCHK(c->ltabs.ensure(zs_inflate_lane_scratch_bytes() * (size_t)n));
-    HIPCHK(c->lres.ensure(sizeof(zs_lane_res) * (size_t)n));
-    HIPCHK(c->llen.ensure(8ull * n));
-  }
-  Batch b;
-  if (int r = upload_batch(c, st, ml, m_end + ck_bytes, h, &b, [&](uint8_t* hm) {
-        ck_fill(c->cp, hm + m_end);
-        if (!hasdict) return;
-        memcpy(hm + m_doff, dict->off, 8ull * n);
-        memcpy(hm + m_dlen, dict->len, 4ull * n);
-        memcpy(hm + m_did, ds.id.data(), 4ull * n);
-        memcpy(hm + m_uoff, ds.uoff.data(), 8ull * nu);
-        memcpy(hm + m_ulen, ds.ulen.data(), 4ull * nu);
-      }))
-    return r;
-  zs_dict_args dd = {};
-  if (hasdict) {
-    HIPCHK(c->dadler.ensure(4ull * nu));
-    const uint8_t* dm = c->meta.as<uint8_t>();
-    dd = {dict->d_dict, (const uint64_t*)(dm + m_doff), (const uint32_t*)(dm + m_dlen), (const uint32_t*)(dm + m_did),
-          c->dadler.as<uint32_t>()};
-    // DICTID (zlib): the adler32 of each distinct dictionary, once
-    if (wbits == 15) {
-      zs_k_checksum<<<(uint32_t)nu, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + m_uoff),
-                                                 (const uint32_t*)(dm + m_ulen), c->dadler.as<uint32_t>(), 1);
-      HIPCHK(hipGetLastError());
-    }
-  }
   const size_t smem = zs_inflate_smem_bytes(wbits);
   HIPCHK(hipFuncSetAttribute((const void*)zs_k_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   zs_lane_res* const lres = fastp ? c->lres.as<zs_lane_res>() : nullptr;
@@ -1855,48 +1832,18 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   if (fastp) {
     zs_lane_tabs* const lt = (zs_lane_tabs*)c->ltabs.p;
     uint32_t* const llen = c->llen.as<uint32_t>();
-    if (!p.split.empty()) {
-      const int r = split_launch(c, st, wbits, b, lres);
-      if (r != ZS_OK) return r;
-    }
+    if (!p.split.empty())
+      if (const int r = split_launch(c, st, wbits, b, lres)) return r;
     // the segmented decode after the split kernels are queued: its grids would
     // otherwise fill the chip ahead of the split decode's few long pieces (C5-ii:
     // the 2.19 MB fixture's split decode took 8.0 ms beside it, 2.5 ms alone)
     if (!p.seg.empty()) {
-      // (seg_used: cleared with the call, so still false in a later chunk when the chunks before had no such member)
-      const bool first = !c->seg_used;
-      c->seg_used = true;
-      const int r = seg_launch(c, o, st, wbits, h, b, lres, first);
-      if (r != ZS_OK) return r;
+      if (const int r = seg_launch(c, o, st, wbits, h, b, lres)) return r;
       // (the join below waits for the side stream's last kernel)
       if (p.wave.empty()) HIPCHK(hipEventRecord(c->join, c->side));
     }
-    if (!p.wave.empty()) {
-      const uint32_t nw = (uint32_t)p.wave.size();
-      HIPCHK(c->wlist.ensure(4ull * nw));
-      HIPCHK(hipMemcpyAsync(c->wlist.p, p.wave.data(), 4ull * nw, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(c->fork, st));
-      HIPCHK(hipStreamWaitEvent(c->side, c->fork, 0));
-      const size_t wsm = zs_inflate_wave_lds_bytes(wbits == -16);
-      auto wave = p.wave_refw ? zs_k_inflate_wave<true> : zs_k_inflate_wave<false>;
-      HIPCHK(hipFuncSetAttribute((const void*)wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wsm));
-      if (int r = mark(c, c->side, "start")) return r;
-      if (p.wave_lanes) {
-        const uint32_t B2 = p.wave_lane.block;
-        const size_t lsm2 = B2 * zs_inflate_lane_lds_bytes(p.wave_lane.rt != 0);
-        auto lk2 = lane_kernel(p.wave_lane.rt, true);
-        HIPCHK(hipFuncSetAttribute((const void*)lk2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsm2));
-        lk2<<<(nw + B2 - 1) / B2, B2, lsm2, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits, nw, lt,
-                                                       lres, llen, ZS_INF_REF_WRAP, 0u, c->wlist.as<uint32_t>(),
-                                                       zs_dict_args{});
-      } else {
-        wave<<<nw, 64, wsm, c->side>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits,
-                                       c->wlist.as<uint32_t>(), nw, lres, llen, nullptr);
-      }
-      HIPCHK(hipGetLastError());
-      if (int r = mark(c, c->side, p.wave_lanes ? "inflate_large" : "inflate_wave")) return r;
-      HIPCHK(hipEventRecord(c->join, c->side));
-    }
+    if (!p.wave.empty())
+      if (const int r = wave_launch(c, st, wbits, b, lres)) return r;
     const uint32_t B = p.lane.block;
     const size_t lsm = B * zs_inflate_lane_lds_bytes(p.lane.rt != 0);
     // (a batch with dictionaries: the dictionary instances, for every member of it)
@@ -1923,7 +1870,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
     }
     if (wbits > 0) {  // trailer checks over the decoded bytes: adler32 (zlib) / crc32 (gzip)
       uint32_t* chk = llen + n;
-      ck_launch(c, st, m_end, n, b.out, b.out_off, llen, chk, wbits == 31 ? 2 : 1);
+      ck_launch(c, st, *ck, ck_map, n, b.out, b.out_off, llen, chk, wbits == 31 ? 2 : 1);
       zs_k_inflate_lane_verify<<<(n + 255) / 256, 256, 0, st>>>(lres, chk, n);
       MARK("inflate_check");
     }
@@ -1931,79 +1878,96 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   zs_k_inflate<<<n, 64, smem, st>>>(b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, wbits,
                                     c->istate.as<zs_inflate_result>(), lres, lflags, dd);
   MARK("inflate");
-  HIPCHK(c->lstat.ensure(16));
-  if (!c->keep_counts) HIPCHK(hipMemsetAsync(c->lstat.p, 0, 4, st));
-  zs_k_inflate_finish<<<(n + 255) / 256, 256, 0, st>>>(c->istate.as<zs_inflate_result>(), lres, d_status, d_phase,
-                                                       d_msg, d_out_len, d_consumed, (int)n, c->lstat.as<uint32_t>());
-  if (!c->lane_count_host) {
-    HIPCHK(hipHostMalloc((void**)&c->lane_count_host, 64, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming));
-  }
+  // the lane count of the call: zeroed ahead of its first batch, then every batch's finish adds to it
+  if (!c->call.lanes_zeroed) HIPCHK(hipMemsetAsync(c->lstat.p, 0, 4, st));
+  c->call.lanes_zeroed = true;
+  zs_k_inflate_finish<<<(n + 255) / 256, 256, 0, st>>>(c->istate.as<zs_inflate_result>(), lres, out.status, out.phase,
+                                                       out.msg, out.out_len, out.consumed, (int)n,
+                                                       c->lstat.as<uint32_t>());
   HIPCHK(hipMemcpyAsync(c->lane_count_host, c->lstat.p, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(c->lane_ev, st));
-  if (d_check)
-    zs_k_inflate_check<<<(n + 255) / 256, 256, 0, st>>>(b.in, b.in_off, d_status, d_consumed, wbits, d_check, (int)n);
+  if (out.check)
+    zs_k_inflate_check<<<(n + 255) / 256, 256, 0, st>>>(b.in, b.in_off, out.status, out.consumed, wbits, out.check, (int)n);
   MARK("finish");
   HIPCHK(hipGetLastError());
   return ZS_OK;  // timing marks are collected when queried (no wait here)
 }
 
-extern "C" int zs_inflate_batch_device_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
-                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
-                                          const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
-                                          int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
-                                          uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
-  return inflate_device(c, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_phase, d_msg,
-                        d_out_len, d_consumed, d_check, hip_stream, true);
-}
-
-extern "C" int zs_inflate_batch_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
-                                       const uint32_t* in_len, uint8_t* d_out, const uint64_t* out_off,
-                                       const uint32_t* out_cap, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
-                                       uint32_t* d_out_len, uint32_t* d_consumed, void* hip_stream) {
-  return zs_inflate_batch_device_ex(c, wbits, n, d_in, in_off, in_len, d_out, out_off, out_cap, d_status, d_phase,
-                                    d_msg, d_out_len, d_consumed, nullptr, hip_stream);
-}
-
-extern "C" int zs_inflate_batch(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                                const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                int32_t* status, int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed) {
-  return zs_inflate_batch_ex(c, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, phase, msg, out_len,
-                             consumed, nullptr);
-}
-
-extern "C" int zs_inflate_batch_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
-                                   const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
-                                   const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
-                                   uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  // device regions: the caller's capacity rounded up to whole words (the decoders store dwords)
-  std::vector<uint32_t> ocap(n), creq(out_cap, out_cap + n);
-  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
-  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
-  return host_batch(c, n, in, in_off, in_len, ocap, 6, res, 3, out, out_off,
-                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
-                        uint32_t** dr) {
-                      // regions of ocap (rounded up) bytes; the caller's exact capacities as the limits
-                      return inflate_device(c, wbits,
-                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
-                                             ooff, creq.data() + a},
-                                            (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
-                                            check ? dr[5] : nullptr, c->stream, false);
-                    });
+// A validated, non-empty device batch (a public call's, a chunk of a host call, the segments of a restart
+// call): plan, ensure, upload, launch.  out_cap[i] is the member's capacity as the caller set it
+// (Z_BUF_ERROR past it, exactly); the decoders store whole dwords, so the member's region must reach
+// out_off[i] + out_cap[i] rounded up to 4: the device entries' own buffers with capacities that are
+// multiples of 4, or the host entries' staging.  opts: the options that decide routes and instances, when
+// they are not the context's.
+static int inflate_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, hipStream_t st, const DictIn* dict,
+                         const zs_route_opts* opts) {
+  const zs_route_opts& o = opts ? *opts : c->o;
+  const uint32_t n = h.n;
+  // the members' dictionaries (dict: the _dict entries), the distinct ones found once
+  zs_dict_set& ds = c->dset;
+  ds.any = false;
+  if (dict) zs_dict_distinct(n, dict->off, dict->len, ds);
+  const bool hasdict = ds.any;
+  const bool fastp = o.inflate_fast;
+  if (fastp) zs_plan_inflate(o, wbits, n, h.in_len, h.out_cap, c->ip, hasdict ? dict->len : nullptr);
+  const zs_meta_layout ml(n);
+  // behind the batch's metadata: the members' dictionary offsets, lengths and ids, the distinct ones' too
+  const size_t nu = hasdict ? ds.uoff.size() : 0;
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m_doff = ml.bytes, m_dlen = m_doff + up256(8ull * n), m_did = m_dlen + up256(4ull * n),
+               m_uoff = m_did + up256(4ull * n), m_ulen = m_uoff + up256(8ull * nu),
+               m_end = hasdict ? m_ulen + up256(4ull * nu) : ml.bytes;
+  // ... and the trailer check's part map (its lengths are the decoders': the capacities bound them)
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, fastp && wbits > 0, n, h.out_cap, &ck, &ck_bytes)) return rc;
+  HIPCHK(c->istate.ensure(sizeof(zs_inflate_result) * (size_t)n));
+  if (fastp) {
+    HIPCHK(c->ltabs.ensure(zs_inflate_lane_scratch_bytes() * (size_t)n));
+    HIPCHK(c->lres.ensure(sizeof(zs_lane_res) * (size_t)n));
+    HIPCHK(c->llen.ensure(8ull * n));
+  }
+  if (hasdict) HIPCHK(c->dadler.ensure(4ull * nu));
+  HIPCHK(c->lstat.ensure(16));
+  if (!c->lane_count_host) {
+    HIPCHK(hipHostMalloc((void**)&c->lane_count_host, 64, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming));
+  }
+  Batch b;
+  if (int r = upload_batch(c, st, ml, m_end + ck_bytes, h, &b, [&](uint8_t* hm) {
+        ck_fill(ck, hm + m_end);
+        if (!hasdict) return;
+        memcpy(hm + m_doff, dict->off, 8ull * n);
+        memcpy(hm + m_dlen, dict->len, 4ull * n);
+        memcpy(hm + m_did, ds.id.data(), 4ull * n);
+        memcpy(hm + m_uoff, ds.uoff.data(), 8ull * nu);
+        memcpy(hm + m_ulen, ds.ulen.data(), 4ull * nu);
+      }))
+    return r;
+  zs_dict_args dd = {};
+  if (hasdict) {
+    const uint8_t* dm = c->meta.as<uint8_t>();
+    dd = {dict->d_dict, (const uint64_t*)(dm + m_doff), (const uint32_t*)(dm + m_dlen), (const uint32_t*)(dm + m_did),
+          c->dadler.as<uint32_t>()};
+    // DICTID (zlib): the adler32 of each distinct dictionary, once
+    if (wbits == 15) {
+      zs_k_checksum<<<(uint32_t)nu, 64, 0, st>>>(dict->d_dict, (const uint64_t*)(dm + m_uoff),
+                                                 (const uint32_t*)(dm + m_ulen), c->dadler.as<uint32_t>(), 1);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  return inflate_launch(c, o, st, wbits, h, b, dd, ck, m_end, out);
 }
 
 // ---- restart points (inflateSync, inflate.ts:1267-1337): a stream's segments decoded as the
 // members of one raw batch and joined per stream.  A fault of the arguments is reported before the
-// context is looked at.
+// context is looked at (restart_refused: zs_restart_validate, then the null context).
 struct RestartIn {
   const uint64_t* first;  // host, n + 1 entries: stream i's points are (in[k], out[k]), k in first[i] .. first[i + 1]
   const uint32_t* in;     // host
   const uint32_t* out;    // host
 };
-static int restart_refused(int wbits, const Batch& h, bool device_entry, const RestartIn& rs) {
+static int restart_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry, const RestartIn& rs) {
   zs_restart_call a;
   a.n = h.n;
   a.in_len = h.in_len;
@@ -2014,36 +1978,29 @@ static int restart_refused(int wbits, const Batch& h, bool device_entry, const R
   a.rin = rs.in;
   a.rout = rs.out;
   if (const zs_restart_err e = zs_restart_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_restart_err_text(e));
-  return ZS_OK;
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
 }
 
-// The device decode of a validated call (regions as inflate_device's: the caller's own, or the host
-// entry's staging with the caller's exact capacities).
-static int restart_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
-                          uint32_t* d_out_len, uint32_t* d_consumed, uint32_t* d_check, void* hip_stream,
-                          const RestartIn& rs) {
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  HIPCHK(hipSetDevice(c->device));
+// The device decode of a validated, non-empty batch with restart points (regions as inflate_batch's).
+static int restart_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, hipStream_t st,
+                         const RestartIn& rs) {
   const uint32_t n = h.n;
-  if (n == 0) return ZS_OK;
   zs_restart_plan& p = c->rp;
   zs_plan_restart(n, h.in_len, h.out_cap, rs.first, rs.in, rs.out, p);
   const uint32_t M = p.M;
-  // the segment batch's metadata block is inflate_device's own (it uploads it); this call's section
+  // the segment batch's metadata block is inflate_batch's own (it uploads it); this call's section
   // lies behind it, the streams' checksum map behind that
   const zs_meta_layout ml(M);
   const zs_restart_layout ro(ml.bytes, n, M);
-  size_t ck_bytes = 0;
-  c->cp.split = false;
-  c->ck_parts = c->keep_counts ? c->ck_parts : 0u;
-  if (wbits > 0)
-    if (const int rc = ck_prepare(c, n, h.out_cap, &ck_bytes)) return rc;
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, wbits > 0, n, h.out_cap, &ck, &ck_bytes)) return rc;
   HIPCHK(c->rgather.ensure(p.gather_bytes));
   HIPCHK(c->rstage.ensure(p.stage_bytes));
   HIPCHK(c->rres.ensure(20ull * M + 64));
   HIPCHK(c->rmark.ensure(4ull * M + 16));
   HIPCHK(c->rsum.ensure(8ull * n + 16));
-  HIPCHK(c->meta.ensure(ro.bytes + ck_bytes));  // (before inflate_device's own ensure, which then keeps the block)
+  HIPCHK(c->meta.ensure(ro.bytes + ck_bytes));  // (before inflate_batch's own ensure, which then keeps the block)
   // where each segment lies, decodes and belongs
   std::vector<uint64_t> src(M), ooff(M), dst(M);
   for (uint32_t g = 0; g < M; g++) {
@@ -2073,7 +2030,7 @@ static int restart_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   memcpy(hm(ro.dst), dst.data(), 8ull * M);
   memcpy(hm(ro.gtile), p.gtile.data(), 4ull * (M + 1));
   memcpy(hm(ro.ptile), p.ptile.data(), 4ull * (M + 1));
-  ck_fill(c->cp, hm(ro.bytes));
+  ck_fill(ck, hm(ro.bytes));
   HIPCHK(hipMemcpyAsync(c->meta.as<uint8_t>() + ml.bytes, c->rhmeta.data(), c->rhmeta.size(), hipMemcpyHostToDevice, st));
   const uint8_t* dm = c->meta.as<uint8_t>();
   auto u32 = [&](size_t at) { return (const uint32_t*)(dm + at); };
@@ -2089,40 +2046,121 @@ static int restart_device(zs_ctx* c, int wbits, const Batch& h, int32_t* d_statu
   HIPCHK(hipGetLastError());
   // the segments as M raw members, decoded with zlib semantics: behind a reset there is no call
   // boundary of the reference's to reproduce, whatever the context's inflate_ref_wrap says
-  int32_t* s_status = c->rres.as<int32_t>();
-  int32_t* s_phase = s_status + M;
-  int32_t* s_msg = s_phase + M;
-  uint32_t* s_len = (uint32_t*)(s_msg + M);
-  uint32_t* s_used = s_len + M;
+  int32_t* const sr = c->rres.as<int32_t>();
+  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
   zs_route_opts o2 = c->o;
   o2.inflate_ref_wrap = false;
   const Batch hs = {M, gather, p.goff.data(), p.glen.data(), p.in_place ? h.out : c->rstage.as<uint8_t>(), ooff.data(),
                     p.ocap.data()};
-  // (the raw segment batch plans no checksum and clears the streams' plan flag and part count)
-  const bool ck_split = c->cp.split;
-  const uint32_t ck_parts = c->ck_parts;
-  const int ri = inflate_device(c, -15, hs, s_status, s_phase, s_msg, s_len, s_used, nullptr, st, false, nullptr, &o2);
-  c->cp.split = ck_split;
-  c->ck_parts = ck_parts;
-  if (ri != ZS_OK) return ri;
+  if (const int ri = inflate_batch(c, -15, hs, seg, st, nullptr, &o2)) return ri;
   if (!p.in_place) {
     if (p.ptile[M])
       zs_k_restart_place<<<std::min(p.ptile[M], gmax), 256, 0, st>>>(c->rstage.as<uint8_t>(), u64(ro.ooff), u32(ro.ocap),
-                                                                    s_len, u64(ro.dst), u32(ro.ptile), M, h.out);
+                                                                    seg.out_len, u64(ro.dst), u32(ro.ptile), M, h.out);
     MARK("restart_place");
   }
   uint32_t* sum = c->rsum.as<uint32_t>();
   uint32_t* want = sum + n;
   zs_k_restart_stitch<<<n, 64, 0, st>>>(h.in, u64(ro.in_off), u32(ro.in_len), u32(ro.over), u32(ro.rfirst), u32(ro.soff),
-                                        u32(ro.slen), u32(ro.olen), u32(ro.opos), mark_, s_status, s_msg, s_len, s_used,
-                                        wbits, n, d_status, d_phase, d_msg, d_out_len, d_consumed, want);
+                                        u32(ro.slen), u32(ro.olen), u32(ro.opos), mark_, seg.status, seg.msg, seg.out_len,
+                                        seg.consumed, wbits, n, out.status, out.phase, out.msg, out.out_len, out.consumed, want);
   // the check value over the joined output, the lengths the stitch wrote, against the trailer's
-  if (wbits > 0) ck_launch(c, st, ro.bytes, n, h.out, u64(ro.out_off), d_out_len, sum, wbits == 31 ? 2 : 1);
-  zs_k_restart_check<<<(n + 255) / 256, 256, 0, st>>>(sum, want, wbits, n, d_status, d_phase, d_msg, d_out_len,
-                                                      d_consumed, d_check);
+  if (wbits > 0) ck_launch(c, st, *ck, ro.bytes, n, h.out, u64(ro.out_off), out.out_len, sum, wbits == 31 ? 2 : 1);
+  zs_k_restart_check<<<(n + 255) / 256, 256, 0, st>>>(sum, want, wbits, n, out.status, out.phase, out.msg, out.out_len,
+                                                      out.consumed, out.check);
   MARK("restart_stitch");
   HIPCHK(hipGetLastError());
   return ZS_OK;
+}
+
+// zs_inflate_validate's findings, as the entries report them
+static int inflate_fail(zs_inflate_err e) { return fail(ZS_STREAM_ERROR, "%s", zs_inflate_err_text(e)); }
+// The arrays of a plain or _dict call as validation reads them (the host entries stage their own regions)
+static zs_inflate_call inflate_call(const Batch& h, bool caller_regions, const DictIn* dict) {
+  zs_inflate_call a;
+  a.n = h.n;
+  a.out_off = caller_regions ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = caller_regions;
+  a.dict = dict != nullptr;
+  a.dict_arrays = dict && dict->off && dict->len;
+  a.dict_buf = dict && dict->d_dict;
+  a.dict_len = a.dict_arrays ? dict->len : nullptr;
+  return a;
+}
+
+// The shared body of the public device entries: the call begins once it is neither refused nor empty.
+static int inflate_device(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, void* hip_stream,
+                          const DictIn* dict, const RestartIn* rs) {
+  if (!rs)  // (a restart call has passed restart_refused)
+    if (const zs_inflate_err e = zs_inflate_validate(c != nullptr, wbits, inflate_call(h, true, dict))) return inflate_fail(e);
+  HIPCHK(hipSetDevice(c->device));
+  if (h.n == 0) return ZS_OK;
+  call_begin(c, CALL_INFLATE);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return rs ? restart_batch(c, wbits, h, out, st, *rs) : inflate_batch(c, wbits, h, out, st, dict, nullptr);
+}
+
+// The host decode of every zs_inflate_batch* entry (h, out, dict: the caller's host memory): what the whole
+// batch decides before anything is staged, the dictionaries to the device once, then the call begins and
+// host_batch runs its chunks, each a device batch with a copy of the caller's exact capacities as the limits.
+static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, const DictIn* dict,
+                        const RestartIn* rs) {
+  if (!rs)  // (a restart call has passed restart_refused)
+    if (const zs_inflate_err e = zs_inflate_validate_host(c != nullptr, wbits, inflate_call(h, false, dict)))
+      return inflate_fail(e);
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t n = h.n;
+  if (n == 0) return ZS_OK;
+  std::vector<uint64_t> poff;
+  if (dict)
+    if (const int r = host_dict_upload(c, n, *dict, poff)) return r;
+  const std::vector<uint32_t> creq(h.out_cap, h.out_cap + n);
+  call_begin(c, CALL_INFLATE);
+  uint32_t* res[6] = {(uint32_t*)out.status, (uint32_t*)out.phase, (uint32_t*)out.msg, out.out_len, out.consumed, out.check};
+  return host_batch(c, h, 6, res, 3,
+                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, uint32_t** dr) {
+                      const Batch hb = {b - a, c->d_in.as<uint8_t>(), doff, h.in_len + a, c->d_out.as<uint8_t>(), ooff,
+                                        creq.data() + a};
+                      const InflateOut d = {(int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
+                                            out.check ? dr[5] : nullptr};
+                      // (a chunk's points and dictionaries: the same arrays, the chunk's part of the index)
+                      if (rs) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
+                      const DictIn di = dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
+                      return inflate_batch(c, wbits, hb, d, c->stream, dict ? &di : nullptr, nullptr);
+                    });
+}
+
+extern "C" int zs_inflate_batch_device_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
+                                          const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                          const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                          int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
+                                          uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
+  return inflate_device(c, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap},
+                        {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, hip_stream, nullptr, nullptr);
+}
+
+extern "C" int zs_inflate_batch_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
+                                       const uint32_t* in_len, uint8_t* d_out, const uint64_t* out_off,
+                                       const uint32_t* out_cap, int32_t* d_status, int32_t* d_phase, int32_t* d_msg,
+                                       uint32_t* d_out_len, uint32_t* d_consumed, void* hip_stream) {
+  return zs_inflate_batch_device_ex(c, wbits, n, d_in, in_off, in_len, d_out, out_off, out_cap, d_status, d_phase,
+                                    d_msg, d_out_len, d_consumed, nullptr, hip_stream);
+}
+
+extern "C" int zs_inflate_batch(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                int32_t* status, int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed) {
+  return zs_inflate_batch_ex(c, wbits, n, in, in_off, in_len, out, out_off, out_cap, status, phase, msg, out_len,
+                             consumed, nullptr);
+}
+
+extern "C" int zs_inflate_batch_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                   const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                   const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                   uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+  return inflate_host(c, wbits, {n, in, in_off, in_len, out, out_off, out_cap},
+                      {status, phase, msg, out_len, consumed, check}, nullptr, nullptr);
 }
 
 // inflate.ts:1267-1337 -- device buffers
@@ -2135,9 +2173,8 @@ extern "C" int zs_inflate_batch_restart_device(zs_ctx* c, int wbits, uint32_t n,
                                                const uint32_t* restart_out) {
   const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
   const RestartIn rs = {restart_first, restart_in, restart_out};
-  if (const int r = restart_refused(wbits, h, true, rs)) return r;
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  return restart_device(c, wbits, h, d_status, d_phase, d_msg, d_out_len, d_consumed, d_check, hip_stream, rs);
+  if (const int r = restart_refused(c, wbits, h, true, rs)) return r;
+  return inflate_device(c, wbits, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, hip_stream, nullptr, &rs);
 }
 
 // inflate.ts:1267-1337 -- host buffers
@@ -2147,25 +2184,10 @@ extern "C" int zs_inflate_batch_restart(zs_ctx* c, int wbits, uint32_t n, const 
                                         uint32_t* out_len, uint32_t* consumed, uint32_t* check,
                                         const uint64_t* restart_first, const uint32_t* restart_in,
                                         const uint32_t* restart_out) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
   const RestartIn rs = {restart_first, restart_in, restart_out};
-  if (const int r = restart_refused(wbits, {n, in, in_off, in_len, out, out_off, out_cap}, false, rs)) return r;
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  std::vector<uint32_t> ocap(n), creq(out_cap, out_cap + n);
-  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
-  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
-  return host_batch(c, n, in, in_off, in_len, ocap, 6, res, 3, out, out_off,
-                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
-                        uint32_t** dr) {
-                      // (a chunk's points: the same point arrays, the chunk's part of the index)
-                      const RestartIn ri = {restart_first + a, restart_in, restart_out};
-                      return restart_device(c, wbits,
-                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
-                                             ooff, creq.data() + a},
-                                            (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
-                                            check ? dr[5] : nullptr, c->stream, ri);
-                    });
+  if (const int r = restart_refused(c, wbits, h, false, rs)) return r;
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, &rs);
 }
 
 extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t in_len) {
@@ -2177,12 +2199,12 @@ extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t
 // then the bytes of the segments before it (zs_k_flush_local's scan, which zs_k_flush_place rebases
 // the blocks by).  A host entry's chunks follow each other.
 extern "C" uint64_t zs_last_flush_index(zs_ctx* c, uint32_t* in_pos, uint64_t cap) {
-  if (!c || c->fidx.empty() || !c->fscan.p) return 0;
+  if (!c || c->call.fidx.empty() || !c->fscan.p) return 0;
   if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
-  std::vector<uint64_t> scan(c->fscan_used);
+  std::vector<uint64_t> scan(c->call.fscan_used);
   if (hipMemcpy(scan.data(), c->fscan.p, 8ull * scan.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
   uint64_t k = 0;
-  for (const zs_ctx::FlushIdx& f : c->fidx) {
+  for (const zs_ctx::FlushIdx& f : c->call.fidx) {
     const uint64_t* segx = scan.data() + f.at;
     const uint64_t* tile = segx + f.M + 1;
     auto at = [&](uint32_t x) { return tile[x / ZS_FLUSH_TILE] + segx[x]; };  // the bytes of all segments before x
@@ -2202,8 +2224,8 @@ extern "C" int zs_inflate_batch_dict_device(zs_ctx* c, int wbits, uint32_t n, co
                                             const uint8_t* d_dict, const uint64_t* dict_off,
                                             const uint32_t* dict_len) {
   const DictIn di = {d_dict, dict_off, dict_len};
-  return inflate_device(c, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_phase, d_msg,
-                        d_out_len, d_consumed, d_check, hip_stream, true, &di);
+  return inflate_device(c, wbits, {n, d_in, in_off, in_len, d_out, out_off, out_cap},
+                        {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, hip_stream, &di, nullptr);
 }
 
 extern "C" int zs_inflate_batch_dict(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
@@ -2211,35 +2233,7 @@ extern "C" int zs_inflate_batch_dict(zs_ctx* c, int wbits, uint32_t n, const uin
                                      const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
                                      uint32_t* out_len, uint32_t* consumed, uint32_t* check, const uint8_t* dict,
                                      const uint64_t* dict_off, const uint32_t* dict_len) {
-  if (!c) return fail(ZS_STREAM_ERROR, "null context");
-  if (!dict_off || !dict_len) return fail(ZS_STREAM_ERROR, "null dictionary arrays");
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  // the distinct dictionaries, packed, to the device once (the chunks of host_batch share them)
-  zs_dict_set ds;
-  zs_dict_distinct(n, dict_off, dict_len, ds);
-  if (ds.any && !dict) return fail(ZS_STREAM_ERROR, "null dictionary buffer");
-  if (ds.any && (wbits == 31 || wbits == -16))
-    return fail(ZS_STREAM_ERROR, "dictionaries are for deflate-raw (-15) and zlib (15) only");
-  std::vector<uint64_t> upos, poff;
-  const uint64_t dbytes = zs_dict_pack_layout(ds, n, dict_len, upos, poff);
-  HIPCHK(c->d_dict.ensure(dbytes + 16));
-  if (dbytes) {
-    std::vector<uint8_t> pack(dbytes);
-    zs_dict_pack(ds, upos, dict, pack.data());
-    HIPCHK(hipMemcpy(c->d_dict.p, pack.data(), dbytes, hipMemcpyHostToDevice));
-  }
-  std::vector<uint32_t> ocap(n), creq(out_cap, out_cap + n);
-  for (uint32_t i = 0; i < n; i++) ocap[i] = (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap[i] + 3) & ~3ull);
-  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
-  return host_batch(c, n, in, in_off, in_len, ocap, 6, res, 3, out, out_off,
-                    [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, const uint32_t*,
-                        uint32_t** dr) {
-                      const DictIn di = {c->d_dict.as<uint8_t>(), poff.data() + a, dict_len + a};
-                      return inflate_device(c, wbits,
-                                            {b - a, c->d_in.as<uint8_t>(), doff, in_len + a, c->d_out.as<uint8_t>(),
-                                             ooff, creq.data() + a},
-                                            (int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
-                                            check ? dr[5] : nullptr, c->stream, false, &di);
-                    });
+  const DictIn di = {dict, dict_off, dict_len};  // (host memory here)
+  return inflate_host(c, wbits, {n, in, in_off, in_len, out, out_off, out_cap},
+                      {status, phase, msg, out_len, consumed, check}, &di, nullptr);
 }

@@ -975,6 +975,82 @@ static inline void zs_plan_deflate(const zs_deflate_req& r, const zs_route_opts&
   p.ml = zs_meta_layout(n, (uint32_t)p.segs.size(), p.dict, p.ndict, p.chunks.size());
 }
 
+// ---- an inflate call: the arrays of a plain or _dict entry as far as validation reads them, its
+// faults and the order they win in (the restart entries have zs_restart_validate below)
+struct zs_inflate_call {
+  uint32_t n = 0;
+  const uint64_t* out_off = nullptr;  // (may be null: the host entries stage their own regions)
+  const uint32_t* out_cap = nullptr;
+  bool caller_regions = false;  // the device entries: the capacities must be multiples of 4 too
+  bool dict = false;            // a _dict entry (a batch with every length 0 is the plain batch)
+  bool dict_arrays = false, dict_buf = false;  // the dictionary offsets and lengths / bytes are given
+  const uint32_t* dict_len = nullptr;          // (with dict_arrays)
+};
+enum zs_inflate_err {
+  ZS_IE_OK = 0,
+  ZS_IE_CONTEXT,      // "null context"
+  ZS_IE_WBITS,        // "unsupported windowBits (use -15, 15, 31 or -16)"
+  ZS_IE_DICT_ARRAYS,  // "null dictionary arrays"
+  ZS_IE_DICT_BUFFER,  // "null dictionary buffer"
+  ZS_IE_DICT_FORMAT,  // "dictionaries are for deflate-raw (-15) and zlib (15) only"
+  ZS_IE_ALIGN,        // "output offsets/capacities must be multiples of 4"
+  ZS_IE_COUNT
+};
+static inline const char* zs_inflate_err_text(zs_inflate_err e) {
+  static const char* const kMsg[ZS_IE_COUNT] = {
+      "",
+      "null context",
+      "unsupported windowBits (use -15, 15, 31 or -16)",
+      "null dictionary arrays",
+      "null dictionary buffer",
+      "dictionaries are for deflate-raw (-15) and zlib (15) only",
+      "output offsets/capacities must be multiples of 4",
+  };
+  return kMsg[e];
+}
+static inline bool zs_inflate_any_dict(const zs_inflate_call& a) {
+  for (uint32_t i = 0; a.dict && a.dict_len && i < a.n; i++)
+    if (a.dict_len[i]) return true;
+  return false;
+}
+// The first fault of a device batch, in the order the entries have always reported them: the format
+// (inflateInit2_ / inflateReset2, inflate.ts:138-192) even of an empty batch; the dictionaries -- gzip
+// is never in DICT mode (inflateSetDictionary returns Z_STREAM_ERROR, inflate.ts:1229), the 64 KiB
+// window of deflate64 is not covered; the alignment last (the decoders store whole dwords).
+// ctx: the entry was given a context.
+static inline zs_inflate_err zs_inflate_validate(bool ctx, int wbits, const zs_inflate_call& a) {
+  if (!ctx) return ZS_IE_CONTEXT;
+  if (!(wbits == -15 || wbits == 15 || wbits == 31 || wbits == -16)) return ZS_IE_WBITS;
+  if (a.dict && a.n) {
+    if (!a.dict_arrays) return ZS_IE_DICT_ARRAYS;
+    if (zs_inflate_any_dict(a)) {
+      if (!a.dict_buf) return ZS_IE_DICT_BUFFER;
+      if (wbits == 31 || wbits == -16) return ZS_IE_DICT_FORMAT;
+    }
+  }
+  for (uint32_t i = 0; i < a.n; i++)
+    if ((a.out_off && (a.out_off[i] & 3)) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_IE_ALIGN;
+  return ZS_IE_OK;
+}
+// What a host entry decides of the whole batch before it stages anything.  An empty batch is done
+// whatever its windowBits; the _dict entry wants its arrays even then, and names a dictionary's
+// faults before the format's.
+static inline zs_inflate_err zs_inflate_validate_host(bool ctx, int wbits, const zs_inflate_call& a) {
+  if (!ctx) return ZS_IE_CONTEXT;
+  if (a.dict && !a.dict_arrays) return ZS_IE_DICT_ARRAYS;
+  if (a.n == 0) return ZS_IE_OK;
+  if (zs_inflate_any_dict(a)) {
+    if (!a.dict_buf) return ZS_IE_DICT_BUFFER;
+    if (wbits == 31 || wbits == -16) return ZS_IE_DICT_FORMAT;
+  }
+  return zs_inflate_validate(true, wbits, a);
+}
+// A host entry's device regions: the caller's capacity rounded up to whole words (the kernels store
+// dwords); the caller's exact capacities stay the Z_BUF_ERROR limits
+static inline uint32_t zs_host_region_cap(uint32_t out_cap) {
+  return (uint32_t)std::min<uint64_t>(0xfffffffcull, ((uint64_t)out_cap + 3) & ~3ull);
+}
+
 // ---- inflate with restart points (inflateSync, inflate.ts:1267-1337).  Behind a full-flush
 // marker the bit stream is byte-aligned and the window empty, so the piece from one restart point to
 // the next is a raw deflate stream of its own but for its end: it closes with the marker's empty stored
