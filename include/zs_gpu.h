@@ -465,7 +465,7 @@ int zs_pool_deflate_batch_flush(zs_pool *pool, int level, int wbits, uint32_t n_
  *    an in_pos less than 5 bytes (a marker alone) behind the point before; a decreasing out_pos; an
  *    in_pos past in_len[i]; for the device entry, out_off / out_cap that are no multiples of 4.
  *  - Preset dictionaries and the unbounded (_auto) output are not built with restart points: there are
- *    no _dict or _auto forms.  Finding the points (a batched syncsearch) is not built either.
+ *    no _dict or _auto forms.  A caller without an index uses the _sync entries below, which find the points.
  *  - Timing phases: "restart_gather", "restart_place", "restart_stitch", around the decoders' own. */
 /* inflate.ts:1267-1337 -- device buffers (as zs_inflate_batch_device_ex) */
 int zs_inflate_batch_restart_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
@@ -499,6 +499,68 @@ uint32_t zs_wrapper_header_len(int wbits, const uint8_t *in, uint32_t in_len);
  * 0 when the last compress call had no flush point.  Not offered on the pool (its shards' contexts are
  * its own). */
 uint64_t zs_last_flush_index(zs_ctx *ctx, uint32_t *in_pos, uint64_t cap);
+
+/* Restart points found from the bytes: a batched syncsearch (inflate.ts:1267-1283) for a caller who has
+ * no index -- a seekable .gz of another writer, or this engine's own flushed output after the index was
+ * lost.  The entries take EXACTLY the arguments of zs_inflate_batch_device_ex / zs_inflate_batch_ex /
+ * zs_pool_inflate_batch (sharded by stream), no point arrays; for every stream they find the points and
+ * run the restart entries' decode with them, whose contract holds with the found points:
+ *  - For every stream that zlib's inflate decodes (the plain entry with inflate_ref_wrap = 0) the output,
+ *    out_len, consumed and check are the plain entry's, with ZS_STREAM_END.  A stream without a marker is
+ *    one segment and decodes as the plain entry does.  A stream that does not decode reports the restart
+ *    entries' one failure (ZS_DATA_ERROR, ZS_PHASE_PROCESS, "restart points do not decode the stream",
+ *    lengths 0) or their capacity outcome (ZS_BUF_ERROR, "output capacity exceeded"); its neighbours are
+ *    untouched and no store leaves a stream's region rounded up to 4.  A malformed header is that failure
+ *    too (a zlib stream with FDICT fails its header check).
+ *  - How: a scan lists every offset behind the bytes 00 00 FF FF (CANDIDATES: a stored block may hold the
+ *    same bytes); a count-only decode, one lane per START (the first point, behind the wrapper's header,
+ *    and every candidate), records where and how the lane ended -- at the next candidate with a block
+ *    just closed on a byte boundary, at the final block, at an error, or at its work bound -- the bytes
+ *    it produced and how far its copies reach back before its start; the host follows the records from
+ *    the first point, which gives the true points and their out_pos, and drops the points behind which
+ *    the window is not empty (Z_SYNC_FLUSH / Z_PARTIAL_FLUSH markers: a stream with only those decodes
+ *    as one segment, correct and no faster).  Where the chain stops before the final block (an error, or
+ *    the work bound) the rest of the stream is one last segment.
+ *  - The work bound: a lane started at candidate j of its stream stops at candidate j + sync_pass + 1
+ *    (option "sync_pass", 1 .. 64, default 8), so every input byte is decoded by at most sync_pass + 1
+ *    lanes whatever the bytes are.  A true segment that holds more than sync_pass false candidates ends
+ *    the chain there: the decode stays correct and loses the points behind it (the rest of such a stream is
+ *    sized once more, to its end, for how far its copies reach back: one more lane per such stream).
+ *  - zlib semantics always, capacities must be given; wbits -16, one the plain entry refuses, a null
+ *    out_cap and, for the device entry, out_off / out_cap that are no multiples of 4 are refused with
+ *    ZS_STREAM_ERROR before the context is looked at, in that order.  More than 67,108,863 candidates plus
+ *    streams in one call is ZS_STREAM_ERROR (the restart entries' segment cap): split the batch.
+ *  - The points are planned on the host: the DEVICE entry synchronises hip_stream once in the middle
+ *    (behind the scan and the size decode; a second time in a call whose candidates outgrow the list the
+ *    context keeps from earlier calls, or in which a chain ends at its work bound), and is asynchronous
+ *    from there on.  Its first points are computed
+ *    on the device by the parse of zs_wrapper_header_len; the host entries run that function on their bytes.
+ *  - The HOST entries run as one chunk (zs_last_host_chunks = 1) whatever the batch's size: the scan is
+ *    not chunked.
+ *  - Timing phases: "sync_scan", "sync_size", in front of the restart phases.
+ *  - Not built: the chunked host pipeline for these calls; decoding only a range of segments (a seek);
+ *    _auto capacities; dictionaries; deflate64; multi-member gzip files; cutting at dynamic-block
+ *    boundaries (what the split decode does inside one member); zs_last_restart_points on the pool. */
+int zs_inflate_batch_sync_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                 int32_t *d_phase, int32_t *d_msg, uint32_t *d_out_len, uint32_t *d_consumed,
+                                 uint32_t *d_check, void *hip_stream);
+int zs_inflate_batch_sync(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                          const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                          int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
+                          uint32_t *check);
+int zs_pool_inflate_batch_sync(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                               const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                               const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
+                               uint32_t *out_len, uint32_t *consumed, uint32_t *check);
+/* The points the last zs_inflate_batch_sync_device / zs_inflate_batch_sync call on the context used, in
+ * the layout the restart entries take, every stream's first point included: restart_first gets
+ * n_streams + 1 entries (from 0), restart_in / restart_out at most cap points; returns the count of
+ * points.  A caller can keep them as an index and call zs_inflate_batch_restart* next time.  0 when the
+ * last inflate call on the context was no _sync call.  Not offered on the pool. */
+uint64_t zs_last_restart_points(zs_ctx *ctx, uint64_t *restart_first, uint32_t *restart_in, uint32_t *restart_out,
+                                uint64_t cap);
 
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);

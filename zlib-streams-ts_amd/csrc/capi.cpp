@@ -118,6 +118,7 @@ struct zs_ctx {
     size_t fscan_at = 0, fscan_used = 0;  // the current device call's scan in fscan; u64 values in use
     bool seg_ran = false;       // a segmented launch has run: its count of members finished goes on
     bool lanes_zeroed = false;  // the lane counter (lstat) has been zeroed
+    bool sync = false;          // the points were found by the call (zs_last_restart_points)
   } call;
   // a batch with restart points: the plan, the closed copies of the segments, the staging
   // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
@@ -125,6 +126,10 @@ struct zs_ctx {
   zs_restart_plan rp;
   Buf rgather, rstage, rres, rmark, rsum;
   std::vector<uint8_t> rhmeta;
+  // a batch that finds its restart points: the streams' arrays and first points, the scan's
+  // tiles, the candidates, the lanes' records; the plan's points, which zs_last_restart_points returns
+  Buf ymeta, ytile, ycand, yrec, ytail;
+  zs_sync_plan yp;
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
@@ -168,7 +173,7 @@ static void call_begin(zs_ctx* c, CallKind kind) {
     k.fidx.clear();
     k.fscan_at = k.fscan_used = 0;
   }
-  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = false;
+  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = k.sync = false;
 }
 static void fold_marks(zs_ctx* c);
 
@@ -277,6 +282,7 @@ static const Option kOptions[] = {
             "checksum_part must be a power of two, 1024 .. 1048576"),
     OPT_INT("host_chunk_min", o.host_chunk_min, zs_host_chunk_min_ok(v), "host_chunk_min must be >= 0"),
     OPT_INT("host_pack_min", o.host_pack_min, zs_host_pack_min_ok(v), "host_pack_min must be >= 0"),
+    OPT_INT("sync_pass", o.sync_pass, zs_sync_pass_ok(v), "sync_pass must be 1 .. 64"),
 };
 
 extern "C" {
@@ -1057,7 +1063,7 @@ __global__ void zs_k_compact(const uint8_t* __restrict__ src, const uint64_t* __
 // res_host[len_idx] is the output length.  Outputs land at h.out + h.out_off[i].
 template <class Launch>
 static int host_batch_run(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* const* res_host, uint32_t len_idx,
-                          Launch launch) {
+                          Launch launch, bool one_chunk) {
   const uint32_t n = h.n;
   std::vector<uint64_t> doff(n), ooff(n);
   std::vector<uint32_t> ocap(n);
@@ -1083,6 +1089,7 @@ static int host_batch_run(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* co
   HIPCHK(c->h_offs.ensure(16ull * n + 16));
   std::vector<uint32_t> bnd;
   zs_plan_host_chunks(c->o, n, tin, bnd);
+  if (one_chunk) bnd = {0u, n};  // (a call that finds its restart points: its scan is not chunked)
   const uint32_t K = (uint32_t)bnd.size() - 1;
   while (c->hev.size() < 3 * K) {
     hipEvent_t e;
@@ -1180,8 +1187,8 @@ static int host_batch_run(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* co
 // are waited for before returning (the next call reuses the staging buffers)
 template <class Launch>
 static int host_batch(zs_ctx* c, const Batch& h, uint32_t nres, uint32_t* const* res_host, uint32_t len_idx,
-                      Launch launch) {
-  const int rc = host_batch_run(c, h, nres, res_host, len_idx, launch);
+                      Launch launch, bool one_chunk = false) {
+  const int rc = host_batch_run(c, h, nres, res_host, len_idx, launch, one_chunk);
   if (rc != ZS_OK) {
     (void)hipStreamSynchronize(c->h2d);
     (void)hipStreamSynchronize(c->stream);
@@ -2073,6 +2080,123 @@ static int restart_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut&
   return ZS_OK;
 }
 
+// ---- restart points found from the bytes (inflateSync / syncsearch, inflate.ts:1267-1337).
+// A fault of the arguments is reported before the context is looked at (zs_sync_validate, then the null
+// context).
+static int sync_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
+  zs_inflate_call a;
+  a.n = h.n;
+  a.out_off = device_entry ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = device_entry;
+  if (const zs_sync_err e = zs_sync_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_sync_err_text(e));
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
+}
+
+// The device decode of a validated, non-empty batch that finds its own points (regions as
+// inflate_batch's).  first: the streams' first points where the caller has the bytes (the host
+// entries), else zs_k_sync_first computes them.  The scan and the size decode run on st, which is
+// then waited for: the points are planned here, from the candidates and the lanes' records.  The
+// candidate list has the size the calls before needed; when this call has more, the emit pass and
+// the size decode run once more over the grown list (and st is waited for a second time); so it is
+// where a chain ends at a lane its bound stopped (zs_k_sync_tail).
+static int sync_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, hipStream_t st, const uint32_t* first) {
+  const uint32_t n = h.n;
+  std::vector<uint32_t> sh16(n), stile;
+  uint64_t tin = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    sh16[i] = (uint32_t)(((uintptr_t)h.in + h.in_off[i]) & 15u);
+    tin += h.in_len[i];
+  }
+  zs_plan_sync_tiles(n, h.in_len, sh16.data(), stile);
+  const uint32_t T = stile[n];
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m_off = 0, m_len = up256(8ull * n), m_first = m_len + up256(4ull * n), m_tile = m_first + up256(4ull * n),
+               m_end = m_tile + up256(4ull * (n + 1));
+  HIPCHK(c->ymeta.ensure(m_end));
+  HIPCHK(c->ytile.ensure(8ull * T + 16));
+  HIPCHK(c->ycand.ensure(4ull * (tin / 2048 + 1024)));
+  std::vector<uint8_t> hm(m_end, 0);
+  memcpy(hm.data() + m_off, h.in_off, 8ull * n);
+  memcpy(hm.data() + m_len, h.in_len, 4ull * n);
+  if (first) memcpy(hm.data() + m_first, first, 4ull * n);
+  memcpy(hm.data() + m_tile, stile.data(), 4ull * (n + 1));
+  HIPCHK(hipMemcpyAsync(c->ymeta.p, hm.data(), m_end, hipMemcpyHostToDevice, st));
+  const uint8_t* dm = c->ymeta.as<uint8_t>();
+  const uint64_t* d_off = (const uint64_t*)(dm + m_off);
+  const uint32_t* d_len = (const uint32_t*)(dm + m_len);
+  uint32_t* d_first = (uint32_t*)(c->ymeta.as<uint8_t>() + m_first);
+  const uint32_t* d_tile = (const uint32_t*)(dm + m_tile);
+  uint64_t* tcount = c->ytile.as<uint64_t>();
+  const uint32_t grid = std::max(1u, std::min(T, 32u * c->o.ncu));
+  MARK("start");
+  if (!first) zs_k_sync_first<<<(n + 255) / 256, 256, 0, st>>>(h.in, d_off, d_len, wbits, n, d_first);
+  zs_k_sync_scan<false><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_first, d_tile, n, tcount, nullptr, 0);
+  zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tcount, T + 1);
+  HIPCHK(hipGetLastError());
+  std::vector<uint64_t> tpre(T + 1);
+  for (int round = 0;; round++) {
+    const uint64_t cap = c->ycand.cap / 4;
+    HIPCHK(c->yrec.ensure(sizeof(zs_sync_rec) * (n + cap)));
+    zs_k_sync_scan<true><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_first, d_tile, n, tcount, c->ycand.as<uint32_t>(), cap);
+    MARK("sync_scan");
+    // (a lane per stream and per place of the list: the lanes past the candidates' count return at once)
+    const uint64_t lanes = std::min<uint64_t>(n + cap, ZS_RESTART_SEG_MAX);
+    zs_k_sync_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
+        h.in, d_off, d_len, d_first, d_tile, n, tcount, c->ycand.as<uint32_t>(), cap, c->o.sync_pass,
+        c->yrec.as<zs_sync_rec>());
+    MARK("sync_size");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(tpre.data(), tcount, 8ull * (T + 1), hipMemcpyDeviceToHost));
+    if (!zs_sync_count_ok(n, tpre[T]))
+      return fail(ZS_STREAM_ERROR, "%s", "too many restart candidates (more than 67,108,863 with the streams in one call)");
+    if (tpre[T] <= cap) break;
+    if (round) return fail(ZS_MEM_ERROR, "%s", "the restart candidates' list did not settle");
+    HIPCHK(c->ycand.ensure(4ull * tpre[T]));
+  }
+  const uint64_t C = tpre[T];
+  std::vector<uint32_t> cand(C), hfirst(n);
+  std::vector<zs_sync_rec> rec(n + C);
+  if (C) HIPCHK(hipMemcpy(cand.data(), c->ycand.p, 4ull * C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec.data(), c->yrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hfirst.data(), d_first, 4ull * n, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> cfirst(n + 1);
+  for (uint32_t i = 0; i <= n; i++) cfirst[i] = tpre[stile[i]];
+  zs_plan_sync(n, h.in_len, hfirst.data(), cfirst.data(), cand.data(), rec.data(), c->yp);
+  if (const uint32_t m = (uint32_t)c->yp.tstream.size()) {
+    // chains that end at a lane its bound stopped: the whole tail's reach (zs_k_sync_tail), then the plan again
+    const size_t t_start = up256(4ull * m);
+    HIPCHK(c->ytail.ensure(2 * t_start + sizeof(zs_sync_rec) * m));
+    uint8_t* dt = c->ytail.as<uint8_t>();
+    HIPCHK(hipMemcpyAsync(dt, c->yp.tstream.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dt + t_start, c->yp.tstart.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    zs_k_sync_tail<<<(m + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES, ZS_SYNC_LANES, 0, st>>>(
+        h.in, d_off, d_len, (const uint32_t*)dt, (const uint32_t*)(dt + t_start), m, (zs_sync_rec*)(dt + 2 * t_start));
+    MARK("sync_size");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<zs_sync_rec> tail(m);
+    HIPCHK(hipMemcpy(tail.data(), dt + 2 * t_start, sizeof(zs_sync_rec) * m, hipMemcpyDeviceToHost));
+    const std::vector<uint64_t> trec = c->yp.trec;
+    for (uint32_t k = 0; k < m; k++) rec[trec[k]].reach = std::max(rec[trec[k]].reach, tail[k].reach);
+    zs_plan_sync(n, h.in_len, hfirst.data(), cfirst.data(), cand.data(), rec.data(), c->yp);
+  }
+  {  // the plan's points pass the restart entries' validation by construction: nothing is launched otherwise
+    zs_restart_call a;
+    a.n = n;
+    a.in_len = h.in_len;
+    a.out_cap = h.out_cap;
+    a.rfirst = c->yp.rfirst.data();
+    a.rin = c->yp.rin.data();
+    a.rout = c->yp.rout.data();
+    if (const zs_restart_err e = zs_restart_validate(wbits, a))
+      return fail(ZS_MEM_ERROR, "the found restart points are refused: %s", zs_restart_err_text(e));
+  }
+  c->call.sync = true;
+  return restart_batch(c, wbits, h, out, st, {c->yp.rfirst.data(), c->yp.rin.data(), c->yp.rout.data()});
+}
+
 // zs_inflate_validate's findings, as the entries report them
 static int inflate_fail(zs_inflate_err e) { return fail(ZS_STREAM_ERROR, "%s", zs_inflate_err_text(e)); }
 // The arrays of a plain or _dict call as validation reads them (the host entries stage their own regions)
@@ -2105,8 +2229,8 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, const InflateOut
 // batch decides before anything is staged, the dictionaries to the device once, then the call begins and
 // host_batch runs its chunks, each a device batch with a copy of the caller's exact capacities as the limits.
 static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, const DictIn* dict,
-                        const RestartIn* rs) {
-  if (!rs)  // (a restart call has passed restart_refused)
+                        const RestartIn* rs, bool sync = false) {
+  if (!rs && !sync)  // (a restart call has passed restart_refused, one that finds its points sync_refused)
     if (const zs_inflate_err e = zs_inflate_validate_host(c != nullptr, wbits, inflate_call(h, false, dict)))
       return inflate_fail(e);
   HIPCHK(hipSetDevice(c->device));
@@ -2126,9 +2250,16 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                                             out.check ? dr[5] : nullptr};
                       // (a chunk's points and dictionaries: the same arrays, the chunk's part of the index)
                       if (rs) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
+                      if (sync) {  // the first points where the bytes are: the caller's memory
+                        std::vector<uint32_t> first(b - a);
+                        for (uint32_t i = a; i < b; i++)
+                          first[i - a] = std::min(zs_wrapper_header_len(wbits, h.in + h.in_off[i], h.in_len[i]), h.in_len[i]);
+                        return sync_batch(c, wbits, hb, d, c->stream, first.data());
+                      }
                       const DictIn di = dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
                       return inflate_batch(c, wbits, hb, d, c->stream, dict ? &di : nullptr, nullptr);
-                    });
+                    },
+                    sync);
 }
 
 extern "C" int zs_inflate_batch_device_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
@@ -2188,6 +2319,44 @@ extern "C" int zs_inflate_batch_restart(zs_ctx* c, int wbits, uint32_t n, const 
   const RestartIn rs = {restart_first, restart_in, restart_out};
   if (const int r = restart_refused(c, wbits, h, false, rs)) return r;
   return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, &rs);
+}
+
+// inflate.ts:1267-1337 -- the points found from the bytes; device buffers
+extern "C" int zs_inflate_batch_sync_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
+                                            const uint32_t* in_len, uint8_t* d_out, const uint64_t* out_off,
+                                            const uint32_t* out_cap, int32_t* d_status, int32_t* d_phase,
+                                            int32_t* d_msg, uint32_t* d_out_len, uint32_t* d_consumed,
+                                            uint32_t* d_check, void* hip_stream) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  if (const int r = sync_refused(c, wbits, h, true)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  call_begin(c, CALL_INFLATE);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return sync_batch(c, wbits, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, nullptr);
+}
+
+// ... host buffers
+extern "C" int zs_inflate_batch_sync(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                     const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                     const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                     uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
+  if (const int r = sync_refused(c, wbits, h, false)) return r;
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, true);
+}
+
+// The points the last call on the context found, in the layout the restart entries take: restart_first
+// (n + 1 entries, from 0), then at most `cap` points.  0 when the last inflate call found none itself.
+extern "C" uint64_t zs_last_restart_points(zs_ctx* c, uint64_t* restart_first, uint32_t* restart_in,
+                                           uint32_t* restart_out, uint64_t cap) {
+  if (!c || !c->call.sync) return 0;
+  const zs_sync_plan& p = c->yp;
+  if (restart_first) memcpy(restart_first, p.rfirst.data(), 8ull * p.rfirst.size());
+  const uint64_t k = std::min<uint64_t>(cap, p.rin.size());
+  if (restart_in) memcpy(restart_in, p.rin.data(), 4ull * k);
+  if (restart_out) memcpy(restart_out, p.rout.data(), 4ull * k);
+  return p.rin.size();
 }
 
 extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t in_len) {

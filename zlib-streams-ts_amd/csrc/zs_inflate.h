@@ -101,3 +101,17 @@ __global__ void zs_k_restart_stitch(const uint8_t* in, const uint64_t* in_off, c
                                     int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* want);
 __global__ void zs_k_restart_check(const uint32_t* sum, const uint32_t* want, int wbits, uint32_t n, int32_t* status,
                                    int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* check);
+
+// restart points found from the bytes (inflate_sync.hip): the first points, the candidates
+// (<false> counts per tile, <true> emits), the count-only decode from every start
+struct zs_sync_rec;
+__global__ void zs_k_sync_first(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, int wbits, uint32_t n,
+                                uint32_t* first);
+template <bool EMIT>
+__global__ void zs_k_sync_scan(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* first,
+                               const uint32_t* stile, uint32_t n, uint64_t* tcount, uint32_t* cand, uint64_t cap);
+__global__ void zs_k_sync_size(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* first,
+                               const uint32_t* stile, uint32_t n, const uint64_t* tpre, const uint32_t* cand, uint64_t cap,
+                               uint32_t pass, zs_sync_rec* rec);
+__global__ void zs_k_sync_tail(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* tstream,
+                               const uint32_t* tstart, uint32_t m, zs_sync_rec* rec);

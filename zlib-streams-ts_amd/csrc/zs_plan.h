@@ -97,6 +97,8 @@ struct zs_route_opts {
   // the host-buffer entries' pipeline (zs_plan_host_chunks, zs_plan_host_pack0)
   uint64_t host_chunk_min = 32ull << 20;  // input bytes from which a batch of ZS_HOST_CHUNK_STREAMS runs as four chunks; 0: never
   uint64_t host_pack_min = 64ull << 20;   // the floor of the pack buffers' first guess, in bytes
+  // the restart-point search (zs_k_sync_size): a lane started at candidate j stops at candidate j + sync_pass + 1
+  uint32_t sync_pass = 8;
 };
 
 // ---- the host-buffer entries' pipeline (capi.cpp, host_batch_run)
@@ -1255,5 +1257,130 @@ struct zs_restart_layout {
     bytes = o;
   }
 };
+
+// ---- inflate that finds its own restart points (inflateSync / syncsearch,
+// inflate.ts:1267-1337).  zs_k_sync_scan lists every offset behind the bytes 00 00 FF FF (the
+// CANDIDATES: a stored block may hold the same bytes), zs_k_sync_size decodes from the first point
+// and from every candidate without storing (one lane per START, zs_sync.h) and records how and
+// where each lane ended, the bytes it produced and how far its copies reach back before its start;
+// zs_plan_sync follows the records from the first point and emits the points in the restart
+// entries' layout, which restart_batch then decodes unchanged.
+#define ZS_SYNC_TILE 4096u   // bytes per workgroup step of the scan: 256 lanes, one aligned 16-byte unit each
+#define ZS_SYNC_LANES 16u    // starts per workgroup of the size decode (their Huffman state: 2,164 bytes of LDS each)
+static inline bool zs_sync_pass_ok(int v) { return v >= 1 && v <= 64; }  // zs_set_option's values of "sync_pass"
+// how a lane of zs_k_sync_size ended
+#define ZS_SYNC_LANDED 1u  // a block closed at a byte boundary behind the marker: `end` is a candidate
+#define ZS_SYNC_FINAL 2u   // the final block closed: `end` = the bytes consumed
+#define ZS_SYNC_ERROR 3u   // the bytes are no deflate data, or the input is exhausted
+#define ZS_SYNC_PASSED 4u  // the work bound: the lane reached candidate j + sync_pass + 1 of its stream
+struct zs_sync_rec {
+  uint32_t how, end;  // ZS_SYNC_*; the byte offset in the stream's input
+  uint32_t len;       // bytes produced up to there
+  uint32_t reach;     // the largest (distance - bytes produced so far) over the lane's copies, 0: none positive
+};
+enum zs_sync_err {
+  ZS_SE_OK = 0,
+  ZS_SE_WBITS,  // "unsupported windowBits (use -15, 15 or 31)"
+  ZS_SE_D64,    // "deflate64 has no restart points"
+  ZS_SE_CAPS,   // "restart points are found with given capacities only"
+  ZS_SE_ALIGN,  // "output offsets/capacities must be multiples of 4"
+  ZS_SE_COUNT
+};
+static inline const char* zs_sync_err_text(zs_sync_err e) {
+  static const char* const kMsg[ZS_SE_COUNT] = {
+      "",
+      "unsupported windowBits (use -15, 15 or 31)",
+      "deflate64 has no restart points",
+      "restart points are found with given capacities only",
+      "output offsets/capacities must be multiples of 4",
+  };
+  return kMsg[e];
+}
+// The fault that wins, in the restart entries' order without their index: the format, even of an
+// empty batch; the capacities; the device entry's alignment rule last.  Nothing here looks at a context.
+static inline zs_sync_err zs_sync_validate(int wbits, const zs_inflate_call& a) {
+  if (wbits == -16) return ZS_SE_D64;
+  if (!(wbits == -15 || wbits == 15 || wbits == 31)) return ZS_SE_WBITS;
+  if (a.n == 0) return ZS_SE_OK;
+  if (!a.out_cap) return ZS_SE_CAPS;
+  for (uint32_t i = 0; a.out_off && i < a.n; i++)
+    if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_SE_ALIGN;
+  return ZS_SE_OK;
+}
+// candidates plus streams of one call: every one becomes a lane and may become a segment
+static inline bool zs_sync_count_ok(uint32_t n, uint64_t candidates) { return candidates + n <= ZS_RESTART_SEG_MAX; }
+// The scan's tiles: stream i lies `sh16[i]` bytes into its first aligned 16-byte unit; stile: n + 1 prefix sums
+static inline void zs_plan_sync_tiles(uint32_t n, const uint32_t* in_len, const uint32_t* sh16, std::vector<uint32_t>& stile) {
+  stile.assign(1, 0u);
+  for (uint32_t i = 0; i < n; i++)
+    stile.push_back(stile.back() + (in_len[i] ? (uint32_t)(((uint64_t)sh16[i] + in_len[i] + ZS_SYNC_TILE - 1) / ZS_SYNC_TILE) : 0u));
+}
+struct zs_sync_plan {
+  std::vector<uint64_t> rfirst;    // n + 1
+  std::vector<uint32_t> rin, rout;  // the points, every stream's first included
+  // the chains that end at a PASSED lane behind the first point: the stream, the lane's start and its record's
+  // index.  The record's reach covers the tail only up to the bound: the caller sizes the tail to its end
+  // (zs_k_sync_tail), raises the record's reach to the whole tail's and plans again.
+  std::vector<uint32_t> tstream, tstart;
+  std::vector<uint64_t> trec;
+};
+// Stream i has the first point first[i] (the wrapper's header length, cut at in_len[i]: a header that
+// does not fit fails its check in the restart path), the candidates cand[cfirst[i] .. cfirst[i + 1])
+// in increasing order, the record rec[i] of the lane started at its first point and rec[n + k] of
+// the lane started at candidate k.
+//   1. the chain: from the first point, a LANDED lane's end is the next point (a candidate, found by
+//      binary search; the chain also stops where it is none, or where the output passes 2^32 - 1)
+//   2. the chain's last lane is FINAL, or its start is the last point and the rest of the stream one
+//      tail segment, which the restart path decodes or fails as any last segment (a PASSED lane's
+//      record knows the tail's reach only up to its bound: see zs_sync_plan's tstream)
+//   3. a point behind which the window is not empty (Z_SYNC_FLUSH, Z_PARTIAL_FLUSH) goes: a segment
+//      with reach > 0 loses its own point and every earlier kept point that its reach extends past
+//      (a stack); the first point is never dropped
+//   4. out_pos: the prefix sums of the chain's lengths
+// The result passes zs_restart_validate by construction.
+static inline void zs_plan_sync(uint32_t n, const uint32_t* in_len, const uint32_t* first, const uint64_t* cfirst,
+                                const uint32_t* cand, const zs_sync_rec* rec, zs_sync_plan& p) {
+  p.rfirst.assign(1, 0);
+  p.rin.clear();
+  p.rout.clear();
+  p.tstream.clear();
+  p.tstart.clear();
+  p.trec.clear();
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t* c0 = cand + cfirst[i];
+    const uint32_t* c1 = cand + cfirst[i + 1];
+    const size_t base = p.rin.size();  // the stream's first point: the bottom of the stack
+    uint32_t pos = std::min(first[i], in_len[i]);
+    uint64_t out = 0;
+    const zs_sync_rec* r = &rec[i];
+    for (;;) {
+      if (p.rin.size() == base || r->reach == 0) {
+        p.rin.push_back(pos);
+        p.rout.push_back((uint32_t)out);
+      } else {
+        // this segment's copies read output from out - reach on: every point behind that byte goes too
+        const uint64_t low = out > r->reach ? out - r->reach : 0;
+        while (p.rin.size() > base + 1 && p.rout.back() > low) {
+          p.rin.pop_back();
+          p.rout.pop_back();
+        }
+      }
+      if (r->how == ZS_SYNC_PASSED && r != &rec[i]) {  // (the first point is never dropped: its reach decides nothing)
+        p.tstream.push_back(i);
+        p.tstart.push_back(pos);
+        p.trec.push_back((uint64_t)(r - rec));
+      }
+      if (r->how != ZS_SYNC_LANDED || (uint64_t)r->end < (uint64_t)pos + ZS_RESTART_MIN_GAP || r->end > in_len[i] ||
+          out + r->len > 0xffffffffull)
+        break;
+      const uint32_t* at = std::lower_bound(c0, c1, r->end);
+      if (at == c1 || *at != r->end) break;
+      pos = r->end;
+      out += r->len;
+      r = &rec[n + (size_t)(at - cand)];
+    }
+    p.rfirst.push_back(p.rin.size());
+  }
+}
 
 #endif

@@ -59,8 +59,11 @@ export interface DecompressBatchOptions extends BatchOptions {
    * as one stream, with zlib semantics (the reference's window-wrap copy is not reproduced on this path).  A
    * stream whose points do not decode it fails with "process error: -3", zmsg "restart points do not decode
    * the stream"; points out of order, or past the input, fail with "init failed: -2" (code "-2").  Needs
-   * `outCapacity`; without it, with `dictionary` or for "deflate64-raw" it is a TypeError. */
-  restartPoints?: ([number, number][] | null)[];
+   * `outCapacity`; without it, with `dictionary` or for "deflate64-raw" it is a TypeError.
+   * "scan": the engine finds the points from the bytes (a batched syncsearch, inflate.ts:1267-1283) -- for a
+   * seekable .gz of another writer, or a flushed stream whose index was lost.  The same conditions and the
+   * same results; a stream without a full-flush marker decodes as one segment. */
+  restartPoints?: ([number, number][] | null)[] | "scan";
 }
 /** The length of the wrapper's header in front of the deflate data: 0 for "deflate-raw", 2 for "deflate", for
  * "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC, or 0 when that header is malformed or does not fit. */

@@ -192,6 +192,8 @@ export function wrapperHeaderLength(input, format = "gzip") {
 // uncompressed bytes before it (zs_inflate_batch_restart in zs_gpu.h; inflateSync, inflate.ts:1267-1337).
 // The segments decode in parallel, with zlib semantics.  Needs outCapacity; with a dictionary it is a
 // TypeError (not built).  Returns, per input, the flat pairs with the start -- [header length, 0] -- first.
+// restartPoints: "scan": the engine finds the points from the bytes (zs_inflate_batch_sync in zs_gpu.h), for
+// a caller without an index; the same conditions, and the same result as with the true points.
 function restartOf(options, ins, format) {
   const r = options.restartPoints;
   if (r === undefined || r === null) return undefined;
@@ -200,6 +202,7 @@ function restartOf(options, ins, format) {
   if (options.outCapacity === undefined || options.outCapacity === null)
     throw new TypeError("restartPoints need outCapacity");
   if (format === "deflate64-raw") throw new TypeError("deflate64-raw has no restart points");
+  if (r === "scan") return r;
   if (!Array.isArray(r) || r.length !== ins.length)
     throw new TypeError("restartPoints must be an array with one entry per input");
   const u32 = (x) => Number.isInteger(x) && x >= 0 && x <= 0xffffffff;

@@ -220,6 +220,7 @@ typedef struct {
    * (restart_in[k], restart_out[k]) for k in restart_first[i] .. restart_first[i + 1]; NULL: none given */
   uint64_t *restart_first;
   uint32_t *restart_in, *restart_out;
+  int restart_scan;    /* restart "scan": the points are found from the bytes (zs_pool_inflate_batch_sync) */
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -275,6 +276,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
                                        j->dict_off, j->dict_len);
+  else if (j->inflate && j->restart_scan)
+    j->rc = zs_pool_inflate_batch_sync(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off, j->cap,
+                                       j->status, j->phase, j->msg, j->olen, j->cons, j->check);
   else if (j->inflate && j->restart_first)
     j->rc = zs_pool_inflate_batch_restart(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                           j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check,
@@ -645,13 +649,14 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
 }
 
 /* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,
- *                 dictionaries: (Uint8Array | null)[] | undefined, restart: number[][] | undefined) ->
+ *                 dictionaries: (Uint8Array | null)[] | undefined, restart: number[][] | "scan" | undefined) ->
  *   Promise<{status, phase: Int32Array, message: string[], outputs: Uint8Array[], consumed: Int32Array,
  *            check: Uint32Array}>
  * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto).
  * restart: per input the flat pairs in_pos, out_pos of its points, the start first (zs_pool_inflate_batch_restart,
- * zs_gpu.h); needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any
- * device is touched. */
+ * zs_gpu.h), or the string "scan": the points are found from the bytes (zs_pool_inflate_batch_sync); either
+ * needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any device is
+ * touched. */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
   size_t argc = 6;
   napi_value argv[6];
@@ -722,7 +727,16 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
   }
   napi_valuetype rt = napi_undefined;
   if (argc > 5) napi_typeof(env, argv[5], &rt);
-  if (rt != napi_undefined && rt != napi_null) {
+  if (rt == napi_string) {
+    char word[8] = "";
+    size_t len = 0;
+    napi_get_value_string_utf8(env, argv[5], word, sizeof word, &len);
+    if (strcmp(word, "scan") != 0) {
+      job_free(j);
+      return throw_code(env, ZS_STREAM_ERROR, "restart must be number[][] or \"scan\"");
+    }
+    j->restart_scan = 1;
+  } else if (rt != napi_undefined && rt != napi_null) {
     const int rc = copy_restart(env, j, argv[5]);
     if (rc != 0) {
       job_free(j);

@@ -230,6 +230,13 @@ def lib():
         L.zs_wrapper_header_len.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32]
         L.zs_last_flush_index.restype = ctypes.c_uint64
         L.zs_last_flush_index.argtypes = [_P, _U32P, ctypes.c_uint64]
+    if hasattr(L, "zs_inflate_batch_sync"):  # exactly the counterparts' arguments: the points are found
+        L.zs_inflate_batch_sync.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_pool_inflate_batch_sync.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_inflate_batch_sync_device.argtypes = [_P, ctypes.c_int, ctypes.c_uint32, _P, _U64P, _U32P, _P, _U64P, _U32P,
+                                                   _P, _P, _P, _P, _P, _P, _P]
+        L.zs_last_restart_points.restype = ctypes.c_uint64
+        L.zs_last_restart_points.argtypes = [_P, _U64P, _U32P, _U32P, ctypes.c_uint64]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -328,6 +335,18 @@ def wrapper_header_len(data: bytes, fmt: str = "gzip") -> int:
     FHCRC), or 0 when that header is malformed or does not fit.  Host arithmetic, no GPU."""
     data = bytes(data)
     return int(lib().zs_wrapper_header_len(decompress_wbits(fmt), data, len(data)))
+
+
+def decompress_scan(restart, out_caps, zdict=None) -> bool:
+    """restart="scan": the entry finds the points itself (zs_inflate_batch_sync*).  The capacities must
+    be given and dictionaries are not built with it: ValueError, before any call."""
+    if not (isinstance(restart, str) and restart == "scan"):
+        return False
+    if out_caps is None:
+        raise ValueError("restart points need out_caps (the unbounded output is not built with them)")
+    if zdict is not None:
+        raise ValueError("restart points with a preset dictionary are not built")
+    return True
 
 
 def decompress_restart(inputs, fmt, restart, out_caps, zdict=None):
@@ -510,13 +529,18 @@ class Engine:
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only (zs_inflate_batch_dict*).
         restart: one list per input of (in_pos, out_pos) restart points (decompress_restart;
-        zs_inflate_batch_restart: the segments decode in parallel, zlib semantics; needs out_caps)."""
+        zs_inflate_batch_restart: the segments decode in parallel, zlib semantics; needs out_caps), or
+        "scan": the points are found from the bytes (zs_inflate_batch_sync; last_restart_points())."""
         return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                                   out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
+        if decompress_scan(restart, out_caps, zdict):
+            res = _inflate_host(L, L.zs_inflate_batch_sync, self._ctx, inputs, fmt, out_caps, self._check)
+            self._sync_n = len(inputs)  # (a refused call leaves the context's record, and this count, alone)
+            return res
         if restart is not None:
             rs = decompress_restart(inputs, fmt, restart, out_caps, zdict)
             return _inflate_host(L, L.zs_inflate_batch_restart, self._ctx, inputs, fmt, out_caps, self._check, rs)
@@ -532,6 +556,22 @@ class Engine:
     def decompress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                          out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None) -> List[bytes]:
         return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart))
+
+    def last_restart_points(self) -> List[List[tuple]]:
+        """zs_last_restart_points: the points the last restart="scan" call on this engine found, one
+        list per stream of (in_pos, out_pos) WITHOUT the start -- the shape `restart=` takes, so a
+        caller can keep them as an index.  [] when the last decompress call was no scan call."""
+        n = getattr(self, "_sync_n", 0)
+        if not n:
+            return []
+        first = (ctypes.c_uint64 * (n + 1))()
+        total = int(self._L.zs_last_restart_points(self._ctx, first, None, None, 0))
+        if total == 0:
+            return []
+        rin, rout = (ctypes.c_uint32 * total)(), (ctypes.c_uint32 * total)()
+        if int(self._L.zs_last_restart_points(self._ctx, first, rin, rout, total)) != total or first[n] != total:
+            raise ZsError("zs_last_restart_points: the count changed between two queries")
+        return [[(int(rin[k]), int(rout[k])) for k in range(first[i] + 1, first[i + 1])] for i in range(n)]
 
     def last_flush_index(self) -> List[List[int]]:
         """zs_last_flush_index: for the last compress call with flush points on this engine
@@ -615,7 +655,17 @@ class Engine:
         restart: one list per stream of (in_pos, out_pos) restart points without the start
         (zs_inflate_batch_restart_device); the streams' bytes are on the device, so `headers` gives the
         first bytes of each stream on the host (enough to hold its wrapper's header; not needed for
-        "deflate-raw" and "deflate") for the first point."""
+        "deflate-raw" and "deflate") for the first point.  restart="scan": the points are found from the
+        bytes on the device (zs_inflate_batch_sync_device, which waits for hip_stream once in the
+        middle); no `headers`."""
+        if decompress_scan(restart, out_cap, None if dict_off is None else dict_off):
+            r = self._L.zs_inflate_batch_sync_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
+                                                     _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase), _P(d_msg),
+                                                     _P(d_out_len), _P(d_consumed), _P(d_check) if d_check else None,
+                                                     _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_inflate_batch_sync_device")
+            self._sync_n = n
+            return
         if restart is not None:
             if dict_off is not None:
                 raise ValueError("restart points with a preset dictionary are not built")
@@ -908,6 +958,8 @@ class Pool:
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
         L = self._L
+        if decompress_scan(restart, out_caps, zdict):
+            return _inflate_host(L, L.zs_pool_inflate_batch_sync, self._pool, inputs, fmt, out_caps, self._check)
         if restart is not None:  # (zs_last_flush_index is not offered on the pool: an index comes from an Engine)
             rs = decompress_restart(inputs, fmt, restart, out_caps, zdict)
             return _inflate_host(L, L.zs_pool_inflate_batch_restart, self._pool, inputs, fmt, out_caps, self._check, rs)
