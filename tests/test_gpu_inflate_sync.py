@@ -127,6 +127,39 @@ def test_no_marker_at_all_is_one_point_and_the_plain_decode(engine, fmt):
     assert engine.last_seg_count() > 0  # (the 200,000-byte stream took a large decoder)
 
 
+def test_hand_built_headers_in_one_batch_as_the_plain_entry(engine):
+    """tests/bitbuild.py header_cases() in one deflate-raw batch: no stream holds a marker, so each is one point,
+    the first point's lane sizes it (incomplete and empty distance sets, over-subscribed sets, every refusal of a
+    header) and the plain decode follows.  Every stream the plain entry decodes comes back field for field as
+    the plain entry's (status, phase, message, bytes, consumed, check), and those are the 11 zlib decodes, with
+    zlib's bytes; every stream the plain entry rejects is the restart entries' one failure, as the entry's
+    contract says (include/zs_gpu.h: lengths 0, not the plain entry's message and consumed), a data error there too."""
+    import bitbuild
+
+    made = [bitbuild.blocks(parts) for _, parts in bitbuild.header_cases()]
+    streams = [m for m, _ in made]
+    assert len(streams) == 29 and all(synccases.candidates(s, 0) == [] for s in streams)
+    caps = [cap4(len(e)) + 64 for _, e in made]
+    try:
+        engine.set_option("inflate_ref_wrap", 0)
+        plain = engine.decompress_batch_detailed(streams, "deflate-raw", out_caps=caps)
+    finally:
+        engine.set_option("inflate_ref_wrap", 1)
+    got, pts = scan(engine, "deflate-raw", streams, caps)
+    assert pts == [[]] * 29
+    decoded = 0
+    for s, g, p in zip(streams, got, plain):
+        z = zlib.decompressobj(-15)
+        try:
+            out = z.decompress(s)
+        except zlib.error:
+            assert p[0] == FAILED[0] and g == FAILED
+            continue
+        assert z.eof and g == p == good(out, s, "deflate-raw")
+        decoded += 1
+    assert decoded == 11
+
+
 def test_false_candidates_are_skipped(engine):
     for src, at, level, n_cand, true_at in synccases.FALSE_SOURCES:
         s, idx = flushed(src, [at], "deflate-raw", level)

@@ -144,3 +144,25 @@ def test_lane_kernel_on_host_large_members_reference_calls(lane_host, fmt):
     if fmt == "deflate-raw":
         out = run(lane_host, members[-1:], fmt, flags=3)[0][4]
         assert corpus.sha256(out) == j["ref_out_sha256"] and out != wrap_src
+
+
+HEADERS_DECODED = ["repeat16_across", "hclen19", "both_trees_15_deep", "both_trees_15_deep_rle", "all_316_codes",
+                   "bit_length_codes_of_7_bits"]
+
+
+def test_lane_kernel_on_host_hand_built_headers(lane_host):
+    """tests/bitbuild.py header_cases(): the lane decodes zlib's bytes for the six whose code sets are all
+    complete and bails on the rest -- the 18 zlib rejects, and the five with an incomplete or empty distance
+    set, which zlib takes (inftrees.ts:128-139) and the exact path decodes"""
+    import bitbuild
+
+    names = [name for name, _ in bitbuild.header_cases()]
+    streams = [bitbuild.blocks(parts)[0] for _, parts in bitbuild.header_cases()]
+    assert len(streams) == 29
+    res = run(lane_host, [(s, 1024) for s in streams], "deflate-raw", flags=1)
+    decoded = []
+    for name, s, (bail, olen, cons, want, out) in zip(names, streams, res):
+        if not bail:
+            assert out == zlib.decompressobj(-15).decompress(s) and cons == len(s), name
+            decoded.append(name)
+    assert decoded == HEADERS_DECODED

@@ -126,3 +126,27 @@ def test_a_passed_tail_is_sized_to_its_end_for_its_reach(host):
     # bytes; the lane from there sees the copies, which reach back across both points
     (_, _, recs, pts), = synccases.run(host, [s], "deflate-raw", 12)
     assert recs[1] == (LANDED, cand[12], 156, 0) and recs[13][0] == FINAL and recs[13][3] > 156 and pts == [(0, 0)]
+
+
+def test_hand_built_headers_end_as_zlib_does(host):
+    """tests/bitbuild.py header_cases() as deflate-raw streams, the lane from offset 0: FINAL at the stream's end
+    with zlib's length where zlib decodes the stream, ERROR where it rejects it.  Five of the decoded ones have
+    an incomplete or empty distance set (a lone code of length 1, or none: inftrees.ts:128-139)."""
+    import bitbuild
+    from test_huffman_cases import HEADERS_ACCEPTED
+
+    names = [name for name, _ in bitbuild.header_cases()]
+    streams = [bitbuild.blocks(parts)[0] for _, parts in bitbuild.header_cases()]
+    assert len(streams) == 29
+    decoded = []
+    for name, s, (_, recs) in zip(names, streams, synccases.run_every_offset(host, streams, "deflate-raw")):
+        how, end, n, _ = recs[0]
+        z = zlib.decompressobj(-15)
+        try:
+            out = z.decompress(s)
+        except zlib.error:
+            assert how == ERROR, name
+            continue
+        assert z.eof and (how, end, n) == (FINAL, len(s), len(out)), name
+        decoded.append(name)
+    assert decoded == HEADERS_ACCEPTED and len(decoded) == 11

@@ -10,7 +10,7 @@ nothing from the search.  Prints one JSON line: per configuration the median, mi
 the call's device time (zs_last_batch_ms: first to last mark on the stream, so the sync entry's host
 planning in the middle counts) and of its wall time (the call and the wait for the stream) over
 --steps timed calls, taken in --rounds rounds that alternate the configurations, after --warmup untimed
-calls of each; the phase medians ("sync_scan", "sync_size" and the restart phases).
+calls of each; the phases' medians, minima and maxima ("sync_scan", "sync_size" and the restart phases).
 
     python tools/bench_sync.py [--segments 1024] [--members 4096] [--stream-bytes 65536]
 
@@ -139,7 +139,9 @@ def main():
     q = lambda v: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
     for c in configs:
         out["configs"][name(c)] = {"calls": len(dev[name(c)]), "device_ms": q(dev[name(c)]), "wall_ms": q(wall[name(c)]),
-                                   "phase_ms": {k: round(statistics.median(v), 4) for k, v in phases[name(c)].items()}}
+                                   "phase_ms": {k: round(statistics.median(v), 4) for k, v in phases[name(c)].items()},
+                                   "phase_ms_min_max": {k: [round(min(v), 4), round(max(v), 4)]
+                                                        for k, v in phases[name(c)].items()}}
     print(json.dumps(out))
 
 

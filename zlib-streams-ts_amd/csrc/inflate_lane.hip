@@ -1,15 +1,14 @@
 // inflate_lane.hip -- the lane-per-member inflate path of zs_inflate_batch*
-// (see the comment below); zs_k_inflate in inflate.hip is the exact path.
+// (see the comment below); zs_k_inflate in inflate.hip is the exact path.  A
+// lane's Huffman code (canonical decode, root tables, the dynamic header's code
+// lengths) is zs_lane_huff.h's, shared with the restart-point search's size decode.
 #include <hip/hip_runtime.h>
 #include "zs_common.h"
 #include "zs_inflate.h"
 #include "zs_inftab.h"
-#include "zs_lane_reader.h"
+#include "zs_lane_huff.h"
 #include "zs_refcalls.h"
-#ifndef ZS_OPAQUE  // (the host stand-in of tools/lane_host defines these away)
-#define ZS_OPAQUE(x) asm("" : "+v"(x))
-#endif
-#ifndef ZS_LANE_WAVES
+#ifndef ZS_LANE_WAVES  // (the host stand-in of tools/lane_host defines it away)
 #define ZS_LANE_WAVES(n) __attribute__((amdgpu_waves_per_eu(n)))
 #endif
 #ifndef ZS_IL_EXP
@@ -41,21 +40,6 @@ struct zs_lane_tabs {
   uint16_t lens[320];  // the block's code lengths (lit/len then distance; the header's code-length code first)
 };
 
-// Canonical Huffman decoding (RFC 1951 3.2.2) with the code's shape in
-// registers.  lim[l-1] is the end of the length-l codes left-justified to 15
-// bits, so with the next 15 input bits read MSB first (rev), a code's length is
-// one more than the number of limits <= rev, and its rank in (length, symbol)
-// order is rev shifted down to that length plus D[length-1].  The symbols by
-// rank are the only table, in LDS.  No memory access before the symbol itself
-// and none in HBM: zlib's two-level tables (8-bit LDS roots before this) sent
-// every code longer than the root to a second-level table in HBM, and some lane
-// of a wave needed one in 68% of the C3 symbol steps -- a full memory latency
-// for the whole wave each time.
-struct zs_canon {
-  uint32_t lim[15];
-  uint32_t D[16];
-};
-
 // A lane's LDS: 548 B (a CU's 160 KB holds four 64-lane workgroups).
 struct zs_lane_lds {
   uint32_t ring[32];  // the last 128 output bytes (zs_lane_out)
@@ -71,7 +55,6 @@ struct zs_lane_lds {
 // most codes cost one LDS read instead of the ~45-instruction compare chain;
 // with few lanes per wave the VALU work per symbol is what each SIMD's lone
 // wave waits on (C5-i: 8,192 members, eight lanes per wave).
-#define ZS_LROOT 9u
 #ifndef ZS_DROOT
 #define ZS_DROOT 8u
 #endif
@@ -87,108 +70,10 @@ struct zs_lane_lds_root {
   __attribute__((aligned(16))) zs_canon cd;
 };
 
-// C from lens[0..n) (the member's scratch in HBM); false unless the code is
-// complete.  zlib's inflate_table rejects over-subscribed sets and incomplete
-// ones but for a lone code of length 1 (inftrees.ts:128-139); a lane bails on
-// every incomplete set and leaves that case to the exact path.
-static __device__ bool zs_canon_build(zs_canon& C, uint32_t* cnt, uint8_t* sym8, uint32_t* hi, const uint16_t* lens,
-                                      uint32_t n) {
-#pragma unroll
-  for (int l = 0; l < 16; l++) cnt[l] = 0;
-  if (hi)
-#pragma unroll
-    for (int w = 0; w < 9; w++) hi[w] = 0;
-#pragma unroll 8
-  for (uint32_t i = 0; i < n; i++) atomicAdd(&cnt[lens[i]], 1u);
-  uint32_t code = 0, rank = 0;
-  int left = 1;
-#pragma unroll
-  for (int l = 1; l <= 15; l++) {
-    const uint32_t c = cnt[l];
-    left = 2 * left - (int)c;  // once negative (over-subscribed) it stays so
-    C.lim[l - 1] = (code + c) << (15 - l);
-    C.D[l - 1] = rank - code;
-    cnt[l] = rank;
-    rank += c;
-    code = (code + c) << 1;
-  }
-  C.D[15] = 0;
-  if (left != 0) return false;
-#pragma unroll 8
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t l = lens[i];
-    if (l) {
-      const uint32_t k = atomicAdd(&cnt[l], 1u);
-      sym8[k] = (uint8_t)i;
-      if (hi && (i >> 8)) atomicOr(&hi[k >> 5], 1u << (k & 31u));
-    }
-  }
-  return true;
-}
-
-// root[r] for every code of length <= rbits (after zs_canon_build: cnt[l] is
-// the rank past the last length-l code, and a rank k of length l has code k - D[l-1])
-static __device__ void zs_root_fill(uint16_t* root, uint32_t rbits, const zs_canon& C, const uint32_t* cnt,
-                                    const uint8_t* sym8, const uint32_t* hi) {
-  for (uint32_t k = 0; k < (1u << rbits) / 2u; k++) reinterpret_cast<uint32_t*>(root)[k] = 0;
-  uint32_t k = 0;
-#pragma unroll
-  for (uint32_t l = 1; l <= ZS_LROOT; l++) {
-    if (l > rbits) break;
-    const uint32_t end = cnt[l];
-    for (; k < end; k++) {
-      const uint32_t code = k - C.D[l - 1];
-      const uint32_t r = __builtin_bitreverse32(code) >> (32u - l);  // the stream sends codes MSB first
-      const uint32_t sym = sym8[k] | (hi ? ((hi[k >> 5] >> (k & 31u)) & 1u) << 8 : 0u);
-      for (uint32_t x = r; x < (1u << rbits); x += 1u << l) root[x] = (uint16_t)((l << 12) | sym);
-    }
-  }
-}
-
-// the rank of the code at the front of the bit buffer; L = its length (16: no
-// such code -- the caller bails)
-static __device__ __forceinline__ uint32_t zs_canon_rank(const zs_canon& C, const zs_lane_reader& R, uint32_t& L) {
-  const uint32_t rev = __builtin_bitreverse32((uint32_t)R.hold) >> 17;
-  // the values pass an empty asm so each select below is between registers (the
-  // compiler otherwise selects an address into C and keeps C in scratch)
-  uint32_t d[16];
-#pragma unroll
-  for (int l = 0; l < 16; l++) {
-    d[l] = C.D[l];
-    ZS_OPAQUE(d[l]);
-  }
-  uint32_t n = 1, D = d[0];
-#pragma unroll
-  for (int l = 0; l < 15; l++) {
-    const bool c = rev >= C.lim[l];
-    n += c;
-    D = c ? d[l + 1] : D;
-  }
-  L = n;
-  return (rev >> ((15u - n) & 31u)) + D;
-}
-// the same from a code kept in LDS: the limits in four 16-byte reads, then the
-// one D[] entry of the code's length
-static __device__ __forceinline__ uint32_t zs_canon_rank_lds(const zs_canon& C, const zs_lane_reader& R,
-                                                             uint32_t& L) {
-  const uint32_t rev = __builtin_bitreverse32((uint32_t)R.hold) >> 17;
-  const uint4* l4 = reinterpret_cast<const uint4*>(C.lim);  // lim[0..14] (+ D[0], unused)
-  const uint4 q0 = l4[0], q1 = l4[1], q2 = l4[2], q3 = l4[3];
-  const uint32_t lim[15] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z};
-  uint32_t n = 1;
-#pragma unroll
-  for (int l = 0; l < 15; l++) n += rev >= lim[l] ? 1u : 0u;
-  L = n;
-  return (rev >> ((15u - n) & 31u)) + C.D[(n - 1u) & 15u];
-}
-template <bool LDS>
-static __device__ __forceinline__ uint32_t zs_canon_rank_t(const zs_canon& C, const zs_lane_reader& R, uint32_t& L) {
-  if constexpr (LDS) return zs_canon_rank_lds(C, R, L);
-  else return zs_canon_rank(C, R, L);
-}
-
 // a root-table symbol as the zlib table entry the decoder consumes (zs_lbase /
-// zs_dbase's ops: 16 + extra bits, deflate64 128 + extra bits)
+// zs_dbase's ops: 16 + extra bits, deflate64 128 + extra bits).  Those two's
+// values in a form of branches: built on their selects, the symbol loop needs
+// one or two more VGPRs in every instance and <2, true, false> loses a wave per SIMD.
 static __device__ __forceinline__ zcode zs_lit_entry(uint32_t sym, bool d64) {
   if (sym < 256) return zpack(0, 0, sym);
   if (sym == 256) return zpack(32 + 64, 0, 0);
@@ -475,56 +360,23 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
     if (type == 1) {  // fixed codes (inflate.ts:218-280)
       nlen = 288;
       ndist = 32;
-      for (uint32_t sym = 0; sym < 320; sym++)
-        T.lens[sym] = sym < 144 ? 8 : sym < 256 ? 9 : sym < 280 ? 7 : sym < 288 ? 8 : 5;
+      zs_lane_fixed_lengths(T.lens);
     } else if (type == 2) {  // dynamic (inflate.ts:662-836)
-      nlen = zs_lr_take(R, 5) + 257;
-      ndist = zs_lr_take(R, 5) + 1;
-      const uint32_t ncode = zs_lr_take(R, 4) + 4;
-      if (nlen > 286 || (!d64 && ndist > 30)) { bail = true; break; }
-      uint32_t i;
-      for (i = 0; i < ncode; i++) T.lens[ZS_BL_ORDER[i]] = (uint16_t)zs_lr_take(R, 3);
-      for (; i < 19; i++) T.lens[ZS_BL_ORDER[i]] = 0;
-      if (!zs_canon_build(CD, F.cnt, F.dsym, nullptr, T.lens, 19)) { bail = true; break; }
-      i = 0;
-      uint32_t prev = 0;
-      while (i < nlen + ndist) {
-        if (R.bits < 32) zs_lr_fill(R);
-        uint32_t L;
-        const uint32_t k = zs_canon_rank_t<LCAN>(CD, R, L);
-        if (L > 15) { bail = true; break; }
-        zs_lr_drop(R, L);
-        const uint32_t v = F.dsym[k];
-        if (v < 16) {
-          T.lens[i++] = (uint16_t)v;
-          prev = v;
-          continue;
-        }
-        uint32_t rep, val = 0;
-        if (v == 16) {
-          if (i == 0) { bail = true; break; }
-          val = prev;
-          rep = 3 + zs_lr_take(R, 2);
-        } else if (v == 17) {
-          rep = 3 + zs_lr_take(R, 3);
-        } else {
-          rep = 11 + zs_lr_take(R, 7);
-        }
-        if (i + rep > nlen + ndist) { bail = true; break; }
-        while (rep--) T.lens[i++] = (uint16_t)val;
-        prev = val;
+      if (!zs_lane_code_lengths<LCAN>(R, d64, CD, F.cnt, F.dsym, T.lens, nlen, ndist) || zs_lr_over(R)) {
+        bail = true;
+        break;
       }
-      if (bail || zs_lr_over(R) || T.lens[256] == 0) { bail = true; break; }
     } else {
       bail = true;  // "invalid block type"
       break;
     }
-    if (!zs_canon_build(CL, F.cnt, F.lsym, F.lhi, T.lens, nlen)) {
+    // (an incomplete set that zlib takes, ZS_CODE_PARTIAL, is the exact path's too)
+    if (zs_canon_build(CL, F.cnt, F.lsym, F.lhi, T.lens, nlen, false) != ZS_CODE_COMPLETE) {
       bail = true;
       break;
     }
     if (ROOT) zs_root_fill(lroot, ZS_LROOT, CL, F.cnt, F.lsym, F.lhi);
-    if (!zs_canon_build(CD, F.cnt, F.dsym, nullptr, T.lens + nlen, ndist)) {
+    if (zs_canon_build(CD, F.cnt, F.dsym, nullptr, T.lens + nlen, ndist, false) != ZS_CODE_COMPLETE) {
       bail = true;
       break;
     }

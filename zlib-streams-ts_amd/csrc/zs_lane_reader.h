@@ -1,8 +1,10 @@
 // zs_lane_reader.h -- one lane's bit reader over a member's input, shared by the
-// lane-per-member kernel (inflate_lane.hip) and the segmented walk and decode
-// (inflate_seg.hip): clamped aligned words, one refill ahead, zero past the end.
-// Plain C++ but for the funnel shift, so the host stand-in of tools/lane_host
-// compiles it too.
+// lane-per-member kernel (inflate_lane.hip), the segmented walk and decode
+// (inflate_seg.hip) and the restart-point search's size decode (zs_sync.h), the
+// first and the last with the per-lane Huffman code of zs_lane_huff.h on top:
+// clamped aligned words, one refill ahead, zero past the end.  Plain C++ but for
+// the funnel shift, so the host stand-ins of tools/lane_host and tools/sync_host
+// compile it too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,11 +56,11 @@ static __device__ __forceinline__ void zs_lr_rewind(zs_lane_reader& R, uint32_t 
   R.bits = 0;
   R.pf = zs_lr_load4(R, at);
 }
-// (re)start at any bit
-static __device__ __forceinline__ void zs_lr_seek(zs_lane_reader& R, uint32_t bit) {
-  zs_lr_rewind(R, (bit >> 5) << 2);
+// (re)start at any bit (64-bit: the restart-point search seeks to any byte of a stream of up to 4 GiB)
+static __device__ __forceinline__ void zs_lr_seek(zs_lane_reader& R, uint64_t bit) {
+  zs_lr_rewind(R, (uint32_t)(bit >> 5) << 2);
   zs_lr_fill(R);
-  zs_lr_drop(R, bit & 31u);
+  zs_lr_drop(R, (uint32_t)bit & 31u);
 }
 // bits consumed so far
 static __device__ __forceinline__ uint64_t zs_lr_bitpos(const zs_lane_reader& R) {

@@ -1266,7 +1266,7 @@ struct zs_restart_layout {
 // zs_plan_sync follows the records from the first point and emits the points in the restart
 // entries' layout, which restart_batch then decodes unchanged.
 #define ZS_SYNC_TILE 4096u   // bytes per workgroup step of the scan: 256 lanes, one aligned 16-byte unit each
-#define ZS_SYNC_LANES 16u    // starts per workgroup of the size decode (their Huffman state: 2,164 bytes of LDS each)
+#define ZS_SYNC_LANES 16u    // starts per workgroup of the size decode (their Huffman state: 2,148 bytes of LDS each)
 static inline bool zs_sync_pass_ok(int v) { return v >= 1 && v <= 64; }  // zs_set_option's values of "sync_pass"
 // how a lane of zs_k_sync_size ended
 #define ZS_SYNC_LANDED 1u  // a block closed at a byte boundary behind the marker: `end` is a candidate
