@@ -38,11 +38,14 @@
  *     describes the last failure on the calling thread.
  *   - Output offsets and capacities of the device entry points must be
  *     multiples of 4 bytes (the engine writes 32-bit words; ZS_STREAM_ERROR
- *     otherwise): no store leaves [out_off[i], out_off[i] + out_cap[i]).  The
- *     host-buffer entries, deflate and inflate, take any capacity exactly as
- *     given and any output offset (they round the capacity up inside their
- *     own staging, report Z_BUF_ERROR past the caller's value and copy back
- *     only the bytes produced).  Inputs may be packed at any byte offset.
+ *     otherwise): no store leaves [out_off[i], out_off[i] + out_cap[i]).  Only
+ *     the device entries have that rule.  BOTH host-buffer entries,
+ *     zs_deflate_batch_ex and zs_inflate_batch_ex with their siblings, take
+ *     exact, unaligned capacities and any output offset: they round the
+ *     capacity up inside their own staging, report Z_BUF_ERROR past the
+ *     caller's value (never for a capacity that is enough but no multiple of
+ *     4) and copy back only the bytes produced.  Inputs may be packed at any
+ *     byte offset.
  */
 #ifndef ZS_GPU_H
 #define ZS_GPU_H
@@ -539,8 +542,9 @@ uint64_t zs_last_flush_index(zs_ctx *ctx, uint32_t *in_pos, uint64_t cap);
  *    not chunked.
  *  - Timing phases: "sync_scan", "sync_size", in front of the restart phases.
  *  - Not built: the chunked host pipeline for these calls; decoding only a range of segments (a seek);
- *    _auto capacities; dictionaries; deflate64; multi-member gzip files; cutting at dynamic-block
- *    boundaries (what the split decode does inside one member); zs_last_restart_points on the pool. */
+ *    _auto capacities; dictionaries; deflate64; cutting at dynamic-block boundaries (what the split decode
+ *    does inside one member); zs_last_restart_points on the pool.  These entries decode a gzip stream's
+ *    first member, as the plain ones: multi-member gzip files are the _members entries' (below). */
 int zs_inflate_batch_sync_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
                                  const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
                                  const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
@@ -561,6 +565,73 @@ int zs_pool_inflate_batch_sync(zs_pool *pool, int wbits, uint32_t n_streams, con
  * last inflate call on the context was no _sync call.  Not offered on the pool. */
 uint64_t zs_last_restart_points(zs_ctx *ctx, uint64_t *restart_first, uint32_t *restart_in, uint32_t *restart_out,
                                 uint64_t cap);
+
+/* Multi-member gzip files: BGZF / bgzip, WARC records, `cat a.gz b.gz`, appended logs.  The plain entries
+ * decode a stream's first member and ignore the rest, as the reference does (streams.ts:74-76); these
+ * decode EVERY member and concatenate the outputs, as gzip -d, zlib's gzread and Python's gzip.decompress
+ * do.  gzip only.  The entries take EXACTLY the arguments of zs_inflate_batch_device_ex /
+ * zs_inflate_batch_ex / zs_pool_inflate_batch (sharded by stream: members stay inside their stream).
+ *  - The members of stream i, its bytes s[0..n): a member starts at 0; another starts at every position p
+ *    directly behind a member's 8-byte trailer with p + 4 <= n, s[p..p+3) == 1f 8b 08 and
+ *    (s[p+3] & 0xe0) == 0.  Where that test fails the stream ends and the bytes from p on are ignored (zero
+ *    padding, garbage, a lone 1f 8b), as the plain entries ignore trailing bytes: consumed[i] = p.  Where
+ *    it holds the bytes ARE a member, whatever follows: one that is truncated or corrupt fails the stream
+ *    (zlib's gz_look, gzip -d).
+ *  - Success: the output is the concatenation of the members' outputs, out_len[i] the total, status[i]
+ *    ZS_STREAM_END, check[i] the crc32 of the whole output (= zs_crc32_combine over the members' values);
+ *    every member's own CRC32 and ISIZE are verified.
+ *  - Members decode with zlib semantics (the instances inflate_ref_wrap = 0 selects; the context's option
+ *    is neither read nor changed, as in the restart entries): behind the first member there is no
+ *    reference behaviour to reproduce.
+ *  - Failure: let k be the first member that does not end with ZS_STREAM_END.  status[i], phase[i] and
+ *    msg[i] are what zs_inflate_batch_ex with inflate_ref_wrap = 0 reports for the bytes s[start_k..n)
+ *    alone; out_len[i] = out_pos_k (the complete members before k are in the region and valid);
+ *    consumed[i] = start_k; check[i] = 0.  A total that does not fit out_cap[i] is this case: the first
+ *    member that does not fit entirely is given no room and reports the plain entry's capacity outcome
+ *    (ZS_BUF_ERROR, "output capacity exceeded"); so is a total above 2^32 - 1.  One failed stream does not
+ *    touch the others; no store leaves [out_off[i], out_off[i] + out_cap[i]) rounded up to 4.
+ *  - Refused with ZS_STREAM_ERROR before the context is looked at, in this order: wbits other than 31
+ *    ("members are a gzip notion"), a null out_cap, for the device entry out_off / out_cap that are no
+ *    multiples of 4.  More than 67,108,863 candidates plus streams in one call is ZS_STREAM_ERROR (the
+ *    restart entries' segment cap): split the batch.
+ *  - How: where member k + 1 starts is known once member k is decoded, so every plausible start is tried at
+ *    once.  A scan lists every offset q >= 1 that passes the four-byte test (CANDIDATES: compressed data
+ *    and stored blocks hold the same bytes); one lane per START (offset 0 and every candidate) parses the
+ *    header, runs the _sync entries' count-only decode to the final block and requires the trailer's 8
+ *    bytes; the host follows the records from 0.  The members then decode as the members of ONE gzip batch
+ *    on the caller's own input (nothing is copied), in place when every out_pos is a multiple of 4, else
+ *    through 4-aligned staging, and are joined per stream.
+ *  - The work bound is the _sync entries': a lane started at candidate j of its stream reads no byte at or
+ *    past candidate j + sync_pass + 1 (the same option), so every byte is decoded by at most sync_pass + 1
+ *    bounded lanes.  A true member that holds more than sync_pass false candidates (a .tar.gz whose
+ *    stored blocks hold .gz files) is sized once more by an unbounded lane, in a tail round: each round
+ *    settles at least one member of each such stream.
+ *  - The DEVICE entry synchronises hip_stream once in the middle (behind the scan and the size decode; a
+ *    second time in a call whose candidates outgrow the list the context keeps) and once more per tail
+ *    round, and is asynchronous from there on.  The HOST entries run as one chunk (zs_last_host_chunks = 1).
+ *  - Timing phases: "members_scan", "members_size" and "members_stitch", around the decoders' own.
+ *  - Not built: a header-only fast path for BGZF (following BSIZE, trusting ISIZE for the positions);
+ *    restart points inside members; _auto capacities; the chunked host pipeline; zlib or raw "members";
+ *    decoding a range of members (a seek); zs_last_members on the pool. */
+int zs_inflate_batch_members_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                    const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                    const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                    int32_t *d_phase, int32_t *d_msg, uint32_t *d_out_len, uint32_t *d_consumed,
+                                    uint32_t *d_check, void *hip_stream);
+int zs_inflate_batch_members(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                             const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                             int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
+                             uint32_t *check);
+int zs_pool_inflate_batch_members(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                                  const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                                  const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
+                                  uint32_t *out_len, uint32_t *consumed, uint32_t *check);
+/* The members the last zs_inflate_batch_members_device / zs_inflate_batch_members call on the context
+ * decoded, in the layout of zs_last_restart_points: member_first gets n_streams + 1 entries (from 0),
+ * member_in / member_out at most cap members' (in_pos, out_pos), member 0 of a stream being (0, 0);
+ * returns the count of members.  0 when the last inflate call on the context was no _members call.  Not
+ * offered on the pool. */
+uint64_t zs_last_members(zs_ctx *ctx, uint64_t *member_first, uint32_t *member_in, uint32_t *member_out, uint64_t cap);
 
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);

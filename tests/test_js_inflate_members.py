@@ -1,0 +1,31 @@
+"""Multi-member gzip files through the JavaScript host path (js/test/inflate-members.test.mjs):
+decompressBatch*(inputs, "gzip", {outCapacity, members: true}) on two streams of members node's own zlib
+made, one broken stream beside a good one, and the rejection rules.  The argument checks need no GPU."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+JS = os.path.join(ROOT, "zlib-streams-ts_amd", "js")
+ADDON = os.path.join(JS, "zsnapi.node")
+TEST = os.path.join(JS, "test", "inflate-members.test.mjs")
+
+need_node = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(ADDON),
+                               reason="node or the built addon (make -C zlib-streams-ts_amd/js) is missing")
+
+
+@need_node
+def test_js_module_checks_the_members_option_without_a_gpu():
+    r = subprocess.run(["node", TEST, "cpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok ")
+
+
+@need_node
+@pytest.mark.gpu
+def test_js_decompress_every_member():
+    r = subprocess.run(["node", TEST], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok ")

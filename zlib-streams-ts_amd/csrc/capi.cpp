@@ -119,6 +119,7 @@ struct zs_ctx {
     bool seg_ran = false;       // a segmented launch has run: its count of members finished goes on
     bool lanes_zeroed = false;  // the lane counter (lstat) has been zeroed
     bool sync = false;          // the points were found by the call (zs_last_restart_points)
+    bool members = false;       // the members were found by the call (zs_last_members)
   } call;
   // a batch with restart points: the plan, the closed copies of the segments, the staging
   // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
@@ -130,6 +131,13 @@ struct zs_ctx {
   // tiles, the candidates, the lanes' records; the plan's points, which zs_last_restart_points returns
   Buf ymeta, ytile, ycand, yrec, ytail;
   zs_sync_plan yp;
+  // a batch that finds its gzip members: the streams' arrays and the scan's tiles, the candidates,
+  // the lanes' records, the tail rounds' lists and records; the members' arrays for the place and the stitch,
+  // their results (5 arrays of M), the staging route's regions, the lengths the check values are taken over;
+  // the plan, which zs_last_members returns
+  Buf mbmeta, mbtile, mbcand, mbrec, mbtail, mbseg, mbres, mbstage, mblen;
+  std::vector<uint8_t> mbh, mbck;
+  zs_members_plan mp;
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
@@ -173,7 +181,7 @@ static void call_begin(zs_ctx* c, CallKind kind) {
     k.fidx.clear();
     k.fscan_at = k.fscan_used = 0;
   }
-  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = k.sync = false;
+  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = k.sync = k.members = false;
 }
 static void fold_marks(zs_ctx* c);
 
@@ -2197,6 +2205,172 @@ static int sync_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& ou
   return restart_batch(c, wbits, h, out, st, {c->yp.rfirst.data(), c->yp.rin.data(), c->yp.rout.data()});
 }
 
+// ---- a gzip file's members found from the bytes (zlib's gz_look, gzread.c).  A fault of the
+// arguments is reported before the context is looked at (zs_members_validate, then the null context).
+static int members_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
+  zs_inflate_call a;
+  a.n = h.n;
+  a.out_off = device_entry ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = device_entry;
+  if (const zs_members_err e = zs_members_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
+}
+
+// The device decode of a validated, non-empty gzip batch whose streams hold any number of members
+// (regions as inflate_batch's).  The scan and the size decode run on st, which is then waited for: the
+// members are planned here, from the candidates and the lanes' records.  st is waited for once more where
+// the candidates outgrow the list the context keeps, and once per tail round (zs_k_members_tail).  The
+// members then decode as ONE gzip batch on the caller's input, with zlib semantics, and are joined per stream.
+static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st) {
+  const uint32_t n = h.n;
+  std::vector<uint32_t> sh16(n), stile;
+  uint64_t tin = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    sh16[i] = (uint32_t)(((uintptr_t)h.in + h.in_off[i]) & 15u);
+    tin += h.in_len[i];
+  }
+  zs_plan_sync_tiles(n, h.in_len, sh16.data(), stile);
+  const uint32_t T = stile[n];
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m_off = 0, m_len = up256(8ull * n), m_tile = m_len + up256(4ull * n), m_end = m_tile + up256(4ull * (n + 1));
+  HIPCHK(c->mbmeta.ensure(m_end));
+  HIPCHK(c->mbtile.ensure(8ull * T + 16));
+  HIPCHK(c->mbcand.ensure(4ull * (tin / 2048 + 1024)));
+  c->mbh.assign(m_end, 0);
+  memcpy(c->mbh.data() + m_off, h.in_off, 8ull * n);
+  memcpy(c->mbh.data() + m_len, h.in_len, 4ull * n);
+  memcpy(c->mbh.data() + m_tile, stile.data(), 4ull * (n + 1));
+  HIPCHK(hipMemcpyAsync(c->mbmeta.p, c->mbh.data(), m_end, hipMemcpyHostToDevice, st));
+  const uint8_t* dm = c->mbmeta.as<uint8_t>();
+  const uint64_t* d_off = (const uint64_t*)(dm + m_off);
+  const uint32_t* d_len = (const uint32_t*)(dm + m_len);
+  const uint32_t* d_tile = (const uint32_t*)(dm + m_tile);
+  uint64_t* tcount = c->mbtile.as<uint64_t>();
+  const uint32_t grid = std::max(1u, std::min(T, 32u * c->o.ncu));
+  MARK("start");
+  zs_k_members_scan<false><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, nullptr, 0);
+  zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tcount, T + 1);
+  HIPCHK(hipGetLastError());
+  std::vector<uint64_t> tpre(T + 1);
+  for (int round = 0;; round++) {
+    const uint64_t cap = c->mbcand.cap / 4;
+    HIPCHK(c->mbrec.ensure(sizeof(zs_sync_rec) * (n + cap)));
+    zs_k_members_scan<true><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap);
+    MARK("members_scan");
+    // (a lane per stream and per place of the list: the lanes past the candidates' count return at once)
+    const uint64_t lanes = std::min<uint64_t>(n + cap, ZS_RESTART_SEG_MAX);
+    zs_k_members_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
+        h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>());
+    MARK("members_size");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(tpre.data(), tcount, 8ull * (T + 1), hipMemcpyDeviceToHost));
+    if (!zs_sync_count_ok(n, tpre[T]))
+      return fail(ZS_STREAM_ERROR, "%s", "too many member candidates (more than 67,108,863 with the streams in one call)");
+    if (tpre[T] <= cap) break;
+    if (round) return fail(ZS_MEM_ERROR, "%s", "the member candidates' list did not settle");
+    HIPCHK(c->mbcand.ensure(4ull * tpre[T]));
+  }
+  const uint64_t C = tpre[T];
+  std::vector<uint32_t> cand(C);
+  std::vector<zs_sync_rec> rec(n + C);
+  if (C) HIPCHK(hipMemcpy(cand.data(), c->mbcand.p, 4ull * C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec.data(), c->mbrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> cfirst(n + 1);
+  for (uint32_t i = 0; i <= n; i++) cfirst[i] = tpre[stile[i]];
+  zs_members_plan& p = c->mp;
+  for (;;) {
+    zs_plan_members(n, h.in_len, h.out_cap, cfirst.data(), cand.data(), rec.data(), p);
+    const uint32_t m = (uint32_t)p.tstream.size();
+    if (!m) break;
+    // true members that hold more than sync_pass false candidates: sized to the stream's end, then the plan again
+    const size_t t_start = up256(4ull * m);
+    HIPCHK(c->mbtail.ensure(2 * t_start + sizeof(zs_sync_rec) * m));
+    uint8_t* dt = c->mbtail.as<uint8_t>();
+    HIPCHK(hipMemcpyAsync(dt, p.tstream.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dt + t_start, p.tstart.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    zs_k_members_tail<<<(m + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES, ZS_SYNC_LANES, 0, st>>>(
+        h.in, d_off, d_len, (const uint32_t*)dt, (const uint32_t*)(dt + t_start), m, (zs_sync_rec*)(dt + 2 * t_start));
+    MARK("members_size");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<zs_sync_rec> tail(m);
+    HIPCHK(hipMemcpy(tail.data(), dt + 2 * t_start, sizeof(zs_sync_rec) * m, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < m; k++) {
+      if (tail[k].how == ZS_SYNC_PASSED) return fail(ZS_MEM_ERROR, "%s", "a member's tail lane did not settle");
+      rec[p.trec[k]] = tail[k];
+    }
+  }
+  c->call.members = true;
+  const uint32_t M = p.M;
+  // where each member lies, decodes and belongs
+  std::vector<uint64_t> src(M), ooff(M), dst(M);
+  for (uint32_t g = 0; g < M; g++) {
+    const uint32_t i = p.rstream[g];
+    src[g] = h.in_off[i] + p.soff[g];
+    dst[g] = h.out_off[i] + p.opos[g];
+    // (a member without room stores nothing: it stays at its stream's start)
+    ooff[g] = p.in_place ? h.out_off[i] + (p.ocap[g] ? p.opos[g] : 0u) : p.stoff[g];
+  }
+  const size_t g_first = 0, g_soff = up256(4ull * (n + 1)), g_opos = g_soff + up256(4ull * M), g_ocap = g_opos + up256(4ull * M),
+               g_ooff = g_ocap + up256(4ull * M), g_dst = g_ooff + up256(8ull * M), g_ptile = g_dst + up256(8ull * M),
+               g_out = g_ptile + up256(4ull * (M + 1)), g_end = g_out + up256(8ull * n);
+  HIPCHK(c->mbseg.ensure(g_end));
+  HIPCHK(c->mbres.ensure(20ull * M + 64));
+  HIPCHK(c->mbstage.ensure(p.stage_bytes));
+  HIPCHK(c->mblen.ensure(4ull * n + 16));
+  c->mbh.assign(g_end, 0);
+  memcpy(c->mbh.data() + g_first, p.rfirst.data(), 4ull * (n + 1));
+  memcpy(c->mbh.data() + g_soff, p.soff.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_opos, p.opos.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_ocap, p.ocap.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_ooff, ooff.data(), 8ull * M);
+  memcpy(c->mbh.data() + g_dst, dst.data(), 8ull * M);
+  memcpy(c->mbh.data() + g_ptile, p.ptile.data(), 4ull * (M + 1));
+  memcpy(c->mbh.data() + g_out, h.out_off, 8ull * n);
+  HIPCHK(hipMemcpyAsync(c->mbseg.p, c->mbh.data(), g_end, hipMemcpyHostToDevice, st));
+  const uint8_t* dg = c->mbseg.as<uint8_t>();
+  auto u32 = [&](size_t at) { return (const uint32_t*)(dg + at); };
+  auto u64 = [&](size_t at) { return (const uint64_t*)(dg + at); };
+  // the members as M gzip members, decoded with zlib semantics: behind the first member there is no call
+  // boundary of the reference's to reproduce, whatever the context's inflate_ref_wrap says
+  int32_t* const sr = c->mbres.as<int32_t>();
+  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
+  zs_route_opts o2 = c->o;
+  o2.inflate_ref_wrap = false;
+  const Batch hs = {M, h.in, src.data(), p.slen.data(), p.in_place ? h.out : c->mbstage.as<uint8_t>(), ooff.data(),
+                    p.ocap.data()};
+  if (const int ri = inflate_batch(c, 31, hs, seg, st, nullptr, &o2)) return ri;
+  if (!p.in_place) {
+    if (p.ptile[M])
+      zs_k_restart_place<<<std::min(p.ptile[M], 32u * c->o.ncu), 256, 0, st>>>(
+          c->mbstage.as<uint8_t>(), u64(g_ooff), u32(g_ocap), seg.out_len, u64(g_dst), u32(g_ptile), M, h.out);
+    MARK("restart_place");
+  }
+  uint32_t* cklen = c->mblen.as<uint32_t>();
+  zs_k_members_stitch<<<n, 64, 0, st>>>(u32(g_first), u32(g_soff), u32(g_opos), seg.status, seg.phase, seg.msg, seg.out_len,
+                                        seg.consumed, n, out.status, out.phase, out.msg, out.out_len, out.consumed, cklen);
+  HIPCHK(hipGetLastError());
+  if (out.check) {
+    // the check value over the joined output; the members' own values are verified by the decoders.
+    // The part map goes to the front of the metadata block, which the members' batch is done with in stream order.
+    const zs_checksum_plan* ck;
+    size_t ck_bytes;
+    if (const int rc = ck_prepare(c, true, n, h.out_cap, &ck, &ck_bytes)) return rc;
+    if (ck_bytes) {
+      HIPCHK(c->meta.ensure(ck_bytes));
+      c->mbck.assign(ck_bytes, 0);
+      ck_fill(ck, c->mbck.data());
+      HIPCHK(hipMemcpyAsync(c->meta.p, c->mbck.data(), ck_bytes, hipMemcpyHostToDevice, st));
+    }
+    ck_launch(c, st, *ck, 0, n, h.out, u64(g_out), cklen, out.check, 2);
+  }
+  MARK("members_stitch");
+  HIPCHK(hipGetLastError());
+  return ZS_OK;
+}
+
 // zs_inflate_validate's findings, as the entries report them
 static int inflate_fail(zs_inflate_err e) { return fail(ZS_STREAM_ERROR, "%s", zs_inflate_err_text(e)); }
 // The arrays of a plain or _dict call as validation reads them (the host entries stage their own regions)
@@ -2229,8 +2403,9 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, const InflateOut
 // batch decides before anything is staged, the dictionaries to the device once, then the call begins and
 // host_batch runs its chunks, each a device batch with a copy of the caller's exact capacities as the limits.
 static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, const DictIn* dict,
-                        const RestartIn* rs, bool sync = false) {
-  if (!rs && !sync)  // (a restart call has passed restart_refused, one that finds its points sync_refused)
+                        const RestartIn* rs, bool sync = false, bool members = false) {
+  // (a restart call has passed restart_refused, one that finds its points sync_refused, its members members_refused)
+  if (!rs && !sync && !members)
     if (const zs_inflate_err e = zs_inflate_validate_host(c != nullptr, wbits, inflate_call(h, false, dict)))
       return inflate_fail(e);
   HIPCHK(hipSetDevice(c->device));
@@ -2250,6 +2425,7 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                                             out.check ? dr[5] : nullptr};
                       // (a chunk's points and dictionaries: the same arrays, the chunk's part of the index)
                       if (rs) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
+                      if (members) return members_batch(c, hb, d, c->stream);
                       if (sync) {  // the first points where the bytes are: the caller's memory
                         std::vector<uint32_t> first(b - a);
                         for (uint32_t i = a; i < b; i++)
@@ -2259,7 +2435,7 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                       const DictIn di = dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
                       return inflate_batch(c, wbits, hb, d, c->stream, dict ? &di : nullptr, nullptr);
                     },
-                    sync);
+                    sync || members);
 }
 
 extern "C" int zs_inflate_batch_device_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
@@ -2357,6 +2533,46 @@ extern "C" uint64_t zs_last_restart_points(zs_ctx* c, uint64_t* restart_first, u
   if (restart_in) memcpy(restart_in, p.rin.data(), 4ull * k);
   if (restart_out) memcpy(restart_out, p.rout.data(), 4ull * k);
   return p.rin.size();
+}
+
+// zlib's gz_look (gzread.c): every member of a gzip file; device buffers
+extern "C" int zs_inflate_batch_members_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
+                                               const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                               const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                               int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
+                                               uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  if (const int r = members_refused(c, wbits, h, true)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  call_begin(c, CALL_INFLATE);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st);
+}
+
+// ... host buffers
+extern "C" int zs_inflate_batch_members(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                        const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                        uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
+  if (const int r = members_refused(c, wbits, h, false)) return r;
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, false, true);
+}
+
+// The members the last _members call on the context decoded, in the layout of zs_last_restart_points:
+// member_first (n + 1 entries, from 0), then at most `cap` members' (in_pos, out_pos), every stream's
+// member 0 = (0, 0) included.  0 when the last inflate call on the context was no _members call.
+extern "C" uint64_t zs_last_members(zs_ctx* c, uint64_t* member_first, uint32_t* member_in, uint32_t* member_out,
+                                    uint64_t cap) {
+  if (!c || !c->call.members) return 0;
+  const zs_members_plan& p = c->mp;
+  if (member_first)
+    for (size_t i = 0; i < p.rfirst.size(); i++) member_first[i] = p.rfirst[i];
+  const uint64_t k = std::min<uint64_t>(cap, p.M);
+  if (member_in) memcpy(member_in, p.soff.data(), 4ull * k);
+  if (member_out) memcpy(member_out, p.opos.data(), 4ull * k);
+  return p.M;
 }
 
 extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t in_len) {

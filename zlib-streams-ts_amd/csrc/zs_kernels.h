@@ -156,3 +156,18 @@ __global__ void zs_k_checksum_parts(const uint8_t* in, const uint64_t* in_off, c
 __global__ void zs_k_checksum_fold(const uint32_t* in_len, const uint32_t* pfirst, uint32_t part_lg,
                                    const uint32_t* vals, uint32_t* check, int kind, const uint32_t* seeds);
 __global__ void zs_k_selftest(uint32_t* bad, int rounds);
+// a gzip file's members found from its bytes (inflate_members.hip): the candidates' scan, the
+// members sized from offset 0 and from every candidate, the starts a bound stopped sized to the end, the
+// per-stream join of the decoded members' results
+template <bool EMIT>
+__global__ void zs_k_members_scan(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* stile,
+                                  uint32_t n, uint64_t* tcount, uint32_t* cand, uint64_t cap);
+__global__ void zs_k_members_size(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* stile,
+                                  uint32_t n, const uint64_t* tpre, const uint32_t* cand, uint64_t cap, uint32_t pass,
+                                  zs_sync_rec* rec);
+__global__ void zs_k_members_tail(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* tstream,
+                                  const uint32_t* tstart, uint32_t m, zs_sync_rec* rec);
+__global__ void zs_k_members_stitch(const uint32_t* rfirst, const uint32_t* soff, const uint32_t* opos,
+                                    const int32_t* seg_status, const int32_t* seg_phase, const int32_t* seg_msg,
+                                    const uint32_t* seg_len, const uint32_t* seg_used, uint32_t n, int32_t* status,
+                                    int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* cklen);

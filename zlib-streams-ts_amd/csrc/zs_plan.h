@@ -1383,4 +1383,124 @@ static inline void zs_plan_sync(uint32_t n, const uint32_t* in_len, const uint32
   }
 }
 
+// ---- multi-member gzip (zlib's gz_look, gzread.c: behind a member's trailer another member
+// starts where the bytes 1f 8b follow).  A stream's members are found like restart points: zs_k_members_scan
+// lists every offset q >= 1 whose four bytes pass zs_member_magic (the CANDIDATES: compressed data and
+// stored blocks hold the same bytes), zs_k_members_size sizes one member from offset 0 and from every
+// candidate without storing (zs_members.h; zs_sync_rec: how, the offset behind the trailer, the bytes
+// produced), zs_plan_members follows the records from 0 and lays the members out as the members of ONE
+// gzip batch on the caller's own input -- every member ends at its own final block, so nothing is copied.
+enum zs_members_err {
+  ZS_ME_OK = 0,
+  ZS_ME_WBITS,  // "members are a gzip notion (use windowBits 31)"
+  ZS_ME_CAPS,   // "members are found with given capacities only"
+  ZS_ME_ALIGN,  // "output offsets/capacities must be multiples of 4"
+  ZS_ME_COUNT
+};
+static inline const char* zs_members_err_text(zs_members_err e) {
+  static const char* const kMsg[ZS_ME_COUNT] = {
+      "",
+      "members are a gzip notion (use windowBits 31)",
+      "members are found with given capacities only",
+      "output offsets/capacities must be multiples of 4",
+  };
+  return kMsg[e];
+}
+// The fault that wins: the format, even of an empty batch; the capacities; the device entry's
+// alignment rule last.  Nothing here looks at a context.
+static inline zs_members_err zs_members_validate(int wbits, const zs_inflate_call& a) {
+  if (wbits != 31) return ZS_ME_WBITS;
+  if (a.n == 0) return ZS_ME_OK;
+  if (!a.out_cap) return ZS_ME_CAPS;
+  for (uint32_t i = 0; a.out_off && i < a.n; i++)
+    if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_ME_ALIGN;
+  return ZS_ME_OK;
+}
+// the four-byte test of a member's start: the magic, the method, no reserved flag
+ZS_PLAN_FN bool zs_member_magic(const uint8_t* p) { return p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && !(p[3] & 0xe0); }
+
+struct zs_members_plan {
+  uint32_t n = 0, M = 0;          // streams, members
+  bool in_place = true;           // every member's out_pos is a multiple of 4: the members decode where they belong
+  std::vector<uint32_t> rfirst;   // each stream's first member (rfirst[n] = M)
+  std::vector<uint32_t> rstream;  // each member's stream
+  std::vector<uint32_t> soff, slen;  // the member's bytes in its stream's input (the last of a failing chain: to the end)
+  std::vector<uint32_t> opos;     // its first byte in its stream's output
+  std::vector<uint32_t> ocap;     // its capacity: the bytes it produces; 0 where those pass out_cap; the room where unknown
+  std::vector<uint64_t> stoff;    // staging route: its 4-aligned region in the staging buffer
+  std::vector<uint32_t> ptile;    // M + 1: prefix sums of the place's tiles
+  uint64_t stage_bytes = 0;
+  // the starts whose lane its work bound stopped (ZS_SYNC_PASSED): the stream, the start and its record's
+  // index.  The stream's members are planned up to there; the caller sizes these starts to the stream's
+  // end (zs_k_members_tail), replaces the records and plans again, until no start is left.
+  std::vector<uint32_t> tstream, tstart;
+  std::vector<uint64_t> trec;
+};
+// Stream i has the candidates cand[cfirst[i] .. cfirst[i + 1]) in increasing order, the record rec[i] of
+// the lane started at 0 and rec[n + k] of the lane started at candidate k.  From 0:
+//   FINAL   a member; it fits when out_pos + len <= out_cap[i] (64-bit: a total above 2^32 - 1 never fits).
+//           The first member that does not fit gets no room and ends the list: the decoder reports the
+//           capacity outcome for it.  The next start is the member's end, if that is a candidate (found by
+//           binary search: the scan's rule IS the test of a member's start); else the stream ends there.
+//   ERROR   the stream's last member, with the input to the stream's end and the room that is left, so
+//           that the decoder reports the exact error
+//   PASSED  a true member that holds more than sync_pass false candidates: on the tail list
+// Offset 0 is a member whatever its bytes are (the plain entry's outcome for a stream that is no gzip).
+static inline void zs_plan_members(uint32_t n, const uint32_t* in_len, const uint32_t* out_cap, const uint64_t* cfirst,
+                                   const uint32_t* cand, const zs_sync_rec* rec, zs_members_plan& p) {
+  p.n = n;
+  p.in_place = true;
+  p.rfirst.assign(n + 1, 0);
+  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.opos, &p.ocap, &p.tstream, &p.tstart}) v->clear();
+  p.stoff.clear();
+  p.trec.clear();
+  p.ptile.assign(1, 0);
+  uint64_t st = 0;
+  auto member = [&](uint32_t i, uint32_t at, uint32_t len, uint64_t out, uint32_t cap) {
+    if (p.rstream.size() > p.rfirst[i] && (out & 3u)) p.in_place = false;
+    p.rstream.push_back(i);
+    p.soff.push_back(at);
+    p.slen.push_back(len);
+    p.opos.push_back((uint32_t)out);
+    p.ocap.push_back(cap);
+    p.stoff.push_back(st);
+    st += ((uint64_t)cap + 3) & ~3ull;
+    // (the place's words: the destination's leading bytes of its first word count too)
+    p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)cap + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    p.rfirst[i] = (uint32_t)p.rstream.size();
+    const uint32_t* c0 = cand + cfirst[i];
+    const uint32_t* c1 = cand + cfirst[i + 1];
+    uint32_t pos = 0;
+    uint64_t out = 0;
+    const zs_sync_rec* r = &rec[i];
+    for (;;) {
+      if (r->how == ZS_SYNC_PASSED) {
+        p.tstream.push_back(i);
+        p.tstart.push_back(pos);
+        p.trec.push_back((uint64_t)(r - rec));
+        break;  // (the plan is complete, every stream with a member, once no start is listed)
+      }
+      if (r->how != ZS_SYNC_FINAL || r->end <= pos || r->end > in_len[i]) {
+        member(i, pos, in_len[i] - pos, out, out_cap[i] > out ? (uint32_t)(out_cap[i] - out) : 0u);
+        break;
+      }
+      if (out + r->len > out_cap[i]) {
+        member(i, pos, r->end - pos, out, 0u);
+        break;
+      }
+      member(i, pos, r->end - pos, out, r->len);
+      out += r->len;
+      pos = r->end;
+      const uint32_t* at = std::lower_bound(c0, c1, pos);
+      if (at == c1 || *at != pos) break;
+      r = &rec[n + (size_t)(at - cand)];
+    }
+  }
+  p.M = (uint32_t)p.rstream.size();
+  p.rfirst[n] = p.M;
+  p.stage_bytes = p.in_place ? 0 : st + 16;
+}
+
 #endif

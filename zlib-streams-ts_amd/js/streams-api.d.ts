@@ -64,6 +64,14 @@ export interface DecompressBatchOptions extends BatchOptions {
    * seekable .gz of another writer, or a flushed stream whose index was lost.  The same conditions and the
    * same results; a stream without a full-flush marker decodes as one segment. */
   restartPoints?: ([number, number][] | null)[] | "scan";
+  /** Multi-member gzip files (BGZF, WARC records, `cat a.gz b.gz`): decode EVERY member of each input and
+   * concatenate the outputs, as `gzip -d` does, instead of the first member alone.  The members are found from
+   * the bytes: behind a member's trailer another starts where 1f 8b 08 and a flag byte without a reserved bit
+   * follow; anything else ends the stream and is ignored.  A member that is truncated or corrupt fails its
+   * input.  "gzip" only, needs `outCapacity` (the total of an input's members); with another format, without
+   * `outCapacity`, with `dictionary` or with `restartPoints` it is a TypeError.  The members' index
+   * (zs_last_members) is not offered here: the batch entries run on the device pool. */
+  members?: boolean;
 }
 /** The length of the wrapper's header in front of the deflate data: 0 for "deflate-raw", 2 for "deflate", for
  * "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC, or 0 when that header is malformed or does not fit. */

@@ -194,8 +194,19 @@ export function wrapperHeaderLength(input, format = "gzip") {
 // TypeError (not built).  Returns, per input, the flat pairs with the start -- [header length, 0] -- first.
 // restartPoints: "scan": the engine finds the points from the bytes (zs_inflate_batch_sync in zs_gpu.h), for
 // a caller without an index; the same conditions, and the same result as with the true points.
+// options.members: true: every member of multi-member gzip inputs is decoded and the outputs are concatenated
+// (zs_inflate_batch_members in zs_gpu.h).  "gzip" only, needs outCapacity; with a dictionary or restartPoints
+// it is a TypeError (not built).
 function restartOf(options, ins, format) {
   const r = options.restartPoints;
+  if (options.members) {
+    if (format !== "gzip") throw new TypeError("members are a gzip notion (format must be \"gzip\")");
+    if (options.outCapacity === undefined || options.outCapacity === null) throw new TypeError("members need outCapacity");
+    if (options.dictionary !== undefined && options.dictionary !== null)
+      throw new TypeError("members and dictionary cannot be combined");
+    if (r !== undefined && r !== null) throw new TypeError("members and restartPoints cannot be combined");
+    return "members";
+  }
   if (r === undefined || r === null) return undefined;
   if (options.dictionary !== undefined && options.dictionary !== null)
     throw new TypeError("restartPoints and dictionary cannot be combined");

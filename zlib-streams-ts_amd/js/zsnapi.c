@@ -221,6 +221,7 @@ typedef struct {
   uint64_t *restart_first;
   uint32_t *restart_in, *restart_out;
   int restart_scan;    /* restart "scan": the points are found from the bytes (zs_pool_inflate_batch_sync) */
+  int members;         /* restart "members": every member of multi-member gzip inputs (zs_pool_inflate_batch_members) */
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -276,6 +277,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
                                        j->dict_off, j->dict_len);
+  else if (j->inflate && j->members)
+    j->rc = zs_pool_inflate_batch_members(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
+                                          j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check);
   else if (j->inflate && j->restart_scan)
     j->rc = zs_pool_inflate_batch_sync(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off, j->cap,
                                        j->status, j->phase, j->msg, j->olen, j->cons, j->check);
@@ -649,12 +653,14 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
 }
 
 /* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,
- *                 dictionaries: (Uint8Array | null)[] | undefined, restart: number[][] | "scan" | undefined) ->
+ *                 dictionaries: (Uint8Array | null)[] | undefined,
+ *                 restart: number[][] | "scan" | "members" | undefined) ->
  *   Promise<{status, phase: Int32Array, message: string[], outputs: Uint8Array[], consumed: Int32Array,
  *            check: Uint32Array}>
  * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto).
  * restart: per input the flat pairs in_pos, out_pos of its points, the start first (zs_pool_inflate_batch_restart,
- * zs_gpu.h), or the string "scan": the points are found from the bytes (zs_pool_inflate_batch_sync); either
+ * zs_gpu.h), or the string "scan": the points are found from the bytes (zs_pool_inflate_batch_sync), or the
+ * string "members": every member of multi-member gzip inputs is decoded (zs_pool_inflate_batch_members); each
  * needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any device is
  * touched. */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
@@ -731,11 +737,14 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
     char word[8] = "";
     size_t len = 0;
     napi_get_value_string_utf8(env, argv[5], word, sizeof word, &len);
-    if (strcmp(word, "scan") != 0) {
+    if (strcmp(word, "members") == 0) {
+      j->members = 1;
+    } else if (strcmp(word, "scan") == 0) {
+      j->restart_scan = 1;
+    } else {
       job_free(j);
-      return throw_code(env, ZS_STREAM_ERROR, "restart must be number[][] or \"scan\"");
+      return throw_code(env, ZS_STREAM_ERROR, "restart must be number[][], \"scan\" or \"members\"");
     }
-    j->restart_scan = 1;
   } else if (rt != napi_undefined && rt != napi_null) {
     const int rc = copy_restart(env, j, argv[5]);
     if (rc != 0) {

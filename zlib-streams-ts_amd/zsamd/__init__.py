@@ -237,6 +237,12 @@ def lib():
                                                    _P, _P, _P, _P, _P, _P, _P]
         L.zs_last_restart_points.restype = ctypes.c_uint64
         L.zs_last_restart_points.argtypes = [_P, _U64P, _U32P, _U32P, ctypes.c_uint64]
+    if hasattr(L, "zs_inflate_batch_members"):  # exactly the counterparts' arguments: the members are found
+        L.zs_inflate_batch_members.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_pool_inflate_batch_members.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_inflate_batch_members_device.argtypes = L.zs_inflate_batch_sync_device.argtypes
+        L.zs_last_members.restype = ctypes.c_uint64
+        L.zs_last_members.argtypes = [_P, _U64P, _U32P, _U32P, ctypes.c_uint64]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -346,6 +352,23 @@ def decompress_scan(restart, out_caps, zdict=None) -> bool:
         raise ValueError("restart points need out_caps (the unbounded output is not built with them)")
     if zdict is not None:
         raise ValueError("restart points with a preset dictionary are not built")
+    return True
+
+
+def decompress_members(members, fmt, out_caps, zdict=None, restart=None) -> bool:
+    """members=True: every member of a multi-member gzip file is decoded and the outputs are
+    concatenated (zs_inflate_batch_members*).  gzip only, the capacities must be given, and neither
+    dictionaries nor restart points are built with it: ValueError."""
+    if not members:
+        return False
+    if fmt != "gzip":
+        raise ValueError("members are a gzip notion (fmt must be \"gzip\")")
+    if out_caps is None:
+        raise ValueError("members need out_caps (the unbounded output is not built with them)")
+    if zdict is not None:
+        raise ValueError("members with a preset dictionary are not built")
+    if restart is not None:
+        raise ValueError("members with restart points are not built")
     return True
 
 
@@ -523,20 +546,26 @@ class Engine:
                                                       flush_at, flush_every))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                             out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None):
+                             out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
         """Returns [(status, phase, msg, bytes, consumed)].  out_caps None: unbounded
         output, as DecompressionStream (zs_inflate_batch_auto); else per-stream caps.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only (zs_inflate_batch_dict*).
         restart: one list per input of (in_pos, out_pos) restart points (decompress_restart;
         zs_inflate_batch_restart: the segments decode in parallel, zlib semantics; needs out_caps), or
-        "scan": the points are found from the bytes (zs_inflate_batch_sync; last_restart_points())."""
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart)]
+        "scan": the points are found from the bytes (zs_inflate_batch_sync; last_restart_points()).
+        members=True: every member of multi-member gzip inputs, concatenated (decompress_members;
+        zs_inflate_batch_members; last_members())."""
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                                  out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None):
+                                  out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
+        if decompress_members(members, fmt, out_caps, zdict, restart):
+            res = _inflate_host(L, L.zs_inflate_batch_members, self._ctx, inputs, fmt, out_caps, self._check)
+            self._members_n = len(inputs)  # (a refused call leaves the context's record, and this count, alone)
+            return res
         if decompress_scan(restart, out_caps, zdict):
             res = _inflate_host(L, L.zs_inflate_batch_sync, self._ctx, inputs, fmt, out_caps, self._check)
             self._sync_n = len(inputs)  # (a refused call leaves the context's record, and this count, alone)
@@ -554,8 +583,24 @@ class Engine:
         return _inflate_host(L, L.zs_inflate_batch_ex, self._ctx, inputs, fmt, out_caps, self._check)
 
     def decompress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                         out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None) -> List[bytes]:
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart))
+                         out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False) -> List[bytes]:
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members))
+
+    def last_members(self) -> List[List[tuple]]:
+        """zs_last_members: the members the last members=True call on this engine decoded, one list per
+        stream of (in_pos, out_pos), member 0 = (0, 0) included.  [] when the last decompress call was
+        no members call."""
+        n = getattr(self, "_members_n", 0)
+        if not n:
+            return []
+        first = (ctypes.c_uint64 * (n + 1))()
+        total = int(self._L.zs_last_members(self._ctx, first, None, None, 0))
+        if total == 0:
+            return []
+        min_, mout = (ctypes.c_uint32 * total)(), (ctypes.c_uint32 * total)()
+        if int(self._L.zs_last_members(self._ctx, first, min_, mout, total)) != total or first[n] != total:
+            raise ZsError("zs_last_members: the count changed between two queries")
+        return [[(int(min_[k]), int(mout[k])) for k in range(first[i], first[i + 1])] for i in range(n)]
 
     def last_restart_points(self) -> List[List[tuple]]:
         """zs_last_restart_points: the points the last restart="scan" call on this engine found, one
@@ -649,7 +694,7 @@ class Engine:
     def decompress_device(self, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                           d_status: int, d_phase: int, d_msg: int, d_out_len: int, d_consumed: int,
                           hip_stream: int = 0, d_dict: int = 0, dict_off=None, dict_len=None, d_check: int = 0,
-                          restart=None, headers=None):
+                          restart=None, headers=None, members=False):
         """d_dict / dict_off / dict_len: preset dictionaries (zs_inflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
         restart: one list per stream of (in_pos, out_pos) restart points without the start
@@ -657,7 +702,17 @@ class Engine:
         first bytes of each stream on the host (enough to hold its wrapper's header; not needed for
         "deflate-raw" and "deflate") for the first point.  restart="scan": the points are found from the
         bytes on the device (zs_inflate_batch_sync_device, which waits for hip_stream once in the
-        middle); no `headers`."""
+        middle); no `headers`.  members=True: every member of multi-member gzip streams
+        (zs_inflate_batch_members_device, which waits for hip_stream as the scan call does)."""
+        if decompress_members(members, fmt, out_cap, None if dict_off is None else dict_off, restart):
+            r = self._L.zs_inflate_batch_members_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
+                                                        _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase),
+                                                        _P(d_msg), _P(d_out_len), _P(d_consumed),
+                                                        _P(d_check) if d_check else None,
+                                                        _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_inflate_batch_members_device")
+            self._members_n = n
+            return
         if decompress_scan(restart, out_cap, None if dict_off is None else dict_off):
             r = self._L.zs_inflate_batch_sync_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
                                                      _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase), _P(d_msg),
@@ -956,8 +1011,10 @@ class Pool:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
                                                       flush_at, flush_every))
 
-    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
+    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
         L = self._L
+        if decompress_members(members, fmt, out_caps, zdict, restart):  # (zs_last_members is not offered on the pool)
+            return _inflate_host(L, L.zs_pool_inflate_batch_members, self._pool, inputs, fmt, out_caps, self._check)
         if decompress_scan(restart, out_caps, zdict):
             return _inflate_host(L, L.zs_pool_inflate_batch_sync, self._pool, inputs, fmt, out_caps, self._check)
         if restart is not None:  # (zs_last_flush_index is not offered on the pool: an index comes from an Engine)
@@ -972,11 +1029,11 @@ class Pool:
             return _inflate_host_auto(L, L.zs_pool_inflate_batch_auto, self._pool, inputs, fmt, self._check)
         return _inflate_host(L, L.zs_pool_inflate_batch, self._pool, inputs, fmt, out_caps, self._check)
 
-    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart)]
+    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members)]
 
-    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None):
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart))
+    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members))
 
 
 _default: Optional[Engine] = None
