@@ -610,8 +610,9 @@ uint64_t zs_last_restart_points(zs_ctx *ctx, uint64_t *restart_first, uint32_t *
  *    second time in a call whose candidates outgrow the list the context keeps) and once more per tail
  *    round, and is asynchronous from there on.  The HOST entries run as one chunk (zs_last_host_chunks = 1).
  *  - Timing phases: "members_scan", "members_size" and "members_stitch", around the decoders' own.
- *  - Not built: a header-only fast path for BGZF (following BSIZE, trusting ISIZE for the positions);
- *    restart points inside members; _auto capacities; the chunked host pipeline; zlib or raw "members";
+ *  - These entries recompute every length from the data.  The header-only fast path for BGZF (following BSIZE,
+ *    trusting ISIZE for the positions) is the _bgzf entries' (below).
+ *  - Not built: restart points inside members; _auto capacities; the chunked host pipeline; zlib or raw "members";
  *    decoding a range of members (a seek); zs_last_members on the pool. */
 int zs_inflate_batch_members_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
                                     const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
@@ -626,12 +627,77 @@ int zs_pool_inflate_batch_members(zs_pool *pool, int wbits, uint32_t n_streams, 
                                   const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
                                   const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
                                   uint32_t *out_len, uint32_t *consumed, uint32_t *check);
-/* The members the last zs_inflate_batch_members_device / zs_inflate_batch_members call on the context
- * decoded, in the layout of zs_last_restart_points: member_first gets n_streams + 1 entries (from 0),
- * member_in / member_out at most cap members' (in_pos, out_pos), member 0 of a stream being (0, 0);
- * returns the count of members.  0 when the last inflate call on the context was no _members call.  Not
- * offered on the pool. */
+/* The members the last zs_inflate_batch_members_device / zs_inflate_batch_members call (or _bgzf call,
+ * below) on the context decoded, in the layout of zs_last_restart_points: member_first gets n_streams + 1
+ * entries (from 0), member_in / member_out at most cap members' (in_pos, out_pos), member 0 of a stream
+ * being (0, 0); returns the count of members.  0 when the last inflate call on the context was neither.
+ * Not offered on the pool. */
 uint64_t zs_last_members(zs_ctx *ctx, uint64_t *member_first, uint32_t *member_in, uint32_t *member_out, uint64_t cap);
+
+/* BGZF files (bgzip output, BAM, tabix-indexed VCF; the SAM specification, section 4.1): the _members entries
+ * with the members SIZED FROM THEIR HEADERS where those can be trusted.  A BGZF block states in its header
+ * where it ends (BSIZE) and in its trailer how many bytes it produces (ISIZE); the _members entries decode
+ * every member once, without storing, to find both.  A header that lies would change their results, so this is
+ * a mode with its own entries; the _members entries stay as they are.  gzip only.
+ *  - Entries: EXACTLY the arguments of the _members entries.  Refusals are theirs and in their order, before
+ *    the context is looked at: wbits other than 31, a null out_cap, the device entry's alignment.  The
+ *    candidate cap is the same.
+ *  - The header at start p of stream s[0..n) is TRUSTED when all of these hold: p + 18 <= n and s[p..p+4) is
+ *    1f 8b 08 04 (FLG exactly 4: FEXTRA alone, as the specification writes it); XLEN (u16 at p + 10) has
+ *    p + 12 + XLEN <= n; the subfields (SI1 SI2 SLEN data) tile the XLEN bytes exactly; one subfield is 'B' 'C'
+ *    with SLEN 2, the first such one giving BSIZE (it need not be the first subfield); with total = BSIZE + 1,
+ *    total > 12 + XLEN + 8 (at least one byte of deflate data) and p + total <= n; ISIZE (u32 at
+ *    p + total - 4) <= 65536.  A trusted start is a member of total bytes that produces ISIZE bytes, and no
+ *    byte of its deflate data is read to say so.  EVERY OTHER start -- a plain gzip member, an FNAME flag, a
+ *    truncated block, a BSIZE that does not fit, a false candidate -- is sized from the data exactly as in the
+ *    _members entries, so mixed files, `cat a.gz b.bgz`, trailing bytes and truncation behave as there.
+ *  - Well-formed input: for every stream whose trusted headers tell the truth -- any gzip file, BGZF or not --
+ *    every field equals the _members entry's: the output, out_len, consumed, status, phase, msg and check,
+ *    failures included (a corrupt member, truncation, capacity).
+ *  - Lying headers: where a trusted header lies, member k decodes from its BSIZE + 1 bytes into ISIZE bytes of
+ *    room.  The stream reports for k what zs_inflate_batch_ex with inflate_ref_wrap = 0 reports for those
+ *    bytes alone, with one mapping: a trusted member that was given its ISIZE for room and ends with the
+ *    capacity outcome (ZS_BUF_ERROR, "output capacity exceeded") produced more than its ISIZE says and is
+ *    reported as ZS_DATA_ERROR, ZS_PHASE_PROCESS, "incorrect length check" (zlib's words for an ISIZE that
+ *    does not match), so that a caller can tell it from a capacity of their own that is too small.  (The
+ *    first member that does not fit the stream's out_cap is given no room, is not such a member and reports
+ *    the capacity outcome, as in _members.  An ISIZE that is too large is the decoder's own "incorrect length
+ *    check"; a BSIZE that is too small is input that ends early, ZS_BUF_ERROR without a message.)
+ *    out_len[i] = out_pos_k, consumed[i] = start_k, check[i] = 0; the complete members before k are valid, as
+ *    in _members; one failed stream does not touch its neighbours; no store leaves a stream's region rounded
+ *    up to 4.  NOT verified: a BSIZE that is too large and still fits the input ends member k cleanly (the
+ *    plain entry ignores the bytes behind a member) and the chain goes on at p + BSIZE + 1, where it ends
+ *    unless those bytes pass the four-byte test: the stream reports success with the members up to k.
+ *  - zs_last_members answers after a _bgzf call as after a _members call.
+ *  - zs_last_bgzf_trusted(ctx): for tests and tuning, the number of planned members of the last _bgzf call
+ *    on the context whose size came from their header; 0 after any other inflate call.  It is known when
+ *    the call returns (the plan is made on the host).  Not offered on the pool.
+ *  - zs_bgzf_out_len: host arithmetic, needs no context.  It follows trusted headers from offset 0 by the
+ *    members' ending rule (the chain ends where the four-byte test fails or the input ends); returns 1 and
+ *    writes the sum of ISIZE to *total when every member on the chain is trusted, 0 (and *total = 0) when
+ *    the chain meets an untrusted member -- so for an empty input, whose offset 0 is one.  The capacity a
+ *    truthful BGZF file needs.
+ *  - The DEVICE entry synchronises hip_stream as the _members entry does; a trusted member never needs a
+ *    tail round, whatever its data holds.  The HOST entries run as one chunk (zs_last_host_chunks = 1).
+ *  - Timing phases: "members_scan", "bgzf_size" (the sizing launch; a tail round stays "members_size") and
+ *    "members_stitch", around the decoders' own.
+ *  - Not built: a range of members (a seek by virtual offset); a BGZF writer; _auto entries (Python and JS size
+ *    the output with zs_bgzf_out_len); the chunked host pipeline (one chunk, as _members). */
+int zs_inflate_batch_bgzf_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                 int32_t *d_phase, int32_t *d_msg, uint32_t *d_out_len, uint32_t *d_consumed,
+                                 uint32_t *d_check, void *hip_stream);
+int zs_inflate_batch_bgzf(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                          const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                          int32_t *status, int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed,
+                          uint32_t *check);
+int zs_pool_inflate_batch_bgzf(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                               const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                               const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
+                               uint32_t *out_len, uint32_t *consumed, uint32_t *check);
+uint64_t zs_last_bgzf_trusted(zs_ctx *ctx);
+int zs_bgzf_out_len(const uint8_t *in, uint32_t in_len, uint64_t *total);
 
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);

@@ -22,6 +22,8 @@
 #include "zs_plan.h"
 #include "zs_sweep_ring.h"
 #include "zs_dict.h"
+#define ZS_BGZF_HOST_ONLY 1
+#include "zs_bgzf.h"
 
 
 namespace {
@@ -120,6 +122,7 @@ struct zs_ctx {
     bool lanes_zeroed = false;  // the lane counter (lstat) has been zeroed
     bool sync = false;          // the points were found by the call (zs_last_restart_points)
     bool members = false;       // the members were found by the call (zs_last_members)
+    uint32_t bgzf_trusted = 0;  // a _bgzf call's planned members sized from their headers (zs_last_bgzf_trusted)
   } call;
   // a batch with restart points: the plan, the closed copies of the segments, the staging
   // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
@@ -134,8 +137,8 @@ struct zs_ctx {
   // a batch that finds its gzip members: the streams' arrays and the scan's tiles, the candidates,
   // the lanes' records, the tail rounds' lists and records; the members' arrays for the place and the stitch,
   // their results (5 arrays of M), the staging route's regions, the lengths the check values are taken over;
-  // the plan, which zs_last_members returns
-  Buf mbmeta, mbtile, mbcand, mbrec, mbtail, mbseg, mbres, mbstage, mblen;
+  // the plan, which zs_last_members returns; a _bgzf call's byte per record
+  Buf mbmeta, mbtile, mbcand, mbrec, mbtail, mbseg, mbres, mbstage, mblen, mbtrust;
   std::vector<uint8_t> mbh, mbck;
   zs_members_plan mp;
   zs_dict_set dset;
@@ -181,7 +184,10 @@ static void call_begin(zs_ctx* c, CallKind kind) {
     k.fidx.clear();
     k.fscan_at = k.fscan_used = 0;
   }
-  if (kind == CALL_INFLATE) k.seg_ran = k.lanes_zeroed = k.sync = k.members = false;
+  if (kind == CALL_INFLATE) {
+    k.seg_ran = k.lanes_zeroed = k.sync = k.members = false;
+    k.bgzf_trusted = 0;
+  }
 }
 static void fold_marks(zs_ctx* c);
 
@@ -1728,7 +1734,7 @@ static int seg_launch(zs_ctx* c, const zs_route_opts& o, hipStream_t st, int wbi
                              : p.large ? zs_k_seg_walk<false, 1024u, true> : zs_k_seg_walk<false, 1024u, false>);
   walk<<<p.nwalk, 64, 0, sd>>>(b.in, b.in_off, b.in_len, gl, ng, c->gbig.as<uint32_t>(), nbig, wbits, gf,
                                c->gspb.as<uint32_t>(), gb, gln, gt, ge, gm, cnt + 2, c->gspl.as<uint32_t>(), p.walk_bits,
-                               p.split);
+                               p.split, p.refw ? 0 : 1);
   if (int r = mark(c, sd, "seg_walk")) return r;
   zs_k_seg_plan<<<ng, 64, 0, sd>>>(b.in, b.in_off, b.in_len, b.out_cap, gl, ng, wbits, p.refw ? 1 : 0, gb, gln, ge, gm,
                                    c->gpbase.as<uint32_t>(), c->gplist.as<uint4>());
@@ -2222,7 +2228,10 @@ static int members_refused(zs_ctx* c, int wbits, const Batch& h, bool device_ent
 // members are planned here, from the candidates and the lanes' records.  st is waited for once more where
 // the candidates outgrow the list the context keeps, and once per tail round (zs_k_members_tail).  The
 // members then decode as ONE gzip batch on the caller's input, with zlib semantics, and are joined per stream.
-static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st) {
+// bgzf: the _bgzf entries' mode.  It differs in three places: the sizing launch is zs_k_bgzf_size,
+// which trusts the headers it can; the plan's members get their flags (zs_plan_bgzf_trusted); the stitch
+// reports a flagged member's capacity outcome as its header's lie.
+static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st, bool bgzf = false) {
   const uint32_t n = h.n;
   std::vector<uint32_t> sh16(n), stile;
   uint64_t tin = 0;
@@ -2256,13 +2265,21 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   for (int round = 0;; round++) {
     const uint64_t cap = c->mbcand.cap / 4;
     HIPCHK(c->mbrec.ensure(sizeof(zs_sync_rec) * (n + cap)));
+    if (bgzf) HIPCHK(c->mbtrust.ensure(n + cap));
     zs_k_members_scan<true><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap);
     MARK("members_scan");
     // (a lane per stream and per place of the list: the lanes past the candidates' count return at once)
     const uint64_t lanes = std::min<uint64_t>(n + cap, ZS_RESTART_SEG_MAX);
-    zs_k_members_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
-        h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>());
-    MARK("members_size");
+    if (bgzf) {
+      zs_k_bgzf_size<<<(uint32_t)((lanes + ZS_BGZF_THREADS - 1) / ZS_BGZF_THREADS), ZS_BGZF_THREADS, 0, st>>>(
+          h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>(),
+          c->mbtrust.as<uint8_t>());
+      MARK("bgzf_size");
+    } else {
+      zs_k_members_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
+          h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>());
+      MARK("members_size");
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(tpre.data(), tcount, 8ull * (T + 1), hipMemcpyDeviceToHost));
@@ -2277,6 +2294,11 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   std::vector<zs_sync_rec> rec(n + C);
   if (C) HIPCHK(hipMemcpy(cand.data(), c->mbcand.p, 4ull * C, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(rec.data(), c->mbrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> rtrusted, trusted;  // per record, per planned member
+  if (bgzf) {
+    rtrusted.resize(n + C);
+    HIPCHK(hipMemcpy(rtrusted.data(), c->mbtrust.p, n + C, hipMemcpyDeviceToHost));
+  }
   std::vector<uint64_t> cfirst(n + 1);
   for (uint32_t i = 0; i <= n; i++) cfirst[i] = tpre[stile[i]];
   zs_members_plan& p = c->mp;
@@ -2304,6 +2326,8 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   }
   c->call.members = true;
   const uint32_t M = p.M;
+  // (a tail round replaces records of untrusted starts only: a trusted one is never PASSED)
+  if (bgzf) c->call.bgzf_trusted += zs_plan_bgzf_trusted(p, h.out_cap, cfirst.data(), cand.data(), rec.data(), rtrusted.data(), trusted);
   // where each member lies, decodes and belongs
   std::vector<uint64_t> src(M), ooff(M), dst(M);
   for (uint32_t g = 0; g < M; g++) {
@@ -2315,7 +2339,8 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   }
   const size_t g_first = 0, g_soff = up256(4ull * (n + 1)), g_opos = g_soff + up256(4ull * M), g_ocap = g_opos + up256(4ull * M),
                g_ooff = g_ocap + up256(4ull * M), g_dst = g_ooff + up256(8ull * M), g_ptile = g_dst + up256(8ull * M),
-               g_out = g_ptile + up256(4ull * (M + 1)), g_end = g_out + up256(8ull * n);
+               g_out = g_ptile + up256(4ull * (M + 1)), g_trust = g_out + up256(8ull * n),
+               g_end = g_trust + (bgzf ? up256(M) : 0);
   HIPCHK(c->mbseg.ensure(g_end));
   HIPCHK(c->mbres.ensure(20ull * M + 64));
   HIPCHK(c->mbstage.ensure(p.stage_bytes));
@@ -2329,6 +2354,7 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   memcpy(c->mbh.data() + g_dst, dst.data(), 8ull * M);
   memcpy(c->mbh.data() + g_ptile, p.ptile.data(), 4ull * (M + 1));
   memcpy(c->mbh.data() + g_out, h.out_off, 8ull * n);
+  if (bgzf) memcpy(c->mbh.data() + g_trust, trusted.data(), M);
   HIPCHK(hipMemcpyAsync(c->mbseg.p, c->mbh.data(), g_end, hipMemcpyHostToDevice, st));
   const uint8_t* dg = c->mbseg.as<uint8_t>();
   auto u32 = [&](size_t at) { return (const uint32_t*)(dg + at); };
@@ -2350,7 +2376,8 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   }
   uint32_t* cklen = c->mblen.as<uint32_t>();
   zs_k_members_stitch<<<n, 64, 0, st>>>(u32(g_first), u32(g_soff), u32(g_opos), seg.status, seg.phase, seg.msg, seg.out_len,
-                                        seg.consumed, n, out.status, out.phase, out.msg, out.out_len, out.consumed, cklen);
+                                        seg.consumed, n, out.status, out.phase, out.msg, out.out_len, out.consumed, cklen,
+                                        bgzf ? dg + g_trust : nullptr);
   HIPCHK(hipGetLastError());
   if (out.check) {
     // the check value over the joined output; the members' own values are verified by the decoders.
@@ -2403,7 +2430,7 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, const InflateOut
 // batch decides before anything is staged, the dictionaries to the device once, then the call begins and
 // host_batch runs its chunks, each a device batch with a copy of the caller's exact capacities as the limits.
 static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, const DictIn* dict,
-                        const RestartIn* rs, bool sync = false, bool members = false) {
+                        const RestartIn* rs, bool sync = false, bool members = false, bool bgzf = false) {
   // (a restart call has passed restart_refused, one that finds its points sync_refused, its members members_refused)
   if (!rs && !sync && !members)
     if (const zs_inflate_err e = zs_inflate_validate_host(c != nullptr, wbits, inflate_call(h, false, dict)))
@@ -2425,7 +2452,7 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                                             out.check ? dr[5] : nullptr};
                       // (a chunk's points and dictionaries: the same arrays, the chunk's part of the index)
                       if (rs) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
-                      if (members) return members_batch(c, hb, d, c->stream);
+                      if (members) return members_batch(c, hb, d, c->stream, bgzf);
                       if (sync) {  // the first points where the bytes are: the caller's memory
                         std::vector<uint32_t> first(b - a);
                         for (uint32_t i = a; i < b; i++)
@@ -2560,7 +2587,44 @@ extern "C" int zs_inflate_batch_members(zs_ctx* c, int wbits, uint32_t n, const 
   return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, false, true);
 }
 
-// The members the last _members call on the context decoded, in the layout of zs_last_restart_points:
+// BGZF files, the members sized from their headers where those can be trusted; device buffers
+extern "C" int zs_inflate_batch_bgzf_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
+                                            const uint32_t* in_len, uint8_t* d_out, const uint64_t* out_off,
+                                            const uint32_t* out_cap, int32_t* d_status, int32_t* d_phase,
+                                            int32_t* d_msg, uint32_t* d_out_len, uint32_t* d_consumed,
+                                            uint32_t* d_check, void* hip_stream) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  if (const int r = members_refused(c, wbits, h, true)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  call_begin(c, CALL_INFLATE);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, true);
+}
+
+// ... host buffers
+extern "C" int zs_inflate_batch_bgzf(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                     const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                     const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
+                                     uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
+  if (const int r = members_refused(c, wbits, h, false)) return r;
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, false, true, true);
+}
+
+// The planned members of the last _bgzf call on the context whose size came from their header; 0 after any
+// other inflate call.  Known when the call returns: the plan is made on the host.
+extern "C" uint64_t zs_last_bgzf_trusted(zs_ctx* c) { return c ? c->call.bgzf_trusted : 0; }
+
+// Host arithmetic, no context: the trusted headers followed from 0 (zs_bgzf.h)
+extern "C" int zs_bgzf_out_len(const uint8_t* in, uint32_t in_len, uint64_t* total) {
+  uint64_t t = 0;
+  const int r = in ? zs_bgzf_chain(in, in_len, t) : 0;
+  if (total) *total = r ? t : 0;
+  return r;
+}
+
+// The members the last _members or _bgzf call on the context decoded, in the layout of zs_last_restart_points:
 // member_first (n + 1 entries, from 0), then at most `cap` members' (in_pos, out_pos), every stream's
 // member 0 = (0, 0) included.  0 when the last inflate call on the context was no _members call.
 extern "C" uint64_t zs_last_members(zs_ctx* c, uint64_t* member_first, uint32_t* member_in, uint32_t* member_out,

@@ -34,7 +34,8 @@ extern "C" int zs_il_member_cycles(unsigned long long* out, int n) {
 // to HBM and match history read back from it.  A member takes the exact path
 // instead (zs_k_inflate over the bailed members) on ANY condition that is not a
 // clean end of stream -- a data error, truncated input, a dictionary request,
-// gzip header fields, a checksum or length mismatch, or output capacity -- so
+// gzip header fields (but an extra field alone where zlib semantics hold: a
+// BGZF block), a checksum or length mismatch, or output capacity -- so
 // statuses, phases and messages always come from the exact state machine.
 struct zs_lane_tabs {
   uint16_t lens[320];  // the block's code lengths (lit/len then distance; the header's code-length code first)
@@ -320,7 +321,16 @@ __global__ __launch_bounds__(64) ZS_LANE_WAVES(4) void zs_k_inflate_lane(const u
       const uint32_t cm = zs_lr_take(R, 8), flg = zs_lr_take(R, 8);
       zs_lr_take(R, 32);  // MTIME
       zs_lr_take(R, 16);  // XFL, OS
-      if (cm != 8 || flg != 0) bail = true;  // FEXTRA / FNAME / FCOMMENT / FHCRC / reserved: exact path
+      if (cm == 8 && flg == 4 && !(flags & ZS_INF_REF_WRAP)) {
+        // FEXTRA alone, with zlib semantics (a BGZF block): the field is skipped, whatever it holds
+        // (inflate.ts:624-664 stores it in a header record nobody asked for).  A field that passes the input
+        // leaves the reader past its end: the member bails below.  With the reference's calls to reproduce
+        // the member stays the exact kernel's, as every other flag.
+        const uint32_t xlen = zs_lr_take(R, 16);
+        zs_lr_seek(R, 8ull * (12u + xlen));
+      } else if (cm != 8 || flg != 0) {
+        bail = true;  // FNAME / FCOMMENT / FHCRC / reserved: exact path
+      }
     } else if (wrap & 1) {
       if (((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (!DICT && (b1 & 0x20))) bail = true;
       if (DICT && !bail) {

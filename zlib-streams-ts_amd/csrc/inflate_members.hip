@@ -138,12 +138,18 @@ __global__ __launch_bounds__(ZS_SYNC_LANES) void zs_k_members_tail(
 // (the decoder's own, for the bytes from its start on), out_len = its out_pos (the members before it
 // are complete), consumed = its start.  cklen[s]: the bytes the stream's check value is taken over --
 // the total, or 0 for a stream that failed (the crc32 of no bytes is 0).
+// trusted (null in the _members calls; the _bgzf calls'): one byte per member, set where the
+// member's room was its header's ISIZE.  Such a member that ends with the capacity outcome (Z_BUF_ERROR,
+// "output capacity exceeded") produced more than its ISIZE says: it is reported as Z_DATA_ERROR, "incorrect
+// length check" -- zlib's words for an ISIZE that does not match -- so that the caller can tell it from a
+// capacity of their own that is too small.  (Z_BUF_ERROR with no message is input that ended early, a BSIZE
+// that is too small: it stays as the decoder reports it.)
 __global__ __launch_bounds__(64) void zs_k_members_stitch(
     const uint32_t* __restrict__ rfirst, const uint32_t* __restrict__ soff, const uint32_t* __restrict__ opos,
     const int32_t* __restrict__ seg_status, const int32_t* __restrict__ seg_phase, const int32_t* __restrict__ seg_msg,
     const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ seg_used, uint32_t n,
     int32_t* __restrict__ status, int32_t* __restrict__ phase, int32_t* __restrict__ msg, uint32_t* __restrict__ out_len,
-    uint32_t* __restrict__ consumed, uint32_t* __restrict__ cklen) {
+    uint32_t* __restrict__ consumed, uint32_t* __restrict__ cklen, const uint8_t* __restrict__ trusted) {
   const uint32_t s = blockIdx.x;
   if (s >= n) return;
   const uint32_t g0 = rfirst[s], g1 = rfirst[s + 1];
@@ -157,9 +163,10 @@ __global__ __launch_bounds__(64) void zs_k_members_stitch(
   if (threadIdx.x != 0) return;
   const bool ok = bad == 0xffffffffu;
   const uint32_t g = ok ? g1 - 1u : bad;
-  status[s] = seg_status[g];
-  phase[s] = seg_phase[g];
-  msg[s] = seg_msg[g];
+  const bool lied = trusted && trusted[g] && seg_status[g] == ZS_Z_BUF_ERROR && seg_msg[g] == ZS_MSG_CAPACITY;
+  status[s] = lied ? ZS_Z_DATA_ERROR : seg_status[g];
+  phase[s] = lied ? ZS_PHASE_PROCESS_ : seg_phase[g];
+  msg[s] = lied ? ZS_MSG_LENGTH_CHECK : seg_msg[g];
   out_len[s] = ok ? opos[g] + seg_len[g] : opos[g];
   consumed[s] = ok ? soff[g] + seg_used[g] : soff[g];
   cklen[s] = ok ? opos[g] + seg_len[g] : 0u;

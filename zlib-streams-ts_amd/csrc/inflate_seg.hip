@@ -595,7 +595,7 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
                                                     zs_seg_lane* __restrict__ lanes, zcode* __restrict__ tcache,
                                                     zs_seg_ent* __restrict__ ents, zs_seg_mem* __restrict__ mem,
                                                     uint32_t* __restrict__ nspan, uint32_t* __restrict__ spans,
-                                                    uint32_t sbits, int split) {
+                                                    uint32_t sbits, int split, int extra_ok) {
   __shared__ zs_sg_walk_lds<W> L;
   const uint32_t lane = threadIdx.x;
   // the entry: blocks [0, n_list): entry 0 of list member blockIdx.x; then
@@ -642,7 +642,8 @@ __global__ __launch_bounds__(64) void zs_k_seg_walk(const uint8_t* __restrict__ 
   zs_wr_start(R, start);
   const int wrap = wbits < 0 ? 0 : (wbits >> 4) + 5;  // inflate.ts:152-160
   bool good = true;
-  if (e == 0 && wrap) good = zs_wr_wrapper_header(R, wrap);  // plain zlib / gzip headers only, as the lane path
+  // plain zlib / gzip headers only, as the lane path (extra_ok: zlib semantics, an extra field alone is skipped)
+  if (e == 0 && wrap) good = zs_wr_wrapper_header(R, wrap, extra_ok != 0);
   uint32_t hdr = (uint32_t)zs_wr_bitpos(R);
   uint32_t pe0 = e == 0 ? 0u : start;  // sub-chunk events before the first symbol go to it
   uint32_t prevb = ZS_SEG_NONE;       // the entry's last span
@@ -1586,7 +1587,7 @@ __global__ __launch_bounds__(T) void zs_k_seg_resolve(const uint32_t* __restrict
   template __global__ void zs_k_seg_walk<D, W, ST>(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*,  \
                                                uint32_t, const uint32_t*, uint32_t, int, const uint64_t*,          \
                                                const uint32_t*, zs_seg_blk*, zs_seg_lane*, zcode*, zs_seg_ent*,    \
-                                               zs_seg_mem*, uint32_t*, uint32_t*, uint32_t, int);
+                                               zs_seg_mem*, uint32_t*, uint32_t*, uint32_t, int, int);
 ZS_SEG_WALK_INST(false, 1024u, false)
 ZS_SEG_WALK_INST(false, 1024u, true)
 ZS_SEG_WALK_INST(true, 1024u, false)

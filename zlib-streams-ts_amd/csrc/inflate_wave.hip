@@ -83,7 +83,7 @@ static __device__ __forceinline__ void zs_wave_member(uint8_t* zs_wsm, const uin
     }
   };
   // ---- wrapper header (inflate.ts:377-580): plain zlib / gzip headers only, as the lane path
-  if (wrap && !zs_wr_wrapper_header(R, wrap)) bail = true;
+  if (wrap && !zs_wr_wrapper_header(R, wrap, !REFW)) bail = true;
   uint32_t last = 0;
   while (!bail && !last) {
     // the header and zlib's tables (zs_wr_block_header, the serial inflate_table)

@@ -170,4 +170,10 @@ __global__ void zs_k_members_tail(const uint8_t* in, const uint64_t* in_off, con
 __global__ void zs_k_members_stitch(const uint32_t* rfirst, const uint32_t* soff, const uint32_t* opos,
                                     const int32_t* seg_status, const int32_t* seg_phase, const int32_t* seg_msg,
                                     const uint32_t* seg_len, const uint32_t* seg_used, uint32_t n, int32_t* status,
-                                    int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* cklen);
+                                    int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* cklen,
+                                    const uint8_t* trusted);
+// the same search over BGZF files (inflate_bgzf.hip): zs_k_members_size's arguments, lanes and
+// records, a start whose header can be trusted sized from BSIZE and ISIZE; trusted: one byte per record
+__global__ void zs_k_bgzf_size(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* stile,
+                               uint32_t n, const uint64_t* tpre, const uint32_t* cand, uint64_t cap, uint32_t pass,
+                               zs_sync_rec* rec, uint8_t* trusted);

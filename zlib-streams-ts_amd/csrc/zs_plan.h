@@ -1267,6 +1267,8 @@ struct zs_restart_layout {
 // entries' layout, which restart_batch then decodes unchanged.
 #define ZS_SYNC_TILE 4096u   // bytes per workgroup step of the scan: 256 lanes, one aligned 16-byte unit each
 #define ZS_SYNC_LANES 16u    // starts per workgroup of the size decode (their Huffman state: 2,148 bytes of LDS each)
+#define ZS_BGZF_THREADS 256u  // starts per workgroup of the BGZF sizing (inflate_bgzf.hip) ...
+#define ZS_BGZF_SLOTS 4u      // ... and the Huffman states a wave of it owns for its starts that must decode
 static inline bool zs_sync_pass_ok(int v) { return v >= 1 && v <= 64; }  // zs_set_option's values of "sync_pass"
 // how a lane of zs_k_sync_size ended
 #define ZS_SYNC_LANDED 1u  // a block closed at a byte boundary behind the marker: `end` is a candidate
@@ -1501,6 +1503,36 @@ static inline void zs_plan_members(uint32_t n, const uint32_t* in_len, const uin
   p.M = (uint32_t)p.rstream.size();
   p.rfirst[n] = p.M;
   p.stage_bytes = p.in_place ? 0 : st + 16;
+}
+
+// The _bgzf entries' flags over a finished plan.  rtrusted: one byte per record, in the
+// records' order, set where the record came from a header that was trusted (zs_bgzf.h) and not from the
+// data.  trusted[g] is set when planned member g came from such a record and was given the record's full
+// len for room: its room is its header's ISIZE, so a capacity outcome of its decode is the header's lie
+// and not the caller's capacity.  Not set for the member that got no room because the stream's out_cap is
+// passed.  Returns the count of flags set.
+static inline uint32_t zs_plan_bgzf_trusted(const zs_members_plan& p, const uint32_t* out_cap, const uint64_t* cfirst,
+                                            const uint32_t* cand, const zs_sync_rec* rec, const uint8_t* rtrusted,
+                                            std::vector<uint8_t>& trusted) {
+  trusted.assign(p.M, 0);
+  uint32_t count = 0;
+  for (uint32_t g = 0; g < p.M; g++) {
+    const uint32_t i = p.rstream[g], at = p.soff[g];
+    size_t x = i;  // the member's record: offset 0's, or its candidate's (every planned start behind 0 is one)
+    if (at) {
+      const uint32_t* c0 = cand + cfirst[i];
+      const uint32_t* c1 = cand + cfirst[i + 1];
+      const uint32_t* f = std::lower_bound(c0, c1, at);
+      if (f == c1 || *f != at) continue;
+      x = p.n + (size_t)(f - cand);
+    }
+    const zs_sync_rec& r = rec[x];
+    if (!rtrusted[x] || r.how != ZS_SYNC_FINAL || r.end != at + p.slen[g]) continue;
+    if ((uint64_t)p.opos[g] + r.len > out_cap[i] || p.ocap[g] != r.len) continue;
+    trusted[g] = 1;
+    count++;
+  }
+  return count;
 }
 
 #endif

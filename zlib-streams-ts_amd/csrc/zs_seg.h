@@ -78,7 +78,7 @@ __global__ void zs_k_seg_walk(const uint8_t* in, const uint64_t* in_off, const u
                               uint32_t n_list, const uint32_t* big, uint32_t n_big, int wbits, const uint64_t* found,
                               const uint32_t* spb, zs_seg_blk* blk, zs_seg_lane* lanes, zcode* tcache,
                               zs_seg_ent* ents, zs_seg_mem* mem, uint32_t* nspan, uint32_t* spans, uint32_t sbits,
-                              int split);
+                              int split, int extra_ok);
 __global__ void zs_k_seg_plan(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                               const uint32_t* out_cap, const uint32_t* list, uint32_t n_list, int wbits, int refw,
                               const zs_seg_blk* blk, zs_seg_lane* lanes, const zs_seg_ent* ents, zs_seg_mem* mem,

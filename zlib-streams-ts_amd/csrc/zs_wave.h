@@ -108,13 +108,22 @@ static __device__ __forceinline__ void zs_wr_start(zs_wave_reader& R, uint64_t b
 
 // The wrapper header (inflate.ts:377-580) of a zlib / gzip member (wrap != 0,
 // inflate.ts:152-160): plain headers only -- gzip header fields, FDICT or a
-// failed check are false, and the exact path reports them.
-static __device__ __forceinline__ bool zs_wr_wrapper_header(zs_wave_reader& R, int wrap) {
+// failed check are false, and the exact path reports them.  extra_ok (zlib
+// semantics: no call of the reference's to reproduce): a gzip header whose one
+// flag is FEXTRA -- a BGZF block, DESIGN 4.15 -- is taken too, the field skipped
+// whatever it holds, as the lane path does; a field that passes the input leaves
+// the reader past its end, which the block header behind it refuses.
+static __device__ __forceinline__ bool zs_wr_wrapper_header(zs_wave_reader& R, int wrap, bool extra_ok) {
   const uint32_t b0 = zs_wr_take(R, 8), b1 = zs_wr_take(R, 8);
   if ((wrap & 2) && b0 == 0x1f && b1 == 0x8b) {
     const uint32_t cm = zs_wr_take(R, 8), flg = zs_wr_take(R, 8);
     zs_wr_take(R, 32);  // MTIME
     zs_wr_take(R, 16);  // XFL, OS
+    if (cm == 8 && flg == 4 && extra_ok) {
+      const uint32_t xlen = zs_wr_take(R, 16);
+      zs_wr_start(R, 8ull * (12u + xlen));
+      return true;
+    }
     return cm == 8 && flg == 0;
   }
   if (wrap & 1) return !(((b0 << 8) | b1) % 31 || (b0 & 15) != 8 || (b0 >> 4) + 8 > 15 || (b1 & 0x20));

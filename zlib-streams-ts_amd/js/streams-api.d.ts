@@ -70,9 +70,17 @@ export interface DecompressBatchOptions extends BatchOptions {
    * follow; anything else ends the stream and is ignored.  A member that is truncated or corrupt fails its
    * input.  "gzip" only, needs `outCapacity` (the total of an input's members); with another format, without
    * `outCapacity`, with `dictionary` or with `restartPoints` it is a TypeError.  The members' index
-   * (zs_last_members) is not offered here: the batch entries run on the device pool. */
-  members?: boolean;
+   * (zs_last_members) is not offered here: the batch entries run on the device pool.
+   * "bgzf": the same for BGZF files (bgzip output, BAM, tabix-indexed VCF), with every block whose header can be
+   * trusted sized from its BSIZE and ISIZE instead of a decode of its data (zs_inflate_batch_bgzf in zs_gpu.h).
+   * Every input whose headers tell the truth decodes exactly as with `true`; a block whose ISIZE is too small fails
+   * its input with zmsg "incorrect length check".  Without `outCapacity` each input's capacity is its
+   * `bgzfOutLength`; an input that is not BGZF throughout is then a TypeError that names it. */
+  members?: boolean | "bgzf";
 }
+/** The bytes a BGZF file produces, read from its headers (the sum of ISIZE over the blocks followed from offset 0),
+ * or null when a member on the way is no BGZF block whose header can be trusted.  Host arithmetic, no GPU. */
+export function bgzfOutLength(input: Uint8Array): number | null;
 /** The length of the wrapper's header in front of the deflate data: 0 for "deflate-raw", 2 for "deflate", for
  * "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC, or 0 when that header is malformed or does not fit. */
 export function wrapperHeaderLength(input: Uint8Array, format?: string): number;

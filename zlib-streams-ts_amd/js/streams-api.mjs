@@ -196,16 +196,20 @@ export function wrapperHeaderLength(input, format = "gzip") {
 // a caller without an index; the same conditions, and the same result as with the true points.
 // options.members: true: every member of multi-member gzip inputs is decoded and the outputs are concatenated
 // (zs_inflate_batch_members in zs_gpu.h).  "gzip" only, needs outCapacity; with a dictionary or restartPoints
-// it is a TypeError (not built).
+// it is a TypeError (not built).  options.members: "bgzf": the same, with BGZF blocks sized from their headers
+// (zs_inflate_batch_bgzf in zs_gpu.h); without outCapacity the output is sized from the headers too (capacityOf).
 function restartOf(options, ins, format) {
   const r = options.restartPoints;
   if (options.members) {
+    const bgzf = options.members === "bgzf";
+    if (typeof options.members === "string" && !bgzf) throw new TypeError("members must be true, false or \"bgzf\"");
     if (format !== "gzip") throw new TypeError("members are a gzip notion (format must be \"gzip\")");
-    if (options.outCapacity === undefined || options.outCapacity === null) throw new TypeError("members need outCapacity");
+    if (!bgzf && (options.outCapacity === undefined || options.outCapacity === null))
+      throw new TypeError("members need outCapacity");
     if (options.dictionary !== undefined && options.dictionary !== null)
       throw new TypeError("members and dictionary cannot be combined");
     if (r !== undefined && r !== null) throw new TypeError("members and restartPoints cannot be combined");
-    return "members";
+    return bgzf ? "bgzf" : "members";
   }
   if (r === undefined || r === null) return undefined;
   if (options.dictionary !== undefined && options.dictionary !== null)
@@ -230,6 +234,25 @@ function restartOf(options, ins, format) {
   });
 }
 
+// The capacities of a decompress call: the caller's; for members: "bgzf" without them each input's bgzfOutLength
+// (zs_bgzf_out_len: the sum of ISIZE over its blocks' headers) rounded up to 4 -- a TypeError naming the input that
+// is not BGZF throughout.
+function capacityOf(options, ins) {
+  const c = options.outCapacity;
+  if (options.members !== "bgzf" || (c !== undefined && c !== null)) return c;
+  return ins.map((x, i) => {
+    const n = addon.bgzfOutLength(x);
+    if (n < 0) throw new TypeError("input " + i + " is not BGZF throughout: give outCapacity");
+    return (n + 3) - ((n + 3) % 4);
+  });
+}
+
+/** The bytes a BGZF file produces, read from its headers, or null when it is not BGZF throughout. */
+export function bgzfOutLength(input) {
+  const n = addon.bgzfOutLength(input);
+  return n < 0 ? null : n;
+}
+
 async function runDecompress(inputs, format, options) {
   options = options || {};
   const wbits = decompressWbits(format);
@@ -238,8 +261,9 @@ async function runDecompress(inputs, format, options) {
   // (a dictionary for "gzip" / "deflate64-raw" rejects with code "-2": inflateSetDictionary's Z_STREAM_ERROR)
   let res;
   try {
-    res = await addon.decompressBatch(ins, wbits, options.outCapacity, devicesOf(options),
-                                      dictionariesOf(options, ins.length), restartOf(options, ins, format));
+    const restart = restartOf(options, ins, format);
+    res = await addon.decompressBatch(ins, wbits, capacityOf(options, ins), devicesOf(options),
+                                      dictionariesOf(options, ins.length), restart);
   } catch (e) {
     // points the entry refuses (zs_gpu.h): ZS_STREAM_ERROR, reported as the stream layer reports it
     if (options.restartPoints && e.code === String(Z_STREAM_ERROR))
@@ -299,8 +323,9 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {
   options = options || {};
   const ins = checkInputs(inputs);
-  return addon.decompressBatch(ins, decompressWbits(format), options.outCapacity, devicesOf(options),
-                               dictionariesOf(options, ins.length), restartOf(options, ins, format));
+  const restart = restartOf(options, ins, format);
+  return addon.decompressBatch(ins, decompressWbits(format), capacityOf(options, ins), devicesOf(options),
+                               dictionariesOf(options, ins.length), restart);
 }
 export const engineVersion = () => addon.version();
 export const selfTest = (device = 0) => addon.selfTest(device);

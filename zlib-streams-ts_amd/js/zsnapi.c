@@ -221,7 +221,8 @@ typedef struct {
   uint64_t *restart_first;
   uint32_t *restart_in, *restart_out;
   int restart_scan;    /* restart "scan": the points are found from the bytes (zs_pool_inflate_batch_sync) */
-  int members;         /* restart "members": every member of multi-member gzip inputs (zs_pool_inflate_batch_members) */
+  int members;         /* restart "members": every member of multi-member gzip inputs (zs_pool_inflate_batch_members);
+                          2 = restart "bgzf": BGZF blocks sized from their headers (zs_pool_inflate_batch_bgzf) */
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -277,6 +278,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
                                        j->dict_off, j->dict_len);
+  else if (j->inflate && j->members == 2)
+    j->rc = zs_pool_inflate_batch_bgzf(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off, j->cap,
+                                       j->status, j->phase, j->msg, j->olen, j->cons, j->check);
   else if (j->inflate && j->members)
     j->rc = zs_pool_inflate_batch_members(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                           j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check);
@@ -654,13 +658,14 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
 
 /* decompressBatch(inputs: Uint8Array[], wbits, outCapacity: number | number[] | undefined, devices,
  *                 dictionaries: (Uint8Array | null)[] | undefined,
- *                 restart: number[][] | "scan" | "members" | undefined) ->
+ *                 restart: number[][] | "scan" | "members" | "bgzf" | undefined) ->
  *   Promise<{status, phase: Int32Array, message: string[], outputs: Uint8Array[], consumed: Int32Array,
  *            check: Uint32Array}>
  * outCapacity undefined: unbounded output, as DecompressionStream (zs_pool_inflate_batch_auto).
  * restart: per input the flat pairs in_pos, out_pos of its points, the start first (zs_pool_inflate_batch_restart,
  * zs_gpu.h), or the string "scan": the points are found from the bytes (zs_pool_inflate_batch_sync), or the
- * string "members": every member of multi-member gzip inputs is decoded (zs_pool_inflate_batch_members); each
+ * string "members": every member of multi-member gzip inputs is decoded (zs_pool_inflate_batch_members), or the
+ * string "bgzf": the same with BGZF blocks sized from their headers (zs_pool_inflate_batch_bgzf); each
  * needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any device is
  * touched. */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
@@ -739,11 +744,13 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
     napi_get_value_string_utf8(env, argv[5], word, sizeof word, &len);
     if (strcmp(word, "members") == 0) {
       j->members = 1;
+    } else if (strcmp(word, "bgzf") == 0) {
+      j->members = 2;
     } else if (strcmp(word, "scan") == 0) {
       j->restart_scan = 1;
     } else {
       job_free(j);
-      return throw_code(env, ZS_STREAM_ERROR, "restart must be number[][], \"scan\" or \"members\"");
+      return throw_code(env, ZS_STREAM_ERROR, "restart must be number[][], \"scan\", \"members\" or \"bgzf\"");
     }
   } else if (rt != napi_undefined && rt != napi_null) {
     const int rc = copy_restart(env, j, argv[5]);
@@ -763,6 +770,26 @@ static napi_value DeflateBound(napi_env env, napi_callback_info info) {
   double len = 0;
   napi_get_value_double(env, argv[0], &len);
   NAPI_OK(napi_create_double(env, (double)zs_deflate_bound((uint64_t)len, argc > 1 ? arg_i32(env, argv[1], -15) : -15), &r));
+  return r;
+}
+
+/* bgzfOutLength(input: Uint8Array) -> number: the bytes a BGZF file produces, read from its headers
+ * (zs_bgzf_out_len: host arithmetic), or -1 when a member on the way is no BGZF block whose header can be trusted */
+static napi_value BgzfOutLength(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], r;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool is_ta = false;
+  if (argc) napi_is_typedarray(env, argv[0], &is_ta);
+  napi_typedarray_type type = napi_int8_array;
+  size_t len = 0;
+  void *data = NULL;
+  if (is_ta) napi_get_typedarray_info(env, argv[0], &type, &len, &data, NULL, NULL);
+  if (!is_ta || type != napi_uint8_array || len > 0xffffffffu)
+    return throw_code(env, ZS_STREAM_ERROR, "bgzfOutLength(input: Uint8Array)");
+  uint64_t total = 0;
+  const int ok = len ? zs_bgzf_out_len((const uint8_t *)data, (uint32_t)len, &total) : 0;
+  NAPI_OK(napi_create_double(env, ok ? (double)total : -1.0, &r));
   return r;
 }
 
@@ -791,6 +818,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"compressBatch", NULL, CompressBatch, NULL, NULL, NULL, napi_default, NULL},
       {"decompressBatch", NULL, DecompressBatch, NULL, NULL, NULL, napi_default, NULL},
       {"deflateBound", NULL, DeflateBound, NULL, NULL, NULL, napi_default, NULL},
+      {"bgzfOutLength", NULL, BgzfOutLength, NULL, NULL, NULL, napi_default, NULL},
       {"version", NULL, Version, NULL, NULL, NULL, napi_default, NULL},
       {"selfTest", NULL, SelfTest, NULL, NULL, NULL, napi_default, NULL},
   };

@@ -243,6 +243,13 @@ def lib():
         L.zs_inflate_batch_members_device.argtypes = L.zs_inflate_batch_sync_device.argtypes
         L.zs_last_members.restype = ctypes.c_uint64
         L.zs_last_members.argtypes = [_P, _U64P, _U32P, _U32P, ctypes.c_uint64]
+    if hasattr(L, "zs_inflate_batch_bgzf"):  # ... the members' arguments: BGZF blocks are sized from their headers
+        L.zs_inflate_batch_bgzf.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_pool_inflate_batch_bgzf.argtypes = L.zs_inflate_batch_ex.argtypes
+        L.zs_inflate_batch_bgzf_device.argtypes = L.zs_inflate_batch_sync_device.argtypes
+        L.zs_last_bgzf_trusted.restype = ctypes.c_uint64
+        L.zs_last_bgzf_trusted.argtypes = [_P]
+        L.zs_bgzf_out_len.argtypes = [ctypes.c_char_p, ctypes.c_uint32, _U64P]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -355,12 +362,21 @@ def decompress_scan(restart, out_caps, zdict=None) -> bool:
     return True
 
 
-def decompress_members(members, fmt, out_caps, zdict=None, restart=None) -> bool:
+def decompress_members(members, fmt, out_caps, zdict=None, restart=None):
     """members=True: every member of a multi-member gzip file is decoded and the outputs are
     concatenated (zs_inflate_batch_members*).  gzip only, the capacities must be given, and neither
-    dictionaries nor restart points are built with it: ValueError."""
+    dictionaries nor restart points are built with it: ValueError.  members="bgzf": the same, with BGZF
+    blocks sized from their headers (zs_inflate_batch_bgzf*); the host entries size the output themselves
+    when out_caps is None (bgzf_out_caps).  Returns False, True or "bgzf"."""
     if not members:
         return False
+    if isinstance(members, str):
+        if members != "bgzf":
+            raise ValueError("members must be True, False or \"bgzf\"")
+        if out_caps is None:
+            out_caps = ()  # (sized from the headers)
+    else:
+        members = True
     if fmt != "gzip":
         raise ValueError("members are a gzip notion (fmt must be \"gzip\")")
     if out_caps is None:
@@ -369,7 +385,27 @@ def decompress_members(members, fmt, out_caps, zdict=None, restart=None) -> bool
         raise ValueError("members with a preset dictionary are not built")
     if restart is not None:
         raise ValueError("members with restart points are not built")
-    return True
+    return members
+
+
+def bgzf_out_len(data) -> Optional[int]:
+    """zs_bgzf_out_len: the bytes a BGZF file produces, read from its headers -- the sum of ISIZE over the
+    blocks followed from offset 0 -- or None when a member on the way is no BGZF block whose header can be
+    trusted.  Host arithmetic, no GPU."""
+    data = bytes(data)
+    total = ctypes.c_uint64(0)
+    return int(total.value) if lib().zs_bgzf_out_len(data, len(data), ctypes.byref(total)) else None
+
+
+def bgzf_out_caps(inputs) -> List[int]:
+    """the capacities members="bgzf" uses when none are given: each stream's bgzf_out_len rounded up to 4"""
+    caps = []
+    for i, s in enumerate(inputs):
+        n = bgzf_out_len(s)
+        if n is None:
+            raise ValueError("stream %d is not BGZF throughout: give out_caps" % i)
+        caps.append((n + 3) & ~3)
+    return caps
 
 
 def decompress_restart(inputs, fmt, restart, out_caps, zdict=None):
@@ -555,14 +591,22 @@ class Engine:
         zs_inflate_batch_restart: the segments decode in parallel, zlib semantics; needs out_caps), or
         "scan": the points are found from the bytes (zs_inflate_batch_sync; last_restart_points()).
         members=True: every member of multi-member gzip inputs, concatenated (decompress_members;
-        zs_inflate_batch_members; last_members())."""
+        zs_inflate_batch_members; last_members()).  members="bgzf": the same for BGZF files, the blocks
+        sized from their headers (zs_inflate_batch_bgzf; last_bgzf_trusted()); out_caps None: sized from
+        the headers too (bgzf_out_caps; ValueError for a stream that is not BGZF throughout)."""
         return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                                   out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
-        if decompress_members(members, fmt, out_caps, zdict, restart):
+        mode = decompress_members(members, fmt, out_caps, zdict, restart)
+        if mode == "bgzf":
+            caps = bgzf_out_caps(inputs) if out_caps is None else out_caps
+            res = _inflate_host(L, L.zs_inflate_batch_bgzf, self._ctx, inputs, fmt, caps, self._check)
+            self._members_n = len(inputs)
+            return res
+        if mode:
             res = _inflate_host(L, L.zs_inflate_batch_members, self._ctx, inputs, fmt, out_caps, self._check)
             self._members_n = len(inputs)  # (a refused call leaves the context's record, and this count, alone)
             return res
@@ -601,6 +645,11 @@ class Engine:
         if int(self._L.zs_last_members(self._ctx, first, min_, mout, total)) != total or first[n] != total:
             raise ZsError("zs_last_members: the count changed between two queries")
         return [[(int(min_[k]), int(mout[k])) for k in range(first[i], first[i + 1])] for i in range(n)]
+
+    def last_bgzf_trusted(self) -> int:
+        """zs_last_bgzf_trusted: the planned members of the last members="bgzf" call on this engine whose
+        size came from their header; 0 after any other decompress call."""
+        return int(self._L.zs_last_bgzf_trusted(self._ctx))
 
     def last_restart_points(self) -> List[List[tuple]]:
         """zs_last_restart_points: the points the last restart="scan" call on this engine found, one
@@ -703,14 +752,18 @@ class Engine:
         "deflate-raw" and "deflate") for the first point.  restart="scan": the points are found from the
         bytes on the device (zs_inflate_batch_sync_device, which waits for hip_stream once in the
         middle); no `headers`.  members=True: every member of multi-member gzip streams
-        (zs_inflate_batch_members_device, which waits for hip_stream as the scan call does)."""
-        if decompress_members(members, fmt, out_cap, None if dict_off is None else dict_off, restart):
-            r = self._L.zs_inflate_batch_members_device(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len,
-                                                        _P(d_out), out_off, out_cap, _P(d_status), _P(d_phase),
-                                                        _P(d_msg), _P(d_out_len), _P(d_consumed),
-                                                        _P(d_check) if d_check else None,
-                                                        _P(hip_stream) if hip_stream else None)
-            self._check(r, "zs_inflate_batch_members_device")
+        (zs_inflate_batch_members_device, which waits for hip_stream as the scan call does); members="bgzf":
+        BGZF blocks sized from their headers (zs_inflate_batch_bgzf_device)."""
+        mode = decompress_members(members, fmt, out_cap, None if dict_off is None else dict_off, restart)
+        if mode:
+            bgzf = mode == "bgzf"  # (the regions are the caller's: out_cap is needed, as with members=True)
+            if out_cap is None:
+                raise ValueError("members on the device need out_cap")
+            fn = self._L.zs_inflate_batch_bgzf_device if bgzf else self._L.zs_inflate_batch_members_device
+            r = fn(self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
+                   _P(d_status), _P(d_phase), _P(d_msg), _P(d_out_len), _P(d_consumed),
+                   _P(d_check) if d_check else None, _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_inflate_batch_bgzf_device" if bgzf else "zs_inflate_batch_members_device")
             self._members_n = n
             return
         if decompress_scan(restart, out_cap, None if dict_off is None else dict_off):
@@ -1013,7 +1066,11 @@ class Pool:
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
         L = self._L
-        if decompress_members(members, fmt, out_caps, zdict, restart):  # (zs_last_members is not offered on the pool)
+        mode = decompress_members(members, fmt, out_caps, zdict, restart)  # (zs_last_members is not offered on the pool)
+        if mode == "bgzf":
+            caps = bgzf_out_caps(inputs) if out_caps is None else out_caps
+            return _inflate_host(L, L.zs_pool_inflate_batch_bgzf, self._pool, inputs, fmt, caps, self._check)
+        if mode:
             return _inflate_host(L, L.zs_pool_inflate_batch_members, self._pool, inputs, fmt, out_caps, self._check)
         if decompress_scan(restart, out_caps, zdict):
             return _inflate_host(L, L.zs_pool_inflate_batch_sync, self._pool, inputs, fmt, out_caps, self._check)
