@@ -422,6 +422,71 @@ int zs_pool_deflate_batch_flush(zs_pool *pool, int level, int wbits, uint32_t n_
                                 const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
                                 int flush, const uint64_t *flush_first, const uint32_t *flush_pos);
 
+/* BGZF: one file's 64 KiB blocks compressed in parallel (SAM specification 4.1, "The BGZF compression
+ * format").  Stream i of L = in_len[i] bytes with block size B becomes ceil(L / B) data blocks and then
+ * the end-of-file block; an empty stream is the end-of-file block alone.  Data block j covers
+ * in[jB .. min((j + 1)B, L)) and is one gzip member:
+ *  - header, 18 bytes: 1f 8b 08 04 | 00 00 00 00 | 00 | ff | 06 00 | 42 43 02 00 | BSIZE -- FLG 4
+ *    (FEXTRA), MTIME 0, XFL 0 at every level, OS 255, XLEN 6, the subfield 'B' 'C' with SLEN 2, and
+ *    BSIZE = the block's total size - 1, little-endian u16 (htslib's bgzf_compress header; the plain
+ *    gzip wrapper's XFL by level does not apply);
+ *  - data, levels 1..9 (-1 is 6): the bytes zs_deflate_batch_ex(level, -15) produces for that piece
+ *    alone -- deflateInit2_(level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY), all input, Z_FINISH.  Every
+ *    piece is finished: its last block carries BFINAL and is padded to a byte, a piece whose symbols end
+ *    on the 16,383-symbol cut keeps its trailing empty static block, and no marker is written;
+ *  - data, level 0: one final stored block, 01 | LEN | ~LEN | the piece (RFC 1951 3.2.4).  These bytes
+ *    are the definition; deflate_stored's cuts and the stream layer play no part;
+ *  - trailer, 8 bytes: crc32 of the piece and the piece's length, little-endian u32 each.
+ * The end-of-file block is the 28 bytes 1f8b08040000000000ff0600424302001b0003000000000000000000.
+ * block_bytes is B: 0 means ZS_BGZF_BLOCK (65,280, htslib's BGZF_BLOCK_SIZE), 1 .. 65,280 are taken.
+ * zs_deflate_bound(65280, -15) + 26 = 65,331 <= 65,536, so a block always fits BSIZE and no piece is
+ * ever retried with less input; a block that came out larger all the same would fail its stream with
+ * ZS_STREAM_ERROR, never write a wrapped BSIZE.
+ * As a consequence the output is what bgzip built against zlib 1.2.11 writes single-threaded at the same
+ * level (one-shot Z_FINISH and the 32 KiB feeding of the plain entry give the same bytes for a piece
+ * this short); the contract is the bytes above.  bgzip, samtools, tabix, gzip -d and
+ * zs_inflate_batch_bgzf* read it.
+ * The entries take the arguments of zs_deflate_batch_device_ex / zs_deflate_batch_ex /
+ * zs_pool_deflate_batch without wbits, then block_bytes.
+ *  - status[i] and out_len[i] as the plain entries; ZS_BUF_ERROR against the stream's own out_cap[i],
+ *    exactly, with nothing stored for that stream; check[i] is the crc32 of the WHOLE input (what a
+ *    reader that concatenates the members computes), 0 for a failed stream; the device form's 4-byte
+ *    alignment rule as the other device entries;
+ *  - refused with ZS_STREAM_ERROR before the context is looked at, in this order: a level outside
+ *    -1 .. 9 ("invalid level"); block_bytes above 65,280 ("invalid BGZF block size"); n_streams > 0 with
+ *    a null offset, length or capacity array ("null arrays"); for the device entry streams + data
+ *    blocks above 65,535 in the call ("too many BGZF blocks (streams + blocks above 65,535 in one
+ *    call)": split the batch) -- a host call is checked chunk by chunk;
+ *  - a call whose streams are all empty is still a BGZF call: end-of-file blocks;
+ *  - preset dictionaries, strategies and windowBits / memLevel are not built: there are no _dict,
+ *    _strategy or _params forms.  Size outputs with zs_deflate_bound_bgzf. */
+#define ZS_BGZF_BLOCK 65280
+/* The sum over the blocks of zs_deflate_bound(piece, -15) + 26, plus 28, in closed form; level 0's stored
+ * form (piece + 5 + 26) is smaller, so one bound serves all levels.  0 for a block_bytes above 65,280. */
+uint64_t zs_deflate_bound_bgzf(uint64_t source_len, uint32_t block_bytes);
+/* device buffers (as zs_deflate_batch_device_ex) */
+int zs_deflate_batch_bgzf_device(zs_ctx *ctx, int level, uint32_t n_streams, const uint8_t *d_in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                 const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                 uint32_t *d_out_len, uint32_t *d_check, void *hip_stream, uint32_t block_bytes);
+/* host buffers (as zs_deflate_batch_ex) */
+int zs_deflate_batch_bgzf(zs_ctx *ctx, int level, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                          const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                          int32_t *status, uint32_t *out_len, uint32_t *check, uint32_t block_bytes);
+/* the pool (as zs_pool_deflate_batch; sharded by stream) */
+int zs_pool_deflate_batch_bgzf(zs_pool *pool, int level, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                               const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                               int32_t *status, uint32_t *out_len, uint32_t *check, uint32_t block_bytes);
+/* The blocks of the last BGZF compress call on the context, in the layout of zs_last_members: block_first
+ * (n_streams + 1 entries, from 0), then at most `cap` blocks' block_in (the offset of the block's first
+ * input byte) and block_out (the offset of the block's first byte in the stream's output).  Stream i has
+ * its data blocks' entries and the end-of-file block's, (in_len[i], out_len[i] - 28): a .gzi index plus
+ * the end; writing a .gzi file is the caller's job.  Returns the number of entries (0 when the last
+ * compress call on the context was no BGZF call); waits for the call's kernels.  Right after a host
+ * call that ran as several chunks too. */
+uint64_t zs_last_bgzf_blocks(zs_ctx *ctx, uint64_t *block_first, uint32_t *block_in, uint32_t *block_out,
+                             uint64_t cap);
+
 /* Restart points: one stream's segments decoded in parallel.  Behind a Z_FULL_FLUSH marker (00 00 FF FF)
  * the bit stream is byte-aligned and the window empty; inflateSync (inflate.ts:1285-1337; syncsearch
  * :1267-1283) looks for those bytes and resets the stream there, the window with it.  These entries are

@@ -110,6 +110,11 @@ struct zs_ctx {
     size_t at;  // u64 index of the device call's scan in fscan
     uint32_t n, M, hl;
     std::vector<uint32_t> sfirst;
+    // a BGZF device call (zs_last_bgzf_blocks): the segments' input offsets, the streams' lengths, and at
+    // level 0, where no scan runs, the members' size
+    bool bgzf = false;
+    std::vector<uint32_t> soff, in_len;
+    uint32_t stored_member = 0;
   };
   struct Call {
     uint32_t ck_parts = 0;     // the data checksum's parts (zs_last_checksum_parts)
@@ -607,6 +612,9 @@ static int deflate_fail(zs_deflate_err e) {
       "invalid flush positions",
       "level 0 with a flush point is not built",
       "too many flush points (streams + flush points above 65,535 in one call)",
+      "invalid BGZF block size",
+      "null arrays",
+      "too many BGZF blocks (streams + blocks above 65,535 in one call)",
   };
   return fail(ZS_STREAM_ERROR, "%s", kMsg[e]);
 }
@@ -660,13 +668,27 @@ static fast_par_fn fast_par_kernel(int nice_bucket, bool lane_order) {
 struct FlushDev {
   const uint32_t* sfirst;   // device: each stream's first segment
   const uint32_t* sstream;  // ... each segment's stream
+  uint32_t bgzf = 0;        // a BGZF batch's block size: the segments are finished members
 };
+// The layout of a BGZF batch of M segments and n streams (deflate_bgzf.hip); M may be 0: end-of-file blocks alone
+static void bgzf_layout(zs_ctx* c, hipStream_t st, const FlushDev& fl, const uint32_t* d_blk, zs_block* d_bk,
+                        zs_stream* d_st, zs_stream* d_res, const Batch& data, uint32_t M) {
+  const uint32_t tiles = M / ZS_FLUSH_TILE + 1;
+  uint64_t* segx = c->fscan.as<uint64_t>() + c->call.fscan_at;
+  uint64_t* tile = segx + M + 1;
+  zs_k_bgzf_local<<<tiles, ZS_FLUSH_TILE, 0, st>>>(d_blk, d_bk, d_st, fl.sstream, d_res, segx, tile, M);
+  zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tile, tiles);
+  zs_k_bgzf_place<<<std::max(M, data.n) / ZS_FLUSH_TILE + 1, ZS_FLUSH_TILE, 0, st>>>(
+      d_blk, d_bk, d_st, fl.sfirst, fl.sstream, d_res, segx, tile, data.out_cap, data.out, data.out_off, M, data.n);
+}
 static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, const Batch& b, const Batch& data,
                           int32_t* d_status, uint32_t* d_out_len, const zs_checksum_plan* ck, size_t ck_map,
                           const FlushDev* fl = nullptr) {
   const zs_level_cfg& cfg = zs_level_cfgs[p.cfg];
   const zs_meta_layout& ml = p.ml;
-  const int wrap = p.req.wrap, level = p.req.level;
+  const bool bgzf = fl && fl->bgzf;
+  // (a BGZF batch's segments are raw streams to the kernels; the gzip frames are zs_k_bgzf_frame's)
+  const int wrap = bgzf ? 0 : p.req.wrap, level = p.req.level;
   const bool par = p.variant == ZS_VAR_PAR;  // non-default windowBits / memLevel: the *_par instances
   const zs_kpar kp = p.req.q.kpar();
   const uint32_t n = p.n;
@@ -685,7 +707,34 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   const int nthreads_s = 256, nblocks_s = (int)p.g_streams;
   const int nblocks_r = (int)((n_res + 255) / 256);
   MARK("start");
-  if (fl) HIPCHK(hipMemsetAsync(d_res, 0, sizeof(zs_stream) * (size_t)n_res, st));
+  if (fl && !p.stored) HIPCHK(hipMemsetAsync(d_res, 0, sizeof(zs_stream) * (size_t)n_res, st));
+  if (bgzf) {
+    // the streams' crc32 (check[i]: what a reader that concatenates the members computes), and behind them
+    // the members' own -- one wave each: a piece is far below any parts threshold
+    uint32_t* seg_check = check + n_res;
+    ck_launch(c, st, *ck, ck_map, n_res, data.in, data.in_off, data.in_len, check, 2);
+    if (n) zs_k_checksum<<<n, 64, 0, st>>>(b.in, b.in_off, b.in_len, seg_check, 2);
+    MARK("checksum");
+    if (p.stored) {
+      const uint32_t member = fl->bgzf + ZS_BGZF_HEADER + 5 + ZS_BGZF_TRAILER;
+      zs_k_bgzf_stored<<<dim3(member / 4096 + 1, n + n_res), 256, 0, st>>>(
+          b.in, b.in_off, b.in_len, seg_check, fl->sfirst, fl->sstream, data.in_len, data.out, data.out_off,
+          data.out_cap, fl->bgzf, n, d_status, d_out_len);
+      MARK("stored");
+      return ZS_OK;
+    }
+    zs_k_copy_check<<<nblocks_r, nthreads_s, 0, st>>>(check, d_res, (int)n_res);
+    if (n == 0) {  // every stream is empty: end-of-file blocks alone
+      bgzf_layout(c, st, *fl, d_blk, d_bk, d_st, d_res, data, 0);
+      MARK("layout");
+      zs_k_bgzf_frame<<<n_res / 256 + 1, 256, 0, st>>>(d_st, fl->sstream, d_res, b.in_len, seg_check, data.out,
+                                                       data.out_off, 0, n_res);
+      MARK("bgzf_frame");
+      zs_k_finish<<<nblocks_r, nthreads_s, 0, st>>>(d_res, d_status, d_out_len, (int)n_res);
+      MARK("finish");
+      return ZS_OK;
+    }
+  }
   if (p.stored) {
     if (wrap) {
       ck_launch(c, st, *ck, ck_map, n, b.in, b.in_off, b.in_len, check, wrap == 1 ? 1 : 2);
@@ -774,6 +823,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   MARK("trees");
   if (p.dict) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
                                                                  d_start);
+  else if (bgzf) bgzf_layout(c, st, *fl, d_blk, d_bk, d_st, d_res, data, n);
   else if (fl) {
     // per segment, joined by a scan of the segments' bytes (deflate_flush.hip)
     const zs_flush_layout fo(ml.bytes, n_res, n);
@@ -788,6 +838,11 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
   zs_k_emit<<<dim3(p.max_blk, n), 256, 0, st>>>(b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st,
                                                 c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), b.out, b.out_off, wrap);
   MARK("emit");
+  if (bgzf) {
+    zs_k_bgzf_frame<<<(n + n_res) / 256 + 1, 256, 0, st>>>(d_st, fl->sstream, d_res, b.in_len, check + n_res, data.out,
+                                                           data.out_off, n, n_res);
+    MARK("bgzf_frame");
+  }
   if (wrap && p.dict)
     zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, d_start,
                                                      (const uint32_t*)(dm + ml.did), c->dadler.as<uint32_t>());
@@ -869,11 +924,14 @@ static int deflate_finish(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, u
 }
 static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush);
+static int deflate_batch_bgzf(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                              uint32_t* d_out_len, uint32_t* d_check, hipStream_t st);
 // A validated, non-empty device batch (a public call's, or a chunk of a host call): plan, ensure, upload, launch.
 static int deflate_batch(zs_ctx* c, const zs_deflate_req& req_in, const zs_deflate_call& a, const Batch& h,
                          int32_t* d_status, uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const DictIn* dict,
                          const FlushIn* flush) {
   if (zs_deflate_any_flush(req_in, a)) return deflate_batch_flush(c, req_in, h, d_status, d_out_len, d_check, st, *flush);
+  if (req_in.bgzf) return deflate_batch_bgzf(c, req_in, h, d_status, d_out_len, d_check, st);
   zs_deflate_req req = req_in;
   req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
   const uint32_t n = h.n;
@@ -986,6 +1044,74 @@ static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch
   const Batch real = {n, h.in, (const uint64_t*)(dm + fo.in_off), (const uint32_t*)(dm + fo.in_len), h.out,
                       (const uint64_t*)(dm + fo.out_off), (const uint32_t*)(dm + fo.out_cap)};
   const FlushDev fd = {(const uint32_t*)(dm + fo.sfirst), (const uint32_t*)(dm + fo.sstream)};
+  const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, ck, fo.bytes, &fd);
+  if (rl != ZS_OK) return rl;
+  return deflate_finish(c, st, p, n, d_status, d_check);
+}
+
+// A BGZF batch (validated): the plan runs over the SEGMENTS -- the pieces of req.bgzf bytes, each
+// a finished raw stream to the match, parse, trees and emit kernels -- and the BGZF layout frames them per
+// stream (deflate_bgzf.hip).  Level 0 plans no parse: zs_k_bgzf_stored writes the members from the maps alone.
+static int deflate_batch_bgzf(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
+                              uint32_t* d_out_len, uint32_t* d_check, hipStream_t st) {
+  const uint32_t n = h.n;
+  zs_flush_plan& f = c->fp;
+  zs_plan_bgzf(n, h.in_len, req.bgzf, f);
+  const uint32_t M = f.M;
+  zs_deflate_plan& p = c->dp;
+  zs_plan_deflate(req, c->o, c->fast_group, c->lane_order, M, f.slen.data(), nullptr, 0, p);
+  const zs_meta_layout& ml = p.ml;
+  const zs_flush_layout fo(ml.bytes, n, M);
+  HIPCHK(c->check.ensure(4ull * ((size_t)n + M)));  // the streams' crc32, then the members'
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, true, n, h.in_len, &ck, &ck_bytes)) return rc;
+  if (const int rc = deflate_ensure(c, p)) return rc;
+  zs_ctx::Call& k = c->call;
+  zs_ctx::FlushIdx idx = {0, n, M, 0, f.sfirst};
+  idx.bgzf = true;
+  idx.soff = f.soff;
+  idx.in_len.assign(h.in_len, h.in_len + n);
+  if (p.stored) {
+    idx.stored_member = req.bgzf + ZS_BGZF_HEADER + 5 + ZS_BGZF_TRAILER;
+  } else {
+    HIPCHK(c->fstreams.ensure(sizeof(zs_stream) * (size_t)n));
+    // this batch's scan behind those of the call's chunks before it (deflate_host sized fscan for all)
+    k.fscan_at = k.fscan_used;
+    HIPCHK(c->fscan.ensure(8ull * k.fscan_at + fo.scan_bytes));
+    k.fscan_used += fo.scan_bytes / 8;
+    idx.at = k.fscan_at;
+  }
+  k.fidx.push_back(std::move(idx));
+  // the segments as a batch: their bytes where they lie in their streams, every one with its stream's output
+  std::vector<uint64_t> sin(M + 1), sout(M + 1);
+  std::vector<uint32_t> slen(M + 1);
+  for (uint32_t g = 0; g < M; g++) {
+    sin[g] = h.in_off[f.sstream[g]] + f.soff[g];
+    sout[g] = h.out_off[f.sstream[g]];
+    slen[g] = f.slen[g];
+  }
+  const Batch hs = {M, h.in, sin.data(), slen.data(), h.out, sout.data(), nullptr};
+  Batch b;
+  const int r = upload_batch(c, st, ml, fo.bytes + ck_bytes, hs, &b, [&](uint8_t* hm) {
+    ck_fill(ck, hm + fo.bytes);
+    if (!p.stored && M) {
+      memcpy(hm + ml.pos_base, p.pos.data(), 8ull * M);
+      memcpy(hm + ml.blk_base, p.blk.data(), 4ull * M);
+      if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
+    }
+    memcpy(hm + fo.in_off, h.in_off, 8ull * n);
+    memcpy(hm + fo.in_len, h.in_len, 4ull * n);
+    memcpy(hm + fo.out_off, h.out_off, 8ull * n);
+    memcpy(hm + fo.out_cap, h.out_cap, 4ull * n);
+    memcpy(hm + fo.sfirst, f.sfirst.data(), 4ull * (n + 1));
+    memcpy(hm + fo.sstream, f.sstream.data(), 4ull * (M + 1));
+  });
+  if (r != ZS_OK) return r;
+  const uint8_t* dm = c->meta.as<uint8_t>();
+  const Batch real = {n, h.in, (const uint64_t*)(dm + fo.in_off), (const uint32_t*)(dm + fo.in_len), h.out,
+                      (const uint64_t*)(dm + fo.out_off), (const uint32_t*)(dm + fo.out_cap)};
+  const FlushDev fd = {(const uint32_t*)(dm + fo.sfirst), (const uint32_t*)(dm + fo.sstream), req.bgzf};
   const int rl = deflate_launch(c, st, p, b, real, d_status, d_out_len, ck, fo.bytes, &fd);
   if (rl != ZS_OK) return rl;
   return deflate_finish(c, st, p, n, d_status, d_check);
@@ -1252,6 +1378,11 @@ static int deflate_host(zs_ctx* c, const zs_deflate_req& req, const Batch& h, in
     const uint64_t mt = (uint64_t)n + (flush->first[n] - flush->first[0]);
     HIPCHK(c->fscan.ensure(8ull * (mt + mt / ZS_FLUSH_TILE + 16)));
   }
+  if (rq.bgzf) {  // ... and a BGZF batch's, before zs_last_bgzf_blocks reads them
+    uint64_t mt = n;
+    for (uint32_t i = 0; i < n; i++) mt += zs_bgzf_blocks(h.in_len[i], rq.bgzf);
+    HIPCHK(c->fscan.ensure(8ull * (mt + mt / ZS_FLUSH_TILE + 16)));
+  }
   call_begin(c, CALL_DEFLATE);
   uint32_t* res[3] = {(uint32_t*)status, out_len, check};
   return host_batch(c, h, 3, res, 1,
@@ -1313,6 +1444,80 @@ extern "C" int zs_deflate_batch_flush(zs_ctx* c, int level, int wbits, uint32_t 
   if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
   const FlushIn fi = {flush_first, flush_pos};
   return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr, &fi);
+}
+
+// ---- BGZF (SAM specification 4.1): the level's, the block size's, the arrays' and the count's
+// faults are reported before the context is looked at, in that order
+extern "C" uint64_t zs_deflate_bound_bgzf(uint64_t source_len, uint32_t block_bytes) {
+  return zs_bgzf_bound(source_len, block_bytes);
+}
+
+// device: the streams + blocks of the one device call are counted; a host call's chunks count their own
+static int bgzf_req(int level, uint32_t block_bytes, const Batch& h, bool device, zs_deflate_req* req) {
+  if (const zs_deflate_err e = zs_deflate_make_req_bgzf(level, block_bytes, req)) return deflate_fail(e);
+  zs_deflate_call a;
+  a.n = h.n;
+  a.in_len = h.in_len;
+  a.null_arrays = h.n && (!h.in_off || !h.in_len || !h.out_off || !h.out_cap);
+  if (const zs_deflate_err e = zs_deflate_validate_bgzf(*req, a, device)) return deflate_fail(e);
+  return ZS_OK;
+}
+
+extern "C" int zs_deflate_batch_bgzf_device(zs_ctx* c, int level, uint32_t n, const uint8_t* d_in, const uint64_t* in_off,
+                                            const uint32_t* in_len, uint8_t* d_out, const uint64_t* out_off,
+                                            const uint32_t* out_cap, int32_t* d_status, uint32_t* d_out_len,
+                                            uint32_t* d_check, void* hip_stream, uint32_t block_bytes) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  zs_deflate_req req;
+  if (const int r = bgzf_req(level, block_bytes, h, true, &req)) return r;
+  return deflate_device(c, req, h, d_status, d_out_len, d_check, hip_stream, nullptr);
+}
+
+extern "C" int zs_deflate_batch_bgzf(zs_ctx* c, int level, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                     const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                     const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check,
+                                     uint32_t block_bytes) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
+  zs_deflate_req req;
+  if (const int r = bgzf_req(level, block_bytes, h, false, &req)) return r;
+  return deflate_host(c, req, h, status, out_len, check, nullptr);
+}
+
+// The blocks of the last BGZF compress call on the context, in the layout of zs_last_members: block_first
+// (n + 1 entries, from 0), then at most `cap` blocks' (offset of the block's first input byte, offset of
+// its first byte in the stream's output), every stream's end-of-file block included: (in_len, out_len - 28).
+// The output offsets are the layout's scan (zs_k_bgzf_local's, which zs_k_bgzf_place rebases the blocks
+// by); a host entry's chunks follow each other.  A stream that failed has the offsets it would have had.
+extern "C" uint64_t zs_last_bgzf_blocks(zs_ctx* c, uint64_t* block_first, uint32_t* block_in, uint32_t* block_out,
+                                        uint64_t cap) {
+  if (!c || c->call.fidx.empty() || !c->call.fidx[0].bgzf) return 0;
+  std::vector<uint64_t> scan(c->call.fscan_used);
+  if (!scan.empty()) {
+    if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
+    if (hipMemcpy(scan.data(), c->fscan.p, 8ull * scan.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  }
+  uint64_t k = 0, s_all = 0;
+  auto put = [&](uint32_t in_pos, uint64_t out_pos) {
+    if (k < cap) {
+      if (block_in) block_in[k] = in_pos;
+      if (block_out) block_out[k] = (uint32_t)out_pos;
+    }
+    k++;
+  };
+  if (block_first) block_first[0] = 0;
+  for (const zs_ctx::FlushIdx& f : c->call.fidx) {
+    const uint64_t* segx = f.stored_member ? nullptr : scan.data() + f.at;
+    const uint64_t* tile = f.stored_member ? nullptr : segx + f.M + 1;
+    // the bytes of all members before x
+    auto at = [&](uint32_t x) { return segx ? tile[x / ZS_FLUSH_TILE] + segx[x] : 0; };
+    for (uint32_t s = 0; s < f.n; s++, s_all++) {
+      const uint32_t g0 = f.sfirst[s], g1 = f.sfirst[s + 1];
+      for (uint32_t g = g0; g < g1; g++) put(f.soff[g], segx ? at(g) - at(g0) : (uint64_t)(g - g0) * f.stored_member);
+      put(f.in_len[s], segx ? at(g1) - at(g0) : f.in_len[s] + (uint64_t)(g1 - g0) * (ZS_BGZF_HEADER + 5 + ZS_BGZF_TRAILER));
+      if (block_first) block_first[s_all + 1] = k;
+    }
+  }
+  return k;
 }
 
 // ---- compression strategies (deflateInit2_'s strategy: validation deflate.ts:289-290, dispatch :923-931)
@@ -2648,7 +2853,7 @@ extern "C" uint32_t zs_wrapper_header_len(int wbits, const uint8_t* in, uint32_t
 // then the bytes of the segments before it (zs_k_flush_local's scan, which zs_k_flush_place rebases
 // the blocks by).  A host entry's chunks follow each other.
 extern "C" uint64_t zs_last_flush_index(zs_ctx* c, uint32_t* in_pos, uint64_t cap) {
-  if (!c || c->call.fidx.empty() || !c->fscan.p) return 0;
+  if (!c || c->call.fidx.empty() || c->call.fidx[0].bgzf || !c->fscan.p) return 0;
   if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
   std::vector<uint64_t> scan(c->call.fscan_used);
   if (hipMemcpy(scan.data(), c->fscan.p, 8ull * scan.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;

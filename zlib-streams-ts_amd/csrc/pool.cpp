@@ -374,6 +374,28 @@ extern "C" int zs_pool_deflate_batch_dict(zs_pool* p, int level, int wbits, uint
   });
 }
 
+// BGZF: sharded by stream; the faults of the level, the block size and the arrays first, as the
+// context's entries name them
+extern "C" int zs_pool_deflate_batch_bgzf(zs_pool* p, int level, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                          const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                          const uint32_t* out_cap, int32_t* status, uint32_t* out_len, uint32_t* check,
+                                          uint32_t block_bytes) {
+  const char* msg = level < -1 || level > 9                               ? "invalid level"
+                    : block_bytes > ZS_BGZF_BLOCK                         ? "invalid BGZF block size"
+                    : n && (!in_off || !in_len || !out_off || !out_cap)   ? "null arrays"
+                                                                          : nullptr;
+  if (msg) {
+    zs_set_last_error(msg);
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_deflate_batch_bgzf(p->ctx[k], level, s.b - s.a, in, in_off + s.a, in_len + s.a, out, out_off + s.a,
+                                 out_cap + s.a, status + s.a, out_len + s.a, check ? check + s.a : nullptr,
+                                 block_bytes);
+  });
+}
+
 // with Z_FULL_FLUSH points (deflate.ts:942-961): sharded by stream, every shard reads the caller's one
 // position array through its part of the index
 extern "C" int zs_pool_deflate_batch_flush(zs_pool* p, int level, int wbits, uint32_t n, const uint8_t* in,

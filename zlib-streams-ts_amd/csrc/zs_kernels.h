@@ -139,6 +139,19 @@ __global__ void zs_k_flush_tiles(uint64_t* tile, uint32_t T);
 __global__ void zs_k_flush_place(const uint32_t* blk_base, zs_block* blocks, zs_stream* segs, const uint32_t* sfirst,
                                  const uint32_t* sstream, zs_stream* streams, const uint64_t* segx, const uint64_t* tile,
                                  const uint32_t* out_cap, uint8_t* out, const uint64_t* out_off, int wrap, uint32_t M);
+// the layout and the frames of a BGZF batch (deflate_bgzf.hip)
+__global__ void zs_k_bgzf_local(const uint32_t* blk_base, zs_block* blocks, zs_stream* segs, const uint32_t* sstream,
+                                zs_stream* streams, uint64_t* segx, uint64_t* tile, uint32_t M);
+__global__ void zs_k_bgzf_place(const uint32_t* blk_base, zs_block* blocks, zs_stream* segs, const uint32_t* sfirst,
+                                const uint32_t* sstream, zs_stream* streams, const uint64_t* segx, const uint64_t* tile,
+                                const uint32_t* out_cap, uint8_t* out, const uint64_t* out_off, uint32_t M, uint32_t n);
+__global__ void zs_k_bgzf_frame(const zs_stream* segs, const uint32_t* sstream, const zs_stream* streams,
+                                const uint32_t* seg_len, const uint32_t* seg_check, uint8_t* out,
+                                const uint64_t* out_off, uint32_t M, uint32_t n);
+__global__ void zs_k_bgzf_stored(const uint8_t* in, const uint64_t* seg_in_off, const uint32_t* seg_len,
+                                 const uint32_t* seg_check, const uint32_t* sfirst, const uint32_t* sstream,
+                                 const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                 uint32_t B, uint32_t M, int32_t* status, uint32_t* out_len_res);
 __global__ void zs_k_emit(const uint8_t* in, const uint64_t* in_off, const uint64_t* pos_base, const uint32_t* blk_base,
                           const uint32_t* syms, const zs_block* blocks, const zs_stream* streams, const uint32_t* codes,
                           const uint32_t* hdr, uint8_t* out, const uint64_t* out_off, int wrap);

@@ -535,7 +535,15 @@ struct zs_deflate_req {
   bool dict = false;  // the call carries preset dictionaries (a batch with every length 0 is the plain batch)
   // 0, or ZS_FLUSH_FULL: the call carries Z_FULL_FLUSH positions (a batch without any is the plain batch)
   int flush = 0;
+  // 0, or the block size 1..ZS_BGZF_BLOCK_MAX of a BGZF call: every stream is cut into
+  // pieces of that many bytes, each a finished raw-deflate stream in a gzip frame of its own
+  uint32_t bgzf = 0;
 };
+#define ZS_BGZF_BLOCK_MAX 65280u  // htslib's BGZF_BLOCK_SIZE (0xff00): the input of one block at most
+#define ZS_BGZF_HEADER 18u        // the gzip header with the BC subfield ...
+#define ZS_BGZF_TRAILER 8u        // ... and crc32 + ISIZE
+#define ZS_BGZF_EOF 28u           // the end-of-file block
+#define ZS_BGZF_MEMBER_MAX 65536u // BSIZE is 16 bits of (total size - 1)
 #define ZS_FLUSH_FULL 3  // Z_FULL_FLUSH, common/constants.ts
 // streams + flush points of one device call at most: the segments are the y dimension of the
 // trees' and emit's grids
@@ -562,6 +570,9 @@ enum zs_deflate_err {
   ZS_DE_FLUSH_POS,     // "invalid flush positions"
   ZS_DE_FLUSH_LEVEL0,  // "level 0 with a flush point is not built"
   ZS_DE_FLUSH_MANY,    // "too many flush points (streams + flush points above 65,535 in one call)"
+  ZS_DE_BGZF_BLOCK,    // "invalid BGZF block size"
+  ZS_DE_BGZF_ARRAYS,   // "null arrays"
+  ZS_DE_BGZF_MANY,     // "too many BGZF blocks (streams + blocks above 65,535 in one call)"
   ZS_DE_COUNT
 };
 // The request of the plain, _strategy and _dict entries: wbits -15 / 15 / 31.  Only a strategy out of
@@ -597,6 +608,31 @@ static inline zs_deflate_err zs_deflate_make_req_flush(int level, int wbits, int
   r->flush = flush;
   return ZS_DE_OK;
 }
+// ... and of the _bgzf entries: gzip members, block_bytes 0 = ZS_BGZF_BLOCK_MAX.  The level's
+// fault is named before the block size's, both before the context is looked at.
+static inline zs_deflate_err zs_deflate_make_req_bgzf(int level, uint32_t block_bytes, zs_deflate_req* r) {
+  zs_deflate_make_req(level, 31, ZS_STRAT_DEFAULT, false, r);
+  if (r->level < 0 || r->level > 9) return ZS_DE_LEVEL;
+  if (block_bytes > ZS_BGZF_BLOCK_MAX) return ZS_DE_BGZF_BLOCK;
+  r->bgzf = block_bytes ? block_bytes : ZS_BGZF_BLOCK_MAX;
+  return ZS_DE_OK;
+}
+// The most a piece of n bytes becomes as a finished raw-deflate stream (zs_deflate_bound(n, -15), deflate.ts:615-674)
+ZS_PLAN_FN uint64_t zs_bgzf_piece_bound(uint64_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) + 7; }
+// A full block fits BSIZE's 16 bits, so no piece is ever retried with less input (htslib's loop)
+static_assert(ZS_BGZF_BLOCK_MAX + (ZS_BGZF_BLOCK_MAX >> 12) + (ZS_BGZF_BLOCK_MAX >> 14) + (ZS_BGZF_BLOCK_MAX >> 25) + 7 +
+                      ZS_BGZF_HEADER + ZS_BGZF_TRAILER <= ZS_BGZF_MEMBER_MAX,
+              "a BGZF block of ZS_BGZF_BLOCK_MAX input bytes must fit 65,536 bytes");
+// zs_deflate_bound_bgzf: the blocks' bounds and frames, then the end-of-file block.  The stored form of
+// level 0 (piece + 5 + 26) is smaller, so one bound serves all levels.
+ZS_PLAN_FN uint64_t zs_bgzf_bound(uint64_t source_len, uint32_t block_bytes) {
+  const uint64_t B = block_bytes ? block_bytes : ZS_BGZF_BLOCK_MAX;
+  if (B > ZS_BGZF_BLOCK_MAX) return 0;
+  const uint64_t q = source_len / B, r = source_len % B, fr = ZS_BGZF_HEADER + ZS_BGZF_TRAILER;
+  return q * (zs_bgzf_piece_bound(B) + fr) + (r ? zs_bgzf_piece_bound(r) + fr : 0) + ZS_BGZF_EOF;
+}
+// The data blocks of a stream of len bytes
+ZS_PLAN_FN uint64_t zs_bgzf_blocks(uint64_t len, uint32_t B) { return (len + B - 1) / B; }
 // The arrays of a call, as far as validation reads them
 struct zs_deflate_call {
   uint32_t n = 0;
@@ -609,7 +645,18 @@ struct zs_deflate_call {
   // requests with flush set: stream i's flush positions are flush_pos[flush_first[i] .. flush_first[i + 1])
   const uint64_t* flush_first = nullptr;
   const uint32_t* flush_pos = nullptr;
+  bool null_arrays = false;  // a _bgzf entry was given n streams and a null offset, length or capacity array
 };
+// A BGZF call (r.bgzf): its arrays, then streams + data blocks of one device call against the trees' and
+// emit's grid limit (as the flush points')
+static inline zs_deflate_err zs_deflate_validate_bgzf(const zs_deflate_req& r, const zs_deflate_call& a, bool count) {
+  if (!r.bgzf || a.n == 0) return ZS_DE_OK;
+  if (a.null_arrays) return ZS_DE_BGZF_ARRAYS;
+  if (!count) return ZS_DE_OK;
+  uint64_t m = a.n;
+  for (uint32_t i = 0; i < a.n; i++) m += zs_bgzf_blocks(a.in_len[i], r.bgzf);
+  return m > ZS_FLUSH_SEG_MAX ? ZS_DE_BGZF_MANY : ZS_DE_OK;
+}
 static inline bool zs_deflate_any_flush(const zs_deflate_req& r, const zs_deflate_call& a) {
   return r.flush && a.n && a.flush_first && a.flush_first[a.n] > a.flush_first[0];
 }
@@ -640,6 +687,7 @@ static inline bool zs_deflate_any_dict(const zs_deflate_req& r, const zs_deflate
 // after it, whatever its level.  The chunks then pass zs_deflate_validate one by one.
 static inline zs_deflate_err zs_deflate_validate_host(const zs_deflate_req& r, const zs_deflate_call& a) {
   if (r.dict && !a.dict_arrays) return ZS_DE_DICT_ARRAYS;
+  if (r.bgzf) return zs_deflate_validate_bgzf(r, a, false);  // (the chunks count their own blocks)
   if (r.flush) {  // (no entry takes flush positions and dictionaries): the device batches' order
     if (a.n == 0) return ZS_DE_OK;
     if (r.wrap < 0) return ZS_DE_WBITS;
@@ -670,9 +718,12 @@ static inline zs_deflate_err zs_deflate_validate(const zs_deflate_req& r, const 
     }
   }
   if (a.n == 0) return ZS_DE_OK;
+  if (r.bgzf && a.null_arrays) return ZS_DE_BGZF_ARRAYS;
   for (uint32_t i = 0; i < a.n; i++)
     if ((a.out_off[i] & 3) || (a.caller_regions && (a.out_cap[i] & 3))) return ZS_DE_ALIGN;
   if (const zs_deflate_err e = zs_deflate_validate_flush(r, a)) return e;
+  if (const zs_deflate_err e = zs_deflate_validate_bgzf(r, a, true)) return e;
+  if (r.bgzf) return ZS_DE_OK;  // (level 0 is zs_k_bgzf_stored's, whatever the layer above)
   if (r.level == 0) return r.q.is_default() ? ZS_DE_OK : ZS_DE_PARAMS_LEVEL0;
   if (zs_plan_strategy(o, r.level, r.strategy).tally == ZS_TALLY_RLE)  // (zs_k_rle_tally's 32-bit positions run 4,416 past a stream's end)
     for (uint32_t i = 0; i < a.n; i++)
@@ -746,6 +797,27 @@ static inline void zs_plan_flush(uint32_t n, const uint32_t* in_len, const uint6
     f.sstream.push_back(i);  // the piece Z_FINISH closes (empty after a flush at the stream's end)
     f.soff.push_back(at);
     f.slen.push_back(in_len[i] - at);
+  }
+  f.M = (uint32_t)f.sstream.size();
+  f.sfirst[n] = f.M;
+  f.sstream.push_back(n);
+}
+// ---- BGZF: stream i is cut every B bytes into ceil(len / B) segments, each a finished raw
+// stream in a gzip frame of its own; an empty stream has none (its output is the end-of-file block alone).
+// The maps are zs_plan_flush's, and zs_plan_deflate runs over the segments' lengths without the marker's slot.
+static inline void zs_plan_bgzf(uint32_t n, const uint32_t* in_len, uint32_t B, zs_flush_plan& f) {
+  f.n = n;
+  f.sfirst.assign(n + 1, 0);
+  f.sstream.clear();
+  f.soff.clear();
+  f.slen.clear();
+  for (uint32_t i = 0; i < n; i++) {
+    f.sfirst[i] = (uint32_t)f.sstream.size();
+    for (uint64_t at = 0; at < in_len[i]; at += B) {
+      f.sstream.push_back(i);
+      f.soff.push_back((uint32_t)at);
+      f.slen.push_back((uint32_t)std::min<uint64_t>(B, in_len[i] - at));
+    }
   }
   f.M = (uint32_t)f.sstream.size();
   f.sfirst[n] = f.M;

@@ -39,7 +39,15 @@ export interface CompressBatchOptions extends BatchOptions {
   flushAt?: number[] | (number[] | null)[];
   /** flushAt at N, 2N, ... below each input's length. */
   flushEvery?: number;
+  /** BGZF (SAM specification 4.1), format "gzip" only, levels 0..9: every input becomes blocks of 65,280 input
+   * bytes (true) or of this many (1 .. 65,280), each a gzip member with the BC subfield and BSIZE, then the 28-byte
+   * end-of-file block -- what bgzip, samtools, tabix, gzip -d and {members: "bgzf"} read.  The blocks compress in
+   * parallel.  A block size above 65,280 fails with "init failed: -2" (code "-2"); another format, or together
+   * with `dictionary`, a `strategy` other than 0, `windowBits` / `memLevel` other than 15 / 8 or flush points, it
+   * is a TypeError. */
+  bgzf?: boolean | number;
 }
+export const BGZF_BLOCK: 65280;
 export const Z_DEFAULT_STRATEGY: 0;
 export const Z_FILTERED: 1;
 export const Z_HUFFMAN_ONLY: 2;

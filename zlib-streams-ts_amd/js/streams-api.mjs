@@ -143,6 +143,29 @@ function flushOf(options, ins) {
   });
 }
 
+// options.bgzf: true, or the block's bytes 1 .. 65,280: every input becomes a BGZF file (SAM specification 4.1;
+// zs_deflate_batch_bgzf in zs_gpu.h) -- blocks of that many input bytes (true: 65,280), each a gzip member with
+// BSIZE, then the end-of-file block.  Returns block_bytes as the addon takes it (0 = 65,280), or undefined.
+// Format "gzip" only; together with a dictionary, a strategy, windowBits / memLevel other than 15 / 8 or flush
+// points a TypeError (not built); a block size out of range fails with "init failed: -2".
+export const BGZF_BLOCK = 65280;
+function bgzfOf(options, format) {
+  const b = options.bgzf;
+  if (b === undefined || b === null || b === false) return undefined;
+  if (format !== "gzip") throw new TypeError('bgzf needs format "gzip"');
+  const has = (x) => x !== undefined && x !== null;
+  if (has(options.dictionary)) throw new TypeError("bgzf and dictionary cannot be combined");
+  if (typeof options.strategy == "number" && options.strategy !== 0)
+    throw new TypeError("bgzf and strategy cannot be combined");
+  if ((typeof options.windowBits == "number" && options.windowBits !== 15) ||
+      (typeof options.memLevel == "number" && options.memLevel !== 8))
+    throw new TypeError("bgzf and windowBits / memLevel cannot be combined");
+  if (has(options.flushAt) || has(options.flushEvery)) throw new TypeError("bgzf and flush points cannot be combined");
+  if (b === true) return 0;
+  if (!Number.isInteger(b) || b <= 0) throw new TypeError("bgzf is true or the block's bytes");
+  return b;
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
@@ -153,8 +176,9 @@ async function runCompress(inputs, format, options) {
   let res;
   try {
     const ins = checkInputs(inputs);
+    const bgzf = bgzfOf(options, format);
     res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                                    strategyOf(options), memLevel, flushOf(options, ins));
+                                    strategyOf(options), memLevel, flushOf(options, ins), bgzf);
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -316,8 +340,9 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
   const level = typeof options.level == "number" ? options.level : -1;
   const ins = checkInputs(inputs);
   const [wbits, memLevel] = paramsOf(options, format);
+  const bgzf = bgzfOf(options, format);
   return addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                             strategyOf(options), memLevel, flushOf(options, ins));
+                             strategyOf(options), memLevel, flushOf(options, ins), bgzf);
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

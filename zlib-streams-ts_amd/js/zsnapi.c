@@ -216,6 +216,8 @@ typedef struct {
    * flush_first[i + 1]); NULL: none given */
   uint64_t *flush_first;
   uint32_t *flush_pos;
+  int bgzf;            /* compress: a BGZF file per input (zs_pool_deflate_batch_bgzf) ... */
+  uint32_t block_bytes;  /* ... in blocks of this many bytes (0: ZS_BGZF_BLOCK) */
   /* restart points (zs_pool_inflate_batch_restart): input i's points, its start included, are
    * (restart_in[k], restart_out[k]) for k in restart_first[i] .. restart_first[i + 1]; NULL: none given */
   uint64_t *restart_first;
@@ -301,6 +303,9 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_deflate_batch_dict(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                        j->out_off, j->cap, j->status, j->olen, j->check, j->dict, j->dict_off,
                                        j->dict_len);
+  else if (j->bgzf)
+    j->rc = zs_pool_deflate_batch_bgzf(j->pool, j->level, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
+                                       j->cap, j->status, j->olen, j->check, j->block_bytes);
   else if (j->flush_first)
     j->rc = zs_pool_deflate_batch_flush(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                         j->out_off, j->cap, j->status, j->olen, j->check, ZS_FULL_FLUSH, j->flush_first,
@@ -560,7 +565,11 @@ static int copy_restart(napi_env env, job *j, napi_value arr) {
 
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
  *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined,
- *               memLevel: number | undefined, flushAt: (number[] | null)[] | undefined) ->
+ *               memLevel: number | undefined, flushAt: (number[] | null)[] | undefined,
+ *               bgzf: number | undefined) ->
+ * bgzf: the block's bytes of a BGZF file per input (zs_gpu.h: 0 = 65,280; above that code "-2", "invalid BGZF
+ * block size"); wbits must be 31, and together with dictionaries, a strategy, windowBits / memLevel other than
+ * 15 / 8 or flushAt it throws code "-2" (not built), before any device is touched.
  * flushAt: Z_FULL_FLUSH positions, one array per input (zs_gpu.h: increasing, at most the input's length;
  * levels 1..9); together with dictionaries, a strategy or windowBits / memLevel other than 15 / 8 it throws
  * code "-2" (not built), before any device is touched.
@@ -571,12 +580,12 @@ static int copy_restart(napi_env env, job *j, napi_value arr) {
  * (deflate.ts:289-290; no dictionaries with a strategy, zs_gpu.h) before any device is touched ->
  *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
 static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 8;
-  napi_value argv[8];
+  size_t argc = 9;
+  napi_value argv[9];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 3)
     return throw_code(env, ZS_STREAM_ERROR,
-                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel[, flushAt]]]]])");
+                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel[, flushAt[, bgzf]]]]]])");
   const int32_t strategy = argc > 5 ? arg_i32(env, argv[5], 0) : 0;
   if (strategy < 0 || strategy > ZS_FIXED) return throw_code(env, ZS_STREAM_ERROR, "invalid strategy");
   napi_valuetype dt = napi_undefined;
@@ -599,6 +608,16 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   if (flush && (params || strategy || (dt != napi_undefined && dt != napi_null)))
     return throw_code(env, ZS_STREAM_ERROR,
                       "flush points with preset dictionaries, a strategy or windowBits / memLevel are not built");
+  napi_valuetype bt = napi_undefined;
+  if (argc > 8) napi_typeof(env, argv[8], &bt);
+  const int bgzf = bt == napi_number;
+  double block = 0;
+  if (bgzf) napi_get_value_double(env, argv[8], &block);
+  if (bgzf && (wbits != 31 || params || strategy || flush || (dt != napi_undefined && dt != napi_null)))
+    return throw_code(env, ZS_STREAM_ERROR,
+                      "BGZF is gzip without preset dictionaries, a strategy, windowBits / memLevel or flush points");
+  if (bgzf && !(block >= 0 && block <= ZS_BGZF_BLOCK && block == (double)(uint32_t)block))
+    return throw_code(env, ZS_STREAM_ERROR, "invalid BGZF block size");
   view *v = NULL;
   uint32_t n = 0;
   if (get_views(env, argv[0], &v, &n) != 0) return throw_code(env, ZS_STREAM_ERROR, "inputs must be Uint8Array[]");
@@ -614,6 +633,8 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   j->pool = pool;
   j->wbits = wbits;
   j->level = arg_i32(env, argv[2], -1);
+  j->bgzf = bgzf;
+  j->block_bytes = (uint32_t)block;
   j->strategy = strategy;
   j->params = params;
   j->mem_level = mem_level;
@@ -640,7 +661,8 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   uint64_t tout = 0;
   for (uint32_t i = 0; i < n; i++) {
     j->out_off[i] = tout;
-    const uint64_t bound = params ? zs_deflate_bound_params(v[i].n, wbits, mem_level, j->level == -1 ? 6 : j->level)
+    const uint64_t bound = bgzf ? zs_deflate_bound_bgzf(v[i].n, j->block_bytes)
+                           : params ? zs_deflate_bound_params(v[i].n, wbits, mem_level, j->level == -1 ? 6 : j->level)
                            : j->flush_first ? zs_deflate_bound_flush(v[i].n, j->wbits, j->flush_first[i + 1] - j->flush_first[i])
                                   : zs_deflate_bound_dict(v[i].n, j->wbits, j->dict_len ? j->dict_len[i] : 0);
     j->cap[i] = (uint32_t)((bound + 3) & ~3ull);

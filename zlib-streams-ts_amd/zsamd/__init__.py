@@ -137,6 +137,35 @@ def compress_flush(lens, flush_at=None, flush_every=None, zdict=None, strategy=0
     return per
 
 
+BGZF_BLOCK = 65280  # ZS_BGZF_BLOCK in zs_gpu.h: the input of one BGZF block at most
+
+
+def compress_bgzf(bgzf, fmt="gzip", zdict=None, strategy=0, window_bits=None, mem_level=8, flush_at=None,
+                  flush_every=None) -> Optional[int]:
+    """The `bgzf` keyword of the compress entries (zs_deflate_batch_bgzf; SAM specification 4.1): True for
+    blocks of 65,280 input bytes, or the block's bytes.  Returns block_bytes as the C entries take it
+    (0 = 65,280), or None for a call without the keyword.  BGZF is a gzip notion and is not built with a
+    preset dictionary, a strategy, window_bits / mem_level or flush points (ValueError); a block size out
+    of range is left to the engine, which refuses it."""
+    if bgzf is None or bgzf is False:
+        return None
+    if fmt != "gzip":
+        raise ValueError('bgzf needs fmt="gzip"')
+    if zdict is not None:
+        raise ValueError("bgzf with a preset dictionary is not built")
+    if strategy:
+        raise ValueError("bgzf with strategy %d is not built" % strategy)
+    if not _params_default(window_bits, mem_level):
+        raise ValueError("bgzf with window_bits / mem_level is not built")
+    if flush_at is not None or flush_every is not None:
+        raise ValueError("bgzf with flush points is not built")
+    if bgzf is True:
+        return 0
+    if not isinstance(bgzf, int) or bgzf <= 0 or bgzf >= 1 << 32:
+        raise ValueError("bgzf is True or the block's bytes")
+    return bgzf
+
+
 def _flush_arrays(per):
     """(flush_first, flush_pos) ctypes arrays of compress_flush's position lists"""
     first, pos = [0], []
@@ -220,6 +249,15 @@ def lib():
         L.zs_pool_deflate_batch_flush.argtypes = L.zs_deflate_batch_ex.argtypes + _fl
         L.zs_deflate_bound_flush.restype = ctypes.c_uint64
         L.zs_deflate_bound_flush.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
+    if hasattr(L, "zs_deflate_batch_bgzf"):  # no wbits; block_bytes behind the counterpart's arguments
+        _nowb = lambda a: a[:2] + a[3:] + [ctypes.c_uint32]
+        L.zs_deflate_batch_bgzf.argtypes = _nowb(L.zs_deflate_batch_ex.argtypes)
+        L.zs_deflate_batch_bgzf_device.argtypes = _nowb(L.zs_deflate_batch_device_ex.argtypes)
+        L.zs_pool_deflate_batch_bgzf.argtypes = _nowb(L.zs_deflate_batch_ex.argtypes)
+        L.zs_deflate_bound_bgzf.restype = ctypes.c_uint64
+        L.zs_deflate_bound_bgzf.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        L.zs_last_bgzf_blocks.restype = ctypes.c_uint64
+        L.zs_last_bgzf_blocks.argtypes = [_P, _U64P, _U32P, _U32P, ctypes.c_uint64]
     if hasattr(L, "zs_inflate_batch_restart"):  # restart_first, restart_in, restart_out behind the counterpart's arguments
         _rs = [_U64P, _U32P, _U32P]
         L.zs_inflate_batch_restart.argtypes = L.zs_inflate_batch_ex.argtypes + _rs
@@ -324,10 +362,16 @@ def _arr(ctype, values):
     return a
 
 
-def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0, n_flush: int = 0) -> int:
+def deflate_bound(n: int, fmt: str = "deflate-raw", dict_len: int = 0, n_flush: int = 0, bgzf=None) -> int:
     """deflateBound (deflate.ts:615-674) for a fresh stream, memLevel 8; dict_len: the
     length of its preset dictionary (zs_deflate_bound_dict: DICTID, deflate.ts:633);
-    n_flush: its Z_FULL_FLUSH points (zs_deflate_bound_flush: 12 bytes each)."""
+    n_flush: its Z_FULL_FLUSH points (zs_deflate_bound_flush: 12 bytes each);
+    bgzf=True or the block's bytes: its BGZF file (zs_deflate_bound_bgzf; fmt "gzip")."""
+    block = compress_bgzf(bgzf, fmt, b"" if dict_len else None, flush_every=n_flush or None)
+    if block is not None:
+        if block > BGZF_BLOCK:
+            raise ValueError("invalid BGZF block size")
+        return int(lib().zs_deflate_bound_bgzf(n, block))
     if n_flush:
         if dict_len:
             raise ValueError("flush points with a preset dictionary are not built")
@@ -539,7 +583,7 @@ class Engine:
     # ---------------------------------------------------------- host buffers
     def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
                            strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                           flush_every=None) -> List[Tuple[int, bytes]]:
+                           flush_every=None, bgzf=None) -> List[Tuple[int, bytes]]:
         """Returns [(status, bytes)] -- status Z_STREAM_END on success.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
@@ -548,15 +592,24 @@ class Engine:
         window_bits (8..15, None = 15), mem_level (1..9): deflateInit2_'s windowBits and memLevel
         (zs_deflate_batch_params; other than 15 / 8 not with zdict or a strategy, levels 1..9).
         flush_at (positions for every stream, or a list per stream), flush_every=N: Z_FULL_FLUSH
-        points (zs_deflate_batch_flush; levels 1..9, not with any of the above)."""
+        points (zs_deflate_batch_flush; levels 1..9, not with any of the above).
+        bgzf=True or the block's bytes: BGZF blocks and the end-of-file block (zs_deflate_batch_bgzf;
+        fmt "gzip", levels 0..9, not with any of the above)."""
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level, flush_at, flush_every)]
+                                                                     mem_level, flush_at, flush_every, bgzf)]
 
     def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
                                 strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                                flush_every=None) -> List[Tuple[int, bytes, int]]:
+                                flush_every=None, bgzf=None) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
+        block = compress_bgzf(bgzf, fmt, zdict, strategy, window_bits, mem_level, flush_at, flush_every)
+        self._bgzf_n = 0
+        if block is not None:
+            self._flush_counts = None
+            self._bgzf_n = len(inputs)
+            return _deflate_host_bgzf(self._L, self._L.zs_deflate_batch_bgzf, self._ctx, inputs, level, self._check,
+                                      block)
         compress_strategy(strategy, zdict)
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
         per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
@@ -577,9 +630,10 @@ class Engine:
         return _deflate_host(self._L, self._L.zs_deflate_batch_ex, self._ctx, inputs, fmt, level, self._check)
 
     def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
-                       strategy: int = 0, window_bits=None, mem_level=8, flush_at=None, flush_every=None) -> List[bytes]:
+                       strategy: int = 0, window_bits=None, mem_level=8, flush_at=None, flush_every=None,
+                       bgzf=None) -> List[bytes]:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
-                                                      flush_at, flush_every))
+                                                      flush_at, flush_every, bgzf))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
@@ -651,6 +705,23 @@ class Engine:
         size came from their header; 0 after any other decompress call."""
         return int(self._L.zs_last_bgzf_trusted(self._ctx))
 
+    def last_bgzf_blocks(self) -> List[List[tuple]]:
+        """zs_last_bgzf_blocks: the blocks of the last bgzf= compress call on this engine, one list per
+        stream of (in_pos, out_pos) -- the offset of the block's first input byte and of its first byte
+        in the stream's output -- the end-of-file block's (len(input), len(output) - 28) last: a .gzi
+        index plus the end.  [] when the last compress call was no bgzf call.  Synchronises."""
+        n = getattr(self, "_bgzf_n", 0)
+        if not n:
+            return []
+        first = (ctypes.c_uint64 * (n + 1))()
+        total = int(self._L.zs_last_bgzf_blocks(self._ctx, first, None, None, 0))
+        if total == 0:
+            return []
+        bin_, bout = (ctypes.c_uint32 * total)(), (ctypes.c_uint32 * total)()
+        if int(self._L.zs_last_bgzf_blocks(self._ctx, first, bin_, bout, total)) != total or first[n] != total:
+            raise ZsError("zs_last_bgzf_blocks: the count changed between two queries")
+        return [[(int(bin_[k]), int(bout[k])) for k in range(first[i], first[i + 1])] for i in range(n)]
+
     def last_restart_points(self) -> List[List[tuple]]:
         """zs_last_restart_points: the points the last restart="scan" call on this engine found, one
         list per stream of (in_pos, out_pos) WITHOUT the start -- the shape `restart=` takes, so a
@@ -690,13 +761,25 @@ class Engine:
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                         d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
                         dict_off=None, dict_len=None, strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                        flush_every=None):
+                        flush_every=None, bgzf=None):
         """Device pointers (ints) + host layout arrays (ctypes arrays).
+        bgzf=True or the block's bytes: BGZF (zs_deflate_batch_bgzf_device; fmt "gzip", not with the others).
         flush_at / flush_every: Z_FULL_FLUSH points (zs_deflate_batch_flush_device; not with the others).
         d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
         strategy: zs_deflate_batch_strategy_device (not with dictionaries).
         window_bits / mem_level: zs_deflate_batch_params_device (other than 15 / 8 not with either)."""
+        block = compress_bgzf(bgzf, fmt, dict_off, strategy, window_bits, mem_level, flush_at, flush_every)
+        self._bgzf_n = 0
+        if block is not None:
+            self._flush_counts = None
+            r = self._L.zs_deflate_batch_bgzf_device(self._ctx, compress_level(level), n, _P(d_in), in_off, in_len,
+                                                     _P(d_out), out_off, out_cap, _P(d_status), _P(d_out_len),
+                                                     _P(d_check) if d_check else None,
+                                                     _P(hip_stream) if hip_stream else None, block)
+            self._check(r, "zs_deflate_batch_bgzf_device")
+            self._bgzf_n = n
+            return
         compress_strategy(strategy, dict_off)
         code = compress_params(fmt, window_bits, mem_level, dict_off, strategy)
         per = compress_flush([in_len[i] for i in range(n)], flush_at, flush_every, dict_off, strategy, window_bits,
@@ -804,10 +887,20 @@ class Engine:
         self._check(r, "zs_inflate_batch_device")
 
     def compress_host(self, level: int, fmt: str, n: int, h_in: int, in_off, in_len, h_out: int, out_off, out_cap,
-                      status, out_len, strategy: int = 0, window_bits=None, mem_level=8):
+                      status, out_len, strategy: int = 0, window_bits=None, mem_level=8, bgzf=None):
         """zs_deflate_batch on caller-owned host memory (pointers as ints,
         layout/result arrays as ctypes arrays): the end-to-end host->host path
-        (strategy: zs_deflate_batch_strategy; window_bits / mem_level: zs_deflate_batch_params)."""
+        (strategy: zs_deflate_batch_strategy; window_bits / mem_level: zs_deflate_batch_params;
+        bgzf: zs_deflate_batch_bgzf, fmt "gzip")."""
+        block = compress_bgzf(bgzf, fmt, None, strategy, window_bits, mem_level)
+        self._bgzf_n = 0
+        if block is not None:
+            self._flush_counts = None
+            r = self._L.zs_deflate_batch_bgzf(self._ctx, compress_level(level), n, ctypes.cast(h_in, ctypes.c_char_p),
+                                              in_off, in_len, _P(h_out), out_off, out_cap, status, out_len, None, block)
+            self._check(r, "zs_deflate_batch_bgzf")
+            self._bgzf_n = n
+            return
         compress_strategy(strategy)
         code = compress_params(fmt, window_bits, mem_level, None, strategy)
         if not _params_default(window_bits, mem_level):
@@ -904,6 +997,27 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=N
     mid = (wbits,) if params is None else (wbits, params[1])
     r = fn(handle, *lead, *mid, n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
            out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk, *zdict)
+    check(r, "deflate batch")
+    raw = out.raw
+    return [(status[i], raw[ooffs[i]: ooffs[i] + olen[i]], chk[i]) for i in range(n)]
+
+
+def _deflate_host_bgzf(L, fn, handle, inputs, level, check, block):
+    """_deflate_host for a _bgzf entry (fn), which takes no wbits and block_bytes behind `check`."""
+    n = len(inputs)
+    if n == 0:
+        return []
+    blob, offs, lens = _layout(inputs)
+    # (a block size the engine will refuse has no bound: the call is made all the same, for its error)
+    caps = [(int(L.zs_deflate_bound_bgzf(len(b), min(block, 0xffffffff))) + 3) & ~3 for b in inputs]
+    ooffs, oo = [], 0
+    for c in caps:
+        ooffs.append(oo)
+        oo += c
+    out = ctypes.create_string_buffer(max(1, oo))
+    status, olen, chk = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
+    r = fn(handle, compress_level(level), n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens), out,
+           _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), status, olen, chk, block)
     check(r, "deflate batch")
     raw = out.raw
     return [(status[i], raw[ooffs[i]: ooffs[i] + olen[i]], chk[i]) for i in range(n)]
@@ -1036,7 +1150,11 @@ class Pool:
         Engine._check(self, r, what)
 
     def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                                mem_level=8, flush_at=None, flush_every=None):
+                                mem_level=8, flush_at=None, flush_every=None, bgzf=None):
+        block = compress_bgzf(bgzf, fmt, zdict, strategy, window_bits, mem_level, flush_at, flush_every)
+        if block is not None:
+            return _deflate_host_bgzf(self._L, self._L.zs_pool_deflate_batch_bgzf, self._pool, inputs, level,
+                                      self._check, block)
         compress_strategy(strategy, zdict)
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
         per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
@@ -1055,14 +1173,14 @@ class Pool:
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
     def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                           mem_level=8, flush_at=None, flush_every=None):
+                           mem_level=8, flush_at=None, flush_every=None, bgzf=None):
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level, flush_at, flush_every)]
+                                                                     mem_level, flush_at, flush_every, bgzf)]
 
     def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                       mem_level=8, flush_at=None, flush_every=None):
+                       mem_level=8, flush_at=None, flush_every=None, bgzf=None):
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
-                                                      flush_at, flush_every))
+                                                      flush_at, flush_every, bgzf))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
         L = self._L
