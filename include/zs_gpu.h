@@ -678,7 +678,8 @@ uint64_t zs_last_restart_points(zs_ctx *ctx, uint64_t *restart_first, uint32_t *
  *  - These entries recompute every length from the data.  The header-only fast path for BGZF (following BSIZE,
  *    trusting ISIZE for the positions) is the _bgzf entries' (below).
  *  - Not built: restart points inside members; _auto capacities; the chunked host pipeline; zlib or raw "members";
- *    decoding a range of members (a seek); zs_last_members on the pool. */
+ *    decoding a range of members (a seek) of a plain multi-member file -- BGZF blocks between two virtual
+ *    offsets are the _bgzf_range entries'; zs_last_members on the pool. */
 int zs_inflate_batch_members_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
                                     const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
                                     const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
@@ -746,8 +747,10 @@ uint64_t zs_last_members(zs_ctx *ctx, uint64_t *member_first, uint32_t *member_i
  *    tail round, whatever its data holds.  The HOST entries run as one chunk (zs_last_host_chunks = 1).
  *  - Timing phases: "members_scan", "bgzf_size" (the sizing launch; a tail round stays "members_size") and
  *    "members_stitch", around the decoders' own.
- *  - Not built: a range of members (a seek by virtual offset); a BGZF writer; _auto entries (Python and JS size
- *    the output with zs_bgzf_out_len); the chunked host pipeline (one chunk, as _members). */
+ *  - A range of blocks (a seek by virtual offset) is the _bgzf_range entries' (below); a BGZF writer is
+ *    zs_deflate_batch_bgzf*.
+ *  - Not built: _auto entries (Python and JS size the output with zs_bgzf_out_len); the chunked host pipeline
+ *    (one chunk, as _members). */
 int zs_inflate_batch_bgzf_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
                                  const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
                                  const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
@@ -763,6 +766,79 @@ int zs_pool_inflate_batch_bgzf(zs_pool *pool, int wbits, uint32_t n_streams, con
                                uint32_t *out_len, uint32_t *consumed, uint32_t *check);
 uint64_t zs_last_bgzf_trusted(zs_ctx *ctx);
 int zs_bgzf_out_len(const uint8_t *in, uint32_t in_len, uint64_t *total);
+
+/* BGZF ranges by virtual offset: random access, what BGZF exists for (the SAM specification, section 4.1.1).  A
+ * virtual offset is coffset << 16 | uoffset: coffset the start of a block in the compressed file, uoffset a
+ * position in that block's data.  Every .bai, .tbi and .csi index consists of pairs of them; a region query is
+ * "the bytes between these two virtual offsets".  These entries take the _bgzf entries' arguments plus two HOST
+ * arrays of n_streams virtual offsets behind in_len.
+ *  - Stream i is a BGZF file, or any piece of one that starts at a block; coffset counts from in_off[i].  SEVERAL
+ *    STREAMS MAY NAME THE SAME INPUT BYTES: the input is only read, so thousands of region queries over one file
+ *    are one call.  The host entries stage only each range's slice of its stream.
+ *  - With cb, ub = voff_begin[i] >> 16, & 0xffff and ce, ue likewise: the chain starts at cb and follows trusted
+ *    headers (the _bgzf entries' rule, unchanged) while the start is < ce; it must land on ce exactly.  The
+ *    decoded members are those with a start in [cb, ce), plus the member at ce when ue > 0, whose header must
+ *    then be trusted.  The output is out(m_0)[ub:] | out(m_1) | ... | out(m_e)[:ue]; with cb == ce it is
+ *    out(m_0)[ub:ue].  ub == ISIZE is legal and contributes nothing.  With ue == 0 the block at ce is neither
+ *    required nor decoded, so ce == in_len[i] is legal; voff_begin == voff_end with ue == 0 decodes nothing and
+ *    succeeds with out_len 0, consumed = cb, check 0.
+ *  - Success: ZS_STREAM_END; out_len the delivered length; consumed the offset (from the stream's start) behind
+ *    the last decoded member, or ce when none follows; check the crc32 of the delivered bytes.  Whole blocks are
+ *    decoded, so every decoded block's own CRC32 and ISIZE are still verified.
+ *  - Refusals of the whole call (ZS_STREAM_ERROR): the _bgzf entries' in their order; then, still before the
+ *    context is looked at, a null voff_begin or voff_end ("null virtual offset arrays"), voff_begin[i] >
+ *    voff_end[i] ("a range's begin lies behind its end"), ce > in_len[i] ("a range's end lies past the stream's
+ *    input").  The candidate and segment caps are those of the _members entries, over the ranges' slices.
+ *  - Failures found from the headers, before anything of that stream decodes: an untrusted header at a chain
+ *    start (so cb in the middle of a block), a chain that steps over ce, ub or ue above that block's ISIZE.  The
+ *    stream reports ZS_DATA_ERROR, ZS_PHASE_PROCESS, "virtual offsets do not follow a chain of BGZF blocks",
+ *    out_len 0, consumed = the offending start, check 0; its region is untouched.
+ *    The message has index 23: zs_inflate_message(22), the index behind the restart entries' message, stays the
+ *    empty string, which existing callers may test for.
+ *  - Capacity is known from the headers: the members before the first whose clipped piece does not fit are
+ *    decoded and delivered, and the stream reports what the _bgzf entries report for a total that passes
+ *    out_cap; out_len the delivered length, consumed that member's start, check 0.
+ *  - Decoder failures and lying headers follow the _bgzf entries' contract for member k, its mapping of the
+ *    capacity outcome to "incorrect length check" included; out_len the delivered bytes of the complete members
+ *    before k, clipped; consumed = start_k; check 0.
+ *  - One failed stream does not touch its neighbours; no store leaves [out_off, out_off + out_cap) rounded up to
+ *    4, and none touches a byte of the region behind the delivered length rounded up to 4.
+ *  - For a truthful stream that is BGZF throughout (zs_bgzf_out_len answers 1) the range (0, consumed_full << 16),
+ *    consumed_full being what the _bgzf entry reports, equals that entry's result in every field.  A stream with
+ *    another kind of member on the chain (a plain gzip member, a name in the header, BSIZE 0) fails at that member,
+ *    by the chain rule above; the _bgzf entries read such files.
+ *  - zs_bgzf_range_out_len: host arithmetic over the same rule, no context: 1 and the delivered length, or 0 (and
+ *    *total = 0) where the headers fail the stream or the range is refused.
+ *  - zs_bgzf_voffset: an uncompressed position's virtual offset from one stream's index, `count` entries in
+ *    increasing order, the end entry included where present: block_in the blocks' offsets in the COMPRESSED
+ *    file, block_out their offsets in the uncompressed data -- zs_last_members' member_in and member_out; of
+ *    zs_last_bgzf_blocks, whose input is the uncompressed side, block_out and block_in in this order.  It takes
+ *    the last block with block_out <= upos.  0 when upos lies behind the last entry (or in front of the first)
+ *    or the difference does not fit 16 bits.
+ *  - The DEVICE entry synchronises hip_stream as the _bgzf entry does, and once more in front of that where a
+ *    range ends inside a block (ue > 0): the header of the block at ce is read first, so that the bytes behind
+ *    that block are not searched.  The HOST entries run as one chunk.
+ *  - Timing phases: the _bgzf entries', "bgzf_range_end" (the kernel that reads the end blocks' headers),
+ *    "bgzf_range_wait" (the host's wait for it, up to the scan) and "bgzf_range_place".  zs_last_bgzf_trusted counts the planned blocks;
+ *    zs_last_members does not answer after these entries.
+ *  - Not built: de-duplicating blocks shared by overlapping ranges of one call; parsing .bai / .tbi / .csi /
+ *    .gzi files; ranges over non-BGZF multi-member gzip or over restart points; _auto entries. */
+int zs_inflate_batch_bgzf_range_device(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                       const uint64_t *in_off, const uint32_t *in_len, const uint64_t *voff_begin,
+                                       const uint64_t *voff_end, uint8_t *d_out, const uint64_t *out_off,
+                                       const uint32_t *out_cap, int32_t *d_status, int32_t *d_phase, int32_t *d_msg,
+                                       uint32_t *d_out_len, uint32_t *d_consumed, uint32_t *d_check, void *hip_stream);
+int zs_inflate_batch_bgzf_range(zs_ctx *ctx, int wbits, uint32_t n_streams, const uint8_t *in, const uint64_t *in_off,
+                                const uint32_t *in_len, const uint64_t *voff_begin, const uint64_t *voff_end,
+                                uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, int32_t *status,
+                                int32_t *phase, int32_t *msg, uint32_t *out_len, uint32_t *consumed, uint32_t *check);
+int zs_pool_inflate_batch_bgzf_range(zs_pool *pool, int wbits, uint32_t n_streams, const uint8_t *in,
+                                     const uint64_t *in_off, const uint32_t *in_len, const uint64_t *voff_begin,
+                                     const uint64_t *voff_end, uint8_t *out, const uint64_t *out_off,
+                                     const uint32_t *out_cap, int32_t *status, int32_t *phase, int32_t *msg,
+                                     uint32_t *out_len, uint32_t *consumed, uint32_t *check);
+int zs_bgzf_range_out_len(const uint8_t *in, uint32_t in_len, uint64_t voff_begin, uint64_t voff_end, uint64_t *total);
+int zs_bgzf_voffset(const uint32_t *block_in, const uint32_t *block_out, uint64_t count, uint64_t upos, uint64_t *voff);
 
 /* The z_stream message for a d_msg index (inflate.ts:397-1031, inffast.ts:108,197,210). */
 const char *zs_inflate_message(int32_t msg_index);

@@ -146,6 +146,7 @@ struct zs_ctx {
   Buf mbmeta, mbtile, mbcand, mbrec, mbtail, mbseg, mbres, mbstage, mblen, mbtrust;
   std::vector<uint8_t> mbh, mbck;
   zs_members_plan mp;
+  zs_bgzf_range_plan brp;  // a _bgzf_range call's plan
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
@@ -1810,6 +1811,8 @@ static const char* kInflateMsgs[ZS_MSG_COUNT] = {
     "incorrect length check",
     "output capacity exceeded",
     "restart points do not decode the stream",
+    "",
+    "virtual offsets do not follow a chain of BGZF blocks",
 };
 
 extern "C" const char* zs_inflate_message(int32_t i) { return (i >= 0 && i < ZS_MSG_COUNT) ? kInflateMsgs[i] : ""; }
@@ -2436,7 +2439,20 @@ static int members_refused(zs_ctx* c, int wbits, const Batch& h, bool device_ent
 // bgzf: the _bgzf entries' mode.  It differs in three places: the sizing launch is zs_k_bgzf_size,
 // which trusts the headers it can; the plan's members get their flags (zs_plan_bgzf_trusted); the stitch
 // reports a flagged member's capacity outcome as its header's lie.
-static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st, bool bgzf = false) {
+// The search of members_batch and of bgzf_range_batch: the scan's two passes and the sizing launch over the
+// streams of h, st waited for, then the candidates, the lanes' records and (bgzf) their trusted bytes on the host
+struct MembersFound {
+  std::vector<uint32_t> cand;
+  std::vector<zs_sync_rec> rec;
+  std::vector<uint8_t> rtrusted;  // per record
+  std::vector<uint64_t> cfirst;
+  const uint64_t* d_off = nullptr;  // the streams' offsets and lengths on the device (c->mbmeta)
+  const uint32_t* d_len = nullptr;
+};
+// first_mark: the name of the mark in front of the scan ("start": the call's first; a caller that has run
+// something on st before names what that mark ends)
+static int members_search(zs_ctx* c, const Batch& h, hipStream_t st, bool bgzf, MembersFound& f,
+                          const char* first_mark = "start") {
   const uint32_t n = h.n;
   std::vector<uint32_t> sh16(n), stile;
   uint64_t tin = 0;
@@ -2462,7 +2478,7 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   const uint32_t* d_tile = (const uint32_t*)(dm + m_tile);
   uint64_t* tcount = c->mbtile.as<uint64_t>();
   const uint32_t grid = std::max(1u, std::min(T, 32u * c->o.ncu));
-  MARK("start");
+  MARK(first_mark);
   zs_k_members_scan<false><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, nullptr, 0);
   zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tcount, T + 1);
   HIPCHK(hipGetLastError());
@@ -2495,17 +2511,33 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
     HIPCHK(c->mbcand.ensure(4ull * tpre[T]));
   }
   const uint64_t C = tpre[T];
-  std::vector<uint32_t> cand(C);
-  std::vector<zs_sync_rec> rec(n + C);
-  if (C) HIPCHK(hipMemcpy(cand.data(), c->mbcand.p, 4ull * C, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rec.data(), c->mbrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
-  std::vector<uint8_t> rtrusted, trusted;  // per record, per planned member
+  f.cand.resize(C);
+  f.rec.resize(n + C);
+  if (C) HIPCHK(hipMemcpy(f.cand.data(), c->mbcand.p, 4ull * C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(f.rec.data(), c->mbrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
   if (bgzf) {
-    rtrusted.resize(n + C);
-    HIPCHK(hipMemcpy(rtrusted.data(), c->mbtrust.p, n + C, hipMemcpyDeviceToHost));
+    f.rtrusted.resize(n + C);
+    HIPCHK(hipMemcpy(f.rtrusted.data(), c->mbtrust.p, n + C, hipMemcpyDeviceToHost));
   }
-  std::vector<uint64_t> cfirst(n + 1);
-  for (uint32_t i = 0; i <= n; i++) cfirst[i] = tpre[stile[i]];
+  f.cfirst.resize(n + 1);
+  for (uint32_t i = 0; i <= n; i++) f.cfirst[i] = tpre[stile[i]];
+  f.d_off = d_off;
+  f.d_len = d_len;
+  return ZS_OK;
+}
+
+static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st, bool bgzf = false) {
+  const uint32_t n = h.n;
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  MembersFound found;
+  if (const int rs = members_search(c, h, st, bgzf, found)) return rs;
+  std::vector<uint32_t>& cand = found.cand;
+  std::vector<zs_sync_rec>& rec = found.rec;
+  const std::vector<uint8_t>& rtrusted = found.rtrusted;
+  const std::vector<uint64_t>& cfirst = found.cfirst;
+  const uint64_t* d_off = found.d_off;
+  const uint32_t* d_len = found.d_len;
+  std::vector<uint8_t> trusted;  // per planned member
   zs_members_plan& p = c->mp;
   for (;;) {
     zs_plan_members(n, h.in_len, h.out_cap, cfirst.data(), cand.data(), rec.data(), p);
@@ -2600,6 +2632,148 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
   }
   MARK("members_stitch");
   HIPCHK(hipGetLastError());
+  return ZS_OK;
+}
+
+// ---- BGZF ranges by virtual offset.  The refusals: the _bgzf entries' in their order, then the
+// virtual offsets' (zs_bgzf_range_validate), then the null context.
+static int bgzf_range_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry, const uint64_t* vb,
+                              const uint64_t* ve) {
+  zs_inflate_call a;
+  a.n = h.n;
+  a.out_off = device_entry ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = device_entry;
+  if (const zs_members_err e = zs_members_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
+  if (const zs_bgzf_range_err e = zs_bgzf_range_validate(h.n, h.in_len, vb, ve))
+    return fail(ZS_STREAM_ERROR, "%s", zs_bgzf_range_err_text(e));
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
+}
+
+// The device decode of a validated, non-empty batch of ranges (regions as inflate_batch's; several streams may
+// name the same input bytes, which are only read).  The scan and the sizing run over the ranges' SLICES as over
+// streams of their own (members_search, st waited for once); the plan follows the trusted headers
+// (zs_plan_bgzf_range); the planned blocks decode whole, as ONE gzip batch on the caller's input, into staging;
+// the stitch writes the streams' fields and the place kernel moves the delivered bytes behind it.
+// A slice with ue > 0 reaches 65,536 bytes behind ce (zs_bgzf_range_slice), which holds two or three blocks behind
+// the one that is needed and cuts the last of them short: a start no header can size, so its lane would decode it
+// (5.7 ms for one range).  So the slices are first cut at the end of the block at ce, read from its header
+// (zs_k_bgzf_range_end; st is waited for once more) -- where that header cannot be trusted the slice stays as it is
+// and the plan fails the stream.  trimmed: the caller has done so (the host entries, from the caller's bytes).
+static int bgzf_range_batch(zs_ctx* c, const Batch& h, const uint64_t* vb, const uint64_t* ve, const InflateOut& out,
+                            hipStream_t st, bool trimmed = false) {
+  const uint32_t n = h.n;
+  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  std::vector<uint64_t> sl_off(n);
+  std::vector<uint32_t> sl_len(n), rce(n);
+  bool any_end = false, cut = false;
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t off;
+    zs_bgzf_range_slice(h.in_len[i], vb[i], ve[i], off, sl_len[i]);
+    sl_off[i] = h.in_off[i] + off;
+    rce[i] = (uint32_t)((ve[i] >> 16) - (vb[i] >> 16));
+    any_end = any_end || rce[i] < sl_len[i];
+  }
+  if (any_end && !trimmed) {
+    const size_t e_len = up256(8ull * n), e_rce = e_len + up256(4ull * n), e_end = e_rce + up256(4ull * n),
+                 e_bytes = e_end + up256(4ull * n);
+    HIPCHK(c->mbtail.ensure(e_bytes));
+    c->mbh.assign(e_end, 0);
+    memcpy(c->mbh.data(), sl_off.data(), 8ull * n);
+    memcpy(c->mbh.data() + e_len, sl_len.data(), 4ull * n);
+    memcpy(c->mbh.data() + e_rce, rce.data(), 4ull * n);
+    uint8_t* de = c->mbtail.as<uint8_t>();
+    HIPCHK(hipMemcpyAsync(de, c->mbh.data(), e_end, hipMemcpyHostToDevice, st));
+    MARK("start");
+    zs_k_bgzf_range_end<<<n / 256 + 1, 256, 0, st>>>(h.in, (const uint64_t*)de, (const uint32_t*)(de + e_len),
+                                                     (const uint32_t*)(de + e_rce), n, (uint32_t*)(de + e_end));
+    HIPCHK(hipGetLastError());
+    MARK("bgzf_range_end");
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<uint32_t> end(n);
+    HIPCHK(hipMemcpy(end.data(), de + e_end, 4ull * n, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++)
+      if (end[i] > rce[i] && end[i] <= sl_len[i]) sl_len[i] = end[i];
+    cut = true;
+  }
+  MembersFound found;
+  const Batch hsl = {n, h.in, sl_off.data(), sl_len.data(), h.out, h.out_off, h.out_cap};
+  // (behind the cut the search's first mark ends the host's wait for the ends: "bgzf_range_wait")
+  if (const int rs = members_search(c, hsl, st, true, found, cut ? "bgzf_range_wait" : "start")) return rs;
+  zs_bgzf_range_plan& p = c->brp;
+  zs_plan_bgzf_range(n, h.out_cap, vb, ve, found.cfirst.data(), found.cand.data(), found.rec.data(),
+                     found.rtrusted.data(), p);
+  const uint32_t M = p.M;
+  for (uint32_t g = 0; g < M; g++) c->call.bgzf_trusted += p.trusted[g];
+  // where each member lies and where its delivered bytes belong
+  std::vector<uint64_t> src(M), dst(M);
+  for (uint32_t g = 0; g < M; g++) {
+    const uint32_t i = p.rstream[g];
+    src[g] = h.in_off[i] + p.soff[g];
+    dst[g] = h.out_off[i] + p.opos[g];
+  }
+  const size_t g_first = 0, g_soff = up256(4ull * (n + 1)), g_opos = g_soff + up256(4ull * M), g_ocap = g_opos + up256(4ull * M),
+               g_skip = g_ocap + up256(4ull * M), g_take = g_skip + up256(4ull * M), g_rstream = g_take + up256(4ull * M),
+               g_stoff = g_rstream + up256(4ull * M), g_dst = g_stoff + up256(8ull * M), g_ptile = g_dst + up256(8ull * M),
+               g_out = g_ptile + up256(4ull * (M + 1)), g_verdict = g_out + up256(8ull * n),
+               g_vcons = g_verdict + up256(4ull * n), g_trust = g_vcons + up256(4ull * n), g_end = g_trust + up256(M);
+  HIPCHK(c->mbseg.ensure(g_end));
+  HIPCHK(c->mbres.ensure(20ull * M + 64));
+  HIPCHK(c->mbstage.ensure(p.stage_bytes));
+  HIPCHK(c->mblen.ensure(4ull * n + 16));
+  c->mbh.assign(g_end, 0);
+  memcpy(c->mbh.data() + g_first, p.rfirst.data(), 4ull * (n + 1));
+  memcpy(c->mbh.data() + g_soff, p.soff.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_opos, p.opos.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_ocap, p.ocap.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_skip, p.skip.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_take, p.take.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_rstream, p.rstream.data(), 4ull * M);
+  memcpy(c->mbh.data() + g_stoff, p.stoff.data(), 8ull * M);
+  memcpy(c->mbh.data() + g_dst, dst.data(), 8ull * M);
+  memcpy(c->mbh.data() + g_ptile, p.ptile.data(), 4ull * (M + 1));
+  memcpy(c->mbh.data() + g_out, h.out_off, 8ull * n);
+  memcpy(c->mbh.data() + g_verdict, p.verdict.data(), 4ull * n);
+  memcpy(c->mbh.data() + g_vcons, p.vcons.data(), 4ull * n);
+  memcpy(c->mbh.data() + g_trust, p.trusted.data(), M);
+  HIPCHK(hipMemcpyAsync(c->mbseg.p, c->mbh.data(), g_end, hipMemcpyHostToDevice, st));
+  const uint8_t* dg = c->mbseg.as<uint8_t>();
+  auto u32 = [&](size_t at) { return (const uint32_t*)(dg + at); };
+  auto u64 = [&](size_t at) { return (const uint64_t*)(dg + at); };
+  int32_t* const sr = c->mbres.as<int32_t>();
+  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
+  if (M) {  // (the blocks as M gzip members with zlib semantics, as in members_batch)
+    zs_route_opts o2 = c->o;
+    o2.inflate_ref_wrap = false;
+    const Batch hs = {M, h.in, src.data(), p.slen.data(), c->mbstage.as<uint8_t>(), p.stoff.data(), p.ocap.data()};
+    if (const int ri = inflate_batch(c, 31, hs, seg, st, nullptr, &o2)) return ri;
+  }
+  uint32_t* cklen = c->mblen.as<uint32_t>();
+  zs_k_bgzf_range_stitch<<<n, 64, 0, st>>>(u32(g_first), u32(g_soff), u32(g_opos), u32(g_take), u32(g_verdict), u32(g_vcons),
+                                           seg.status, seg.phase, seg.msg, seg.consumed, n, out.status, out.phase, out.msg,
+                                           out.out_len, out.consumed, cklen, dg + g_trust);
+  HIPCHK(hipGetLastError());
+  MARK("members_stitch");
+  if (p.ptile[M])
+    zs_k_bgzf_range_place<<<std::min(p.ptile[M], 32u * c->o.ncu), 256, 0, st>>>(
+        c->mbstage.as<uint8_t>(), u64(g_stoff), u32(g_ocap), seg.out_len, u32(g_skip), u32(g_take), u32(g_opos),
+        u32(g_rstream), out.out_len, u64(g_dst), u32(g_ptile), M, h.out);
+  HIPCHK(hipGetLastError());
+  MARK("bgzf_range_place");
+  if (out.check) {  // the check value over the delivered bytes, as in members_batch
+    const zs_checksum_plan* ck;
+    size_t ck_bytes;
+    if (const int rc = ck_prepare(c, true, n, h.out_cap, &ck, &ck_bytes)) return rc;
+    if (ck_bytes) {
+      HIPCHK(c->meta.ensure(ck_bytes));
+      c->mbck.assign(ck_bytes, 0);
+      ck_fill(ck, c->mbck.data());
+      HIPCHK(hipMemcpyAsync(c->meta.p, c->mbck.data(), ck_bytes, hipMemcpyHostToDevice, st));
+    }
+    ck_launch(c, st, *ck, 0, n, h.out, u64(g_out), cklen, out.check, 2);
+    HIPCHK(hipGetLastError());
+    MARK("checksum");
+  }
   return ZS_OK;
 }
 
@@ -2826,6 +3000,81 @@ extern "C" int zs_bgzf_out_len(const uint8_t* in, uint32_t in_len, uint64_t* tot
   uint64_t t = 0;
   const int r = in ? zs_bgzf_chain(in, in_len, t) : 0;
   if (total) *total = r ? t : 0;
+  return r;
+}
+
+// BGZF ranges by virtual offset; device buffers.  hip_stream is waited for as in the _bgzf entry.
+extern "C" int zs_inflate_batch_bgzf_range_device(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
+                                                  const uint64_t* in_off, const uint32_t* in_len,
+                                                  const uint64_t* voff_begin, const uint64_t* voff_end, uint8_t* d_out,
+                                                  const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                                  int32_t* d_phase, int32_t* d_msg, uint32_t* d_out_len,
+                                                  uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
+  const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
+  if (const int r = bgzf_range_refused(c, wbits, h, true, voff_begin, voff_end)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  call_begin(c, CALL_INFLATE);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return bgzf_range_batch(c, h, voff_begin, voff_end, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st);
+}
+
+// ... host buffers: only each range's slice of its stream is staged, as a stream of its own whose range begins
+// in its first block; the slices' results are the streams' but for consumed, which counts from the slice
+extern "C" int zs_inflate_batch_bgzf_range(zs_ctx* c, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
+                                           const uint32_t* in_len, const uint64_t* voff_begin, const uint64_t* voff_end,
+                                           uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                           int32_t* status, int32_t* phase, int32_t* msg, uint32_t* out_len,
+                                           uint32_t* consumed, uint32_t* check) {
+  const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
+  if (const int r = bgzf_range_refused(c, wbits, h, false, voff_begin, voff_end)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (n == 0) return ZS_OK;
+  std::vector<uint64_t> sl_off(n), svb(n), sve(n);
+  std::vector<uint32_t> sl_len(n), cb(n);
+  for (uint32_t i = 0; i < n; i++) {
+    zs_bgzf_range_slice(in_len[i], voff_begin[i], voff_end[i], cb[i], sl_len[i]);
+    sl_off[i] = in_off[i] + cb[i];
+    svb[i] = voff_begin[i] & 0xffffu;
+    sve[i] = voff_end[i] - ((uint64_t)cb[i] << 16);
+    // (the slice cut at the end of the block at ce, as bgzf_range_batch cuts it: read here, where the bytes are)
+    const uint32_t rce = (uint32_t)(sve[i] >> 16);
+    uint32_t e = 0, isize = 0;
+    if (rce < sl_len[i] && zs_bgzf_header(in + sl_off[i], sl_len[i], rce, e, isize)) sl_len[i] = e;
+  }
+  const Batch hsl = {n, in, sl_off.data(), sl_len.data(), out, out_off, out_cap};
+  const std::vector<uint32_t> creq(out_cap, out_cap + n);
+  call_begin(c, CALL_INFLATE);
+  uint32_t* res[6] = {(uint32_t*)status, (uint32_t*)phase, (uint32_t*)msg, out_len, consumed, check};
+  const int rc = host_batch(c, hsl, 6, res, 3,
+                            [&](uint32_t a, uint32_t b, const uint64_t* doff, const uint64_t* ooff, uint32_t** dr) {
+                              const Batch hb = {b - a, c->d_in.as<uint8_t>(), doff, sl_len.data() + a,
+                                                c->d_out.as<uint8_t>(), ooff, creq.data() + a};
+                              const InflateOut d = {(int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
+                                                    check ? dr[5] : nullptr};
+                              return bgzf_range_batch(c, hb, svb.data() + a, sve.data() + a, d, c->stream, true);
+                            },
+                            true);
+  if (rc == ZS_OK && consumed)
+    for (uint32_t i = 0; i < n; i++) consumed[i] += cb[i];
+  return rc;
+}
+
+// Host arithmetic, no context: the rule of zs_plan_bgzf_range over the headers (zs_bgzf.h)
+extern "C" int zs_bgzf_range_out_len(const uint8_t* in, uint32_t in_len, uint64_t voff_begin, uint64_t voff_end,
+                                     uint64_t* total) {
+  uint64_t t = 0;
+  const int r = (in || !in_len) ? zs_bgzf_range_chain(in, in_len, voff_begin, voff_end, t) : 0;
+  if (total) *total = r ? t : 0;
+  return r;
+}
+
+// ... an uncompressed position's virtual offset from one stream's index of blocks
+extern "C" int zs_bgzf_voffset(const uint32_t* block_in, const uint32_t* block_out, uint64_t count, uint64_t upos,
+                               uint64_t* voff) {
+  uint64_t v = 0;
+  const int r = zs_bgzf_voffset_of(block_in, block_out, count, upos, v);
+  if (voff) *voff = v;
   return r;
 }
 

@@ -481,6 +481,32 @@ extern "C" int zs_pool_inflate_batch_bgzf(zs_pool* p, int wbits, uint32_t n, con
   });
 }
 
+// BGZF ranges by virtual offset: sharded by stream as the _bgzf entry, the refusals first
+extern "C" int zs_pool_inflate_batch_bgzf_range(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,
+                                                const uint64_t* in_off, const uint32_t* in_len,
+                                                const uint64_t* voff_begin, const uint64_t* voff_end, uint8_t* out,
+                                                const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                                int32_t* phase, int32_t* msg, uint32_t* out_len, uint32_t* consumed,
+                                                uint32_t* check) {
+  zs_inflate_call a;
+  a.n = n;
+  a.out_cap = out_cap;
+  if (const zs_members_err e = zs_members_validate(wbits, a)) {
+    zs_set_last_error(zs_members_err_text(e));
+    return ZS_STREAM_ERROR;
+  }
+  if (const zs_bgzf_range_err e = zs_bgzf_range_validate(n, in_len, voff_begin, voff_end)) {
+    zs_set_last_error(zs_bgzf_range_err_text(e));
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_inflate_batch_bgzf_range(p->ctx[k], wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, voff_begin + s.a,
+                                       voff_end + s.a, out, out_off + s.a, out_cap + s.a, status + s.a, phase + s.a,
+                                       msg + s.a, out_len + s.a, consumed + s.a, check ? check + s.a : nullptr);
+  });
+}
+
 // from restart points (inflate.ts:1267-1337): sharded by stream, every shard reads the caller's point arrays
 // through its part of the index
 extern "C" int zs_pool_inflate_batch_restart(zs_pool* p, int wbits, uint32_t n, const uint8_t* in,

@@ -96,3 +96,55 @@ ZS_BGZF_FN int zs_bgzf_chain(const uint8_t* s, uint32_t n, uint64_t& total) {
     if ((uint64_t)p + 4u > n || !zs_member_magic(s + p)) return 1;
   }
 }
+
+// ---- a range by virtual offset (the SAM specification, section 4.1.1: a virtual offset is
+// coffset << 16 | uoffset, coffset a block's start in the file and uoffset a position in the block's data).
+// Headers are trusted inside the range's slice (zs_bgzf_range_slice, zs_plan.h): a block that passes its end
+// is not.
+// Host arithmetic over one range (zs_bgzf_range_out_len), by the rule zs_plan_bgzf_range applies to the
+// device's records: the chain of trusted headers from cb lands on ce exactly, the block at ce is trusted when
+// ue > 0, ub and ue lie inside their blocks.  1 and the delivered length; 0 where the plan fails the stream.
+ZS_BGZF_FN int zs_bgzf_range_chain(const uint8_t* s, uint32_t n, uint64_t vb, uint64_t ve, uint64_t& total) {
+  total = 0;
+  const uint64_t cb = vb >> 16, ce = ve >> 16;
+  const uint32_t ub = (uint32_t)(vb & 0xffffu), ue = (uint32_t)(ve & 0xffffu);
+  if (vb > ve || ce > n) return 0;
+  uint32_t off, len;
+  zs_bgzf_range_slice(n, vb, ve, off, len);
+  const uint8_t* z = s + off;
+  const uint32_t rce = (uint32_t)(ce - cb);
+  uint32_t p = 0, end, isize;
+  uint64_t sum = 0;
+  while (p < rce) {
+    if (!zs_bgzf_header(z, len, p, end, isize) || end > rce) return 0;
+    if (p == 0 && ub > isize) return 0;
+    sum += isize;
+    p = end;
+  }
+  if (ue) {
+    if (!zs_bgzf_header(z, len, p, end, isize) || ue > isize) return 0;
+    sum += ue;
+  }
+  total = sum - ub;  // (cb == ce: ub <= ue, both in the one block)
+  return 1;
+}
+
+// The virtual offset of uncompressed position upos from one stream's index of (block_in, block_out), `count`
+// entries in increasing order, the end entry included where present (zs_last_bgzf_blocks, zs_last_members):
+// the last block with block_out <= upos.  0 when upos lies behind the last entry or in front of the first, or
+// the difference does not fit 16 bits.
+static inline int zs_bgzf_voffset_of(const uint32_t* block_in, const uint32_t* block_out, uint64_t count, uint64_t upos,
+                                     uint64_t& voff) {
+  voff = 0;
+  if (!count || !block_in || !block_out || upos > block_out[count - 1] || upos < block_out[0]) return 0;
+  uint64_t lo = 0, hi = count;  // block_out[lo] <= upos < block_out[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (block_out[mid] <= upos) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t d = upos - block_out[lo];
+  if (d > 0xffffu) return 0;
+  voff = ((uint64_t)block_in[lo] << 16) | d;
+  return 1;
+}

@@ -34,6 +34,8 @@ enum zs_msg_id {
   ZS_MSG_LENGTH_CHECK,
   ZS_MSG_CAPACITY,
   ZS_MSG_RESTART,  // the restart entries: "restart points do not decode the stream"
+  ZS_MSG_UNUSED_22,   // no message: the index behind the restart entries' stays empty (callers test it for "")
+  ZS_MSG_BGZF_RANGE,  // the _bgzf_range entries: "virtual offsets do not follow a chain of BGZF blocks"
   ZS_MSG_COUNT
 };
 

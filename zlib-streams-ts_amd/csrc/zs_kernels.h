@@ -190,3 +190,17 @@ __global__ void zs_k_members_stitch(const uint32_t* rfirst, const uint32_t* soff
 __global__ void zs_k_bgzf_size(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* stile,
                                uint32_t n, const uint64_t* tpre, const uint32_t* cand, uint64_t cap, uint32_t pass,
                                zs_sync_rec* rec, uint8_t* trusted);
+// BGZF ranges by virtual offset (inflate_bgzf_range.hip): the streams' fields from the plan's
+// verdicts and the members' results, then the members' clipped bytes from staging to their places
+__global__ void zs_k_bgzf_range_end(const uint8_t* in, const uint64_t* sl_off, const uint32_t* sl_len, const uint32_t* rce,
+                                    uint32_t n, uint32_t* end);
+__global__ void zs_k_bgzf_range_stitch(const uint32_t* rfirst, const uint32_t* soff, const uint32_t* opos,
+                                       const uint32_t* take, const uint32_t* verdict, const uint32_t* vcons,
+                                       const int32_t* seg_status, const int32_t* seg_phase, const int32_t* seg_msg,
+                                       const uint32_t* seg_used, uint32_t n, int32_t* status, int32_t* phase,
+                                       int32_t* msg, uint32_t* out_len, uint32_t* consumed, uint32_t* cklen,
+                                       const uint8_t* trusted);
+__global__ void zs_k_bgzf_range_place(const uint8_t* stage, const uint64_t* stoff, const uint32_t* ocap,
+                                      const uint32_t* seg_len, const uint32_t* skip, const uint32_t* take,
+                                      const uint32_t* opos, const uint32_t* rstream, const uint32_t* out_len,
+                                      const uint64_t* dst, const uint32_t* ptile, uint32_t M, uint8_t* out);

@@ -1607,4 +1607,155 @@ static inline uint32_t zs_plan_bgzf_trusted(const zs_members_plan& p, const uint
   return count;
 }
 
+// ---- BGZF ranges by virtual offset (the SAM specification, section 4.1.1: a virtual offset is
+// coffset << 16 | uoffset).  Stream i with the range (vb, ve): cb, ub = vb >> 16, vb & 0xffff and ce, ue
+// likewise.  The blocks with a start in [cb, ce), and the block at ce when ue > 0, decode whole into staging;
+// the place kernel drops ub bytes of the first and keeps ue of the last.
+enum zs_bgzf_range_err {
+  ZS_BR_OK = 0,
+  ZS_BR_ARRAYS,    // "null virtual offset arrays"
+  ZS_BR_ORDER,     // "a range's begin lies behind its end"
+  ZS_BR_PAST_END,  // "a range's end lies past the stream's input"
+  ZS_BR_COUNT
+};
+static inline const char* zs_bgzf_range_err_text(zs_bgzf_range_err e) {
+  static const char* const kMsg[ZS_BR_COUNT] = {
+      "",
+      "null virtual offset arrays",
+      "a range's begin lies behind its end",
+      "a range's end lies past the stream's input",
+  };
+  return kMsg[e];
+}
+// The fault that wins, behind zs_members_validate's: the arrays, then stream by stream the order and the end.
+static inline zs_bgzf_range_err zs_bgzf_range_validate(uint32_t n, const uint32_t* in_len, const uint64_t* vb,
+                                                       const uint64_t* ve) {
+  if (n == 0) return ZS_BR_OK;
+  if (!vb || !ve) return ZS_BR_ARRAYS;
+  for (uint32_t i = 0; i < n; i++) {
+    if (vb[i] > ve[i]) return ZS_BR_ORDER;
+    if ((ve[i] >> 16) > in_len[i]) return ZS_BR_PAST_END;
+  }
+  return ZS_BR_OK;
+}
+// The SLICE of a stream of n bytes that the range (vb, ve) reads (vb <= ve, ve >> 16 <= n): from cb to ce when
+// ue is 0 -- the block at ce is neither needed nor looked at -- else to the end of the largest block that can
+// start at ce, cut at the stream's end.
+ZS_PLAN_FN void zs_bgzf_range_slice(uint32_t n, uint64_t vb, uint64_t ve, uint32_t& off, uint32_t& len) {
+  const uint64_t cb = vb >> 16, ce = ve >> 16;
+  const uint64_t end = (ve & 0xffffu) ? (ce + ZS_BGZF_MEMBER_MAX < n ? ce + ZS_BGZF_MEMBER_MAX : n) : ce;
+  off = (uint32_t)cb;
+  len = (uint32_t)(end - cb);
+}
+
+#define ZS_BGZF_RANGE_MEMBERS 0u  // the stream has members: the stitch reads their results
+#define ZS_BGZF_RANGE_EMPTY 1u    // nothing to decode: Z_STREAM_END, out_len 0, consumed = cb
+#define ZS_BGZF_RANGE_CHAIN 2u    // the headers fail the stream: Z_DATA_ERROR, ZS_MSG_BGZF_RANGE, consumed = the start
+struct zs_bgzf_range_plan {
+  uint32_t n = 0, M = 0;          // streams, members
+  std::vector<uint32_t> rfirst;   // each stream's first member (rfirst[n] = M)
+  std::vector<uint32_t> rstream;  // each member's stream
+  std::vector<uint32_t> soff, slen;  // the member's bytes in its STREAM's input (cb + its offset in the slice)
+  std::vector<uint32_t> ocap;     // its room in staging: its ISIZE; 0 for the member the stream's out_cap cuts
+  std::vector<uint32_t> skip, take;  // bytes dropped in front, bytes delivered
+  std::vector<uint32_t> opos;     // where its delivered bytes begin in its stream's output
+  std::vector<uint8_t> trusted;   // its room is its header's ISIZE (zs_k_members_stitch's flag)
+  std::vector<uint64_t> stoff;    // its 4-aligned region in the staging buffer
+  std::vector<uint32_t> ptile;    // M + 1: prefix sums of the place's tiles
+  std::vector<uint32_t> verdict, vcons;  // per stream: ZS_BGZF_RANGE_*, and consumed for the two decided here
+  uint64_t stage_bytes = 0;
+};
+// Stream i's slice (zs_bgzf_range_slice) was scanned and sized as a stream of its own: cand[cfirst[i] ..
+// cfirst[i + 1]) are its candidates, offsets IN THE SLICE in increasing order; rec[i] / rtrusted[i] belong to
+// the slice's offset 0 and rec[n + k] / rtrusted[n + k] to candidate k (zs_k_bgzf_size's).  A start counts only
+// when its header was trusted.  The chain from 0 follows the records' ends while the start lies in front of
+// ce - cb and must land there exactly; with ue > 0 the block at ce is needed too.  Members behind the needed end
+// are dropped whatever their records say.  A stream the headers fail -- an untrusted start on the chain, a step
+// over ce, ub or ue above its block's ISIZE -- contributes no member.  The first member whose delivered bytes
+// pass out_cap gets no room and ends the stream's list: the decoder reports the capacity outcome for it.
+static inline void zs_plan_bgzf_range(uint32_t n, const uint32_t* out_cap, const uint64_t* vb, const uint64_t* ve,
+                                      const uint64_t* cfirst, const uint32_t* cand, const zs_sync_rec* rec,
+                                      const uint8_t* rtrusted, zs_bgzf_range_plan& p) {
+  p.n = n;
+  p.rfirst.assign(n + 1, 0);
+  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.ocap, &p.skip, &p.take, &p.opos}) v->clear();
+  p.trusted.clear();
+  p.stoff.clear();
+  p.ptile.assign(1, 0);
+  p.verdict.assign(n, ZS_BGZF_RANGE_MEMBERS);
+  p.vcons.assign(n, 0);
+  uint64_t st = 0;
+  struct blk { uint32_t at, end, isize; };
+  std::vector<blk> chain;
+  for (uint32_t i = 0; i < n; i++) {
+    p.rfirst[i] = (uint32_t)p.rstream.size();
+    const uint32_t cb = (uint32_t)(vb[i] >> 16), rce = (uint32_t)((ve[i] >> 16) - (vb[i] >> 16));
+    const uint32_t ub = (uint32_t)(vb[i] & 0xffffu), ue = (uint32_t)(ve[i] & 0xffffu);
+    const uint32_t* c0 = cand + cfirst[i];
+    const uint32_t* c1 = cand + cfirst[i + 1];
+    // the trusted record of the start at `pos` of the slice, or null
+    auto record = [&](uint32_t pos) -> const zs_sync_rec* {
+      size_t x = i;
+      if (pos) {
+        const uint32_t* f = std::lower_bound(c0, c1, pos);
+        if (f == c1 || *f != pos) return nullptr;
+        x = n + (size_t)(f - cand);
+      }
+      return rtrusted[x] && rec[x].how == ZS_SYNC_FINAL && rec[x].end > pos ? &rec[x] : nullptr;
+    };
+    auto fail = [&](uint32_t pos) {
+      p.verdict[i] = ZS_BGZF_RANGE_CHAIN;
+      p.vcons[i] = cb + pos;
+    };
+    chain.clear();
+    uint32_t pos = 0;
+    bool ok = true;
+    for (;;) {
+      const bool last = pos == rce;  // (a step over ce fails below: pos never passes it)
+      if (last && !ue) break;
+      const zs_sync_rec* r = record(pos);
+      if (!r || (!last && r->end > rce) || (pos == 0 && ub > r->len) || (last && ue > r->len)) {
+        fail(pos);
+        ok = false;
+        break;
+      }
+      chain.push_back({pos, r->end, r->len});
+      if (last) break;
+      pos = r->end;
+    }
+    if (!ok) continue;
+    if (chain.empty()) {  // (cb == ce and ue == 0, so ub == 0 too)
+      p.verdict[i] = ZS_BGZF_RANGE_EMPTY;
+      p.vcons[i] = cb;
+      continue;
+    }
+    uint64_t out = 0;
+    for (size_t k = 0; k < chain.size(); k++) {
+      const blk& b = chain[k];
+      const uint32_t skip = k == 0 ? ub : 0u;
+      const uint32_t upto = (b.at == rce && ue) ? ue : b.isize;  // (the block at ce is on the chain only when ue > 0)
+      const uint32_t take = upto - skip;
+      const bool fits = out + take <= out_cap[i];
+      const uint32_t room = fits ? b.isize : 0u;
+      p.rstream.push_back(i);
+      p.soff.push_back(cb + b.at);
+      p.slen.push_back(b.end - b.at);
+      p.ocap.push_back(room);
+      p.skip.push_back(skip);
+      p.take.push_back(take);
+      p.opos.push_back((uint32_t)out);
+      p.trusted.push_back(fits ? 1 : 0);
+      p.stoff.push_back(st);
+      st += ((uint64_t)room + 3) & ~3ull;
+      // (the place's words: the destination's leading bytes of its first word count too)
+      p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)(fits ? take : 0u) + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
+      if (!fits) break;
+      out += take;
+    }
+  }
+  p.M = (uint32_t)p.rstream.size();
+  p.rfirst[n] = p.M;
+  p.stage_bytes = st + 16;
+}
+
 #endif

@@ -85,10 +85,21 @@ export interface DecompressBatchOptions extends BatchOptions {
    * its input with zmsg "incorrect length check".  Without `outCapacity` each input's capacity is its
    * `bgzfOutLength`; an input that is not BGZF throughout is then a TypeError that names it. */
   members?: boolean | "bgzf";
+  /** With `members: "bgzf"`: one `[vb, ve]` pair of BigInt virtual offsets (coffset << 16n | uoffset, as .bai / .tbi /
+   * .csi indexes hold them) per input; the result is the input's bytes between the two (zs_inflate_batch_bgzf_range
+   * in zs_gpu.h).  For many ranges over one file pass the same Uint8Array once per range: it is copied once.
+   * Without `outCapacity` each range is sized from the headers (`bgzfRangeOutLength`).  Without `members: "bgzf"`
+   * it is a TypeError. */
+  ranges?: [bigint, bigint][];
 }
 /** The bytes a BGZF file produces, read from its headers (the sum of ISIZE over the blocks followed from offset 0),
  * or null when a member on the way is no BGZF block whose header can be trusted.  Host arithmetic, no GPU. */
 export function bgzfOutLength(input: Uint8Array): number | null;
+/** The bytes the range between two virtual offsets delivers, read from the headers; null where the offsets do not
+ * follow a chain of BGZF blocks. */
+export function bgzfRangeOutLength(input: Uint8Array, vb: bigint, ve: bigint): number | null;
+/** coffset << 16n | uoffset */
+export function virtualOffset(coffset: number | bigint, uoffset?: number | bigint): bigint;
 /** The length of the wrapper's header in front of the deflate data: 0 for "deflate-raw", 2 for "deflate", for
  * "gzip" 10 plus FEXTRA / FNAME / FCOMMENT / FHCRC, or 0 when that header is malformed or does not fit. */
 export function wrapperHeaderLength(input: Uint8Array, format?: string): number;

@@ -258,12 +258,34 @@ function restartOf(options, ins, format) {
   });
 }
 
+// options.ranges with members: "bgzf": [[vb, ve], ...], one pair of BigInt virtual offsets (coffset << 16n |
+// uoffset) per input: the input's bytes between the two (zs_inflate_batch_bgzf_range in zs_gpu.h).  Many ranges
+// over one file: pass the same Uint8Array once per range; it is copied once.  Without members: "bgzf" a TypeError.
+function rangesOf(options, ins) {
+  const r = options.ranges;
+  if (r === undefined || r === null) return undefined;
+  if (options.members !== "bgzf") throw new TypeError('ranges need members: "bgzf"');
+  if (!Array.isArray(r) || r.length !== ins.length) throw new TypeError("ranges must be an array with one [vb, ve] pair per input");
+  return r.map((p) => {
+    if (!Array.isArray(p) || p.length !== 2 || typeof p[0] !== "bigint" || typeof p[1] !== "bigint" || p[0] < 0n ||
+        p[1] < 0n || p[0] >= 1n << 64n || p[1] >= 1n << 64n)
+      throw new TypeError("ranges: [vb, ve] pairs of BigInt virtual offsets");
+    return [p[0], p[1]];
+  });
+}
+
 // The capacities of a decompress call: the caller's; for members: "bgzf" without them each input's bgzfOutLength
 // (zs_bgzf_out_len: the sum of ISIZE over its blocks' headers) rounded up to 4 -- a TypeError naming the input that
-// is not BGZF throughout.
-function capacityOf(options, ins) {
+// is not BGZF throughout; with ranges each range's bgzfRangeOutLength.
+function capacityOf(options, ins, ranges) {
   const c = options.outCapacity;
   if (options.members !== "bgzf" || (c !== undefined && c !== null)) return c;
+  if (ranges)
+    return ins.map((x, i) => {
+      const n = addon.bgzfRangeOutLength(x, ranges[i][0], ranges[i][1]);
+      if (n < 0) throw new TypeError("input " + i + ": the virtual offsets do not follow a chain of BGZF blocks: give outCapacity");
+      return (n + 3) - ((n + 3) % 4);
+    });
   return ins.map((x, i) => {
     const n = addon.bgzfOutLength(x);
     if (n < 0) throw new TypeError("input " + i + " is not BGZF throughout: give outCapacity");
@@ -277,6 +299,16 @@ export function bgzfOutLength(input) {
   return n < 0 ? null : n;
 }
 
+/** The bytes the range between two BigInt virtual offsets delivers, read from the headers, or null where the
+ * offsets do not follow a chain of BGZF blocks. */
+export function bgzfRangeOutLength(input, vb, ve) {
+  const n = addon.bgzfRangeOutLength(input, vb, ve);
+  return n < 0 ? null : n;
+}
+
+/** A virtual offset from a block's start in the compressed file and a position in the block's data. */
+export const virtualOffset = (coffset, uoffset = 0) => (BigInt(coffset) << 16n) | BigInt(uoffset);
+
 async function runDecompress(inputs, format, options) {
   options = options || {};
   const wbits = decompressWbits(format);
@@ -286,8 +318,9 @@ async function runDecompress(inputs, format, options) {
   let res;
   try {
     const restart = restartOf(options, ins, format);
-    res = await addon.decompressBatch(ins, wbits, capacityOf(options, ins), devicesOf(options),
-                                      dictionariesOf(options, ins.length), restart);
+    const ranges = rangesOf(options, ins);
+    res = await addon.decompressBatch(ins, wbits, capacityOf(options, ins, ranges), devicesOf(options),
+                                      dictionariesOf(options, ins.length), restart, ranges);
   } catch (e) {
     // points the entry refuses (zs_gpu.h): ZS_STREAM_ERROR, reported as the stream layer reports it
     if (options.restartPoints && e.code === String(Z_STREAM_ERROR))
@@ -349,8 +382,9 @@ export async function decompressBatchDetailed(inputs, format = "deflate", option
   options = options || {};
   const ins = checkInputs(inputs);
   const restart = restartOf(options, ins, format);
-  return addon.decompressBatch(ins, decompressWbits(format), capacityOf(options, ins), devicesOf(options),
-                               dictionariesOf(options, ins.length), restart);
+  const ranges = rangesOf(options, ins);
+  return addon.decompressBatch(ins, decompressWbits(format), capacityOf(options, ins, ranges), devicesOf(options),
+                               dictionariesOf(options, ins.length), restart, ranges);
 }
 export const engineVersion = () => addon.version();
 export const selfTest = (device = 0) => addon.selfTest(device);

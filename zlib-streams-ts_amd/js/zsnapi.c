@@ -225,6 +225,8 @@ typedef struct {
   int restart_scan;    /* restart "scan": the points are found from the bytes (zs_pool_inflate_batch_sync) */
   int members;         /* restart "members": every member of multi-member gzip inputs (zs_pool_inflate_batch_members);
                           2 = restart "bgzf": BGZF blocks sized from their headers (zs_pool_inflate_batch_bgzf) */
+  /* restart "bgzf" with ranges (zs_pool_inflate_batch_bgzf_range): input i's virtual offsets; NULL: none given */
+  uint64_t *voff_begin, *voff_end;
   uint8_t *out;
   int out_given;       /* out now belongs to the results' external ArrayBuffer */
   int rc;
@@ -238,6 +240,7 @@ static void job_free(job *j) {
   free(j->dict); free(j->dict_off); free(j->dict_len);
   free(j->flush_first); free(j->flush_pos);
   free(j->restart_first); free(j->restart_in); free(j->restart_out);
+  free(j->voff_begin); free(j->voff_end);
   if (!j->out_given) {
     if (j->unbounded) zs_free(j->out);
     else free(j->out);
@@ -280,6 +283,10 @@ static void job_execute(napi_env env, void *data) {
     j->rc = zs_pool_inflate_batch_dict(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->phase, j->msg, j->olen, j->cons, j->check, j->dict,
                                        j->dict_off, j->dict_len);
+  else if (j->inflate && j->members == 2 && j->voff_begin)
+    j->rc = zs_pool_inflate_batch_bgzf_range(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->voff_begin,
+                                             j->voff_end, j->out, j->out_off, j->cap, j->status, j->phase, j->msg, j->olen,
+                                             j->cons, j->check);
   else if (j->inflate && j->members == 2)
     j->rc = zs_pool_inflate_batch_bgzf(j->pool, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off, j->cap,
                                        j->status, j->phase, j->msg, j->olen, j->cons, j->check);
@@ -404,6 +411,52 @@ static int copy_inputs(job *j, const view *v) {
   if (!j->base) return -1;
   for (uint32_t i = 0; i < j->n; i++)
     if (v[i].n) memcpy(j->base + j->in_off[i], v[i].p, v[i].n);
+  return 0;
+}
+
+/* copy_inputs for a call with ranges: an input that is the same bytes as the one before it (the same view: many
+ * ranges over one file) is copied once */
+static int view_same(const view *v, uint32_t i) { return i && v[i].p == v[i - 1].p && v[i].n == v[i - 1].n; }
+static int copy_inputs_shared(job *j, const view *v) {
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < j->n; i++) {
+    const int same = view_same(v, i);
+    j->in_off[i] = same ? j->in_off[i - 1] : tot;
+    j->in_len[i] = (uint32_t)v[i].n;
+    if (!same) tot += v[i].n;
+  }
+  j->base = (uint8_t *)malloc(tot ? tot : 1);
+  if (!j->base) return -1;
+  for (uint32_t i = 0; i < j->n; i++)  /* (the same test, not the offsets: an empty input shares its offset with the next) */
+    if (v[i].n && !view_same(v, i)) memcpy(j->base + j->in_off[i], v[i].p, v[i].n);
+  return 0;
+}
+
+/* ranges: [vb, ve][] of BigInt virtual offsets, one pair per input; 0 ok, -1 out of memory, -2 malformed */
+static int copy_ranges(napi_env env, job *j, napi_value arr) {
+  bool is_arr = false;
+  uint32_t len = 0;
+  napi_is_array(env, arr, &is_arr);
+  if (!is_arr || napi_get_array_length(env, arr, &len) != napi_ok || len != j->n) return -2;
+  j->voff_begin = (uint64_t *)calloc(j->n + 1, 8);
+  j->voff_end = (uint64_t *)calloc(j->n + 1, 8);
+  if (!j->voff_begin || !j->voff_end) return -1;
+  for (uint32_t i = 0; i < j->n; i++) {
+    napi_value pair, e;
+    bool is_pair = false;
+    uint32_t two = 0;
+    if (napi_get_element(env, arr, i, &pair) != napi_ok) return -2;
+    napi_is_array(env, pair, &is_pair);
+    if (!is_pair || napi_get_array_length(env, pair, &two) != napi_ok || two != 2) return -2;
+    for (uint32_t k = 0; k < 2; k++) {
+      bool lossless = false;
+      uint64_t x = 0;
+      if (napi_get_element(env, pair, k, &e) != napi_ok || napi_get_value_bigint_uint64(env, e, &x, &lossless) != napi_ok ||
+          !lossless)
+        return -2;
+      (k ? j->voff_end : j->voff_begin)[i] = x;
+    }
+  }
   return 0;
 }
 
@@ -689,10 +742,12 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
  * string "members": every member of multi-member gzip inputs is decoded (zs_pool_inflate_batch_members), or the
  * string "bgzf": the same with BGZF blocks sized from their headers (zs_pool_inflate_batch_bgzf); each
  * needs outCapacity, and together with dictionaries it throws code "-2" (not built), before any device is
- * touched. */
+ * touched.
+ * ranges (a seventh argument, with restart "bgzf" only): [vb, ve][] of BigInt virtual offsets, one pair per input
+ * (zs_pool_inflate_batch_bgzf_range); consecutive inputs that are the same view are copied once. */
 static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 2)
     return throw_code(env, ZS_STREAM_ERROR,
@@ -740,7 +795,10 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
     tout += j->cap[i];
   }
   j->out = j->unbounded ? NULL : (uint8_t *)malloc(tout ? tout : 1);  /* unbounded: the library allocates it */
-  if ((!j->unbounded && !j->out) || copy_inputs(j, v) != 0) {
+  napi_valuetype gt = napi_undefined;
+  if (argc > 6) napi_typeof(env, argv[6], &gt);
+  const int ranged = gt != napi_undefined && gt != napi_null;
+  if ((!j->unbounded && !j->out) || (ranged ? copy_inputs_shared(j, v) : copy_inputs(j, v)) != 0) {
     free(v);
     job_free(j);
     return throw_code(env, ZS_MEM_ERROR, "out of host memory");
@@ -782,6 +840,15 @@ static napi_value DecompressBatch(napi_env env, napi_callback_info info) {
                       : throw_code(env, ZS_STREAM_ERROR, "restart must be number[][]: in_pos, out_pos pairs, one list per input");
     }
   }
+  if (ranged) {
+    const int rc = j->members == 2 ? copy_ranges(env, j, argv[6]) : -3;
+    if (rc != 0) {
+      job_free(j);
+      return rc == -1   ? throw_code(env, ZS_MEM_ERROR, "out of host memory")
+             : rc == -3 ? throw_code(env, ZS_STREAM_ERROR, "ranges need restart \"bgzf\"")
+                        : throw_code(env, ZS_STREAM_ERROR, "ranges must be [vb, ve][] of BigInt, one pair per input");
+    }
+  }
   return queue_job(env, j, "zs.decompressBatch");
 }
 
@@ -815,6 +882,30 @@ static napi_value BgzfOutLength(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* bgzfRangeOutLength(input: Uint8Array, vb: bigint, ve: bigint) -> number: the bytes the range between two virtual
+ * offsets delivers, read from the headers (zs_bgzf_range_out_len: host arithmetic), or -1 where the offsets do not
+ * follow a chain of BGZF blocks */
+static napi_value BgzfRangeOutLength(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], r;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool is_ta = false, l0 = false, l1 = false;
+  if (argc) napi_is_typedarray(env, argv[0], &is_ta);
+  napi_typedarray_type type = napi_int8_array;
+  size_t len = 0;
+  void *data = NULL;
+  uint64_t vb = 0, ve = 0;
+  if (is_ta) napi_get_typedarray_info(env, argv[0], &type, &len, &data, NULL, NULL);
+  if (!is_ta || type != napi_uint8_array || len > 0xffffffffu || argc < 3 ||
+      napi_get_value_bigint_uint64(env, argv[1], &vb, &l0) != napi_ok || !l0 ||
+      napi_get_value_bigint_uint64(env, argv[2], &ve, &l1) != napi_ok || !l1)
+    return throw_code(env, ZS_STREAM_ERROR, "bgzfRangeOutLength(input: Uint8Array, vb: bigint, ve: bigint)");
+  uint64_t total = 0;
+  const int ok = zs_bgzf_range_out_len((const uint8_t *)data, (uint32_t)len, vb, ve, &total);
+  NAPI_OK(napi_create_double(env, ok ? (double)total : -1.0, &r));
+  return r;
+}
+
 static napi_value Version(napi_env env, napi_callback_info info) {
   napi_value r;
   (void)info;
@@ -841,6 +932,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"decompressBatch", NULL, DecompressBatch, NULL, NULL, NULL, napi_default, NULL},
       {"deflateBound", NULL, DeflateBound, NULL, NULL, NULL, napi_default, NULL},
       {"bgzfOutLength", NULL, BgzfOutLength, NULL, NULL, NULL, napi_default, NULL},
+      {"bgzfRangeOutLength", NULL, BgzfRangeOutLength, NULL, NULL, NULL, napi_default, NULL},
       {"version", NULL, Version, NULL, NULL, NULL, napi_default, NULL},
       {"selfTest", NULL, SelfTest, NULL, NULL, NULL, napi_default, NULL},
   };

@@ -288,6 +288,13 @@ def lib():
         L.zs_last_bgzf_trusted.restype = ctypes.c_uint64
         L.zs_last_bgzf_trusted.argtypes = [_P]
         L.zs_bgzf_out_len.argtypes = [ctypes.c_char_p, ctypes.c_uint32, _U64P]
+    if hasattr(L, "zs_inflate_batch_bgzf_range"):  # ... the _bgzf arguments, two arrays of virtual offsets behind in_len
+        _rng = lambda a: a[:6] + [_U64P, _U64P] + a[6:]
+        L.zs_inflate_batch_bgzf_range.argtypes = _rng(L.zs_inflate_batch_ex.argtypes)
+        L.zs_pool_inflate_batch_bgzf_range.argtypes = _rng(L.zs_inflate_batch_ex.argtypes)
+        L.zs_inflate_batch_bgzf_range_device.argtypes = _rng(L.zs_inflate_batch_sync_device.argtypes)
+        L.zs_bgzf_range_out_len.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _U64P]
+        L.zs_bgzf_voffset.argtypes = [_U32P, _U32P, ctypes.c_uint64, ctypes.c_uint64, _U64P]
     L.zs_free.argtypes = [_P]
     L.zs_pool_create.argtypes = [ctypes.c_uint64, ctypes.POINTER(_P)]
     L.zs_pool_create_list.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]
@@ -448,6 +455,52 @@ def bgzf_out_caps(inputs) -> List[int]:
         n = bgzf_out_len(s)
         if n is None:
             raise ValueError("stream %d is not BGZF throughout: give out_caps" % i)
+        caps.append((n + 3) & ~3)
+    return caps
+
+
+def bgzf_range_out_len(data, vb: int, ve: int) -> Optional[int]:
+    """zs_bgzf_range_out_len: the bytes the range between the virtual offsets vb and ve (coffset << 16 | uoffset)
+    of a BGZF file delivers, read from its headers, or None where the offsets do not follow a chain of BGZF
+    blocks.  Host arithmetic, no GPU."""
+    data = bytes(data)
+    total = ctypes.c_uint64(0)
+    ok = lib().zs_bgzf_range_out_len(data, len(data), int(vb), int(ve), ctypes.byref(total))
+    return int(total.value) if ok else None
+
+
+def bgzf_voffset(blocks, upos: int, written: bool = False) -> Optional[int]:
+    """zs_bgzf_voffset: the virtual offset of uncompressed position upos, from ONE stream's list of pairs: the last
+    block that begins at or before upos.  The list is one of last_members() -- (compressed, uncompressed) offsets -- or,
+    with written=True, one of last_bgzf_blocks(), whose pairs are the writer's (in_pos, out_pos) and so (uncompressed,
+    compressed); its end-of-file block's entry makes the file's last position addressable.  None when upos lies behind
+    the last entry or the difference does not fit 16 bits."""
+    c, u = (1, 0) if written else (0, 1)
+    voff = ctypes.c_uint64(0)
+    ok = lib().zs_bgzf_voffset(_arr(ctypes.c_uint32, [b[c] for b in blocks]), _arr(ctypes.c_uint32, [b[u] for b in blocks]),
+                               len(blocks), int(upos), ctypes.byref(voff))
+    return int(voff.value) if ok else None
+
+
+def decompress_ranges(ranges, members, n):
+    """The `ranges` keyword of the decompress entries: one (vb, ve) pair of virtual offsets per stream
+    (zs_inflate_batch_bgzf_range*).  Only with members="bgzf": ValueError.  Returns the two ctypes arrays, or None."""
+    if ranges is None:
+        return None
+    if not (isinstance(members, str) and members == "bgzf"):
+        raise ValueError("ranges need members=\"bgzf\"")
+    if len(ranges) != n:
+        raise ValueError("ranges: one (vb, ve) pair per stream")
+    return (_arr(ctypes.c_uint64, [int(r[0]) for r in ranges]), _arr(ctypes.c_uint64, [int(r[1]) for r in ranges]))
+
+
+def bgzf_range_out_caps(inputs, ranges) -> List[int]:
+    """the capacities ranges= uses when none are given: each stream's bgzf_range_out_len rounded up to 4"""
+    caps = []
+    for i, (s, r) in enumerate(zip(inputs, ranges)):
+        n = bgzf_range_out_len(s, r[0], r[1])
+        if n is None:
+            raise ValueError("stream %d: the virtual offsets do not follow a chain of BGZF blocks: give out_caps" % i)
         caps.append((n + 3) & ~3)
     return caps
 
@@ -636,7 +689,8 @@ class Engine:
                                                       flush_at, flush_every, bgzf))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                             out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
+                             out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False,
+                             ranges=None):
         """Returns [(status, phase, msg, bytes, consumed)].  out_caps None: unbounded
         output, as DecompressionStream (zs_inflate_batch_auto); else per-stream caps.
         zdict: a preset dictionary for every input (bytes), or one per input (a
@@ -647,14 +701,23 @@ class Engine:
         members=True: every member of multi-member gzip inputs, concatenated (decompress_members;
         zs_inflate_batch_members; last_members()).  members="bgzf": the same for BGZF files, the blocks
         sized from their headers (zs_inflate_batch_bgzf; last_bgzf_trusted()); out_caps None: sized from
-        the headers too (bgzf_out_caps; ValueError for a stream that is not BGZF throughout)."""
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members)]
+        the headers too (bgzf_out_caps; ValueError for a stream that is not BGZF throughout).
+        ranges=[(vb, ve), ...] with members="bgzf": per stream, the bytes between two virtual offsets
+        (zs_inflate_batch_bgzf_range; inputs that are the same object are laid out once, so many ranges may
+        name one file); out_caps None: sized with bgzf_range_out_len."""
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members, ranges)]
 
     def decompress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                                  out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False):
+                                  out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False,
+                                  ranges=None):
         """Returns [(status, phase, msg, bytes, consumed, check)]."""
         L = self._L
+        rng = decompress_ranges(ranges, members, len(inputs))
         mode = decompress_members(members, fmt, out_caps, zdict, restart)
+        if rng is not None:
+            caps = bgzf_range_out_caps(inputs, ranges) if out_caps is None else out_caps
+            self._members_n = 0
+            return _inflate_host(L, L.zs_inflate_batch_bgzf_range, self._ctx, inputs, fmt, caps, self._check, ranges=rng)
         if mode == "bgzf":
             caps = bgzf_out_caps(inputs) if out_caps is None else out_caps
             res = _inflate_host(L, L.zs_inflate_batch_bgzf, self._ctx, inputs, fmt, caps, self._check)
@@ -681,8 +744,9 @@ class Engine:
         return _inflate_host(L, L.zs_inflate_batch_ex, self._ctx, inputs, fmt, out_caps, self._check)
 
     def decompress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
-                         out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False) -> List[bytes]:
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members))
+                         out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False,
+                         ranges=None) -> List[bytes]:
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members, ranges))
 
     def last_members(self) -> List[List[tuple]]:
         """zs_last_members: the members the last members=True call on this engine decoded, one list per
@@ -826,7 +890,7 @@ class Engine:
     def decompress_device(self, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                           d_status: int, d_phase: int, d_msg: int, d_out_len: int, d_consumed: int,
                           hip_stream: int = 0, d_dict: int = 0, dict_off=None, dict_len=None, d_check: int = 0,
-                          restart=None, headers=None, members=False):
+                          restart=None, headers=None, members=False, ranges=None):
         """d_dict / dict_off / dict_len: preset dictionaries (zs_inflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
         restart: one list per stream of (in_pos, out_pos) restart points without the start
@@ -836,8 +900,20 @@ class Engine:
         bytes on the device (zs_inflate_batch_sync_device, which waits for hip_stream once in the
         middle); no `headers`.  members=True: every member of multi-member gzip streams
         (zs_inflate_batch_members_device, which waits for hip_stream as the scan call does); members="bgzf":
-        BGZF blocks sized from their headers (zs_inflate_batch_bgzf_device)."""
+        BGZF blocks sized from their headers (zs_inflate_batch_bgzf_device); with ranges=[(vb, ve), ...] the
+        bytes between two virtual offsets per stream (zs_inflate_batch_bgzf_range_device)."""
+        rng = decompress_ranges(ranges, members, n)
         mode = decompress_members(members, fmt, out_cap, None if dict_off is None else dict_off, restart)
+        if rng is not None:
+            if out_cap is None:
+                raise ValueError("members on the device need out_cap")
+            r = self._L.zs_inflate_batch_bgzf_range_device(
+                self._ctx, decompress_wbits(fmt), n, _P(d_in), in_off, in_len, rng[0], rng[1], _P(d_out), out_off, out_cap,
+                _P(d_status), _P(d_phase), _P(d_msg), _P(d_out_len), _P(d_consumed), _P(d_check) if d_check else None,
+                _P(hip_stream) if hip_stream else None)
+            self._check(r, "zs_inflate_batch_bgzf_range_device")
+            self._members_n = 0
+            return
         if mode:
             bgzf = mode == "bgzf"  # (the regions are the caller's: out_cap is needed, as with members=True)
             if out_cap is None:
@@ -1048,11 +1124,25 @@ def _dict_layout(zdict, n):
     return [b"".join(parts), _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens)]
 
 
-def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check, zdict=()):
+def _layout_shared(inputs):
+    """_layout with inputs that are the same object laid out once (many ranges over one file)"""
+    seen, parts, offs, lens, o = {}, [], [], [], 0
+    for b in inputs:
+        if id(b) not in seen:
+            seen[id(b)] = o
+            parts.append(b)
+            o += len(b)
+        offs.append(seen[id(b)])
+        lens.append(len(b))
+    return b"".join(parts), offs, lens
+
+
+def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check, zdict=(), ranges=None):
+    """ranges: decompress_ranges' arrays for a _bgzf_range entry (fn), which takes them behind in_len."""
     n = len(inputs)
     if n == 0:
         return []
-    blob, offs, lens = _layout(inputs)
+    blob, offs, lens = _layout(inputs) if ranges is None else _layout_shared(inputs)
     # the caller's capacities exactly (Z_BUF_ERROR past them); the host entries decode into their own
     # word-aligned staging and copy out only the produced bytes, so these regions need no alignment
     caps = [min(0xffffffff, int(c)) for c in out_caps]
@@ -1062,8 +1152,8 @@ def _inflate_host(L, fn, handle, inputs, fmt, out_caps, check, zdict=()):
         oo += c
     out = ctypes.create_string_buffer(max(1, oo))
     res = [(ctypes.c_int32 * n)() for _ in range(3)] + [(ctypes.c_uint32 * n)() for _ in range(3)]
-    r = fn(handle, decompress_wbits(fmt), n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens), out,
-           _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), *res, *zdict)
+    r = fn(handle, decompress_wbits(fmt), n, blob, _arr(ctypes.c_uint64, offs), _arr(ctypes.c_uint32, lens),
+           *(ranges or ()), out, _arr(ctypes.c_uint64, ooffs), _arr(ctypes.c_uint32, caps), *res, *zdict)
     check(r, "inflate batch")
     return _inflate_results(L, n, out.raw, ooffs, *res)
 
@@ -1182,9 +1272,14 @@ class Pool:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
                                                       flush_at, flush_every, bgzf))
 
-    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
+    def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False,
+                                  ranges=None):
         L = self._L
+        rng = decompress_ranges(ranges, members, len(inputs))
         mode = decompress_members(members, fmt, out_caps, zdict, restart)  # (zs_last_members is not offered on the pool)
+        if rng is not None:
+            caps = bgzf_range_out_caps(inputs, ranges) if out_caps is None else out_caps
+            return _inflate_host(L, L.zs_pool_inflate_batch_bgzf_range, self._pool, inputs, fmt, caps, self._check, ranges=rng)
         if mode == "bgzf":
             caps = bgzf_out_caps(inputs) if out_caps is None else out_caps
             return _inflate_host(L, L.zs_pool_inflate_batch_bgzf, self._pool, inputs, fmt, caps, self._check)
@@ -1204,11 +1299,13 @@ class Pool:
             return _inflate_host_auto(L, L.zs_pool_inflate_batch_auto, self._pool, inputs, fmt, self._check)
         return _inflate_host(L, L.zs_pool_inflate_batch, self._pool, inputs, fmt, out_caps, self._check)
 
-    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
-        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members)]
+    def decompress_batch_raw(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False,
+                             ranges=None):
+        return [r[:5] for r in self.decompress_batch_detailed(inputs, fmt, out_caps, zdict, restart, members, ranges)]
 
-    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False):
-        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members))
+    def decompress_batch(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False,
+                         ranges=None):
+        return _ok_or_raise_d(self.decompress_batch_raw(inputs, fmt, out_caps, zdict, restart, members, ranges))
 
 
 _default: Optional[Engine] = None
