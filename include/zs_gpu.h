@@ -403,7 +403,8 @@ int zs_pool_deflate_batch_params(zs_pool *pool, int level, int wbits, int mem_le
  *    device form as the plain entries.  Size outputs with zs_deflate_bound_flush. */
 #define ZS_FULL_FLUSH 3 /* Z_FULL_FLUSH, common/constants.ts */
 /* zs_deflate_bound + 12 n_flush: every extra piece costs at most the raw bound's constant 7 and
- * the marker's 5 bytes; the bound's shifted terms are sub-additive. */
+ * the marker's 5 bytes; the bound's shifted terms are sub-additive.  It bounds a primed call's output
+ * too (n_flush points): a raw piece with a dictionary adds no bytes and its marker is the same 5. */
 uint64_t zs_deflate_bound_flush(uint64_t source_len, int wbits, uint64_t n_flush);
 /* deflate.ts:923-961 -- device buffers (as zs_deflate_batch_device_ex) */
 int zs_deflate_batch_flush_device(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *d_in,
@@ -421,6 +422,48 @@ int zs_pool_deflate_batch_flush(zs_pool *pool, int level, int wbits, uint32_t n_
                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
                                 const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
                                 int flush, const uint64_t *flush_first, const uint32_t *flush_pos);
+
+/* Primed pieces: one stream's pieces compressed in parallel without the flush points' ratio loss
+ * (pigz's construction).  Stream i has the positions 0 <= p_1 < ... < p_k <= in_len[i] of the _flush
+ * entries, same arrays, same validation.  Its output is the stream's ordinary wrapper header (zlib: two
+ * bytes, no FDICT; gzip: the ten-byte header, OS 255; raw: none); then for every piece d = in[a, b) in
+ * order the bytes zlib 1.2.11 writes for deflateInit2_(level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY),
+ * deflateSetDictionary(in[max(0, a - 32768), a)) if a > 0, the piece in the stream layer's 32 KiB
+ * sub-chunks, and deflate(Z_SYNC_FLUSH) until drained -- deflate(Z_FINISH) for the last piece; then the
+ * trailer over the whole input.  Every piece but the last ends on a byte boundary with BFINAL clear and
+ * the marker 00 00 FF FF, and a distance into a piece's prime is a distance into the stream's earlier
+ * output: the concatenation is ONE ordinary deflate stream that any decoder reads, at nearly the
+ * single-stream ratio (a piece looks back across its point).  The first piece has no prime.
+ *  - the piece rules are the flushed pieces': the pending block is closed only if it holds symbols, an
+ *    empty last block is dropped, only the block Z_FINISH closes carries BFINAL;
+ *  - all three formats are taken, gzip too (unlike the _dict entries): the pieces are raw, the wrapper
+ *    is the stream's, check[i] is adler32 / crc32 of all its bytes and gzip's ISIZE the whole length;
+ *  - refusals, statuses and messages as the _flush entries, less those of `flush`: null arrays, invalid
+ *    positions, level 0 with a point, streams + points above 65,535 in one call, windowBits, level,
+ *    and the device form's 4-byte alignment rule;
+ *  - a call whose streams have no point is the _ex call: the same plan, kernels and bytes;
+ *  - zs_last_flush_index returns the offsets behind the markers, as after a _flush call.  They are
+ *    not restart points for a parallel decode: the bytes behind one refer back across it;
+ *  - size outputs with zs_deflate_bound_flush: a raw piece with a dictionary adds no bytes (no FDICT,
+ *    no DICTID) and the marker is the same five bytes;
+ *  - the workspace grows with the sum of (prime + piece) over the pieces, not of the pieces alone;
+ *  - caller dictionaries, strategies and windowBits / memLevel are not built with primed pieces. */
+/* device buffers (as zs_deflate_batch_flush_device, without `flush`) */
+int zs_deflate_batch_primed_device(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *d_in,
+                                   const uint64_t *in_off, const uint32_t *in_len, uint8_t *d_out,
+                                   const uint64_t *out_off, const uint32_t *out_cap, int32_t *d_status,
+                                   uint32_t *d_out_len, uint32_t *d_check, void *hip_stream,
+                                   const uint64_t *flush_first, const uint32_t *flush_pos);
+/* host buffers (as zs_deflate_batch_flush) */
+int zs_deflate_batch_primed(zs_ctx *ctx, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                            const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                            const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
+                            const uint64_t *flush_first, const uint32_t *flush_pos);
+/* the pool (as zs_pool_deflate_batch_flush; sharded by stream) */
+int zs_pool_deflate_batch_primed(zs_pool *pool, int level, int wbits, uint32_t n_streams, const uint8_t *in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint8_t *out, const uint64_t *out_off,
+                                 const uint32_t *out_cap, int32_t *status, uint32_t *out_len, uint32_t *check,
+                                 const uint64_t *flush_first, const uint32_t *flush_pos);
 
 /* BGZF: one file's 64 KiB blocks compressed in parallel (SAM specification 4.1, "The BGZF compression
  * format").  Stream i of L = in_len[i] bytes with block size B becomes ceil(L / B) data blocks and then

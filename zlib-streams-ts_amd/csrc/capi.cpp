@@ -666,6 +666,10 @@ static fast_par_fn fast_par_kernel(int nice_bucket, bool lane_order) {
 // the parse starts at the streams' parse starts, the zlib wrapper carries FDICT / DICTID.
 // A batch with flush points (fl): b holds the SEGMENTS (b.out_off the segment's stream's),
 // `data` the streams, whose check values, layout scan, wrapper and results are per stream.
+// A primed batch (p.req.primed) is both: b holds the segments' J -- the prime, then the piece, read
+// where they lie in the caller's input -- the DICT instances parse them from d_start on, and the flushed layout,
+// the plain wrapper and the streams' results follow.  The blocks' in_start / in_end are J's coordinates, as
+// b.in_off is, and the layout kernels read their difference alone: they take no d_start.
 struct FlushDev {
   const uint32_t* sfirst;   // device: each stream's first segment
   const uint32_t* sstream;  // ... each segment's stream
@@ -822,7 +826,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
       b.in, b.in_off, d_pos, d_blk, syms, d_bk, d_st, c->codes.as<uint32_t>(), c->hdr.as<uint32_t>(), (int)n,
       p.fixed ? 1 : 0);
   MARK("trees");
-  if (p.dict) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
+  if (p.dict && !fl) zs_k_layout_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_blk, d_bk, d_st, b.out_cap, b.out, b.out_off, wrap, (int)n,
                                                                  d_start);
   else if (bgzf) bgzf_layout(c, st, *fl, d_blk, d_bk, d_st, d_res, data, n);
   else if (fl) {
@@ -844,7 +848,7 @@ static int deflate_launch(zs_ctx* c, hipStream_t st, const zs_deflate_plan& p, c
                                                            data.out_off, n, n_res);
     MARK("bgzf_frame");
   }
-  if (wrap && p.dict)
+  if (wrap && p.dict && !fl)
     zs_k_wrap_dict<<<nblocks_s, nthreads_s, 0, st>>>(d_st, b.out, b.out_off, b.in_len, wrap, level, (int)n, d_start,
                                                      (const uint32_t*)(dm + ml.did), c->dadler.as<uint32_t>());
   else if (wrap && par)
@@ -898,7 +902,7 @@ static zs_deflate_call deflate_call(const Batch& h, bool caller_regions, const D
 static int deflate_ensure(zs_ctx* c, const zs_deflate_plan& p) {
   if (p.stored) return ZS_OK;
   HIPCHK(c->ghead.ensure(p.ghead_bytes));
-  if (p.dict) {
+  if (p.dict && !p.req.primed) {  // (a primed batch's J are slices of the input: no join, no DICTID)
     HIPCHK(c->djoin.ensure(p.J + 16));
     HIPCHK(c->dadler.ensure(4ull * p.ndict));
   }
@@ -935,6 +939,7 @@ static int deflate_batch(zs_ctx* c, const zs_deflate_req& req_in, const zs_defla
   if (req_in.bgzf) return deflate_batch_bgzf(c, req_in, h, d_status, d_out_len, d_check, st);
   zs_deflate_req req = req_in;
   req.flush = 0;  // no flush point: the plain batch's plan, kernels and bytes
+  req.primed = false;
   const uint32_t n = h.n;
   // the plan (host-side): routes, instances, grids, workspace bases, the sweep's windows and the
   // metadata block; the streams' dictionaries, the distinct ones found once
@@ -997,14 +1002,17 @@ static int deflate_batch(zs_ctx* c, const zs_deflate_req& req_in, const zs_defla
 // A batch with Z_FULL_FLUSH points (validated; levels 1..9): the plan runs over the SEGMENTS -- the
 // pieces between the flush points, each a stream of its own to the match, parse, trees and emit
 // kernels -- and the flushed layout joins them per stream (deflate_flush.hip).
+// A primed batch (req.primed) is the same batch with each segment widened to its J: lp bytes of
+// prime in front (zs_plan_primed), planned as a dictionary of that length, parsed from lp on.
 static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch& h, int32_t* d_status,
                                uint32_t* d_out_len, uint32_t* d_check, hipStream_t st, const FlushIn& flush) {
   const uint32_t n = h.n;
   zs_flush_plan& f = c->fp;
   zs_plan_flush(n, h.in_len, flush.first, flush.pos, f);
+  if (req.primed) zs_plan_primed(f);
   const uint32_t M = f.M;
   zs_deflate_plan& p = c->dp;
-  zs_plan_deflate(req, c->o, c->fast_group, c->lane_order, M, f.slen.data(), nullptr, 0, p);
+  zs_plan_deflate(req, c->o, c->fast_group, c->lane_order, M, f.slen.data(), req.primed ? f.lp.data() : nullptr, 0, p);
   const zs_meta_layout& ml = p.ml;
   const zs_flush_layout fo(ml.bytes, n, M);
   HIPCHK(c->check.ensure(4ull * n));
@@ -1023,13 +1031,14 @@ static int deflate_batch_flush(zs_ctx* c, const zs_deflate_req& req, const Batch
   // the segments as a batch: their bytes where they lie in their streams, every one with its stream's output
   std::vector<uint64_t> sin(M), sout(M);
   for (uint32_t g = 0; g < M; g++) {
-    sin[g] = h.in_off[f.sstream[g]] + f.soff[g];
+    sin[g] = h.in_off[f.sstream[g]] + (req.primed ? f.joff[g] : f.soff[g]);
     sout[g] = h.out_off[f.sstream[g]];
   }
-  const Batch hs = {M, h.in, sin.data(), f.slen.data(), h.out, sout.data(), nullptr};
+  const Batch hs = {M, h.in, sin.data(), req.primed ? f.nv.data() : f.slen.data(), h.out, sout.data(), nullptr};
   Batch b;
   const int r = upload_batch(c, st, ml, fo.bytes + ck_bytes, hs, &b, [&](uint8_t* hm) {
     ck_fill(ck, hm + fo.bytes);
+    if (req.primed) memcpy(hm + ml.start, p.start.data(), 4ull * M);
     memcpy(hm + ml.pos_base, p.pos.data(), 8ull * M);
     memcpy(hm + ml.blk_base, p.blk.data(), 4ull * M);
     if (!p.segs.empty()) memcpy(hm + ml.segs, p.segs.data(), sizeof(zs_sweep_seg) * p.segs.size());
@@ -1443,6 +1452,30 @@ extern "C" int zs_deflate_batch_flush(zs_ctx* c, int level, int wbits, uint32_t 
                                       const uint32_t* flush_pos) {
   zs_deflate_req req;
   if (const zs_deflate_err e = zs_deflate_make_req_flush(level, wbits, flush, &req)) return deflate_fail(e);
+  const FlushIn fi = {flush_first, flush_pos};
+  return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr, &fi);
+}
+
+// ---- primed pieces: the _flush entries without `flush`
+extern "C" int zs_deflate_batch_primed_device(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* d_in,
+                                              const uint64_t* in_off, const uint32_t* in_len, uint8_t* d_out,
+                                              const uint64_t* out_off, const uint32_t* out_cap, int32_t* d_status,
+                                              uint32_t* d_out_len, uint32_t* d_check, void* hip_stream,
+                                              const uint64_t* flush_first, const uint32_t* flush_pos) {
+  zs_deflate_req req;
+  zs_deflate_make_req_primed(level, wbits, &req);
+  const FlushIn fi = {flush_first, flush_pos};
+  return deflate_device(c, req, {n, d_in, in_off, in_len, d_out, out_off, out_cap}, d_status, d_out_len, d_check,
+                        hip_stream, nullptr, &fi);
+}
+
+extern "C" int zs_deflate_batch_primed(zs_ctx* c, int level, int wbits, uint32_t n, const uint8_t* in,
+                                       const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                       const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                       uint32_t* out_len, uint32_t* check, const uint64_t* flush_first,
+                                       const uint32_t* flush_pos) {
+  zs_deflate_req req;
+  zs_deflate_make_req_primed(level, wbits, &req);
   const FlushIn fi = {flush_first, flush_pos};
   return deflate_host(c, req, {n, in, in_off, in_len, out, out_off, out_cap}, status, out_len, check, nullptr, &fi);
 }

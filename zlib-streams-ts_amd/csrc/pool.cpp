@@ -535,6 +535,24 @@ extern "C" int zs_pool_inflate_batch_restart(zs_pool* p, int wbits, uint32_t n, 
   });
 }
 
+// with primed pieces: sharded by stream as the flushed form
+extern "C" int zs_pool_deflate_batch_primed(zs_pool* p, int level, int wbits, uint32_t n, const uint8_t* in,
+                                            const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                            const uint64_t* out_off, const uint32_t* out_cap, int32_t* status,
+                                            uint32_t* out_len, uint32_t* check, const uint64_t* flush_first,
+                                            const uint32_t* flush_pos) {
+  if (n && !flush_first) {
+    zs_set_last_error("null flush arrays");
+    return ZS_STREAM_ERROR;
+  }
+  return run_sharded(p, n, [&](uint32_t k, Shard s) {
+    if (s.a == s.b) return (int)ZS_OK;
+    return zs_deflate_batch_primed(p->ctx[k], level, wbits, s.b - s.a, in, in_off + s.a, in_len + s.a, out,
+                                   out_off + s.a, out_cap + s.a, status + s.a, out_len + s.a,
+                                   check ? check + s.a : nullptr, flush_first + s.a, flush_pos);
+  });
+}
+
 extern "C" int zs_pool_inflate_batch(zs_pool* p, int wbits, uint32_t n, const uint8_t* in, const uint64_t* in_off,
                                      const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                                      const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,

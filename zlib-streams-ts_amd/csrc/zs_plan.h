@@ -535,6 +535,9 @@ struct zs_deflate_req {
   bool dict = false;  // the call carries preset dictionaries (a batch with every length 0 is the plain batch)
   // 0, or ZS_FLUSH_FULL: the call carries Z_FULL_FLUSH positions (a batch without any is the plain batch)
   int flush = 0;
+  // with flush: every piece behind the first is PRIMED with the 32 KiB in front of it as a preset dictionary
+  // (pigz's construction).  Not one of zlib's flush values: a flag of its own.
+  bool primed = false;
   // 0, or the block size 1..ZS_BGZF_BLOCK_MAX of a BGZF call: every stream is cut into
   // pieces of that many bytes, each a finished raw-deflate stream in a gzip frame of its own
   uint32_t bgzf = 0;
@@ -606,6 +609,13 @@ static inline zs_deflate_err zs_deflate_make_req_flush(int level, int wbits, int
   if (flush == 1 || flush == 2 || flush == 5) return ZS_DE_FLUSH_MODE;  // Z_PARTIAL_FLUSH, Z_SYNC_FLUSH, Z_BLOCK
   if (flush != ZS_FLUSH_FULL) return ZS_DE_FLUSH_INVALID;
   r->flush = flush;
+  return ZS_DE_OK;
+}
+// ... and of the _primed entries: the _flush entries' positions, no flush argument; all three formats
+static inline zs_deflate_err zs_deflate_make_req_primed(int level, int wbits, zs_deflate_req* r) {
+  zs_deflate_make_req(level, wbits, ZS_STRAT_DEFAULT, false, r);
+  r->flush = ZS_FLUSH_FULL;  // (the marker's bytes and the piece rules are the full flush's)
+  r->primed = true;
   return ZS_DE_OK;
 }
 // ... and of the _bgzf entries: gzip members, block_bytes 0 = ZS_BGZF_BLOCK_MAX.  The level's
@@ -776,6 +786,9 @@ struct zs_flush_plan {
   std::vector<uint32_t> sstream;  // each segment's stream (sstream[M] = n)
   std::vector<uint32_t> soff;     // each segment's start in its stream ...
   std::vector<uint32_t> slen;     // ... and its length
+  // a primed batch (zs_plan_primed; else empty): each segment's prime length and the length of its J
+  std::vector<uint32_t> lp, nv;
+  std::vector<uint32_t> joff;     // ... and J's start in its stream, soff - lp
 };
 // flush_first / flush_pos: positions that passed zs_deflate_validate_flush (flush_first may be null: none)
 static inline void zs_plan_flush(uint32_t n, const uint32_t* in_len, const uint64_t* flush_first,
@@ -801,6 +814,24 @@ static inline void zs_plan_flush(uint32_t n, const uint32_t* in_len, const uint6
   f.M = (uint32_t)f.sstream.size();
   f.sfirst[n] = f.M;
   f.sstream.push_back(n);
+  f.lp.clear();
+  f.nv.clear();
+  f.joff.clear();
+}
+// ---- Primed pieces.  A piece behind a point is compressed against the 32 KiB in front of
+// it as a preset dictionary (deflateSetDictionary on a raw stream): the dictionary path's "run on J =
+// tail(dict) || data, start the parse at L'" (DESIGN 4.6), where J is a slice of the stream itself:
+// segment g of zs_plan_flush gets the prime length lp = min(soff, 32768), J = [soff - lp, soff + slen)
+// of its stream and the parse start lp.  zs_plan_deflate then runs over the segments with dict_len = lp.
+static inline void zs_plan_primed(zs_flush_plan& f) {
+  f.lp.resize(f.M);
+  f.nv.resize(f.M);
+  f.joff.resize(f.M);
+  for (uint32_t g = 0; g < f.M; g++) {
+    f.lp[g] = f.soff[g] < ZS_W_SIZE ? f.soff[g] : ZS_W_SIZE;
+    f.joff[g] = f.soff[g] - f.lp[g];
+    f.nv[g] = f.lp[g] + f.slen[g];  // (at most the stream's length: no overflow)
+  }
 }
 // ---- BGZF: stream i is cut every B bytes into ceil(len / B) segments, each a finished raw
 // stream in a gzip frame of its own; an empty stream has none (its output is the end-of-file block alone).
@@ -937,7 +968,7 @@ static inline void zs_plan_deflate(const zs_deflate_req& r, const zs_route_opts&
                                    zs_deflate_plan& p) {
   const zs_strategy_plan sp = zs_plan_strategy(o, r.level, r.strategy);
   const zs_deflate_params& q = r.q;
-  if (!r.dict) dict_len = nullptr;
+  if (!r.dict && !r.primed) dict_len = nullptr;  // (a primed batch's are the segments' prime lengths)
   p.req = r;
   p.n = n;
   p.stored = sp.stored;

@@ -39,6 +39,13 @@ export interface CompressBatchOptions extends BatchOptions {
   flushAt?: number[] | (number[] | null)[];
   /** flushAt at N, 2N, ... below each input's length. */
   flushEvery?: number;
+  /** true next to `flushAt` / `flushEvery`: no flush is written at the positions.  The pieces between them are
+   * compressed in parallel, each primed with the 32 KiB in front of it as a preset dictionary (pigz's
+   * construction), and the output is one ordinary stream that any decoder reads, at nearly the single-stream
+   * ratio; every piece but the last still ends with 00 00 FF FF on a byte boundary.  All three formats, levels
+   * 1..9.  Without positions, or with `bgzf`, a TypeError; with `dictionary`, a `strategy` or `windowBits` /
+   * `memLevel` other than 15 / 8 a TypeError, as for the positions. */
+  primed?: boolean;
   /** BGZF (SAM specification 4.1), format "gzip" only, levels 0..9: every input becomes blocks of 65,280 input
    * bytes (true) or of this many (1 .. 65,280), each a gzip member with the BC subfield and BSIZE, then the 28-byte
    * end-of-file block -- what bgzip, samtools, tabix, gzip -d and {members: "bgzf"} read.  The blocks compress in

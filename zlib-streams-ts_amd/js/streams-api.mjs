@@ -166,6 +166,21 @@ function bgzfOf(options, format) {
   return b;
 }
 
+// options.primed: true next to flushAt / flushEvery: no flush is written at the positions; the pieces between
+// them are compressed in parallel, each primed with the 32 KiB in front of it (pigz's construction;
+// zs_deflate_batch_primed in zs_gpu.h), and the output is one ordinary stream at nearly the single-stream
+// ratio.  All three formats.  Without positions, or with bgzf, a TypeError; with a dictionary, a strategy or
+// windowBits / memLevel it is refused as flush points are (flushOf).
+function primedOf(options) {
+  const p = options.primed;
+  if (p === undefined || p === null || p === false) return false;
+  if (p !== true) throw new TypeError("primed is true or false");
+  const has = (x) => x !== undefined && x !== null;
+  if (has(options.bgzf) && options.bgzf !== false) throw new TypeError("primed and bgzf cannot be combined");
+  if (!has(options.flushAt) && !has(options.flushEvery)) throw new TypeError("primed needs flushAt or flushEvery");
+  return true;
+}
+
 // The addon runs each batch on a worker thread (napi_async_work) and settles a
 // Promise: the event loop is not blocked while the GPU works.
 async function runCompress(inputs, format, options) {
@@ -176,9 +191,10 @@ async function runCompress(inputs, format, options) {
   let res;
   try {
     const ins = checkInputs(inputs);
+    const primed = primedOf(options);
     const bgzf = bgzfOf(options, format);
     res = await addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                                    strategyOf(options), memLevel, flushOf(options, ins), bgzf);
+                                    strategyOf(options), memLevel, flushOf(options, ins), bgzf, primed);
   } catch (e) {
     // argument validation of deflateInit2_ (deflate.ts:281-294) surfaces as the stream layer's init error
     if (e.code === String(Z_STREAM_ERROR)) throw streamError(Z_STREAM_ERROR, PHASE_INIT);
@@ -362,7 +378,7 @@ export async function decompressBatchSettled(inputs, format = "deflate", options
   return settle(await runDecompress(inputs, format, options));
 }
 
-// (nFlush: the stream's Z_FULL_FLUSH points, 12 bytes each: zs_deflate_bound_flush)
+// (nFlush: the stream's Z_FULL_FLUSH points, or its points with `primed`, 12 bytes each: zs_deflate_bound_flush)
 export const deflateBound = (length, format = "deflate", nFlush = 0) =>
   addon.deflateBound(length, compressWbits(format)) + 12 * nFlush;
 
@@ -373,9 +389,10 @@ export async function compressBatchDetailed(inputs, format = "deflate", options 
   const level = typeof options.level == "number" ? options.level : -1;
   const ins = checkInputs(inputs);
   const [wbits, memLevel] = paramsOf(options, format);
+  const primed = primedOf(options);
   const bgzf = bgzfOf(options, format);
   return addon.compressBatch(ins, wbits, level, devicesOf(options), dictionariesOf(options, ins.length),
-                             strategyOf(options), memLevel, flushOf(options, ins), bgzf);
+                             strategyOf(options), memLevel, flushOf(options, ins), bgzf, primed);
 }
 
 export async function decompressBatchDetailed(inputs, format = "deflate", options = {}) {

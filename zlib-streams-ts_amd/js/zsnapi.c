@@ -216,6 +216,7 @@ typedef struct {
    * flush_first[i + 1]); NULL: none given */
   uint64_t *flush_first;
   uint32_t *flush_pos;
+  int primed;          /* compress, with flush_first: primed pieces, no flush (zs_pool_deflate_batch_primed) */
   int bgzf;            /* compress: a BGZF file per input (zs_pool_deflate_batch_bgzf) ... */
   uint32_t block_bytes;  /* ... in blocks of this many bytes (0: ZS_BGZF_BLOCK) */
   /* restart points (zs_pool_inflate_batch_restart): input i's points, its start included, are
@@ -313,6 +314,9 @@ static void job_execute(napi_env env, void *data) {
   else if (j->bgzf)
     j->rc = zs_pool_deflate_batch_bgzf(j->pool, j->level, j->n, j->base, j->in_off, j->in_len, j->out, j->out_off,
                                        j->cap, j->status, j->olen, j->check, j->block_bytes);
+  else if (j->flush_first && j->primed)
+    j->rc = zs_pool_deflate_batch_primed(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
+                                         j->out_off, j->cap, j->status, j->olen, j->check, j->flush_first, j->flush_pos);
   else if (j->flush_first)
     j->rc = zs_pool_deflate_batch_flush(j->pool, j->level, j->wbits, j->n, j->base, j->in_off, j->in_len, j->out,
                                         j->out_off, j->cap, j->status, j->olen, j->check, ZS_FULL_FLUSH, j->flush_first,
@@ -619,7 +623,10 @@ static int copy_restart(napi_env env, job *j, napi_value arr) {
 /* compressBatch(inputs: Uint8Array[], wbits, level, devices: number | number[],
  *               dictionaries: (Uint8Array | null)[] | undefined, strategy: number | undefined,
  *               memLevel: number | undefined, flushAt: (number[] | null)[] | undefined,
- *               bgzf: number | undefined) ->
+ *               bgzf: number | undefined, primed: boolean | undefined) ->
+ * primed: true with flushAt: the pieces between the positions are primed with the 32 KiB in front of them and
+ * no flush is written (zs_pool_deflate_batch_primed; all three formats); without flushAt, or with bgzf, it
+ * throws code "-2", before any device is touched.
  * bgzf: the block's bytes of a BGZF file per input (zs_gpu.h: 0 = 65,280; above that code "-2", "invalid BGZF
  * block size"); wbits must be 31, and together with dictionaries, a strategy, windowBits / memLevel other than
  * 15 / 8 or flushAt it throws code "-2" (not built), before any device is touched.
@@ -633,12 +640,12 @@ static int copy_restart(napi_env env, job *j, napi_value arr) {
  * (deflate.ts:289-290; no dictionaries with a strategy, zs_gpu.h) before any device is touched ->
  *   Promise<{status: Int32Array, check: Uint32Array, outputs: Uint8Array[]}> */
 static napi_value CompressBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 9;
-  napi_value argv[9];
+  size_t argc = 10;
+  napi_value argv[10];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 3)
     return throw_code(env, ZS_STREAM_ERROR,
-                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel[, flushAt[, bgzf]]]]]])");
+                      "compressBatch(inputs, wbits, level[, devices[, dictionaries[, strategy[, memLevel[, flushAt[, bgzf[, primed]]]]]]])");
   const int32_t strategy = argc > 5 ? arg_i32(env, argv[5], 0) : 0;
   if (strategy < 0 || strategy > ZS_FIXED) return throw_code(env, ZS_STREAM_ERROR, "invalid strategy");
   napi_valuetype dt = napi_undefined;
@@ -669,6 +676,10 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   if (bgzf && (wbits != 31 || params || strategy || flush || (dt != napi_undefined && dt != napi_null)))
     return throw_code(env, ZS_STREAM_ERROR,
                       "BGZF is gzip without preset dictionaries, a strategy, windowBits / memLevel or flush points");
+  bool primed = false;
+  if (argc > 9 && napi_get_value_bool(env, argv[9], &primed) != napi_ok) primed = false;
+  if (primed && (!flush || bgzf))
+    return throw_code(env, ZS_STREAM_ERROR, "primed pieces need flushAt and are not built with BGZF");
   if (bgzf && !(block >= 0 && block <= ZS_BGZF_BLOCK && block == (double)(uint32_t)block))
     return throw_code(env, ZS_STREAM_ERROR, "invalid BGZF block size");
   view *v = NULL;
@@ -687,6 +698,7 @@ static napi_value CompressBatch(napi_env env, napi_callback_info info) {
   j->wbits = wbits;
   j->level = arg_i32(env, argv[2], -1);
   j->bgzf = bgzf;
+  j->primed = primed;
   j->block_bytes = (uint32_t)block;
   j->strategy = strategy;
   j->params = params;

@@ -137,6 +137,21 @@ def compress_flush(lens, flush_at=None, flush_every=None, zdict=None, strategy=0
     return per
 
 
+def compress_primed(primed, flush_at=None, flush_every=None, bgzf=None) -> bool:
+    """The `primed` keyword of the compress entries (zs_deflate_batch_primed; pigz's construction): the
+    pieces between the positions of flush_at / flush_every are compressed in parallel, each primed with
+    the 32 KiB in front of it, and the output is one ordinary stream at nearly the single-stream ratio.
+    Without positions it is an error, and so it is with bgzf; with zdict, a strategy or window_bits /
+    mem_level it is refused as flush points are (compress_flush).  Returns whether the call is primed."""
+    if not primed:
+        return False
+    if bgzf is not None and bgzf is not False:
+        raise ValueError("primed with bgzf is not built")
+    if flush_at is None and flush_every is None:
+        raise ValueError("primed needs flush_at or flush_every")
+    return True
+
+
 BGZF_BLOCK = 65280  # ZS_BGZF_BLOCK in zs_gpu.h: the input of one BGZF block at most
 
 
@@ -249,6 +264,11 @@ def lib():
         L.zs_pool_deflate_batch_flush.argtypes = L.zs_deflate_batch_ex.argtypes + _fl
         L.zs_deflate_bound_flush.restype = ctypes.c_uint64
         L.zs_deflate_bound_flush.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]
+    if hasattr(L, "zs_deflate_batch_primed"):  # flush_first, flush_pos behind the counterpart's arguments
+        _pr = [_U64P, _U32P]
+        L.zs_deflate_batch_primed.argtypes = L.zs_deflate_batch_ex.argtypes + _pr
+        L.zs_deflate_batch_primed_device.argtypes = L.zs_deflate_batch_device_ex.argtypes + _pr
+        L.zs_pool_deflate_batch_primed.argtypes = L.zs_deflate_batch_ex.argtypes + _pr
     if hasattr(L, "zs_deflate_batch_bgzf"):  # no wbits; block_bytes behind the counterpart's arguments
         _nowb = lambda a: a[:2] + a[3:] + [ctypes.c_uint32]
         L.zs_deflate_batch_bgzf.argtypes = _nowb(L.zs_deflate_batch_ex.argtypes)
@@ -636,7 +656,7 @@ class Engine:
     # ---------------------------------------------------------- host buffers
     def compress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
                            strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                           flush_every=None, bgzf=None) -> List[Tuple[int, bytes]]:
+                           flush_every=None, bgzf=None, primed=False) -> List[Tuple[int, bytes]]:
         """Returns [(status, bytes)] -- status Z_STREAM_END on success.
         zdict: a preset dictionary for every input (bytes), or one per input (a
         list; None = none) -- "deflate-raw" and "deflate" only, levels 1..9
@@ -646,16 +666,19 @@ class Engine:
         (zs_deflate_batch_params; other than 15 / 8 not with zdict or a strategy, levels 1..9).
         flush_at (positions for every stream, or a list per stream), flush_every=N: Z_FULL_FLUSH
         points (zs_deflate_batch_flush; levels 1..9, not with any of the above).
+        primed=True with flush_at / flush_every: no flush but primed pieces between the positions, each
+        compressed against the 32 KiB in front of it (zs_deflate_batch_primed): one ordinary stream.
         bgzf=True or the block's bytes: BGZF blocks and the end-of-file block (zs_deflate_batch_bgzf;
         fmt "gzip", levels 0..9, not with any of the above)."""
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level, flush_at, flush_every, bgzf)]
+                                                                     mem_level, flush_at, flush_every, bgzf, primed)]
 
     def compress_batch_detailed(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
                                 strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                                flush_every=None, bgzf=None) -> List[Tuple[int, bytes, int]]:
+                                flush_every=None, bgzf=None, primed=False) -> List[Tuple[int, bytes, int]]:
         """Returns [(status, bytes, check)]: check = the reference's strm.adler after the
         stream (adler32 / crc32 of the input for deflate / gzip, 1 for deflate-raw)."""
+        primed = compress_primed(primed, flush_at, flush_every, bgzf)
         block = compress_bgzf(bgzf, fmt, zdict, strategy, window_bits, mem_level, flush_at, flush_every)
         self._bgzf_n = 0
         if block is not None:
@@ -669,8 +692,8 @@ class Engine:
         self._flush_counts = None
         if per is not None:
             self._flush_counts = [len(ps) for ps in per]
-            return _deflate_host(self._L, self._L.zs_deflate_batch_flush, self._ctx, inputs, fmt, level, self._check,
-                                 flush=per)
+            fn = self._L.zs_deflate_batch_primed if primed else self._L.zs_deflate_batch_flush
+            return _deflate_host(self._L, fn, self._ctx, inputs, fmt, level, self._check, flush=per, primed=primed)
         if not _params_default(window_bits, mem_level):
             return _deflate_host(self._L, self._L.zs_deflate_batch_params, self._ctx, inputs, fmt, level, self._check,
                                  params=(code, mem_level))
@@ -684,9 +707,9 @@ class Engine:
 
     def compress_batch(self, inputs: Sequence[bytes], fmt: str = "deflate-raw", level: int = -1, zdict=None,
                        strategy: int = 0, window_bits=None, mem_level=8, flush_at=None, flush_every=None,
-                       bgzf=None) -> List[bytes]:
+                       bgzf=None, primed=False) -> List[bytes]:
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
-                                                      flush_at, flush_every, bgzf))
+                                                      flush_at, flush_every, bgzf, primed))
 
     def decompress_batch_raw(self, inputs: Sequence[bytes], fmt: str = "deflate-raw",
                              out_caps: Optional[Sequence[int]] = None, zdict=None, restart=None, members=False,
@@ -825,14 +848,16 @@ class Engine:
     def compress_device(self, level: int, fmt: str, n: int, d_in: int, in_off, in_len, d_out: int, out_off, out_cap,
                         d_status: int, d_out_len: int, hip_stream: int = 0, d_check: int = 0, d_dict: int = 0,
                         dict_off=None, dict_len=None, strategy: int = 0, window_bits=None, mem_level=8, flush_at=None,
-                        flush_every=None, bgzf=None):
+                        flush_every=None, bgzf=None, primed=False):
         """Device pointers (ints) + host layout arrays (ctypes arrays).
+        primed=True with flush_at / flush_every: primed pieces (zs_deflate_batch_primed_device).
         bgzf=True or the block's bytes: BGZF (zs_deflate_batch_bgzf_device; fmt "gzip", not with the others).
         flush_at / flush_every: Z_FULL_FLUSH points (zs_deflate_batch_flush_device; not with the others).
         d_dict / dict_off / dict_len: preset dictionaries (zs_deflate_batch_dict_device:
         device bytes, host ctypes arrays of per-stream offsets and lengths, 0 = none).
         strategy: zs_deflate_batch_strategy_device (not with dictionaries).
         window_bits / mem_level: zs_deflate_batch_params_device (other than 15 / 8 not with either)."""
+        primed = compress_primed(primed, flush_at, flush_every, bgzf)
         block = compress_bgzf(bgzf, fmt, dict_off, strategy, window_bits, mem_level, flush_at, flush_every)
         self._bgzf_n = 0
         if block is not None:
@@ -852,6 +877,13 @@ class Engine:
         if per is not None:
             self._flush_counts = [len(ps) for ps in per]
             first, pos = _flush_arrays(per)
+            if primed:
+                r = self._L.zs_deflate_batch_primed_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
+                                                           _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
+                                                           _P(d_status), _P(d_out_len), _P(d_check) if d_check else None,
+                                                           _P(hip_stream) if hip_stream else None, first, pos)
+                self._check(r, "zs_deflate_batch_primed_device")
+                return
             r = self._L.zs_deflate_batch_flush_device(self._ctx, compress_level(level), compress_wbits(fmt), n,
                                                       _P(d_in), in_off, in_len, _P(d_out), out_off, out_cap,
                                                       _P(d_status), _P(d_out_len), _P(d_check) if d_check else None,
@@ -1044,9 +1076,11 @@ def _layout(inputs):
     return b"".join(inputs), offs, lens
 
 
-def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None, params=None, flush=None):
+def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=None, params=None, flush=None,
+                  primed=False):
     """params: (the windowBits code, mem_level) for a _params entry (fn), which takes mem_level behind wbits.
-    flush: compress_flush's position lists for a _flush entry, which takes them behind `check`."""
+    flush: compress_flush's position lists for a _flush entry, which takes them behind `check`; primed: fn
+    is a _primed entry, which takes them without the flush argument."""
     n = len(inputs)
     if n == 0:
         return []
@@ -1058,7 +1092,7 @@ def _deflate_host(L, fn, handle, inputs, fmt, level, check, zdict=(), strategy=N
                 for b in inputs]
     elif flush is not None:
         caps = [(int(L.zs_deflate_bound_flush(len(b), wbits, len(flush[i]))) + 3) & ~3 for i, b in enumerate(inputs)]
-        zdict = (Z_FULL_FLUSH,) + _flush_arrays(flush)  # (the trailing arguments)
+        zdict = (() if primed else (Z_FULL_FLUSH,)) + _flush_arrays(flush)  # (the trailing arguments)
     elif zdict:
         caps = [(int(L.zs_deflate_bound_dict(len(b), wbits, zdict[2][i])) + 3) & ~3 for i, b in enumerate(inputs)]
     else:
@@ -1240,7 +1274,8 @@ class Pool:
         Engine._check(self, r, what)
 
     def compress_batch_detailed(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                                mem_level=8, flush_at=None, flush_every=None, bgzf=None):
+                                mem_level=8, flush_at=None, flush_every=None, bgzf=None, primed=False):
+        primed = compress_primed(primed, flush_at, flush_every, bgzf)
         block = compress_bgzf(bgzf, fmt, zdict, strategy, window_bits, mem_level, flush_at, flush_every)
         if block is not None:
             return _deflate_host_bgzf(self._L, self._L.zs_pool_deflate_batch_bgzf, self._pool, inputs, level,
@@ -1249,8 +1284,8 @@ class Pool:
         code = compress_params(fmt, window_bits, mem_level, zdict, strategy)
         per = compress_flush([len(b) for b in inputs], flush_at, flush_every, zdict, strategy, window_bits, mem_level)
         if per is not None:
-            return _deflate_host(self._L, self._L.zs_pool_deflate_batch_flush, self._pool, inputs, fmt, level,
-                                 self._check, flush=per)
+            fn = self._L.zs_pool_deflate_batch_primed if primed else self._L.zs_pool_deflate_batch_flush
+            return _deflate_host(self._L, fn, self._pool, inputs, fmt, level, self._check, flush=per, primed=primed)
         if not _params_default(window_bits, mem_level):
             return _deflate_host(self._L, self._L.zs_pool_deflate_batch_params, self._pool, inputs, fmt, level,
                                  self._check, params=(code, mem_level))
@@ -1263,14 +1298,14 @@ class Pool:
         return _deflate_host(self._L, self._L.zs_pool_deflate_batch, self._pool, inputs, fmt, level, self._check)
 
     def compress_batch_raw(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                           mem_level=8, flush_at=None, flush_every=None, bgzf=None):
+                           mem_level=8, flush_at=None, flush_every=None, bgzf=None, primed=False):
         return [(st, b) for st, b, _ in self.compress_batch_detailed(inputs, fmt, level, zdict, strategy, window_bits,
-                                                                     mem_level, flush_at, flush_every, bgzf)]
+                                                                     mem_level, flush_at, flush_every, bgzf, primed)]
 
     def compress_batch(self, inputs, fmt="deflate-raw", level=-1, zdict=None, strategy=0, window_bits=None,
-                       mem_level=8, flush_at=None, flush_every=None, bgzf=None):
+                       mem_level=8, flush_at=None, flush_every=None, bgzf=None, primed=False):
         return _ok_or_raise_c(self.compress_batch_raw(inputs, fmt, level, zdict, strategy, window_bits, mem_level,
-                                                      flush_at, flush_every, bgzf))
+                                                      flush_at, flush_every, bgzf, primed))
 
     def decompress_batch_detailed(self, inputs, fmt="deflate-raw", out_caps=None, zdict=None, restart=None, members=False,
                                   ranges=None):
