@@ -1,5 +1,5 @@
 """CPU check of what csrc/zs_plan.h decides for an inflate batch with restart points
-(zs_restart_validate, zs_plan_restart, zs_restart_layout, zs_plan_inflate over the segments' copies,
+(zs_restart_validate, zs_plan_restart, zs_section_put, zs_plan_inflate over the segments' copies,
 which capi.cpp runs before it launches anything): tools/emu/emu_plan_restart.cpp, plain g++, no ROCm
 headers."""
 import os

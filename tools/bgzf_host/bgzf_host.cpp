@@ -22,24 +22,8 @@
 #include "hip/hip_runtime.h"
 zs_dim3 threadIdx, blockIdx, blockDim;
 #include "../../zlib-streams-ts_amd/csrc/zs_bgzf.h"
-#if defined(__SANITIZE_ADDRESS__)
-#define ZS_ASAN 1
-#elif defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#define ZS_ASAN 1
-#endif
-#endif
-#ifdef ZS_ASAN
-#include <sanitizer/asan_interface.h>
-#endif
-
-static void rd(void* p, size_t n) {
-  if (fread(p, 1, n, stdin) != n) {
-    fprintf(stderr, "bgzf_host: short input\n");
-    exit(2);
-  }
-}
-static void wr(const void* p, size_t n) { fwrite(p, 1, n, stdout); }
+#define ZS_TOOL "bgzf_host"
+#include "host_stream.h"
 static void wr_rec(const zs_sync_rec& r, bool trusted) {
   const uint32_t t = trusted;
   wr(&r, 16);
@@ -57,21 +41,8 @@ int main(int argc, char** argv) {
     uint32_t n, out_cap;
     rd(&n, 4);
     rd(&out_cap, 4);
-    // the stream starts `mis` bytes into a 16-byte aligned buffer that ends with the aligned word of its
-    // last byte; the whole words in front of its first byte are poisoned (a sanitizer build), so any
-    // load outside the aligned words that hold the stream's bytes is reported
-    const uint32_t mis = (i * 7u + 1u) % 16u;
-    const size_t bytes = ((size_t)mis + n + 3) & ~size_t(3);
-    void* raw = nullptr;
-    if (posix_memalign(&raw, 16, bytes ? bytes : 4)) return 2;
-    uint8_t* buf = (uint8_t*)raw;
-    // (a BGZF header's first bytes right around the stream would show if a lane looked there)
-    for (size_t k = 0; k < bytes; k++) buf[k] = (const uint8_t[]){0x1f, 0x8b, 0x08, 0x04}[k & 3u];
-    uint8_t* s = buf + mis;
-    rd(s, n);
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_POISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
+    const HostStream hs(i, n, {0x1f, 0x8b, 0x08, 0x04});  // (bytes that would show as a candidate, or a header)
+    const uint8_t* s = hs.s;
     if (mode == 1) {
       for (uint32_t at = 0; at < n; at++) {
         bool t;
@@ -83,22 +54,16 @@ int main(int argc, char** argv) {
         wr_rec(r, t);
       }
     } else {
-      std::vector<uint32_t> cand;
-      const uint32_t sh16 = (uint32_t)((uintptr_t)s & 15u);
-      for (uint64_t u = 0; n && 16u * u < (uint64_t)sh16 + n; u++) {
-        int64_t q0;
-        uint32_t mask = zs_members_unit(s, n, u, q0);
-        for (uint32_t b = 0; b < 16u; b++)
-          if (mask >> b & 1u) cand.push_back((uint32_t)(q0 + b));
-      }
+      const std::vector<uint32_t> cand = host_scan(s, n, [&](uint64_t u, int64_t& q0) { return zs_members_unit(s, n, u, q0); });
       const uint32_t C = (uint32_t)cand.size();
       std::vector<zs_sync_rec> rec(1 + C);
+      const uint64_t cfirst[2] = {0, C};
       std::vector<uint8_t> rtrusted(1 + C);
       for (uint32_t x = 0; x <= C; x++) {
-        const uint64_t bi = (uint64_t)x + pass;  // lane x - 1 of the candidates: j + pass + 1
-        const uint32_t bound = bi < C ? cand[bi] : n;
+        bool at0;
+        const uint32_t bound = host_lane(x, cand, pass, n, at0);
         bool t;
-        rec[x] = zs_bgzf_size(s, n, x ? cand[x - 1] : 0u, bound, T, t);
+        rec[x] = zs_bgzf_size(s, n, at0 ? 0u : cand[x - 1], bound, T, t);
         rtrusted[x] = t;
         if (rec[x].end > (t ? n : bound)) {  // (a trusted lane reads its trailer's word, wherever its bound is)
           fprintf(stderr, "bgzf_host: stream %u lane %u ended at %u, past its bound %u\n", i, x, rec[x].end, bound);
@@ -109,7 +74,6 @@ int main(int argc, char** argv) {
       wr(cand.data(), 4ull * C);
       for (uint32_t x = 0; x <= C; x++) wr_rec(rec[x], rtrusted[x]);
       zs_members_plan p;
-      const uint64_t cfirst[2] = {0, C};
       uint32_t rounds = 0;
       for (;; rounds++) {  // the tail rounds, as members_batch runs them: members_size's lanes, unbounded
         zs_plan_members(1, &n, &out_cap, cfirst, cand.data(), rec.data(), p);
@@ -149,10 +113,6 @@ int main(int argc, char** argv) {
       wr(&ok, 4);
       wr(&total, 8);
     }
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_UNPOISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
-    free(raw);
   }
   return 0;
 }

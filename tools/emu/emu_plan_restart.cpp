@@ -1,7 +1,7 @@
 // emu_plan_restart.cpp -- what csrc/zs_plan.h decides for an inflate batch with restart points: the
 // validation order (zs_restart_validate), the segments, their copies' places in the gather buffer,
 // their output places and capacities, the route (zs_plan_restart), the call's section of the metadata
-// block (zs_restart_layout) and the segment batch's own plan (zs_plan_inflate over the copies'
+// block (zs_section_put over the plan's arrays) and the segment batch's own plan (zs_plan_inflate over the copies'
 // lengths), printed one line of key=value pairs per case for tests/test_plan_restart.py.  Plain C++,
 // no ROCm headers.
 //   g++ -std=c++17 -O2 -o emu_plan_restart tools/emu/emu_plan_restart.cpp && ./emu_plan_restart
@@ -52,7 +52,12 @@ static void segments(const char* name, int wbits, Call c) {
   zs_restart_plan p;
   zs_plan_restart(a.n, a.in_len, a.out_cap, a.rfirst, a.rin, a.rout, p);
   const zs_meta_layout ml(p.M);
-  const zs_restart_layout ro(ml.bytes, a.n, p.M);
+  // the call's section as restart_batch writes it behind the segment batch's block: the streams' arrays first
+  std::vector<uint8_t> sec;
+  const size_t s_in_off = zs_section_put(sec, nullptr, 8ull * a.n);
+  zs_section_put(sec, a.in_len, 4ull * a.n);
+  zs_section_put(sec, p.soff.data(), 4ull * p.M);
+  const size_t s_ptile = zs_section_put(sec, p.ptile.data(), 4ull * (p.M + 1));
   int aligned = 1, apart = 1, staged = 1;
   for (uint32_t g = 0; g < p.M; g++) {
     aligned &= (p.goff[g] & 15) == 0;
@@ -67,7 +72,7 @@ static void segments(const char* name, int wbits, Call c) {
          list(p.slen).c_str(), list(p.glen).c_str(), list(p.goff).c_str(), list(p.opos).c_str(), list(p.olen).c_str(),
          list(p.ocap).c_str(), list(p.stoff).c_str(), list(p.over).c_str(), list(p.gtile).c_str(), list(p.ptile).c_str(),
          (unsigned long long)p.gather_bytes, (unsigned long long)p.stage_bytes, aligned, apart, staged,
-         (int)(ro.in_off == ml.bytes && ro.bytes > ro.ptile && ro.bytes % 256 == 0));
+         (int)(s_in_off == 0 && sec.size() > s_ptile && (ml.bytes + sec.size()) % 256 == 0));
 }
 
 static void refusal(const char* name, int wbits, Call c, int nulls = 0, bool misalign = false) {

@@ -20,24 +20,8 @@
 #include "hip/hip_runtime.h"
 zs_dim3 threadIdx, blockIdx, blockDim;
 #include "../../zlib-streams-ts_amd/csrc/zs_members.h"
-#if defined(__SANITIZE_ADDRESS__)
-#define ZS_ASAN 1
-#elif defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#define ZS_ASAN 1
-#endif
-#endif
-#ifdef ZS_ASAN
-#include <sanitizer/asan_interface.h>
-#endif
-
-static void rd(void* p, size_t n) {
-  if (fread(p, 1, n, stdin) != n) {
-    fprintf(stderr, "members_host: short input\n");
-    exit(2);
-  }
-}
-static void wr(const void* p, size_t n) { fwrite(p, 1, n, stdout); }
+#define ZS_TOOL "members_host"
+#include "host_stream.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) return 2;
@@ -50,21 +34,8 @@ int main(int argc, char** argv) {
     uint32_t n, out_cap;
     rd(&n, 4);
     rd(&out_cap, 4);
-    // the stream starts `mis` bytes into a 16-byte aligned buffer that ends with the aligned word of its
-    // last byte; the whole words in front of its first byte are poisoned (a sanitizer build), so any
-    // load outside the aligned words that hold the stream's bytes is reported
-    const uint32_t mis = (i * 7u + 1u) % 16u;
-    const size_t bytes = ((size_t)mis + n + 3) & ~size_t(3);
-    void* raw = nullptr;
-    if (posix_memalign(&raw, 16, bytes ? bytes : 4)) return 2;
-    uint8_t* buf = (uint8_t*)raw;
-    // (1f 8b 08 00 right around the stream would show as a candidate if the scan looked there)
-    for (size_t k = 0; k < bytes; k++) buf[k] = (const uint8_t[]){0x1f, 0x8b, 0x08, 0x00}[k & 3u];
-    uint8_t* s = buf + mis;
-    rd(s, n);
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_POISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
+    const HostStream hs(i, n, {0x1f, 0x8b, 0x08, 0x00});  // (bytes that would show as a candidate, or a header)
+    const uint8_t* s = hs.s;
     if (mode == 1) {
       for (uint32_t at = 0; at < n; at++) {
         const zs_sync_rec r = zs_members_size(s, n, at, n, T);
@@ -75,20 +46,14 @@ int main(int argc, char** argv) {
         wr(&r, 16);
       }
     } else {
-      std::vector<uint32_t> cand;
-      const uint32_t sh16 = (uint32_t)((uintptr_t)s & 15u);
-      for (uint64_t u = 0; n && 16u * u < (uint64_t)sh16 + n; u++) {
-        int64_t q0;
-        uint32_t mask = zs_members_unit(s, n, u, q0);
-        for (uint32_t b = 0; b < 16u; b++)
-          if (mask >> b & 1u) cand.push_back((uint32_t)(q0 + b));
-      }
+      const std::vector<uint32_t> cand = host_scan(s, n, [&](uint64_t u, int64_t& q0) { return zs_members_unit(s, n, u, q0); });
       const uint32_t C = (uint32_t)cand.size();
       std::vector<zs_sync_rec> rec(1 + C);
+      const uint64_t cfirst[2] = {0, C};
       for (uint32_t x = 0; x <= C; x++) {
-        const uint64_t bi = (uint64_t)x + pass;  // lane x - 1 of the candidates: j + pass + 1
-        const uint32_t bound = bi < C ? cand[bi] : n;
-        rec[x] = zs_members_size(s, n, x ? cand[x - 1] : 0u, bound, T);
+        bool at0;
+        const uint32_t bound = host_lane(x, cand, pass, n, at0);
+        rec[x] = zs_members_size(s, n, at0 ? 0u : cand[x - 1], bound, T);
         if (rec[x].end > bound) {
           fprintf(stderr, "members_host: stream %u lane %u ended at %u, past its bound %u\n", i, x, rec[x].end, bound);
           return 3;
@@ -98,7 +63,6 @@ int main(int argc, char** argv) {
       wr(cand.data(), 4ull * C);
       wr(rec.data(), 16ull * (1 + C));
       zs_members_plan p;
-      const uint64_t cfirst[2] = {0, C};
       uint32_t rounds = 0;
       for (;; rounds++) {  // the tail rounds, as members_batch runs them
         zs_plan_members(1, &n, &out_cap, cfirst, cand.data(), rec.data(), p);
@@ -120,10 +84,6 @@ int main(int argc, char** argv) {
         wr(&p.ocap[k], 4);
       }
     }
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_UNPOISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
-    free(raw);
   }
   return 0;
 }

@@ -20,24 +20,8 @@
 #include "hip/hip_runtime.h"
 zs_dim3 threadIdx, blockIdx, blockDim;
 #include "../../zlib-streams-ts_amd/csrc/zs_sync.h"
-#if defined(__SANITIZE_ADDRESS__)
-#define ZS_ASAN 1
-#elif defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#define ZS_ASAN 1
-#endif
-#endif
-#ifdef ZS_ASAN
-#include <sanitizer/asan_interface.h>
-#endif
-
-static void rd(void* p, size_t n) {
-  if (fread(p, 1, n, stdin) != n) {
-    fprintf(stderr, "sync_host: short input\n");
-    exit(2);
-  }
-}
-static void wr(const void* p, size_t n) { fwrite(p, 1, n, stdout); }
+#define ZS_TOOL "sync_host"
+#include "host_stream.h"
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;
@@ -49,20 +33,8 @@ int main(int argc, char** argv) {
   for (uint32_t i = 0; i < count; i++) {
     uint32_t n;
     rd(&n, 4);
-    // the stream starts `mis` bytes into a 16-byte aligned buffer that ends with the aligned word of its
-    // last byte; the whole words in front of its first byte are poisoned (a sanitizer build), so any
-    // load outside the aligned words that hold the stream's bytes is reported
-    const uint32_t mis = (i * 7u + 1u) % 16u;
-    const size_t bytes = ((size_t)mis + n + 3) & ~size_t(3);
-    void* raw = nullptr;
-    if (posix_memalign(&raw, 16, bytes ? bytes : 4)) return 2;
-    uint8_t* buf = (uint8_t*)raw;
-    memset(buf, 0xff, bytes);  // (00 00 FF FF right around the stream would show as a candidate)
-    uint8_t* s = buf + mis;
-    rd(s, n);
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_POISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
+    const HostStream hs(i, n, {0xff, 0xff, 0xff, 0xff});  // (bytes that would show as a candidate, or a header)
+    const uint8_t* s = hs.s;
     const uint32_t first = std::min(zs_wrapper_header_len_of(wbits, s, n), n);
     wr(&first, 4);
     if (mode == 1) {
@@ -75,27 +47,20 @@ int main(int argc, char** argv) {
         wr(&r, 16);
       }
     } else {
-      std::vector<uint32_t> cand;
-      const uint32_t sh16 = (uint32_t)((uintptr_t)s & 15u);
-      for (uint64_t u = 0; n && 16u * u < (uint64_t)sh16 + n; u++) {
-        int64_t q0;
-        uint32_t mask = zs_sync_unit(s, n, first, u, q0);
-        for (uint32_t b = 0; b < 16u; b++)
-          if (mask >> b & 1u) cand.push_back((uint32_t)(q0 + b));
-      }
+      const std::vector<uint32_t> cand = host_scan(s, n, [&](uint64_t u, int64_t& q0) { return zs_sync_unit(s, n, first, u, q0); });
       const uint32_t C = (uint32_t)cand.size();
       std::vector<zs_sync_rec> rec(1 + C);
+      const uint64_t cfirst[2] = {0, C};
       for (uint32_t x = 0; x <= C; x++) {
-        const uint64_t bi = (uint64_t)x + pass;  // lane x - 1 of the candidates: j + pass + 1
-        const uint32_t bound = bi < C ? cand[bi] : n;
-        rec[x] = zs_sync_size(s, n, x ? cand[x - 1] : first, bound, T);
+        bool at0;
+        const uint32_t bound = host_lane(x, cand, pass, n, at0);
+        rec[x] = zs_sync_size(s, n, at0 ? first : cand[x - 1], bound, T);
         if (rec[x].end > bound) {
           fprintf(stderr, "sync_host: stream %u lane %u ended at %u, past its bound %u\n", i, x, rec[x].end, bound);
           return 3;
         }
       }
       zs_sync_plan p;
-      const uint64_t cfirst[2] = {0, C};
       zs_plan_sync(1, &n, &first, cfirst, cand.data(), rec.data(), p);
       if (!p.tstream.empty()) {  // a chain that ends at a lane its bound stopped: the whole tail's reach, as sync_batch
         const zs_sync_rec tail = zs_sync_size(s, n, p.tstart[0], n, T, true);
@@ -113,10 +78,6 @@ int main(int argc, char** argv) {
         wr(&p.rout[k], 4);
       }
     }
-#ifdef ZS_ASAN
-    if (mis & ~3u) ASAN_UNPOISON_MEMORY_REGION(buf, mis & ~3u);
-#endif
-    free(raw);
   }
   return 0;
 }

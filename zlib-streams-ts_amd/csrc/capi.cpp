@@ -129,24 +129,23 @@ struct zs_ctx {
     bool members = false;       // the members were found by the call (zs_last_members)
     uint32_t bgzf_trusted = 0;  // a _bgzf call's planned members sized from their headers (zs_last_bgzf_trusted)
   } call;
-  // a batch with restart points: the plan, the closed copies of the segments, the staging
-  // route's regions, the segments' results (5 arrays of M), their marker flags, the streams' checksums
-  // and trailer values (2 arrays of n)
+  // The entries that decode a stream's pieces as the members of one batch (restart points given, DESIGN 4.11, or
+  // found, 4.13; a gzip file's members, 4.14; BGZF blocks, 4.15, and ranges, 4.17).  One public call runs one
+  // search and one piece decode, so each has one family of buffers.
+  // The search (cand_search, cand_tail): the streams' arrays, first points and tiles; the scan's tiles; the
+  // candidates; the lanes' records and, in a _bgzf call, a byte per record; the tail rounds' lists and records
+  Buf fmeta, ftile, fcand, frec, ftail, ftrust;
+  // The pieces (pieces_begin, pieces_decode): a members or range call's arrays for the place and the stitch, the
+  // pieces' results (5 arrays of M), the staging route's regions, the lengths the check values are taken over
+  Buf pseg, pres, pstage, plen;
+  std::vector<uint8_t> hsec, hck;  // the host's copy of the section being uploaded; of a check value's part map
+  // a restart call's own: the closed copies of the segments, their marker flags, the streams' checksums and
+  // trailer values (2 arrays of n)
+  Buf rgather, rmark, rsum;
   zs_restart_plan rp;
-  Buf rgather, rstage, rres, rmark, rsum;
-  std::vector<uint8_t> rhmeta;
-  // a batch that finds its restart points: the streams' arrays and first points, the scan's
-  // tiles, the candidates, the lanes' records; the plan's points, which zs_last_restart_points returns
-  Buf ymeta, ytile, ycand, yrec, ytail;
-  zs_sync_plan yp;
-  // a batch that finds its gzip members: the streams' arrays and the scan's tiles, the candidates,
-  // the lanes' records, the tail rounds' lists and records; the members' arrays for the place and the stitch,
-  // their results (5 arrays of M), the staging route's regions, the lengths the check values are taken over;
-  // the plan, which zs_last_members returns; a _bgzf call's byte per record
-  Buf mbmeta, mbtile, mbcand, mbrec, mbtail, mbseg, mbres, mbstage, mblen, mbtrust;
-  std::vector<uint8_t> mbh, mbck;
-  zs_members_plan mp;
-  zs_bgzf_range_plan brp;  // a _bgzf_range call's plan (DESIGN 4.17)
+  zs_sync_plan yp;         // the found points, which zs_last_restart_points returns
+  zs_members_plan mp;      // the found members, which zs_last_members returns
+  zs_bgzf_range_plan brp;  // a _bgzf_range call's plan
   zs_dict_set dset;
   zs_checksum_plan cp;     // the current batch's data checksum (zs_plan_checksum)
   Buf ckvals;              // ... its parts' values
@@ -2221,6 +2220,88 @@ static int inflate_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut&
   return inflate_launch(c, o, st, wbits, h, b, dd, ck, m_end, out);
 }
 
+// zs_inflate_validate's findings, as the entries report them
+static int inflate_fail(zs_inflate_err e) { return fail(ZS_STREAM_ERROR, "%s", zs_inflate_err_text(e)); }
+// The arrays of a call as validation reads them (the host entries stage their own regions)
+static zs_inflate_call inflate_call(const Batch& h, bool caller_regions, const DictIn* dict) {
+  zs_inflate_call a;
+  a.n = h.n;
+  a.out_off = caller_regions ? h.out_off : nullptr;
+  a.out_cap = h.out_cap;
+  a.caller_regions = caller_regions;
+  a.dict = dict != nullptr;
+  a.dict_arrays = dict && dict->off && dict->len;
+  a.dict_buf = dict && dict->d_dict;
+  a.dict_len = a.dict_arrays ? dict->len : nullptr;
+  return a;
+}
+
+// ---- The entries that decode a stream's PIECES as the members of one batch and join them per stream: the
+// segments between restart points, a gzip file's members (4.14), the blocks of a BGZF range (4.17).
+// pieces_begin: where each piece lies, decodes and belongs (the caller uploads these with its own arrays), and
+// room for the pieces' results and the staging route's regions.
+struct PieceRun {
+  std::vector<uint64_t> src, ooff, dst;
+  InflateOut seg;  // the pieces' results: 5 arrays of M
+};
+static int pieces_begin(zs_ctx* c, const Batch& h, const zs_pieces& p, PieceRun& r) {
+  const uint32_t M = p.M;
+  r.src.resize(M);
+  r.ooff.resize(M);
+  r.dst.resize(M);
+  for (uint32_t g = 0; g < M; g++) {
+    const uint32_t i = p.rstream[g];
+    r.src[g] = h.in_off[i] + p.soff[g];
+    r.dst[g] = h.out_off[i] + p.opos[g];
+    // (a piece without room stores nothing: it stays at its stream's start)
+    r.ooff[g] = p.in_place ? h.out_off[i] + (p.ocap[g] ? p.opos[g] : 0u) : p.stoff[g];
+  }
+  HIPCHK(c->pres.ensure(20ull * M + 64));
+  HIPCHK(c->pstage.ensure(p.stage_bytes));
+  int32_t* const sr = c->pres.as<int32_t>();
+  r.seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
+  return ZS_OK;
+}
+// pieces_decode: the pieces as M members of one batch (in, in_off, in_len: host arrays as inflate_batch's),
+// decoded with zlib semantics -- behind a reset or a member's trailer there is no call boundary of the
+// reference's to reproduce, whatever the context's inflate_ref_wrap says -- and, with d_ptile, moved from
+// staging to their places where the route is staged (d_*: the uploaded r.ooff, p.ocap, r.dst, p.ptile).
+static int pieces_decode(zs_ctx* c, hipStream_t st, int wbits, const Batch& h, const zs_pieces& p, const PieceRun& r,
+                         const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* d_ooff,
+                         const uint32_t* d_ocap, const uint64_t* d_dst, const uint32_t* d_ptile) {
+  const uint32_t M = p.M;
+  if (!M) return ZS_OK;
+  uint8_t* const stage = c->pstage.as<uint8_t>();
+  zs_route_opts o2 = c->o;
+  o2.inflate_ref_wrap = false;
+  const Batch hs = {M, in, in_off, in_len, p.in_place ? h.out : stage, r.ooff.data(), p.ocap.data()};
+  if (const int ri = inflate_batch(c, wbits, hs, r.seg, st, nullptr, &o2)) return ri;
+  if (d_ptile && !p.in_place) {
+    if (p.ptile[M])
+      zs_k_restart_place<<<std::min(p.ptile[M], 32u * c->o.ncu), 256, 0, st>>>(stage, d_ooff, d_ocap, r.seg.out_len, d_dst,
+                                                                               d_ptile, M, h.out);
+    MARK("restart_place");
+  }
+  return ZS_OK;
+}
+// The check value over the joined output, the lengths the stitch wrote; the pieces' own values
+// are verified by the decoders.  The part map goes to the front of the metadata block, which the pieces'
+// batch is done with in stream order.
+static int stream_check(zs_ctx* c, hipStream_t st, const Batch& h, const uint64_t* d_out_off, const uint32_t* cklen,
+                        uint32_t* check) {
+  const zs_checksum_plan* ck;
+  size_t ck_bytes;
+  if (const int rc = ck_prepare(c, true, h.n, h.out_cap, &ck, &ck_bytes)) return rc;
+  if (ck_bytes) {
+    HIPCHK(c->meta.ensure(ck_bytes));
+    c->hck.assign(ck_bytes, 0);
+    ck_fill(ck, c->hck.data());
+    HIPCHK(hipMemcpyAsync(c->meta.p, c->hck.data(), ck_bytes, hipMemcpyHostToDevice, st));
+  }
+  ck_launch(c, st, *ck, 0, h.n, h.out, d_out_off, cklen, check, 2);
+  return ZS_OK;
+}
+
 // ---- restart points (inflateSync, inflate.ts:1267-1337): a stream's segments decoded as the
 // members of one raw batch and joined per stream.  A fault of the arguments is reported before the
 // context is looked at (restart_refused: zs_restart_validate, then the null context).
@@ -2250,84 +2331,54 @@ static int restart_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut&
   zs_restart_plan& p = c->rp;
   zs_plan_restart(n, h.in_len, h.out_cap, rs.first, rs.in, rs.out, p);
   const uint32_t M = p.M;
-  // the segment batch's metadata block is inflate_batch's own (it uploads it); this call's section
-  // lies behind it, the streams' checksum map behind that
-  const zs_meta_layout ml(M);
-  const zs_restart_layout ro(ml.bytes, n, M);
   const zs_checksum_plan* ck;
   size_t ck_bytes;
   if (const int rc = ck_prepare(c, wbits > 0, n, h.out_cap, &ck, &ck_bytes)) return rc;
+  PieceRun r;
+  if (const int rc = pieces_begin(c, h, p, r)) return rc;
   HIPCHK(c->rgather.ensure(p.gather_bytes));
-  HIPCHK(c->rstage.ensure(p.stage_bytes));
-  HIPCHK(c->rres.ensure(20ull * M + 64));
   HIPCHK(c->rmark.ensure(4ull * M + 16));
   HIPCHK(c->rsum.ensure(8ull * n + 16));
-  HIPCHK(c->meta.ensure(ro.bytes + ck_bytes));  // (before inflate_batch's own ensure, which then keeps the block)
-  // where each segment lies, decodes and belongs
-  std::vector<uint64_t> src(M), ooff(M), dst(M);
-  for (uint32_t g = 0; g < M; g++) {
-    const uint32_t i = p.rstream[g];
-    src[g] = h.in_off[i] + p.soff[g];
-    dst[g] = h.out_off[i] + p.opos[g];
-    // (a segment without room stores nothing: it stays at its stream's start)
-    ooff[g] = p.in_place ? h.out_off[i] + (p.ocap[g] ? p.opos[g] : 0u) : p.stoff[g];
-  }
-  c->rhmeta.assign(ro.bytes + ck_bytes - ml.bytes, 0);
-  // (the layout's offsets count from the block's start, this host copy from the section's)
-  auto hm = [&](size_t at) { return c->rhmeta.data() + (at - ml.bytes); };
-  memcpy(hm(ro.in_off), h.in_off, 8ull * n);
-  memcpy(hm(ro.in_len), h.in_len, 4ull * n);
-  memcpy(hm(ro.out_off), h.out_off, 8ull * n);
-  memcpy(hm(ro.over), p.over.data(), 4ull * n);
-  memcpy(hm(ro.rfirst), p.rfirst.data(), 4ull * (n + 1));
-  memcpy(hm(ro.src), src.data(), 8ull * M);
-  memcpy(hm(ro.soff), p.soff.data(), 4ull * M);
-  memcpy(hm(ro.slen), p.slen.data(), 4ull * M);
-  memcpy(hm(ro.goff), p.goff.data(), 8ull * M);
-  memcpy(hm(ro.glen), p.glen.data(), 4ull * M);
-  memcpy(hm(ro.ooff), ooff.data(), 8ull * M);
-  memcpy(hm(ro.ocap), p.ocap.data(), 4ull * M);
-  memcpy(hm(ro.olen), p.olen.data(), 4ull * M);
-  memcpy(hm(ro.opos), p.opos.data(), 4ull * M);
-  memcpy(hm(ro.dst), dst.data(), 8ull * M);
-  memcpy(hm(ro.gtile), p.gtile.data(), 4ull * (M + 1));
-  memcpy(hm(ro.ptile), p.ptile.data(), 4ull * (M + 1));
-  ck_fill(ck, hm(ro.bytes));
-  HIPCHK(hipMemcpyAsync(c->meta.as<uint8_t>() + ml.bytes, c->rhmeta.data(), c->rhmeta.size(), hipMemcpyHostToDevice, st));
+  // the segment batch's metadata block is inflate_batch's own (it uploads it); this call's section lies
+  // behind it: what the restart kernels read of the streams and of the segments, then the streams' checksum map
+  std::vector<uint8_t>& hs = c->hsec;
+  hs.clear();
+  const size_t base = zs_meta_layout(M).bytes;
+  auto put = [&](const void* q, size_t bytes) { return base + zs_section_put(hs, q, bytes); };
+  const size_t s_in_off = put(h.in_off, 8ull * n), s_in_len = put(h.in_len, 4ull * n), s_out_off = put(h.out_off, 8ull * n),
+               s_over = put(p.over.data(), 4ull * n), s_rfirst = put(p.rfirst.data(), 4ull * (n + 1)),
+               s_src = put(r.src.data(), 8ull * M), s_soff = put(p.soff.data(), 4ull * M),
+               s_slen = put(p.slen.data(), 4ull * M), s_goff = put(p.goff.data(), 8ull * M),
+               s_glen = put(p.glen.data(), 4ull * M), s_ooff = put(r.ooff.data(), 8ull * M),
+               s_ocap = put(p.ocap.data(), 4ull * M), s_olen = put(p.olen.data(), 4ull * M),
+               s_opos = put(p.opos.data(), 4ull * M), s_dst = put(r.dst.data(), 8ull * M),
+               s_gtile = put(p.gtile.data(), 4ull * (M + 1)), s_ptile = put(p.ptile.data(), 4ull * (M + 1)),
+               s_ck = put(nullptr, ck_bytes);
+  ck_fill(ck, hs.data() + (s_ck - s_in_off));
+  HIPCHK(c->meta.ensure(s_in_off + hs.size()));  // (before inflate_batch's own ensure, which then keeps the block)
+  HIPCHK(hipMemcpyAsync(c->meta.as<uint8_t>() + s_in_off, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
   const uint8_t* dm = c->meta.as<uint8_t>();
   auto u32 = [&](size_t at) { return (const uint32_t*)(dm + at); };
   auto u64 = [&](size_t at) { return (const uint64_t*)(dm + at); };
   uint8_t* gather = c->rgather.as<uint8_t>();
   uint32_t* mark_ = c->rmark.as<uint32_t>();
-  const uint32_t gmax = 32u * c->o.ncu;  // workgroups of the gather and the place: grid-stride beyond
   MARK("start");
-  if (p.gtile[M])
-    zs_k_restart_gather<<<std::min(p.gtile[M], gmax), 256, 0, st>>>(h.in, u64(ro.src), u32(ro.slen), u32(ro.glen),
-                                                                   u64(ro.goff), u32(ro.gtile), M, gather, mark_);
+  if (p.gtile[M])  // (32 workgroups per CU: grid-stride beyond)
+    zs_k_restart_gather<<<std::min(p.gtile[M], 32u * c->o.ncu), 256, 0, st>>>(h.in, u64(s_src), u32(s_slen), u32(s_glen),
+                                                                              u64(s_goff), u32(s_gtile), M, gather, mark_);
   MARK("restart_gather");
   HIPCHK(hipGetLastError());
-  // the segments as M raw members, decoded with zlib semantics: behind a reset there is no call
-  // boundary of the reference's to reproduce, whatever the context's inflate_ref_wrap says
-  int32_t* const sr = c->rres.as<int32_t>();
-  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
-  zs_route_opts o2 = c->o;
-  o2.inflate_ref_wrap = false;
-  const Batch hs = {M, gather, p.goff.data(), p.glen.data(), p.in_place ? h.out : c->rstage.as<uint8_t>(), ooff.data(),
-                    p.ocap.data()};
-  if (const int ri = inflate_batch(c, -15, hs, seg, st, nullptr, &o2)) return ri;
-  if (!p.in_place) {
-    if (p.ptile[M])
-      zs_k_restart_place<<<std::min(p.ptile[M], gmax), 256, 0, st>>>(c->rstage.as<uint8_t>(), u64(ro.ooff), u32(ro.ocap),
-                                                                    seg.out_len, u64(ro.dst), u32(ro.ptile), M, h.out);
-    MARK("restart_place");
-  }
+  if (const int ri = pieces_decode(c, st, -15, h, p, r, gather, p.goff.data(), p.glen.data(), u64(s_ooff), u32(s_ocap),
+                                   u64(s_dst), u32(s_ptile)))
+    return ri;
+  const InflateOut& seg = r.seg;
   uint32_t* sum = c->rsum.as<uint32_t>();
   uint32_t* want = sum + n;
-  zs_k_restart_stitch<<<n, 64, 0, st>>>(h.in, u64(ro.in_off), u32(ro.in_len), u32(ro.over), u32(ro.rfirst), u32(ro.soff),
-                                        u32(ro.slen), u32(ro.olen), u32(ro.opos), mark_, seg.status, seg.msg, seg.out_len,
+  zs_k_restart_stitch<<<n, 64, 0, st>>>(h.in, u64(s_in_off), u32(s_in_len), u32(s_over), u32(s_rfirst), u32(s_soff),
+                                        u32(s_slen), u32(s_olen), u32(s_opos), mark_, seg.status, seg.msg, seg.out_len,
                                         seg.consumed, wbits, n, out.status, out.phase, out.msg, out.out_len, out.consumed, want);
   // the check value over the joined output, the lengths the stitch wrote, against the trailer's
-  if (wbits > 0) ck_launch(c, st, *ck, ro.bytes, n, h.out, u64(ro.out_off), out.out_len, sum, wbits == 31 ? 2 : 1);
+  if (wbits > 0) ck_launch(c, st, *ck, s_ck, n, h.out, u64(s_out_off), out.out_len, sum, wbits == 31 ? 2 : 1);
   zs_k_restart_check<<<(n + 255) / 256, 256, 0, st>>>(sum, want, wbits, n, out.status, out.phase, out.msg, out.out_len,
                                                       out.consumed, out.check);
   MARK("restart_stitch");
@@ -2335,158 +2386,46 @@ static int restart_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut&
   return ZS_OK;
 }
 
-// ---- restart points found from the bytes (inflateSync / syncsearch, inflate.ts:1267-1337).
-// A fault of the arguments is reported before the context is looked at (zs_sync_validate, then the null
-// context).
-static int sync_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
-  zs_inflate_call a;
-  a.n = h.n;
-  a.out_off = device_entry ? h.out_off : nullptr;
-  a.out_cap = h.out_cap;
-  a.caller_regions = device_entry;
-  if (const zs_sync_err e = zs_sync_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_sync_err_text(e));
-  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
-}
-
-// The device decode of a validated, non-empty batch that finds its own points (regions as
-// inflate_batch's).  first: the streams' first points where the caller has the bytes (the host
-// entries), else zs_k_sync_first computes them.  The scan and the size decode run on st, which is
-// then waited for: the points are planned here, from the candidates and the lanes' records.  The
-// candidate list has the size the calls before needed; when this call has more, the emit pass and
-// the size decode run once more over the grown list (and st is waited for a second time); so it is
-// where a chain ends at a lane its bound stopped (zs_k_sync_tail).
-static int sync_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, hipStream_t st, const uint32_t* first) {
-  const uint32_t n = h.n;
-  std::vector<uint32_t> sh16(n), stile;
-  uint64_t tin = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    sh16[i] = (uint32_t)(((uintptr_t)h.in + h.in_off[i]) & 15u);
-    tin += h.in_len[i];
-  }
-  zs_plan_sync_tiles(n, h.in_len, sh16.data(), stile);
-  const uint32_t T = stile[n];
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t m_off = 0, m_len = up256(8ull * n), m_first = m_len + up256(4ull * n), m_tile = m_first + up256(4ull * n),
-               m_end = m_tile + up256(4ull * (n + 1));
-  HIPCHK(c->ymeta.ensure(m_end));
-  HIPCHK(c->ytile.ensure(8ull * T + 16));
-  HIPCHK(c->ycand.ensure(4ull * (tin / 2048 + 1024)));
-  std::vector<uint8_t> hm(m_end, 0);
-  memcpy(hm.data() + m_off, h.in_off, 8ull * n);
-  memcpy(hm.data() + m_len, h.in_len, 4ull * n);
-  if (first) memcpy(hm.data() + m_first, first, 4ull * n);
-  memcpy(hm.data() + m_tile, stile.data(), 4ull * (n + 1));
-  HIPCHK(hipMemcpyAsync(c->ymeta.p, hm.data(), m_end, hipMemcpyHostToDevice, st));
-  const uint8_t* dm = c->ymeta.as<uint8_t>();
-  const uint64_t* d_off = (const uint64_t*)(dm + m_off);
-  const uint32_t* d_len = (const uint32_t*)(dm + m_len);
-  uint32_t* d_first = (uint32_t*)(c->ymeta.as<uint8_t>() + m_first);
-  const uint32_t* d_tile = (const uint32_t*)(dm + m_tile);
-  uint64_t* tcount = c->ytile.as<uint64_t>();
-  const uint32_t grid = std::max(1u, std::min(T, 32u * c->o.ncu));
-  MARK("start");
-  if (!first) zs_k_sync_first<<<(n + 255) / 256, 256, 0, st>>>(h.in, d_off, d_len, wbits, n, d_first);
-  zs_k_sync_scan<false><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_first, d_tile, n, tcount, nullptr, 0);
-  zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tcount, T + 1);
-  HIPCHK(hipGetLastError());
-  std::vector<uint64_t> tpre(T + 1);
-  for (int round = 0;; round++) {
-    const uint64_t cap = c->ycand.cap / 4;
-    HIPCHK(c->yrec.ensure(sizeof(zs_sync_rec) * (n + cap)));
-    zs_k_sync_scan<true><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_first, d_tile, n, tcount, c->ycand.as<uint32_t>(), cap);
-    MARK("sync_scan");
-    // (a lane per stream and per place of the list: the lanes past the candidates' count return at once)
-    const uint64_t lanes = std::min<uint64_t>(n + cap, ZS_RESTART_SEG_MAX);
-    zs_k_sync_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
-        h.in, d_off, d_len, d_first, d_tile, n, tcount, c->ycand.as<uint32_t>(), cap, c->o.sync_pass,
-        c->yrec.as<zs_sync_rec>());
-    MARK("sync_size");
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(tpre.data(), tcount, 8ull * (T + 1), hipMemcpyDeviceToHost));
-    if (!zs_sync_count_ok(n, tpre[T]))
-      return fail(ZS_STREAM_ERROR, "%s", "too many restart candidates (more than 67,108,863 with the streams in one call)");
-    if (tpre[T] <= cap) break;
-    if (round) return fail(ZS_MEM_ERROR, "%s", "the restart candidates' list did not settle");
-    HIPCHK(c->ycand.ensure(4ull * tpre[T]));
-  }
-  const uint64_t C = tpre[T];
-  std::vector<uint32_t> cand(C), hfirst(n);
-  std::vector<zs_sync_rec> rec(n + C);
-  if (C) HIPCHK(hipMemcpy(cand.data(), c->ycand.p, 4ull * C, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rec.data(), c->yrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hfirst.data(), d_first, 4ull * n, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> cfirst(n + 1);
-  for (uint32_t i = 0; i <= n; i++) cfirst[i] = tpre[stile[i]];
-  zs_plan_sync(n, h.in_len, hfirst.data(), cfirst.data(), cand.data(), rec.data(), c->yp);
-  if (const uint32_t m = (uint32_t)c->yp.tstream.size()) {
-    // chains that end at a lane its bound stopped: the whole tail's reach (zs_k_sync_tail), then the plan again
-    const size_t t_start = up256(4ull * m);
-    HIPCHK(c->ytail.ensure(2 * t_start + sizeof(zs_sync_rec) * m));
-    uint8_t* dt = c->ytail.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(dt, c->yp.tstream.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dt + t_start, c->yp.tstart.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    zs_k_sync_tail<<<(m + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES, ZS_SYNC_LANES, 0, st>>>(
-        h.in, d_off, d_len, (const uint32_t*)dt, (const uint32_t*)(dt + t_start), m, (zs_sync_rec*)(dt + 2 * t_start));
-    MARK("sync_size");
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<zs_sync_rec> tail(m);
-    HIPCHK(hipMemcpy(tail.data(), dt + 2 * t_start, sizeof(zs_sync_rec) * m, hipMemcpyDeviceToHost));
-    const std::vector<uint64_t> trec = c->yp.trec;
-    for (uint32_t k = 0; k < m; k++) rec[trec[k]].reach = std::max(rec[trec[k]].reach, tail[k].reach);
-    zs_plan_sync(n, h.in_len, hfirst.data(), cfirst.data(), cand.data(), rec.data(), c->yp);
-  }
-  {  // the plan's points pass the restart entries' validation by construction: nothing is launched otherwise
-    zs_restart_call a;
-    a.n = n;
-    a.in_len = h.in_len;
-    a.out_cap = h.out_cap;
-    a.rfirst = c->yp.rfirst.data();
-    a.rin = c->yp.rin.data();
-    a.rout = c->yp.rout.data();
-    if (const zs_restart_err e = zs_restart_validate(wbits, a))
-      return fail(ZS_MEM_ERROR, "the found restart points are refused: %s", zs_restart_err_text(e));
-  }
-  c->call.sync = true;
-  return restart_batch(c, wbits, h, out, st, {c->yp.rfirst.data(), c->yp.rin.data(), c->yp.rout.data()});
-}
-
-// ---- a gzip file's members found from the bytes (zlib's gz_look, gzread.c).  A fault of the
-// arguments is reported before the context is looked at (zs_members_validate, then the null context).
-static int members_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
-  zs_inflate_call a;
-  a.n = h.n;
-  a.out_off = device_entry ? h.out_off : nullptr;
-  a.out_cap = h.out_cap;
-  a.caller_regions = device_entry;
-  if (const zs_members_err e = zs_members_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
-  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
-}
-
-// The device decode of a validated, non-empty gzip batch whose streams hold any number of members
-// (regions as inflate_batch's).  The scan and the size decode run on st, which is then waited for: the
-// members are planned here, from the candidates and the lanes' records.  st is waited for once more where
-// the candidates outgrow the list the context keeps, and once per tail round (zs_k_members_tail).  The
-// members then decode as ONE gzip batch on the caller's input, with zlib semantics, and are joined per stream.
-// bgzf: the _bgzf entries' mode.  It differs in three places: the sizing launch is zs_k_bgzf_size,
-// which trusts the headers it can; the plan's members get their flags (zs_plan_bgzf_trusted); the stitch
-// reports a flagged member's capacity outcome as its header's lie.
-// The search of members_batch and of bgzf_range_batch: the scan's two passes and the sizing launch over the
-// streams of h, st waited for, then the candidates, the lanes' records and (bgzf) their trusted bytes on the host
-struct MembersFound {
-  std::vector<uint32_t> cand;
+// ---- The search of the entries that find their pieces from the bytes: restart points (inflateSync /
+// syncsearch, inflate.ts:1267-1337), a gzip file's members (zlib's gz_look, gzread.c),
+// BGZF blocks sized from their headers where those can be trusted.  The kind selects the
+// scan's rule, the sizing and tail kernels, the marks' names and the two refusals' texts.
+enum FoundKind { FOUND_SYNC, FOUND_MEMBERS, FOUND_BGZF };
+static const struct {
+  const char *scan, *size, *many, *unsettled;
+} kFound[3] = {
+    {"sync_scan", "sync_size", "too many restart candidates (more than 67,108,863 with the streams in one call)",
+     "the restart candidates' list did not settle"},
+    {"members_scan", "members_size", "too many member candidates (more than 67,108,863 with the streams in one call)",
+     "the member candidates' list did not settle"},
+    {"members_scan", "bgzf_size", "too many member candidates (more than 67,108,863 with the streams in one call)",
+     "the member candidates' list did not settle"},
+};
+struct Found {
+  std::vector<uint32_t> cand, first;  // first: the streams' first points (FOUND_SYNC)
   std::vector<zs_sync_rec> rec;
-  std::vector<uint8_t> rtrusted;  // per record
+  std::vector<uint8_t> rtrusted;  // per record (FOUND_BGZF)
   std::vector<uint64_t> cfirst;
-  const uint64_t* d_off = nullptr;  // the streams' offsets and lengths on the device (c->mbmeta)
+  const uint64_t* d_off = nullptr;  // the streams' offsets and lengths on the device (c->fmeta)
   const uint32_t* d_len = nullptr;
 };
-// first_mark: the name of the mark in front of the scan ("start": the call's first; a caller that has run
-// something on st before names what that mark ends)
-static int members_search(zs_ctx* c, const Batch& h, hipStream_t st, bool bgzf, MembersFound& f,
-                          const char* first_mark = "start") {
+template <bool EMIT>
+static void cand_scan(FoundKind kind, uint32_t grid, hipStream_t st, const uint8_t* in, const uint64_t* d_off,
+                      const uint32_t* d_len, const uint32_t* d_first, const uint32_t* d_tile, uint32_t n, uint64_t* tcount,
+                      uint32_t* cand, uint64_t cap) {
+  if (kind == FOUND_SYNC) zs_k_sync_scan<EMIT><<<grid, 256, 0, st>>>(in, d_off, d_len, d_first, d_tile, n, tcount, cand, cap);
+  else zs_k_members_scan<EMIT><<<grid, 256, 0, st>>>(in, d_off, d_len, d_tile, n, tcount, cand, cap);
+}
+// The scan's two passes and the sizing launch over the streams of h, st waited for, then the candidates, the
+// lanes' records and (FOUND_BGZF) their trusted bytes on the host.  The candidate list has the size the calls
+// before needed; when this call has more, the emit pass and the sizing run once more over the grown list
+// (and st is waited for a second time).  first (FOUND_SYNC): the streams' first points where the caller has
+// the bytes (the host entries), else zs_k_sync_first computes them.  first_mark: the name of the mark in front
+// of the scan ("start": the call's first; a caller that has run something on st before names what that mark ends).
+static int cand_search(zs_ctx* c, FoundKind kind, int wbits, const Batch& h, hipStream_t st, const uint32_t* first, Found& f,
+                       const char* first_mark = "start") {
   const uint32_t n = h.n;
+  const bool sync = kind == FOUND_SYNC;
   std::vector<uint32_t> sh16(n), stile;
   uint64_t tin = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -2495,62 +2434,66 @@ static int members_search(zs_ctx* c, const Batch& h, hipStream_t st, bool bgzf, 
   }
   zs_plan_sync_tiles(n, h.in_len, sh16.data(), stile);
   const uint32_t T = stile[n];
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t m_off = 0, m_len = up256(8ull * n), m_tile = m_len + up256(4ull * n), m_end = m_tile + up256(4ull * (n + 1));
-  HIPCHK(c->mbmeta.ensure(m_end));
-  HIPCHK(c->mbtile.ensure(8ull * T + 16));
-  HIPCHK(c->mbcand.ensure(4ull * (tin / 2048 + 1024)));
-  c->mbh.assign(m_end, 0);
-  memcpy(c->mbh.data() + m_off, h.in_off, 8ull * n);
-  memcpy(c->mbh.data() + m_len, h.in_len, 4ull * n);
-  memcpy(c->mbh.data() + m_tile, stile.data(), 4ull * (n + 1));
-  HIPCHK(hipMemcpyAsync(c->mbmeta.p, c->mbh.data(), m_end, hipMemcpyHostToDevice, st));
-  const uint8_t* dm = c->mbmeta.as<uint8_t>();
+  std::vector<uint8_t>& hm = c->hsec;
+  hm.clear();
+  const size_t m_off = zs_section_put(hm, h.in_off, 8ull * n), m_len = zs_section_put(hm, h.in_len, 4ull * n),
+               m_first = sync ? zs_section_put(hm, first, 4ull * n) : 0, m_tile = zs_section_put(hm, stile.data(), 4ull * (n + 1));
+  HIPCHK(c->fmeta.ensure(hm.size()));
+  HIPCHK(c->ftile.ensure(8ull * T + 16));
+  HIPCHK(c->fcand.ensure(4ull * (tin / 2048 + 1024)));
+  HIPCHK(hipMemcpyAsync(c->fmeta.p, hm.data(), hm.size(), hipMemcpyHostToDevice, st));
+  uint8_t* dm = c->fmeta.as<uint8_t>();
   const uint64_t* d_off = (const uint64_t*)(dm + m_off);
   const uint32_t* d_len = (const uint32_t*)(dm + m_len);
+  uint32_t* d_first = (uint32_t*)(dm + m_first);
   const uint32_t* d_tile = (const uint32_t*)(dm + m_tile);
-  uint64_t* tcount = c->mbtile.as<uint64_t>();
+  uint64_t* tcount = c->ftile.as<uint64_t>();
   const uint32_t grid = std::max(1u, std::min(T, 32u * c->o.ncu));
   MARK(first_mark);
-  zs_k_members_scan<false><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, nullptr, 0);
+  if (sync && !first) zs_k_sync_first<<<(n + 255) / 256, 256, 0, st>>>(h.in, d_off, d_len, wbits, n, d_first);
+  cand_scan<false>(kind, grid, st, h.in, d_off, d_len, d_first, d_tile, n, tcount, nullptr, 0);
   zs_k_flush_tiles<<<1, ZS_FLUSH_TILE, 0, st>>>(tcount, T + 1);
   HIPCHK(hipGetLastError());
   std::vector<uint64_t> tpre(T + 1);
   for (int round = 0;; round++) {
-    const uint64_t cap = c->mbcand.cap / 4;
-    HIPCHK(c->mbrec.ensure(sizeof(zs_sync_rec) * (n + cap)));
-    if (bgzf) HIPCHK(c->mbtrust.ensure(n + cap));
-    zs_k_members_scan<true><<<grid, 256, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap);
-    MARK("members_scan");
+    const uint64_t cap = c->fcand.cap / 4;
+    HIPCHK(c->frec.ensure(sizeof(zs_sync_rec) * (n + cap)));
+    if (kind == FOUND_BGZF) HIPCHK(c->ftrust.ensure(n + cap));
+    uint32_t* d_cand = c->fcand.as<uint32_t>();
+    zs_sync_rec* d_rec = c->frec.as<zs_sync_rec>();
+    cand_scan<true>(kind, grid, st, h.in, d_off, d_len, d_first, d_tile, n, tcount, d_cand, cap);
+    MARK(kFound[kind].scan);
     // (a lane per stream and per place of the list: the lanes past the candidates' count return at once)
     const uint64_t lanes = std::min<uint64_t>(n + cap, ZS_RESTART_SEG_MAX);
-    if (bgzf) {
-      zs_k_bgzf_size<<<(uint32_t)((lanes + ZS_BGZF_THREADS - 1) / ZS_BGZF_THREADS), ZS_BGZF_THREADS, 0, st>>>(
-          h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>(),
-          c->mbtrust.as<uint8_t>());
-      MARK("bgzf_size");
-    } else {
-      zs_k_members_size<<<(uint32_t)((lanes + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES), ZS_SYNC_LANES, 0, st>>>(
-          h.in, d_off, d_len, d_tile, n, tcount, c->mbcand.as<uint32_t>(), cap, c->o.sync_pass, c->mbrec.as<zs_sync_rec>());
-      MARK("members_size");
-    }
+    const uint32_t per = kind == FOUND_BGZF ? ZS_BGZF_THREADS : ZS_SYNC_LANES, blocks = (uint32_t)((lanes + per - 1) / per);
+    if (sync)
+      zs_k_sync_size<<<blocks, per, 0, st>>>(h.in, d_off, d_len, d_first, d_tile, n, tcount, d_cand, cap, c->o.sync_pass, d_rec);
+    else if (kind == FOUND_MEMBERS)
+      zs_k_members_size<<<blocks, per, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, d_cand, cap, c->o.sync_pass, d_rec);
+    else
+      zs_k_bgzf_size<<<blocks, per, 0, st>>>(h.in, d_off, d_len, d_tile, n, tcount, d_cand, cap, c->o.sync_pass, d_rec,
+                                             c->ftrust.as<uint8_t>());
+    MARK(kFound[kind].size);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(tpre.data(), tcount, 8ull * (T + 1), hipMemcpyDeviceToHost));
-    if (!zs_sync_count_ok(n, tpre[T]))
-      return fail(ZS_STREAM_ERROR, "%s", "too many member candidates (more than 67,108,863 with the streams in one call)");
+    if (!zs_sync_count_ok(n, tpre[T])) return fail(ZS_STREAM_ERROR, "%s", kFound[kind].many);
     if (tpre[T] <= cap) break;
-    if (round) return fail(ZS_MEM_ERROR, "%s", "the member candidates' list did not settle");
-    HIPCHK(c->mbcand.ensure(4ull * tpre[T]));
+    if (round) return fail(ZS_MEM_ERROR, "%s", kFound[kind].unsettled);
+    HIPCHK(c->fcand.ensure(4ull * tpre[T]));
   }
   const uint64_t C = tpre[T];
   f.cand.resize(C);
   f.rec.resize(n + C);
-  if (C) HIPCHK(hipMemcpy(f.cand.data(), c->mbcand.p, 4ull * C, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(f.rec.data(), c->mbrec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
-  if (bgzf) {
+  if (C) HIPCHK(hipMemcpy(f.cand.data(), c->fcand.p, 4ull * C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(f.rec.data(), c->frec.p, sizeof(zs_sync_rec) * (n + C), hipMemcpyDeviceToHost));
+  if (sync) {
+    f.first.resize(n);
+    HIPCHK(hipMemcpy(f.first.data(), d_first, 4ull * n, hipMemcpyDeviceToHost));
+  }
+  if (kind == FOUND_BGZF) {
     f.rtrusted.resize(n + C);
-    HIPCHK(hipMemcpy(f.rtrusted.data(), c->mbtrust.p, n + C, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.rtrusted.data(), c->ftrust.p, n + C, hipMemcpyDeviceToHost));
   }
   f.cfirst.resize(n + 1);
   for (uint32_t i = 0; i <= n; i++) f.cfirst[i] = tpre[stile[i]];
@@ -2558,111 +2501,132 @@ static int members_search(zs_ctx* c, const Batch& h, hipStream_t st, bool bgzf, 
   f.d_len = d_len;
   return ZS_OK;
 }
+// A tail round: the starts a bound stopped (tstream, tstart) once more, a lane each, to their streams' ends
+// (zs_k_sync_tail, zs_k_members_tail); st is waited for and the lanes' records come back.
+static int cand_tail(zs_ctx* c, FoundKind kind, const Batch& h, hipStream_t st, const Found& f,
+                     const std::vector<uint32_t>& tstream, const std::vector<uint32_t>& tstart, std::vector<zs_sync_rec>& tail) {
+  const uint32_t m = (uint32_t)tstream.size(), blocks = (m + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES;
+  const size_t t_start = (4ull * m + 255) & ~size_t(255);
+  HIPCHK(c->ftail.ensure(2 * t_start + sizeof(zs_sync_rec) * m));
+  uint8_t* dt = c->ftail.as<uint8_t>();
+  const uint32_t *d_stream = (const uint32_t*)dt, *d_start = (const uint32_t*)(dt + t_start);
+  zs_sync_rec* d_rec = (zs_sync_rec*)(dt + 2 * t_start);
+  HIPCHK(hipMemcpyAsync(dt, tstream.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dt + t_start, tstart.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  if (kind == FOUND_SYNC) zs_k_sync_tail<<<blocks, ZS_SYNC_LANES, 0, st>>>(h.in, f.d_off, f.d_len, d_stream, d_start, m, d_rec);
+  else zs_k_members_tail<<<blocks, ZS_SYNC_LANES, 0, st>>>(h.in, f.d_off, f.d_len, d_stream, d_start, m, d_rec);
+  MARK(kind == FOUND_SYNC ? "sync_size" : "members_size");
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  tail.resize(m);
+  HIPCHK(hipMemcpy(tail.data(), d_rec, sizeof(zs_sync_rec) * m, hipMemcpyDeviceToHost));
+  return ZS_OK;
+}
 
-static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st, bool bgzf = false) {
+// ---- restart points found from the bytes.  A fault of the arguments is reported before the
+// context is looked at (zs_sync_validate, then the null context).
+static int sync_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
+  if (const zs_sync_err e = zs_sync_validate(wbits, inflate_call(h, device_entry, nullptr)))
+    return fail(ZS_STREAM_ERROR, "%s", zs_sync_err_text(e));
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
+}
+
+// The device decode of a validated, non-empty batch that finds its own points (regions as inflate_batch's;
+// first: as cand_search's).  The points are planned here, from the candidates and the lanes' records; st is
+// waited for once more where a chain ends at a lane its bound stopped (zs_k_sync_tail).
+static int sync_batch(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, hipStream_t st, const uint32_t* first) {
   const uint32_t n = h.n;
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  MembersFound found;
-  if (const int rs = members_search(c, h, st, bgzf, found)) return rs;
-  std::vector<uint32_t>& cand = found.cand;
-  std::vector<zs_sync_rec>& rec = found.rec;
-  const std::vector<uint8_t>& rtrusted = found.rtrusted;
-  const std::vector<uint64_t>& cfirst = found.cfirst;
-  const uint64_t* d_off = found.d_off;
-  const uint32_t* d_len = found.d_len;
-  std::vector<uint8_t> trusted;  // per planned member
+  Found f;
+  if (const int rs = cand_search(c, FOUND_SYNC, wbits, h, st, first, f)) return rs;
+  zs_sync_plan& p = c->yp;
+  zs_plan_sync(n, h.in_len, f.first.data(), f.cfirst.data(), f.cand.data(), f.rec.data(), p);
+  if (!p.tstream.empty()) {
+    // chains that end at a lane its bound stopped: the whole tail's reach, then the plan again
+    std::vector<zs_sync_rec> tail;
+    if (const int rt = cand_tail(c, FOUND_SYNC, h, st, f, p.tstream, p.tstart, tail)) return rt;
+    for (size_t k = 0; k < tail.size(); k++) f.rec[p.trec[k]].reach = std::max(f.rec[p.trec[k]].reach, tail[k].reach);
+    zs_plan_sync(n, h.in_len, f.first.data(), f.cfirst.data(), f.cand.data(), f.rec.data(), p);
+  }
+  {  // the plan's points pass the restart entries' validation by construction: nothing is launched otherwise
+    zs_restart_call a;
+    a.n = n;
+    a.in_len = h.in_len;
+    a.out_cap = h.out_cap;
+    a.rfirst = p.rfirst.data();
+    a.rin = p.rin.data();
+    a.rout = p.rout.data();
+    if (const zs_restart_err e = zs_restart_validate(wbits, a))
+      return fail(ZS_MEM_ERROR, "the found restart points are refused: %s", zs_restart_err_text(e));
+  }
+  c->call.sync = true;
+  return restart_batch(c, wbits, h, out, st, {p.rfirst.data(), p.rin.data(), p.rout.data()});
+}
+
+// ---- a gzip file's members found from the bytes.  A fault of the arguments is reported before
+// the context is looked at (zs_members_validate, then the null context).
+static int members_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry) {
+  if (const zs_members_err e = zs_members_validate(wbits, inflate_call(h, device_entry, nullptr)))
+    return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
+  return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
+}
+
+// The device decode of a validated, non-empty gzip batch whose streams hold any number of members
+// (regions as inflate_batch's).  The members are planned here, from the candidates and the lanes' records
+// (cand_search); st is waited for once more per tail round (zs_k_members_tail).  The members then decode as
+// ONE gzip batch on the caller's input and are joined per stream.
+// FOUND_BGZF: the _bgzf entries' mode.  It differs in three places: the sizing launch is
+// zs_k_bgzf_size, which trusts the headers it can; the plan's members get their flags (zs_plan_bgzf_trusted);
+// the stitch reports a flagged member's capacity outcome as its header's lie.
+static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipStream_t st, FoundKind kind) {
+  const uint32_t n = h.n;
+  const bool bgzf = kind == FOUND_BGZF;
+  Found f;
+  if (const int rs = cand_search(c, kind, 31, h, st, nullptr, f)) return rs;
   zs_members_plan& p = c->mp;
   for (;;) {
-    zs_plan_members(n, h.in_len, h.out_cap, cfirst.data(), cand.data(), rec.data(), p);
-    const uint32_t m = (uint32_t)p.tstream.size();
-    if (!m) break;
+    zs_plan_members(n, h.in_len, h.out_cap, f.cfirst.data(), f.cand.data(), f.rec.data(), p);
+    if (p.tstream.empty()) break;
     // true members that hold more than sync_pass false candidates: sized to the stream's end, then the plan again
-    const size_t t_start = up256(4ull * m);
-    HIPCHK(c->mbtail.ensure(2 * t_start + sizeof(zs_sync_rec) * m));
-    uint8_t* dt = c->mbtail.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(dt, p.tstream.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dt + t_start, p.tstart.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    zs_k_members_tail<<<(m + ZS_SYNC_LANES - 1) / ZS_SYNC_LANES, ZS_SYNC_LANES, 0, st>>>(
-        h.in, d_off, d_len, (const uint32_t*)dt, (const uint32_t*)(dt + t_start), m, (zs_sync_rec*)(dt + 2 * t_start));
-    MARK("members_size");
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<zs_sync_rec> tail(m);
-    HIPCHK(hipMemcpy(tail.data(), dt + 2 * t_start, sizeof(zs_sync_rec) * m, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < m; k++) {
+    std::vector<zs_sync_rec> tail;
+    if (const int rt = cand_tail(c, kind, h, st, f, p.tstream, p.tstart, tail)) return rt;
+    for (size_t k = 0; k < tail.size(); k++) {
       if (tail[k].how == ZS_SYNC_PASSED) return fail(ZS_MEM_ERROR, "%s", "a member's tail lane did not settle");
-      rec[p.trec[k]] = tail[k];
+      f.rec[p.trec[k]] = tail[k];
     }
   }
   c->call.members = true;
   const uint32_t M = p.M;
+  std::vector<uint8_t> trusted;  // per planned member
   // (a tail round replaces records of untrusted starts only: a trusted one is never PASSED)
-  if (bgzf) c->call.bgzf_trusted += zs_plan_bgzf_trusted(p, h.out_cap, cfirst.data(), cand.data(), rec.data(), rtrusted.data(), trusted);
-  // where each member lies, decodes and belongs
-  std::vector<uint64_t> src(M), ooff(M), dst(M);
-  for (uint32_t g = 0; g < M; g++) {
-    const uint32_t i = p.rstream[g];
-    src[g] = h.in_off[i] + p.soff[g];
-    dst[g] = h.out_off[i] + p.opos[g];
-    // (a member without room stores nothing: it stays at its stream's start)
-    ooff[g] = p.in_place ? h.out_off[i] + (p.ocap[g] ? p.opos[g] : 0u) : p.stoff[g];
-  }
-  const size_t g_first = 0, g_soff = up256(4ull * (n + 1)), g_opos = g_soff + up256(4ull * M), g_ocap = g_opos + up256(4ull * M),
-               g_ooff = g_ocap + up256(4ull * M), g_dst = g_ooff + up256(8ull * M), g_ptile = g_dst + up256(8ull * M),
-               g_out = g_ptile + up256(4ull * (M + 1)), g_trust = g_out + up256(8ull * n),
-               g_end = g_trust + (bgzf ? up256(M) : 0);
-  HIPCHK(c->mbseg.ensure(g_end));
-  HIPCHK(c->mbres.ensure(20ull * M + 64));
-  HIPCHK(c->mbstage.ensure(p.stage_bytes));
-  HIPCHK(c->mblen.ensure(4ull * n + 16));
-  c->mbh.assign(g_end, 0);
-  memcpy(c->mbh.data() + g_first, p.rfirst.data(), 4ull * (n + 1));
-  memcpy(c->mbh.data() + g_soff, p.soff.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_opos, p.opos.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_ocap, p.ocap.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_ooff, ooff.data(), 8ull * M);
-  memcpy(c->mbh.data() + g_dst, dst.data(), 8ull * M);
-  memcpy(c->mbh.data() + g_ptile, p.ptile.data(), 4ull * (M + 1));
-  memcpy(c->mbh.data() + g_out, h.out_off, 8ull * n);
-  if (bgzf) memcpy(c->mbh.data() + g_trust, trusted.data(), M);
-  HIPCHK(hipMemcpyAsync(c->mbseg.p, c->mbh.data(), g_end, hipMemcpyHostToDevice, st));
-  const uint8_t* dg = c->mbseg.as<uint8_t>();
+  if (bgzf)
+    c->call.bgzf_trusted +=
+        zs_plan_bgzf_trusted(p, h.out_cap, f.cfirst.data(), f.cand.data(), f.rec.data(), f.rtrusted.data(), trusted);
+  PieceRun r;
+  if (const int rc = pieces_begin(c, h, p, r)) return rc;
+  std::vector<uint8_t>& hs = c->hsec;
+  hs.clear();
+  const size_t g_first = zs_section_put(hs, p.rfirst.data(), 4ull * (n + 1)), g_soff = zs_section_put(hs, p.soff.data(), 4ull * M),
+               g_opos = zs_section_put(hs, p.opos.data(), 4ull * M), g_ocap = zs_section_put(hs, p.ocap.data(), 4ull * M),
+               g_ooff = zs_section_put(hs, r.ooff.data(), 8ull * M), g_dst = zs_section_put(hs, r.dst.data(), 8ull * M),
+               g_ptile = zs_section_put(hs, p.ptile.data(), 4ull * (M + 1)), g_out = zs_section_put(hs, h.out_off, 8ull * n),
+               g_trust = bgzf ? zs_section_put(hs, trusted.data(), M) : 0;
+  HIPCHK(c->pseg.ensure(hs.size()));
+  HIPCHK(c->plen.ensure(4ull * n + 16));
+  HIPCHK(hipMemcpyAsync(c->pseg.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
+  const uint8_t* dg = c->pseg.as<uint8_t>();
   auto u32 = [&](size_t at) { return (const uint32_t*)(dg + at); };
   auto u64 = [&](size_t at) { return (const uint64_t*)(dg + at); };
-  // the members as M gzip members, decoded with zlib semantics: behind the first member there is no call
-  // boundary of the reference's to reproduce, whatever the context's inflate_ref_wrap says
-  int32_t* const sr = c->mbres.as<int32_t>();
-  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
-  zs_route_opts o2 = c->o;
-  o2.inflate_ref_wrap = false;
-  const Batch hs = {M, h.in, src.data(), p.slen.data(), p.in_place ? h.out : c->mbstage.as<uint8_t>(), ooff.data(),
-                    p.ocap.data()};
-  if (const int ri = inflate_batch(c, 31, hs, seg, st, nullptr, &o2)) return ri;
-  if (!p.in_place) {
-    if (p.ptile[M])
-      zs_k_restart_place<<<std::min(p.ptile[M], 32u * c->o.ncu), 256, 0, st>>>(
-          c->mbstage.as<uint8_t>(), u64(g_ooff), u32(g_ocap), seg.out_len, u64(g_dst), u32(g_ptile), M, h.out);
-    MARK("restart_place");
-  }
-  uint32_t* cklen = c->mblen.as<uint32_t>();
+  if (const int ri = pieces_decode(c, st, 31, h, p, r, h.in, r.src.data(), p.slen.data(), u64(g_ooff), u32(g_ocap), u64(g_dst),
+                                   u32(g_ptile)))
+    return ri;
+  const InflateOut& seg = r.seg;
+  uint32_t* cklen = c->plen.as<uint32_t>();
   zs_k_members_stitch<<<n, 64, 0, st>>>(u32(g_first), u32(g_soff), u32(g_opos), seg.status, seg.phase, seg.msg, seg.out_len,
                                         seg.consumed, n, out.status, out.phase, out.msg, out.out_len, out.consumed, cklen,
                                         bgzf ? dg + g_trust : nullptr);
   HIPCHK(hipGetLastError());
-  if (out.check) {
-    // the check value over the joined output; the members' own values are verified by the decoders.
-    // The part map goes to the front of the metadata block, which the members' batch is done with in stream order.
-    const zs_checksum_plan* ck;
-    size_t ck_bytes;
-    if (const int rc = ck_prepare(c, true, n, h.out_cap, &ck, &ck_bytes)) return rc;
-    if (ck_bytes) {
-      HIPCHK(c->meta.ensure(ck_bytes));
-      c->mbck.assign(ck_bytes, 0);
-      ck_fill(ck, c->mbck.data());
-      HIPCHK(hipMemcpyAsync(c->meta.p, c->mbck.data(), ck_bytes, hipMemcpyHostToDevice, st));
-    }
-    ck_launch(c, st, *ck, 0, n, h.out, u64(g_out), cklen, out.check, 2);
-  }
+  if (out.check)
+    if (const int rc = stream_check(c, st, h, u64(g_out), cklen, out.check)) return rc;
   MARK("members_stitch");
   HIPCHK(hipGetLastError());
   return ZS_OK;
@@ -2672,12 +2636,8 @@ static int members_batch(zs_ctx* c, const Batch& h, const InflateOut& out, hipSt
 // virtual offsets' (zs_bgzf_range_validate), then the null context.
 static int bgzf_range_refused(zs_ctx* c, int wbits, const Batch& h, bool device_entry, const uint64_t* vb,
                               const uint64_t* ve) {
-  zs_inflate_call a;
-  a.n = h.n;
-  a.out_off = device_entry ? h.out_off : nullptr;
-  a.out_cap = h.out_cap;
-  a.caller_regions = device_entry;
-  if (const zs_members_err e = zs_members_validate(wbits, a)) return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
+  if (const zs_members_err e = zs_members_validate(wbits, inflate_call(h, device_entry, nullptr)))
+    return fail(ZS_STREAM_ERROR, "%s", zs_members_err_text(e));
   if (const zs_bgzf_range_err e = zs_bgzf_range_validate(h.n, h.in_len, vb, ve))
     return fail(ZS_STREAM_ERROR, "%s", zs_bgzf_range_err_text(e));
   return c ? ZS_OK : fail(ZS_STREAM_ERROR, "null context");
@@ -2685,7 +2645,7 @@ static int bgzf_range_refused(zs_ctx* c, int wbits, const Batch& h, bool device_
 
 // The device decode of a validated, non-empty batch of ranges (regions as inflate_batch's; several streams may
 // name the same input bytes, which are only read).  The scan and the sizing run over the ranges' SLICES as over
-// streams of their own (members_search, st waited for once); the plan follows the trusted headers
+// streams of their own (cand_search, st waited for once); the plan follows the trusted headers
 // (zs_plan_bgzf_range); the planned blocks decode whole, as ONE gzip batch on the caller's input, into staging;
 // the stitch writes the streams' fields and the place kernel moves the delivered bytes behind it.
 // A slice with ue > 0 reaches 65,536 bytes behind ce (zs_bgzf_range_slice), which holds two or three blocks behind
@@ -2696,7 +2656,7 @@ static int bgzf_range_refused(zs_ctx* c, int wbits, const Batch& h, bool device_
 static int bgzf_range_batch(zs_ctx* c, const Batch& h, const uint64_t* vb, const uint64_t* ve, const InflateOut& out,
                             hipStream_t st, bool trimmed = false) {
   const uint32_t n = h.n;
-  auto up256 = [](size_t x) { return (x + 255) & ~size_t(255); };
+  std::vector<uint8_t>& hs = c->hsec;
   std::vector<uint64_t> sl_off(n);
   std::vector<uint32_t> sl_len(n), rce(n);
   bool any_end = false, cut = false;
@@ -2708,15 +2668,13 @@ static int bgzf_range_batch(zs_ctx* c, const Batch& h, const uint64_t* vb, const
     any_end = any_end || rce[i] < sl_len[i];
   }
   if (any_end && !trimmed) {
-    const size_t e_len = up256(8ull * n), e_rce = e_len + up256(4ull * n), e_end = e_rce + up256(4ull * n),
-                 e_bytes = e_end + up256(4ull * n);
-    HIPCHK(c->mbtail.ensure(e_bytes));
-    c->mbh.assign(e_end, 0);
-    memcpy(c->mbh.data(), sl_off.data(), 8ull * n);
-    memcpy(c->mbh.data() + e_len, sl_len.data(), 4ull * n);
-    memcpy(c->mbh.data() + e_rce, rce.data(), 4ull * n);
-    uint8_t* de = c->mbtail.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(de, c->mbh.data(), e_end, hipMemcpyHostToDevice, st));
+    hs.clear();
+    zs_section_put(hs, sl_off.data(), 8ull * n);
+    const size_t e_len = zs_section_put(hs, sl_len.data(), 4ull * n), e_rce = zs_section_put(hs, rce.data(), 4ull * n),
+                 e_end = hs.size();
+    HIPCHK(c->ftail.ensure(e_end + 4ull * n));
+    uint8_t* de = c->ftail.as<uint8_t>();
+    HIPCHK(hipMemcpyAsync(de, hs.data(), e_end, hipMemcpyHostToDevice, st));
     MARK("start");
     zs_k_bgzf_range_end<<<n / 256 + 1, 256, 0, st>>>(h.in, (const uint64_t*)de, (const uint32_t*)(de + e_len),
                                                      (const uint32_t*)(de + e_rce), n, (uint32_t*)(de + e_end));
@@ -2729,59 +2687,35 @@ static int bgzf_range_batch(zs_ctx* c, const Batch& h, const uint64_t* vb, const
       if (end[i] > rce[i] && end[i] <= sl_len[i]) sl_len[i] = end[i];
     cut = true;
   }
-  MembersFound found;
+  Found f;
   const Batch hsl = {n, h.in, sl_off.data(), sl_len.data(), h.out, h.out_off, h.out_cap};
   // (behind the cut the search's first mark ends the host's wait for the ends: "bgzf_range_wait")
-  if (const int rs = members_search(c, hsl, st, true, found, cut ? "bgzf_range_wait" : "start")) return rs;
+  if (const int rs = cand_search(c, FOUND_BGZF, 31, hsl, st, nullptr, f, cut ? "bgzf_range_wait" : "start")) return rs;
   zs_bgzf_range_plan& p = c->brp;
-  zs_plan_bgzf_range(n, h.out_cap, vb, ve, found.cfirst.data(), found.cand.data(), found.rec.data(),
-                     found.rtrusted.data(), p);
+  zs_plan_bgzf_range(n, h.out_cap, vb, ve, f.cfirst.data(), f.cand.data(), f.rec.data(), f.rtrusted.data(), p);
   const uint32_t M = p.M;
   for (uint32_t g = 0; g < M; g++) c->call.bgzf_trusted += p.trusted[g];
-  // where each member lies and where its delivered bytes belong
-  std::vector<uint64_t> src(M), dst(M);
-  for (uint32_t g = 0; g < M; g++) {
-    const uint32_t i = p.rstream[g];
-    src[g] = h.in_off[i] + p.soff[g];
-    dst[g] = h.out_off[i] + p.opos[g];
-  }
-  const size_t g_first = 0, g_soff = up256(4ull * (n + 1)), g_opos = g_soff + up256(4ull * M), g_ocap = g_opos + up256(4ull * M),
-               g_skip = g_ocap + up256(4ull * M), g_take = g_skip + up256(4ull * M), g_rstream = g_take + up256(4ull * M),
-               g_stoff = g_rstream + up256(4ull * M), g_dst = g_stoff + up256(8ull * M), g_ptile = g_dst + up256(8ull * M),
-               g_out = g_ptile + up256(4ull * (M + 1)), g_verdict = g_out + up256(8ull * n),
-               g_vcons = g_verdict + up256(4ull * n), g_trust = g_vcons + up256(4ull * n), g_end = g_trust + up256(M);
-  HIPCHK(c->mbseg.ensure(g_end));
-  HIPCHK(c->mbres.ensure(20ull * M + 64));
-  HIPCHK(c->mbstage.ensure(p.stage_bytes));
-  HIPCHK(c->mblen.ensure(4ull * n + 16));
-  c->mbh.assign(g_end, 0);
-  memcpy(c->mbh.data() + g_first, p.rfirst.data(), 4ull * (n + 1));
-  memcpy(c->mbh.data() + g_soff, p.soff.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_opos, p.opos.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_ocap, p.ocap.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_skip, p.skip.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_take, p.take.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_rstream, p.rstream.data(), 4ull * M);
-  memcpy(c->mbh.data() + g_stoff, p.stoff.data(), 8ull * M);
-  memcpy(c->mbh.data() + g_dst, dst.data(), 8ull * M);
-  memcpy(c->mbh.data() + g_ptile, p.ptile.data(), 4ull * (M + 1));
-  memcpy(c->mbh.data() + g_out, h.out_off, 8ull * n);
-  memcpy(c->mbh.data() + g_verdict, p.verdict.data(), 4ull * n);
-  memcpy(c->mbh.data() + g_vcons, p.vcons.data(), 4ull * n);
-  memcpy(c->mbh.data() + g_trust, p.trusted.data(), M);
-  HIPCHK(hipMemcpyAsync(c->mbseg.p, c->mbh.data(), g_end, hipMemcpyHostToDevice, st));
-  const uint8_t* dg = c->mbseg.as<uint8_t>();
+  PieceRun r;  // (never in place: every block decodes whole at its region of staging, r.ooff = p.stoff)
+  if (const int rc = pieces_begin(c, h, p, r)) return rc;
+  hs.clear();
+  const size_t g_first = zs_section_put(hs, p.rfirst.data(), 4ull * (n + 1)), g_soff = zs_section_put(hs, p.soff.data(), 4ull * M),
+               g_opos = zs_section_put(hs, p.opos.data(), 4ull * M), g_ocap = zs_section_put(hs, p.ocap.data(), 4ull * M),
+               g_skip = zs_section_put(hs, p.skip.data(), 4ull * M), g_take = zs_section_put(hs, p.take.data(), 4ull * M),
+               g_rstream = zs_section_put(hs, p.rstream.data(), 4ull * M), g_stoff = zs_section_put(hs, p.stoff.data(), 8ull * M),
+               g_dst = zs_section_put(hs, r.dst.data(), 8ull * M), g_ptile = zs_section_put(hs, p.ptile.data(), 4ull * (M + 1)),
+               g_out = zs_section_put(hs, h.out_off, 8ull * n), g_verdict = zs_section_put(hs, p.verdict.data(), 4ull * n),
+               g_vcons = zs_section_put(hs, p.vcons.data(), 4ull * n), g_trust = zs_section_put(hs, p.trusted.data(), M);
+  HIPCHK(c->pseg.ensure(hs.size()));
+  HIPCHK(c->plen.ensure(4ull * n + 16));
+  HIPCHK(hipMemcpyAsync(c->pseg.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
+  const uint8_t* dg = c->pseg.as<uint8_t>();
   auto u32 = [&](size_t at) { return (const uint32_t*)(dg + at); };
   auto u64 = [&](size_t at) { return (const uint64_t*)(dg + at); };
-  int32_t* const sr = c->mbres.as<int32_t>();
-  const InflateOut seg = {sr, sr + M, sr + 2 * M, (uint32_t*)(sr + 3 * M), (uint32_t*)(sr + 4 * M), nullptr};
-  if (M) {  // (the blocks as M gzip members with zlib semantics, as in members_batch)
-    zs_route_opts o2 = c->o;
-    o2.inflate_ref_wrap = false;
-    const Batch hs = {M, h.in, src.data(), p.slen.data(), c->mbstage.as<uint8_t>(), p.stoff.data(), p.ocap.data()};
-    if (const int ri = inflate_batch(c, 31, hs, seg, st, nullptr, &o2)) return ri;
-  }
-  uint32_t* cklen = c->mblen.as<uint32_t>();
+  // (the blocks as M gzip members; their delivered bytes are placed behind the stitch, by this entry's own kernel)
+  if (const int ri = pieces_decode(c, st, 31, h, p, r, h.in, r.src.data(), p.slen.data(), nullptr, nullptr, nullptr, nullptr))
+    return ri;
+  const InflateOut& seg = r.seg;
+  uint32_t* cklen = c->plen.as<uint32_t>();
   zs_k_bgzf_range_stitch<<<n, 64, 0, st>>>(u32(g_first), u32(g_soff), u32(g_opos), u32(g_take), u32(g_verdict), u32(g_vcons),
                                            seg.status, seg.phase, seg.msg, seg.consumed, n, out.status, out.phase, out.msg,
                                            out.out_len, out.consumed, cklen, dg + g_trust);
@@ -2789,41 +2723,27 @@ static int bgzf_range_batch(zs_ctx* c, const Batch& h, const uint64_t* vb, const
   MARK("members_stitch");
   if (p.ptile[M])
     zs_k_bgzf_range_place<<<std::min(p.ptile[M], 32u * c->o.ncu), 256, 0, st>>>(
-        c->mbstage.as<uint8_t>(), u64(g_stoff), u32(g_ocap), seg.out_len, u32(g_skip), u32(g_take), u32(g_opos),
+        c->pstage.as<uint8_t>(), u64(g_stoff), u32(g_ocap), seg.out_len, u32(g_skip), u32(g_take), u32(g_opos),
         u32(g_rstream), out.out_len, u64(g_dst), u32(g_ptile), M, h.out);
   HIPCHK(hipGetLastError());
   MARK("bgzf_range_place");
-  if (out.check) {  // the check value over the delivered bytes, as in members_batch
-    const zs_checksum_plan* ck;
-    size_t ck_bytes;
-    if (const int rc = ck_prepare(c, true, n, h.out_cap, &ck, &ck_bytes)) return rc;
-    if (ck_bytes) {
-      HIPCHK(c->meta.ensure(ck_bytes));
-      c->mbck.assign(ck_bytes, 0);
-      ck_fill(ck, c->mbck.data());
-      HIPCHK(hipMemcpyAsync(c->meta.p, c->mbck.data(), ck_bytes, hipMemcpyHostToDevice, st));
-    }
-    ck_launch(c, st, *ck, 0, n, h.out, u64(g_out), cklen, out.check, 2);
+  if (out.check) {  // the check value over the delivered bytes
+    if (const int rc = stream_check(c, st, h, u64(g_out), cklen, out.check)) return rc;
     HIPCHK(hipGetLastError());
     MARK("checksum");
   }
   return ZS_OK;
 }
 
-// zs_inflate_validate's findings, as the entries report them
-static int inflate_fail(zs_inflate_err e) { return fail(ZS_STREAM_ERROR, "%s", zs_inflate_err_text(e)); }
-// The arrays of a plain or _dict call as validation reads them (the host entries stage their own regions)
-static zs_inflate_call inflate_call(const Batch& h, bool caller_regions, const DictIn* dict) {
-  zs_inflate_call a;
-  a.n = h.n;
-  a.out_off = caller_regions ? h.out_off : nullptr;
-  a.out_cap = h.out_cap;
-  a.caller_regions = caller_regions;
-  a.dict = dict != nullptr;
-  a.dict_arrays = dict && dict->off && dict->len;
-  a.dict_buf = dict && dict->d_dict;
-  a.dict_len = a.dict_arrays ? dict->len : nullptr;
-  return a;
+// The device entries' prologue, behind their refusals.  True: the call has begun and *st is its stream; else *rc
+// is the entry's result (a HIP error, or ZS_OK for an empty batch).
+static bool device_begin(zs_ctx* c, uint32_t n, void* hip_stream, hipStream_t* st, int* rc) {
+  const hipError_t e = hipSetDevice(c->device);
+  *rc = e == hipSuccess ? ZS_OK : fail(ZS_MEM_ERROR, "%s", hipGetErrorString(e));
+  if (e != hipSuccess || n == 0) return false;
+  call_begin(c, CALL_INFLATE);
+  *st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  return true;
 }
 
 // The shared body of the public device entries: the call begins once it is neither refused nor empty.
@@ -2831,20 +2751,20 @@ static int inflate_device(zs_ctx* c, int wbits, const Batch& h, const InflateOut
                           const DictIn* dict, const RestartIn* rs) {
   if (!rs)  // (a restart call has passed restart_refused)
     if (const zs_inflate_err e = zs_inflate_validate(c != nullptr, wbits, inflate_call(h, true, dict))) return inflate_fail(e);
-  HIPCHK(hipSetDevice(c->device));
-  if (h.n == 0) return ZS_OK;
-  call_begin(c, CALL_INFLATE);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st;
+  int rc;
+  if (!device_begin(c, h.n, hip_stream, &st, &rc)) return rc;
   return rs ? restart_batch(c, wbits, h, out, st, *rs) : inflate_batch(c, wbits, h, out, st, dict, nullptr);
 }
 
 // The host decode of every zs_inflate_batch* entry (h, out, dict: the caller's host memory): what the whole
 // batch decides before anything is staged, the dictionaries to the device once, then the call begins and
 // host_batch runs its chunks, each a device batch with a copy of the caller's exact capacities as the limits.
+enum HostRoute { HOST_PLAIN, HOST_RESTART, HOST_SYNC, HOST_MEMBERS, HOST_BGZF };  // (HOST_RESTART: rs is given)
 static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& out, const DictIn* dict,
-                        const RestartIn* rs, bool sync = false, bool members = false, bool bgzf = false) {
+                        const RestartIn* rs, HostRoute route) {
   // (a restart call has passed restart_refused, one that finds its points sync_refused, its members members_refused)
-  if (!rs && !sync && !members)
+  if (route == HOST_PLAIN)
     if (const zs_inflate_err e = zs_inflate_validate_host(c != nullptr, wbits, inflate_call(h, false, dict)))
       return inflate_fail(e);
   HIPCHK(hipSetDevice(c->device));
@@ -2863,9 +2783,10 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                       const InflateOut d = {(int32_t*)dr[0], (int32_t*)dr[1], (int32_t*)dr[2], dr[3], dr[4],
                                             out.check ? dr[5] : nullptr};
                       // (a chunk's points and dictionaries: the same arrays, the chunk's part of the index)
-                      if (rs) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
-                      if (members) return members_batch(c, hb, d, c->stream, bgzf);
-                      if (sync) {  // the first points where the bytes are: the caller's memory
+                      if (route == HOST_RESTART) return restart_batch(c, wbits, hb, d, c->stream, {rs->first + a, rs->in, rs->out});
+                      if (route == HOST_MEMBERS) return members_batch(c, hb, d, c->stream, FOUND_MEMBERS);
+                      if (route == HOST_BGZF) return members_batch(c, hb, d, c->stream, FOUND_BGZF);
+                      if (route == HOST_SYNC) {  // the first points where the bytes are: the caller's memory
                         std::vector<uint32_t> first(b - a);
                         for (uint32_t i = a; i < b; i++)
                           first[i - a] = std::min(zs_wrapper_header_len(wbits, h.in + h.in_off[i], h.in_len[i]), h.in_len[i]);
@@ -2874,7 +2795,7 @@ static int inflate_host(zs_ctx* c, int wbits, const Batch& h, const InflateOut& 
                       const DictIn di = dict ? DictIn{c->d_dict.as<uint8_t>(), poff.data() + a, dict->len + a} : DictIn{};
                       return inflate_batch(c, wbits, hb, d, c->stream, dict ? &di : nullptr, nullptr);
                     },
-                    sync || members);
+                    route >= HOST_SYNC);
 }
 
 extern "C" int zs_inflate_batch_device_ex(zs_ctx* c, int wbits, uint32_t n, const uint8_t* d_in,
@@ -2906,7 +2827,7 @@ extern "C" int zs_inflate_batch_ex(zs_ctx* c, int wbits, uint32_t n, const uint8
                                    const uint32_t* out_cap, int32_t* status, int32_t* phase, int32_t* msg,
                                    uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
   return inflate_host(c, wbits, {n, in, in_off, in_len, out, out_off, out_cap},
-                      {status, phase, msg, out_len, consumed, check}, nullptr, nullptr);
+                      {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, HOST_PLAIN);
 }
 
 // inflate.ts:1267-1337 -- device buffers
@@ -2933,7 +2854,7 @@ extern "C" int zs_inflate_batch_restart(zs_ctx* c, int wbits, uint32_t n, const 
   const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
   const RestartIn rs = {restart_first, restart_in, restart_out};
   if (const int r = restart_refused(c, wbits, h, false, rs)) return r;
-  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, &rs);
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, &rs, HOST_RESTART);
 }
 
 // inflate.ts:1267-1337 -- the points found from the bytes; device buffers
@@ -2944,10 +2865,9 @@ extern "C" int zs_inflate_batch_sync_device(zs_ctx* c, int wbits, uint32_t n, co
                                             uint32_t* d_check, void* hip_stream) {
   const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
   if (const int r = sync_refused(c, wbits, h, true)) return r;
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  call_begin(c, CALL_INFLATE);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st;
+  int rc;
+  if (!device_begin(c, n, hip_stream, &st, &rc)) return rc;
   return sync_batch(c, wbits, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, nullptr);
 }
 
@@ -2958,7 +2878,7 @@ extern "C" int zs_inflate_batch_sync(zs_ctx* c, int wbits, uint32_t n, const uin
                                      uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
   const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
   if (const int r = sync_refused(c, wbits, h, false)) return r;
-  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, true);
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, HOST_SYNC);
 }
 
 // The points the last call on the context found, in the layout the restart entries take: restart_first
@@ -2982,11 +2902,10 @@ extern "C" int zs_inflate_batch_members_device(zs_ctx* c, int wbits, uint32_t n,
                                                uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
   const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
   if (const int r = members_refused(c, wbits, h, true)) return r;
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  call_begin(c, CALL_INFLATE);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st);
+  hipStream_t st;
+  int rc;
+  if (!device_begin(c, n, hip_stream, &st, &rc)) return rc;
+  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, FOUND_MEMBERS);
 }
 
 // ... host buffers
@@ -2996,7 +2915,7 @@ extern "C" int zs_inflate_batch_members(zs_ctx* c, int wbits, uint32_t n, const 
                                         uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
   const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
   if (const int r = members_refused(c, wbits, h, false)) return r;
-  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, false, true);
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, HOST_MEMBERS);
 }
 
 // BGZF files, the members sized from their headers where those can be trusted; device buffers
@@ -3007,11 +2926,10 @@ extern "C" int zs_inflate_batch_bgzf_device(zs_ctx* c, int wbits, uint32_t n, co
                                             uint32_t* d_check, void* hip_stream) {
   const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
   if (const int r = members_refused(c, wbits, h, true)) return r;
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  call_begin(c, CALL_INFLATE);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, true);
+  hipStream_t st;
+  int rc;
+  if (!device_begin(c, n, hip_stream, &st, &rc)) return rc;
+  return members_batch(c, h, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st, FOUND_BGZF);
 }
 
 // ... host buffers
@@ -3021,7 +2939,7 @@ extern "C" int zs_inflate_batch_bgzf(zs_ctx* c, int wbits, uint32_t n, const uin
                                      uint32_t* out_len, uint32_t* consumed, uint32_t* check) {
   const Batch h = {n, in, in_off, in_len, out, out_off, out_cap};
   if (const int r = members_refused(c, wbits, h, false)) return r;
-  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, false, true, true);
+  return inflate_host(c, wbits, h, {status, phase, msg, out_len, consumed, check}, nullptr, nullptr, HOST_BGZF);
 }
 
 // The planned members of the last _bgzf call on the context whose size came from their header; 0 after any
@@ -3045,10 +2963,9 @@ extern "C" int zs_inflate_batch_bgzf_range_device(zs_ctx* c, int wbits, uint32_t
                                                   uint32_t* d_consumed, uint32_t* d_check, void* hip_stream) {
   const Batch h = {n, d_in, in_off, in_len, d_out, out_off, out_cap};
   if (const int r = bgzf_range_refused(c, wbits, h, true, voff_begin, voff_end)) return r;
-  HIPCHK(hipSetDevice(c->device));
-  if (n == 0) return ZS_OK;
-  call_begin(c, CALL_INFLATE);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st;
+  int rc;
+  if (!device_begin(c, n, hip_stream, &st, &rc)) return rc;
   return bgzf_range_batch(c, h, voff_begin, voff_end, {d_status, d_phase, d_msg, d_out_len, d_consumed, d_check}, st);
 }
 
@@ -3171,5 +3088,5 @@ extern "C" int zs_inflate_batch_dict(zs_ctx* c, int wbits, uint32_t n, const uin
                                      const uint64_t* dict_off, const uint32_t* dict_len) {
   const DictIn di = {dict, dict_off, dict_len};  // (host memory here)
   return inflate_host(c, wbits, {n, in, in_off, in_len, out, out_off, out_cap},
-                      {status, phase, msg, out_len, consumed, check}, &di, nullptr);
+                      {status, phase, msg, out_len, consumed, check}, &di, nullptr, HOST_PLAIN);
 }

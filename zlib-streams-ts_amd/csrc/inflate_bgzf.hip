@@ -7,6 +7,7 @@
 #include "zs_kernels.h"
 #include "zs_inflate.h"
 #include "zs_bgzf.h"
+#include "zs_cand.h"
 
 // The kernel is shaped by the trusted lane: 256 starts to a workgroup, a start per thread, every thread's
 // header checked at once (the words of its stream's and candidate's lookup, the header's words, the trailer's
@@ -27,24 +28,13 @@ __global__ __launch_bounds__(ZS_BGZF_THREADS) void zs_k_bgzf_size(
   const uint64_t x = (uint64_t)blockIdx.x * ZS_BGZF_THREADS + threadIdx.x;
   const uint64_t C = tpre[stile[n]];
   const bool live = C <= cap && x < n + C;
+  zs_cand_lane l = {0u, ZS_CAND_FIRST, 0u};
   uint32_t s = 0, start = 0;
-  uint64_t bi = pass;  // the bounding candidate's index among the stream's
   bool decode = false;
   if (live) {
-    if (x < n) {
-      s = (uint32_t)x;
-    } else {
-      const uint64_t k = x - n;
-      uint32_t lo = 0, hi = n;  // tpre[stile[lo]] <= k < tpre[stile[hi]]
-      while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (tpre[stile[mid]] <= k) lo = mid;
-        else hi = mid;
-      }
-      s = lo;
-      start = cand[k];
-      bi = k - tpre[stile[s]] + pass + 1u;
-    }
+    l = zs_cand_lookup(x, n, stile, tpre);
+    s = l.s;
+    if (l.k != ZS_CAND_FIRST) start = cand[l.k];
     zs_sync_rec r = {ZS_SYNC_FINAL, 0u, 0u, 0u};
     const bool t = zs_bgzf_header(in + in_off[s], in_len[s], start, r.end, r.len);
     trusted[x] = t ? 1 : 0;
@@ -58,8 +48,7 @@ __global__ __launch_bounds__(ZS_BGZF_THREADS) void zs_k_bgzf_size(
   const uint32_t rounds = ((uint32_t)__popcll(m) + ZS_BGZF_SLOTS - 1u) / ZS_BGZF_SLOTS;
   for (uint32_t round = 0; round < rounds; round++) {
     if (decode && rank / ZS_BGZF_SLOTS == round) {
-      const uint64_t c0 = tpre[stile[s]], c1 = tpre[stile[s + 1]];
-      const uint32_t bound = bi < c1 - c0 ? cand[c0 + bi] : in_len[s];
+      const uint32_t bound = zs_cand_bound(l, stile, tpre, cand, pass, in_len[s]);
       rec[x] = zs_members_size(in + in_off[s], in_len[s], start, bound, tabs[wv * ZS_BGZF_SLOTS + rank % ZS_BGZF_SLOTS]);
     }
   }

@@ -7,6 +7,7 @@
 #ifndef ZS_PLAN_H
 #define ZS_PLAN_H
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -1271,95 +1272,97 @@ ZS_PLAN_FN bool zs_wrapper_header_ok(int wbits, const uint8_t* p, uint32_t n, ui
   return at != 0 && zs_wrapper_header_len_of(wbits, p, n) == at;
 }
 
-struct zs_restart_plan {
-  uint32_t n = 0, M = 0;          // streams, segments
-  bool in_place = true;           // every restart out_pos is a multiple of 4: the segments decode where they belong
-  std::vector<uint32_t> rfirst;   // each stream's first segment (rfirst[n] = M)
-  std::vector<uint32_t> rstream;  // each segment's stream
-  std::vector<uint32_t> soff, slen;  // the segment's bytes in its stream's input
-  std::vector<uint64_t> goff;     // ... its copy's place in the gather buffer (a multiple of 16)
-  std::vector<uint32_t> glen;     // ... and length: slen + 2 (03 00) unless it is its stream's last
-  std::vector<uint32_t> opos;     // the segment's first byte in its stream's output
-  std::vector<uint32_t> olen;     // the bytes it must produce (the last one: its capacity)
-  std::vector<uint32_t> ocap;     // its capacity: olen, cut at the stream's out_cap
+// The PIECES of a call's streams that decode as the members of one batch and are joined per stream: a
+// restart call's segments, a gzip file's members, the blocks of a BGZF range.  A planner calls begin, then
+// stream by stream rfirst[i] = M and push for each of the stream's pieces, then end.
+struct zs_pieces {
+  uint32_t n = 0, M = 0;          // streams, pieces
+  bool in_place = true;           // every piece's out_pos is a multiple of 4: the pieces decode where they belong
+  std::vector<uint32_t> rfirst;   // each stream's first piece (rfirst[n] = M)
+  std::vector<uint32_t> rstream;  // each piece's stream
+  std::vector<uint32_t> soff, slen;  // the piece's bytes in its stream's input
+  std::vector<uint32_t> opos;     // its first byte in its stream's output
+  std::vector<uint32_t> ocap;     // its capacity
   std::vector<uint64_t> stoff;    // staging route: its 4-aligned region in the staging buffer
+  std::vector<uint32_t> ptile;    // M + 1: prefix sums of the place's tiles
+  uint64_t stage_bytes = 0;
+  void begin(uint32_t streams) {
+    n = streams;
+    M = 0;
+    in_place = true;
+    stage_bytes = 0;
+    rfirst.assign(n + 1, 0);
+    for (auto* v : {&rstream, &soff, &slen, &opos, &ocap}) v->clear();
+    stoff.clear();
+    ptile.assign(1, 0);
+  }
+  // `placed`: the bytes the place kernel moves from staging (the capacity; a range's delivered bytes)
+  void push(uint32_t i, uint32_t off, uint32_t len, uint64_t out, uint32_t cap, uint32_t placed) {
+    if (M > rfirst[i] && (out & 3u)) in_place = false;
+    rstream.push_back(i);
+    soff.push_back(off);
+    slen.push_back(len);
+    opos.push_back((uint32_t)out);
+    ocap.push_back(cap);
+    stoff.push_back(stage_bytes);
+    stage_bytes += ((uint64_t)cap + 3) & ~3ull;
+    // (the place's words: the destination's leading bytes of its first word count too)
+    ptile.push_back(ptile.back() + (uint32_t)(((uint64_t)placed + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
+    M++;
+  }
+  void end(bool staged = false) {  // staged: never in place, whatever the positions are
+    rfirst[n] = M;
+    if (staged) in_place = false;
+    stage_bytes = in_place ? 0 : stage_bytes + 16;
+  }
+};
+// A section of a metadata block, written on the host and uploaded in one copy: put appends `bytes` from p
+// (null: zeros) and returns their offset; every array starts on a multiple of 256 bytes, and so ends the section.
+static inline size_t zs_section_put(std::vector<uint8_t>& h, const void* p, size_t bytes) {
+  const size_t at = h.size();
+  h.resize((at + bytes + 255) & ~size_t(255), 0);
+  if (p && bytes) memcpy(h.data() + at, p, bytes);
+  return at;
+}
+
+struct zs_restart_plan : zs_pieces {  // ocap: olen, cut at the stream's out_cap
+  std::vector<uint64_t> goff;     // the segment's copy's place in the gather buffer (a multiple of 16)
+  std::vector<uint32_t> glen;     // ... and length: slen + 2 (03 00) unless it is its stream's last
+  std::vector<uint32_t> olen;     // the bytes it must produce (the last one: its capacity)
   std::vector<uint32_t> over;     // per stream: the last out_pos lies past out_cap (the capacity outcome)
-  std::vector<uint32_t> gtile, ptile;  // M + 1 each: prefix sums of the gather's / the place's tiles
-  uint64_t gather_bytes = 0, stage_bytes = 0;
+  std::vector<uint32_t> gtile;    // M + 1: prefix sums of the gather's tiles
+  uint64_t gather_bytes = 0;
 };
 // points that passed zs_restart_validate
 static inline void zs_plan_restart(uint32_t n, const uint32_t* in_len, const uint32_t* out_cap, const uint64_t* rfirst,
                                    const uint32_t* rin, const uint32_t* rout, zs_restart_plan& p) {
-  p.n = n;
-  p.in_place = true;
-  p.rfirst.assign(n + 1, 0);
+  p.begin(n);
   p.over.assign(n, 0);
-  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.glen, &p.opos, &p.olen, &p.ocap}) v->clear();
+  p.glen.clear();
+  p.olen.clear();
   p.goff.clear();
-  p.stoff.clear();
   p.gtile.assign(1, 0);
-  p.ptile.assign(1, 0);
-  uint64_t g = 0, st = 0;
+  uint64_t g = 0;
   for (uint32_t i = 0; i < n; i++) {
-    p.rfirst[i] = (uint32_t)p.rstream.size();
+    p.rfirst[i] = p.M;
     for (uint64_t k = rfirst[i]; k < rfirst[i + 1]; k++) {
       const bool last = k + 1 == rfirst[i + 1];
       const uint32_t len = (last ? in_len[i] : rin[k + 1]) - rin[k];
       const uint32_t room = out_cap[i] > rout[k] ? out_cap[i] - rout[k] : 0u;
       const uint32_t want = last ? room : rout[k + 1] - rout[k];
       const uint32_t cap = std::min(want, room);
-      if (k > rfirst[i] && (rout[k] & 3u)) p.in_place = false;
       if (last) p.over[i] = rout[k] > out_cap[i];
-      p.rstream.push_back(i);
-      p.soff.push_back(rin[k]);
-      p.slen.push_back(len);
+      p.push(i, rin[k], len, rout[k], cap, cap);
       p.glen.push_back(last ? len : len + 2);
       p.goff.push_back(g);
       g += ((uint64_t)p.glen.back() + 15) & ~15ull;  // (03 00, then zeros: the readers load whole aligned words)
-      p.opos.push_back(rout[k]);
       p.olen.push_back(want);
-      p.ocap.push_back(cap);
-      p.stoff.push_back(st);
-      st += ((uint64_t)cap + 3) & ~3ull;
       p.gtile.push_back(p.gtile.back() + (uint32_t)(((uint64_t)p.glen.back() + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
-      // (the place's words: the destination's leading bytes of its first word count too)
-      p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)cap + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
     }
   }
-  p.M = (uint32_t)p.rstream.size();
-  p.rfirst[n] = p.M;
+  p.end();
   p.gather_bytes = g + 16;
-  p.stage_bytes = p.in_place ? 0 : st + 16;
 }
-// The restart call's section of the metadata block, behind the segment batch's own (zs_meta_layout of
-// M, which inflate_device uploads): what the restart kernels read of the streams and of the segments; the data
-// checksum's part map follows at `bytes`.
-struct zs_restart_layout {
-  size_t in_off, in_len, out_off, over, rfirst, src, soff, slen, goff, glen, ooff, ocap, olen, opos, dst,
-      gtile, ptile, bytes;
-  zs_restart_layout(size_t base, uint32_t n, uint32_t M) {
-    size_t o = base;
-    auto take = [&](size_t b) { size_t r = o; o = (o + b + 255) & ~size_t(255); return r; };
-    in_off = take(8ull * n);
-    in_len = take(4ull * n);
-    out_off = take(8ull * n);
-    over = take(4ull * n);
-    rfirst = take(4ull * (n + 1));
-    src = take(8ull * M);   // the segment's first byte in the caller's input
-    soff = take(4ull * M);  // ... and in its stream's
-    slen = take(4ull * M);
-    goff = take(8ull * M);
-    glen = take(4ull * M);
-    ooff = take(8ull * M);  // where it decodes: in the caller's output (in place) or the staging buffer
-    ocap = take(4ull * M);
-    olen = take(4ull * M);
-    opos = take(4ull * M);
-    dst = take(8ull * M);   // its place in the caller's output
-    gtile = take(4ull * (M + 1));
-    ptile = take(4ull * (M + 1));
-    bytes = o;
-  }
-};
 
 // ---- inflate that finds its own restart points (inflateSync / syncsearch,
 // inflate.ts:1267-1337).  zs_k_sync_scan lists every offset behind the bytes 00 00 FF FF (the
@@ -1524,17 +1527,9 @@ static inline zs_members_err zs_members_validate(int wbits, const zs_inflate_cal
 // the four-byte test of a member's start: the magic, the method, no reserved flag
 ZS_PLAN_FN bool zs_member_magic(const uint8_t* p) { return p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && !(p[3] & 0xe0); }
 
-struct zs_members_plan {
-  uint32_t n = 0, M = 0;          // streams, members
-  bool in_place = true;           // every member's out_pos is a multiple of 4: the members decode where they belong
-  std::vector<uint32_t> rfirst;   // each stream's first member (rfirst[n] = M)
-  std::vector<uint32_t> rstream;  // each member's stream
-  std::vector<uint32_t> soff, slen;  // the member's bytes in its stream's input (the last of a failing chain: to the end)
-  std::vector<uint32_t> opos;     // its first byte in its stream's output
-  std::vector<uint32_t> ocap;     // its capacity: the bytes it produces; 0 where those pass out_cap; the room where unknown
-  std::vector<uint64_t> stoff;    // staging route: its 4-aligned region in the staging buffer
-  std::vector<uint32_t> ptile;    // M + 1: prefix sums of the place's tiles
-  uint64_t stage_bytes = 0;
+// soff, slen: the last member of a failing chain reaches to the stream's end; ocap: the bytes a member
+// produces, 0 where those pass out_cap, the room where unknown
+struct zs_members_plan : zs_pieces {
   // the starts whose lane its work bound stopped (ZS_SYNC_PASSED): the stream, the start and its record's
   // index.  The stream's members are planned up to there; the caller sizes these starts to the stream's
   // end (zs_k_members_tail), replaces the records and plans again, until no start is left.
@@ -1553,28 +1548,13 @@ struct zs_members_plan {
 // Offset 0 is a member whatever its bytes are (the plain entry's outcome for a stream that is no gzip).
 static inline void zs_plan_members(uint32_t n, const uint32_t* in_len, const uint32_t* out_cap, const uint64_t* cfirst,
                                    const uint32_t* cand, const zs_sync_rec* rec, zs_members_plan& p) {
-  p.n = n;
-  p.in_place = true;
-  p.rfirst.assign(n + 1, 0);
-  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.opos, &p.ocap, &p.tstream, &p.tstart}) v->clear();
-  p.stoff.clear();
+  p.begin(n);
+  p.tstream.clear();
+  p.tstart.clear();
   p.trec.clear();
-  p.ptile.assign(1, 0);
-  uint64_t st = 0;
-  auto member = [&](uint32_t i, uint32_t at, uint32_t len, uint64_t out, uint32_t cap) {
-    if (p.rstream.size() > p.rfirst[i] && (out & 3u)) p.in_place = false;
-    p.rstream.push_back(i);
-    p.soff.push_back(at);
-    p.slen.push_back(len);
-    p.opos.push_back((uint32_t)out);
-    p.ocap.push_back(cap);
-    p.stoff.push_back(st);
-    st += ((uint64_t)cap + 3) & ~3ull;
-    // (the place's words: the destination's leading bytes of its first word count too)
-    p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)cap + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
-  };
+  auto member = [&](uint32_t i, uint32_t at, uint32_t len, uint64_t out, uint32_t cap) { p.push(i, at, len, out, cap, cap); };
   for (uint32_t i = 0; i < n; i++) {
-    p.rfirst[i] = (uint32_t)p.rstream.size();
+    p.rfirst[i] = p.M;
     const uint32_t* c0 = cand + cfirst[i];
     const uint32_t* c1 = cand + cfirst[i + 1];
     uint32_t pos = 0;
@@ -1603,9 +1583,7 @@ static inline void zs_plan_members(uint32_t n, const uint32_t* in_len, const uin
       r = &rec[n + (size_t)(at - cand)];
     }
   }
-  p.M = (uint32_t)p.rstream.size();
-  p.rfirst[n] = p.M;
-  p.stage_bytes = p.in_place ? 0 : st + 16;
+  p.end();
 }
 
 // The _bgzf entries' flags over a finished plan.  rtrusted: one byte per record, in the
@@ -1682,19 +1660,12 @@ ZS_PLAN_FN void zs_bgzf_range_slice(uint32_t n, uint64_t vb, uint64_t ve, uint32
 #define ZS_BGZF_RANGE_MEMBERS 0u  // the stream has members: the stitch reads their results
 #define ZS_BGZF_RANGE_EMPTY 1u    // nothing to decode: Z_STREAM_END, out_len 0, consumed = cb
 #define ZS_BGZF_RANGE_CHAIN 2u    // the headers fail the stream: Z_DATA_ERROR, ZS_MSG_BGZF_RANGE, consumed = the start
-struct zs_bgzf_range_plan {
-  uint32_t n = 0, M = 0;          // streams, members
-  std::vector<uint32_t> rfirst;   // each stream's first member (rfirst[n] = M)
-  std::vector<uint32_t> rstream;  // each member's stream
-  std::vector<uint32_t> soff, slen;  // the member's bytes in its STREAM's input (cb + its offset in the slice)
-  std::vector<uint32_t> ocap;     // its room in staging: its ISIZE; 0 for the member the stream's out_cap cuts
+// soff: in the STREAM's input (cb + the block's offset in the slice); ocap: the block's room in staging, its
+// ISIZE, 0 for the one the stream's out_cap cuts; opos: where its delivered bytes begin.  Never in place.
+struct zs_bgzf_range_plan : zs_pieces {
   std::vector<uint32_t> skip, take;  // bytes dropped in front, bytes delivered
-  std::vector<uint32_t> opos;     // where its delivered bytes begin in its stream's output
   std::vector<uint8_t> trusted;   // its room is its header's ISIZE (zs_k_members_stitch's flag)
-  std::vector<uint64_t> stoff;    // its 4-aligned region in the staging buffer
-  std::vector<uint32_t> ptile;    // M + 1: prefix sums of the place's tiles
   std::vector<uint32_t> verdict, vcons;  // per stream: ZS_BGZF_RANGE_*, and consumed for the two decided here
-  uint64_t stage_bytes = 0;
 };
 // Stream i's slice (zs_bgzf_range_slice) was scanned and sized as a stream of its own: cand[cfirst[i] ..
 // cfirst[i + 1]) are its candidates, offsets IN THE SLICE in increasing order; rec[i] / rtrusted[i] belong to
@@ -1707,19 +1678,16 @@ struct zs_bgzf_range_plan {
 static inline void zs_plan_bgzf_range(uint32_t n, const uint32_t* out_cap, const uint64_t* vb, const uint64_t* ve,
                                       const uint64_t* cfirst, const uint32_t* cand, const zs_sync_rec* rec,
                                       const uint8_t* rtrusted, zs_bgzf_range_plan& p) {
-  p.n = n;
-  p.rfirst.assign(n + 1, 0);
-  for (auto* v : {&p.rstream, &p.soff, &p.slen, &p.ocap, &p.skip, &p.take, &p.opos}) v->clear();
+  p.begin(n);
+  p.skip.clear();
+  p.take.clear();
   p.trusted.clear();
-  p.stoff.clear();
-  p.ptile.assign(1, 0);
   p.verdict.assign(n, ZS_BGZF_RANGE_MEMBERS);
   p.vcons.assign(n, 0);
-  uint64_t st = 0;
   struct blk { uint32_t at, end, isize; };
   std::vector<blk> chain;
   for (uint32_t i = 0; i < n; i++) {
-    p.rfirst[i] = (uint32_t)p.rstream.size();
+    p.rfirst[i] = p.M;
     const uint32_t cb = (uint32_t)(vb[i] >> 16), rce = (uint32_t)((ve[i] >> 16) - (vb[i] >> 16));
     const uint32_t ub = (uint32_t)(vb[i] & 0xffffu), ue = (uint32_t)(ve[i] & 0xffffu);
     const uint32_t* c0 = cand + cfirst[i];
@@ -1768,25 +1736,15 @@ static inline void zs_plan_bgzf_range(uint32_t n, const uint32_t* out_cap, const
       const uint32_t take = upto - skip;
       const bool fits = out + take <= out_cap[i];
       const uint32_t room = fits ? b.isize : 0u;
-      p.rstream.push_back(i);
-      p.soff.push_back(cb + b.at);
-      p.slen.push_back(b.end - b.at);
-      p.ocap.push_back(room);
+      p.push(i, cb + b.at, b.end - b.at, out, room, fits ? take : 0u);
       p.skip.push_back(skip);
       p.take.push_back(take);
-      p.opos.push_back((uint32_t)out);
       p.trusted.push_back(fits ? 1 : 0);
-      p.stoff.push_back(st);
-      st += ((uint64_t)room + 3) & ~3ull;
-      // (the place's words: the destination's leading bytes of its first word count too)
-      p.ptile.push_back(p.ptile.back() + (uint32_t)(((uint64_t)(fits ? take : 0u) + 3 + ZS_RESTART_TILE - 1) / ZS_RESTART_TILE));
       if (!fits) break;
       out += take;
     }
   }
-  p.M = (uint32_t)p.rstream.size();
-  p.rfirst[n] = p.M;
-  p.stage_bytes = st + 16;
+  p.end(true);
 }
 
 #endif
